@@ -16,7 +16,10 @@ API with cache building and plan recording inside; `roofline`, `cpu_baseline` (c
 probe); `extra` (batch 32 / 64 / 256, one number each for BASELINE configs 3-5, `dp_overhead_one_rank`: the data-parallel op
 sequence -- gradient bucket -> RCCL all-reduce -> apply -- on ONE rank, host-driven and captured, against the single-GPU step).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--images n] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--images n] [--no-cpu-baseline] [--dump-outputs DIR]
+
+`--dump-outputs DIR` writes what the timed loops computed in their last step as DIR/*.npy (see `dump_outputs`): with the same
+arguments the inputs are the same from run to run, so two builds can be compared output for output.
 
 N > 1: one rank per GPU, each with its own calibration shard and mini-batch (weak scaling), the per-unit alpha-gradient bucket
 all-reduced over RCCL every iteration; rank 0 prints ONE JSON line.  Either launched by `python -m torch.distributed.run
@@ -131,7 +134,12 @@ def parse():
                          "one number each for BASELINE configs 3, 4, 5 (tools/bench_configs.py)")
     ap.add_argument("--sustain-steps", type=int, default=1000,
                     help="steps run AFTER the timed region in windows of 100 to report a sustained rate (0: skip)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed loops computed in their last step to DIR/<name>.npy (float32, at most 64 MB in all)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 # ----------------------------------------------------------------------------- product side
@@ -188,6 +196,46 @@ def build_caches(qnn, units, cali, bs):
         _FpMemo.clear()
         qnn.set_quant_state(True, False)
     return store
+
+
+DUMP_BUDGET_BYTES = 48 * 2 ** 20     # alphas of every unit; the loss rows add a few KB: the whole dump stays under 64 MB
+DUMP_SEED = 1005
+
+
+def dump_outputs(out_dir, engines, last, rank):
+    """What a caller of the timed loops receives after their last step (iteration `last` of every engine), as float32 .npy files:
+
+      <unit>.loss.npy          [total, rec+task, round] of that iteration (`UnitEngine.logs`, averaged over the ranks)
+      <unit>.<op>.alpha.npy    the op's trained rounding parameters (`UnitEngine.alpha_of`), flattened in the logical weight order
+
+    When all alphas together exceed DUMP_BUDGET_BYTES, every op keeps the same fraction of its elements: the first k of
+    randperm(numel) under the generator seed DUMP_SEED, in ascending index order -- a function of the shapes alone.  Collective under
+    data parallelism (`logs` all-reduces): every rank calls it, rank 0 writes."""
+    rows, alphas = {}, {}
+    for uname, e in engines:
+        tot, rt, rd = e.logs()
+        rows[uname] = torch.stack([tot[last], rt[last], rd[last]]).float()
+        for op in e.ops:
+            alphas[f"{uname}.{op}"] = e.alpha_of(op).detach().reshape(-1).float().cpu()
+    if rank != 0:
+        return
+    total = sum(v.numel() for v in alphas.values())
+    budget = DUMP_BUDGET_BYTES // 4
+    os.makedirs(out_dir, exist_ok=True)
+    import numpy as np
+    nbytes = 0
+    for uname, r in rows.items():
+        np.save(os.path.join(out_dir, f"{uname}.loss.npy"), r.numpy())
+        nbytes += r.numel() * 4
+    for key, v in alphas.items():
+        if total > budget:
+            k = max(1, v.numel() * budget // total)
+            pick = torch.randperm(v.numel(), generator=torch.Generator().manual_seed(DUMP_SEED))[:k].sort().values
+            v = v[pick]
+        np.save(os.path.join(out_dir, f"{key}.alpha.npy"), v.numpy())
+        nbytes += v.numel() * 4
+    log(f"outputs of step {last} written to {out_dir}: {len(rows) + len(alphas)} arrays, {nbytes / 2 ** 20:.1f} MiB"
+        + (f" (alphas sampled: {budget} of {total} elements)" if total > budget else ""))
 
 
 def gpu_leg(a, rank, world, device):
@@ -252,6 +300,8 @@ def gpu_leg(a, rank, world, device):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     log(f"timed region done: {dt:.3f}s for {a.steps} steps")
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, engines, a.warmup + a.steps - 1, rank)
     # ---- sustained rate: the driver-sized timed region lasts a fraction of a second on a part whose clock moves with load and
     # temperature; run on for `sustain` more steps in windows of 100 (each closed by the same barrier) and report them
     windows = []

@@ -195,8 +195,8 @@ def test_tape_engine_first_iteration_gradient(golden_dir, name):
     """d(rec + task)/d alpha of the first iteration (rounding regulariser still off): tape engine (data-parallel op sequence,
     plan A only) against torch autograd through the oracle's unit + FP tail.  1e-4 of the largest gradient entry."""
     import subprocess, sys
-    env = dict(os.environ, GRAFT_REPO_ROOT=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    out = subprocess.run([sys.executable, os.path.join(env["GRAFT_REPO_ROOT"], "tools", "nic_grad_check.py"), name], env=env,
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "tools", "nic_grad_check.py"), name],
                          capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     rels = [float(l.split("rel")[1]) for l in out.stdout.splitlines() if " rel " in l]

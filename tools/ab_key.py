@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """Same-process A/B of any tuning key on the plane-input forward conv: python tools/ab_key.py KEY V0 V1 [B H Cin Cout]..."""
 import sys, torch
-sys.path.insert(0, "/root/repo/rdo-ptq_amd")
 import os
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "rdo-ptq_amd"))
 from hipops import ops

@@ -1,5 +1,5 @@
 import os, sys, torch
-sys.path.insert(0, "/root/repo/rdo-ptq_amd")
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "rdo-ptq_amd"))
 from hipops import ops
 def timeit(fn, n=40):
     for _ in range(5): fn()

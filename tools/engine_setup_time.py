@@ -1,5 +1,5 @@
 import os, sys, time, torch
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/rdo-ptq_amd")
+R = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, R); sys.path.insert(0, os.path.join(R, "rdo-ptq_amd"))
 import bench
 from quantization import QuantModel
 from quantization.engine import UnitEngine

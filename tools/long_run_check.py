@@ -1,7 +1,7 @@
 """One layer unit (3x3 conv 192 -> 192 at 16x16 + LeakyReLU) for the reference's full 20 000 iterations in one graph-replay call:
 timing per iteration, loss trajectory sanity and convergence of the soft rounding targets to {0, 1}."""
 import sys, os, time, torch, numpy as np
-R = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, R + '/rdo-ptq_amd')
 import torch.nn as nn
 from quantization.quant_layer import QuantModule

@@ -1,6 +1,6 @@
 """First-iteration alpha gradients of the tape engine vs the oracle for the NIC golden units (used by tests/test_gpu_nic.py)."""
 import sys, os, numpy as np, torch
-R = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, R); sys.path.insert(0, R + '/tests'); sys.path.insert(0, R + '/rdo-ptq_amd')
 import test_gpu_nic as G
 import test_oracle_golden as TG

@@ -1,7 +1,7 @@
 """Stage-by-stage W8A8 comparison of one Swin block of the toy NIC (product on the GPU vs oracle on the CPU) from identical inputs:
 shows which activation-quantisation points are exact and how many elements flip by one 8-bit level (see tests/test_gpu_nic.py)."""
 import sys, os, numpy as np, torch
-R=os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+R=os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0,R); sys.path.insert(0,R+'/tests'); sys.path.insert(0,R+'/rdo-ptq_amd')
 import test_gpu_nic as G
 import test_oracle_golden as TG
