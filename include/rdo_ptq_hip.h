@@ -499,6 +499,15 @@ int rdo_plan_profile(rdo_plan* p, float* ms, void* stream);
 int rdo_ssim_level(const float* x, const float* y, int32_t planes, int32_t H, int32_t W, const float* window11, float c1, float c2,
                    float* ssim_mean, float* cs_mean, void* stream);
 int rdo_avg_pool2(const float* x, int32_t planes, int32_t H, int32_t W, float* out, void* stream);
+/* Backward of the two (the differentiable `ms-ssim` distortion of losses.RateDistortionLoss; pytorch_msssim.ms_ssim as consumed at
+ * losses/losses.py:27,54).  rdo_ssim_level_bwd: dx[planes][H][W] (written, not accumulated) = d/dx of
+ * sum_p g_ssim[p] ssim_mean[p] + g_cs[p] cs_mean[p] of rdo_ssim_level on the same x, y, window11 (HOST pointer), c1, c2; g_ssim, g_cs:
+ * DEVICE arrays [planes]; no gradient to the target y.  rdo_avg_pool2_bwd: the adjoint of rdo_avg_pool2 -- g_out
+ * [planes][(H+2(H%2)-2)/2+1][...] -> dx[planes][H][W] (each input pixel: 1/4 of the gradient of the one window that covers it).
+ * Both are deterministic (no atomics) and capturable (no allocation, no host synchronisation). */
+int rdo_ssim_level_bwd(const float* x, const float* y, int32_t planes, int32_t H, int32_t W, const float* window11, float c1, float c2,
+                       const float* g_ssim, const float* g_cs, float* dx, void* stream);
+int rdo_avg_pool2_bwd(const float* g_out, int32_t planes, int32_t H, int32_t W, float* dx, void* stream);
 
 #ifdef __cplusplus
 }

@@ -273,3 +273,34 @@ class SqDiffSumFn(torch.autograd.Function):
     def backward(ctx, g):
         ac, bc = ctx.saved_tensors
         return g * (2.0 * ctx.scale) * (ac - bc), None, None
+
+
+class SsimLevelFn(torch.autograd.Function):
+    """(ssim_mean, cs_mean) per plane of one MS-SSIM scale (rdo_ssim_level) with the gradient with respect to x
+    (rdo_ssim_level_bwd); x, y: [planes, H, W]; the target y gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, y, window, c1, c2):
+        xc, yc = x.detach().contiguous(), y.detach().contiguous()
+        ctx.consts = (window, c1, c2)
+        ctx.save_for_backward(xc, yc)
+        return ops.ssim_level(xc, yc, window, c1, c2)
+
+    @staticmethod
+    def backward(ctx, g_ssim, g_cs):
+        xc, yc = ctx.saved_tensors
+        window, c1, c2 = ctx.consts
+        return ops.ssim_level_bwd(xc, yc, window, c1, c2, g_ssim.contiguous(), g_cs.contiguous()), None, None, None, None
+
+
+class AvgPool2Fn(torch.autograd.Function):
+    """F.avg_pool2d(x, 2, padding=(H%2, W%2)) of [planes, H, W] (rdo_avg_pool2) with its adjoint (rdo_avg_pool2_bwd)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.hw = tuple(x.shape[1:])
+        return ops.avg_pool2(x.detach().contiguous())
+
+    @staticmethod
+    def backward(ctx, g):
+        return ops.avg_pool2_bwd(g.contiguous(), *ctx.hw)

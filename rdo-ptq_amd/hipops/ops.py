@@ -709,6 +709,30 @@ def avg_pool2(x):
     return out
 
 
+def ssim_level_bwd(x, y, window, c1, c2, g_ssim, g_cs, dx=None):
+    """Gradient with respect to x of sum(g_ssim * ssim_mean + g_cs * cs_mean) of `ssim_level(x, y, window, c1, c2)`; g_ssim, g_cs: [planes]
+    on the device -> dx [planes, H, W]."""
+    planes, H, W = x.shape
+    if y.shape != x.shape or g_ssim.numel() != planes or g_cs.numel() != planes or (dx is not None and dx.shape != x.shape):
+        raise ValueError("ssim_level_bwd: x, y (and dx) must share one [planes, H, W] shape, g_ssim / g_cs hold one value per plane")
+    dx = torch.empty_like(x) if dx is None else dx
+    win = (C.c_float * 11)(*[float(v) for v in window])
+    L.check(L.lib().rdo_ssim_level_bwd(_ptr(x), _ptr(y), planes, H, W, win, c1, c2, _ptr(g_ssim), _ptr(g_cs), _ptr(dx), _stream()),
+            "rdo_ssim_level_bwd")
+    return dx
+
+
+def avg_pool2_bwd(g_out, H, W):
+    """Adjoint of `avg_pool2` on a [planes, H, W] input: g_out [planes, Ho, Wo] -> dx [planes, H, W]."""
+    planes = g_out.shape[0]
+    ph, pw = H % 2, W % 2
+    if tuple(g_out.shape[1:]) != ((H + 2 * ph - 2) // 2 + 1, (W + 2 * pw - 2) // 2 + 1):
+        raise ValueError(f"avg_pool2_bwd: gradient {tuple(g_out.shape)} does not match a {H}x{W} input")
+    dx = torch.empty((planes, H, W), device=g_out.device, dtype=torch.float32)
+    L.check(L.lib().rdo_avg_pool2_bwd(_ptr(g_out), planes, H, W, _ptr(dx), _stream()), "rdo_avg_pool2_bwd")
+    return dx
+
+
 def iter_advance(iter_ptr):
     L.check(L.lib().rdo_iter_advance(_ptr(iter_ptr), _stream()), "rdo_iter_advance")
 

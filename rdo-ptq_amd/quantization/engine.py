@@ -272,10 +272,17 @@ class UnitEngine:
         self.fold_gather = os.environ.get("RDO_GATHER_IN_STEP", "1") != "0"
         self._next_gather = None
         # opt-in R + lambda*D task loss (loss_mode='rd'): dict(model=QuantModel, unit=module, cali=calibration images NCHW on the GPU,
-        # lmbda=float).  The unit output of every iteration is pushed through the REST of the wrapped model on torch's tape
-        # (hipops.autograd) and losses.RateDistortionLoss is differentiated back to it; rec_loss stays the lp term.
+        # lmbda=float, metric='mse' | 'ms-ssim' (optional, default 'mse')).  The unit output of every iteration is pushed through the
+        # REST of the wrapped model on torch's tape (hipops.autograd) and losses.RateDistortionLoss is differentiated back to it;
+        # rec_loss stays the lp term.
         self.rd = rd
         if rd is not None:
+            metric = rd.get("metric", "mse")
+            if metric not in ("mse", "ms-ssim"):
+                raise ValueError(f"loss_mode='rd': unknown metric {metric!r} ('mse' or 'ms-ssim')")
+            if metric == "ms-ssim" and min(rd["cali"].shape[-2:]) <= 160:
+                raise ValueError(f"loss_mode='rd' with metric 'ms-ssim' needs calibration crops with both sides above 160 pixels (five "
+                                 f"scales of an 11-tap window); got {tuple(rd['cali'].shape[-2:])}")
             if not include_act_func:
                 raise NotImplementedError("calibration engine: loss_mode='rd' substitutes the unit's module OUTPUT (after its fused "
                                           "activation); include_act_func=False optimises the pre-activation and cannot be combined with it")
@@ -1620,7 +1627,8 @@ class UnitEngine:
 
     def _rd_tail(self):
         """The current iteration's task loss: the images of the mini-batch through the wrapped model with this unit's output replaced
-        by the engine's soft-quantised output, `RateDistortionLoss` (lambda * 255^2 * MSE + bpp) on the result, gradient back to that
+        by the engine's soft-quantised output, `RateDistortionLoss` (lambda * 255^2 * MSE + bpp, or lambda * (1 - MS-SSIM) + bpp with
+        rd['metric'] = 'ms-ssim') on the result, gradient back to that
         output (HIP kernels under torch's tape: hipops.autograd; the factorised prior and the Gaussian conditional included).  The
         modules behind the unit are whatever the calibration flow left them: trained ones hard-quantised, the others full precision
         (layer_opt.py:15-43).  Device-side throughout (capturable): the mini-batch rows come from the index table through the device
@@ -1646,7 +1654,7 @@ class UnitEngine:
         try:
             with torch.enable_grad():
                 out = rd["model"](x)
-                loss = RateDistortionLoss(lmbda=rd["lmbda"], metric="mse")(out, x)["loss"]
+                loss = RateDistortionLoss(lmbda=rd["lmbda"], metric=rd.get("metric", "mse"))(out, x)["loss"]
                 (g,) = torch.autograd.grad(loss, [leaf], allow_unused=True)
         finally:
             for m_ in patched:

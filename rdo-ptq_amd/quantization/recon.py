@@ -121,6 +121,19 @@ def _unit_modules(unit):
     raise NotImplementedError(f"reconstruction of {type(unit).__name__} is not built yet")
 
 
+def _rd_metric(args, cali_data):
+    """args.rd_metric: the distortion of the loss_mode='rd' task term, 'mse' (default) or 'ms-ssim' (the objective of CompressAI's
+    MS-SSIM checkpoints).  Not `args.metric`: LossFunction.metric is the --task_loss exponent.  Checked before any work is done:
+    the five MS-SSIM scales of an 11-tap window need crops with both sides above 160 pixels."""
+    metric = getattr(args, "rd_metric", "mse") if args is not None else "mse"
+    if metric not in ("mse", "ms-ssim"):
+        raise ValueError(f"unknown rd_metric {metric!r} ('mse' or 'ms-ssim')")
+    if metric == "ms-ssim" and getattr(args, "loss_mode", "lp") == "rd" and min(cali_data.shape[-2:]) <= 160:
+        raise ValueError(f"rd_metric='ms-ssim' needs calibration crops with both sides above 160 pixels (five scales of an 11-tap "
+                         f"window); got {tuple(cali_data.shape[-2:])}")
+    return metric
+
+
 def reconstruct(model, unit, unit_name, cali_data, *a, **kw):
     """`_reconstruct` with the one piece of cross-unit state tidied up on failure: the full-precision cache memo of the schedule
     (quantization/utils.py::_FpMemo) is dropped when a unit raises, so a schedule that dies half-way pins no device memory."""
@@ -146,6 +159,7 @@ def _reconstruct(model, unit, unit_name, cali_data, batch_size=32, iters=20000, 
         raise NotImplementedError("rec_loss is built for p = 2 (the value main2.py passes); --task_loss may be any exponent >= 1")
     if float(task_p) < 1.0:
         raise ValueError("--task_loss < 1 has no finite gradient at zero error")
+    rd_metric = _rd_metric(args, cali_data)
     rank, world_size = dp.world()
     if world_size > 1:                      # data parallel: this rank calibrates on its shard with its share of the batch
         if batch_size % world_size != 0:
@@ -193,7 +207,8 @@ def _reconstruct(model, unit, unit_name, cali_data, batch_size=32, iters=20000, 
     # (layer_opt.py:146-148).  args.loss_mode = 'rd' (default 'lp' = the reference's lp_loss pair)
     rd = None
     if getattr(args, "loss_mode", "lp") == "rd":
-        rd = dict(model=model, unit=unit, cali=cali_data.to(next(model.parameters()).device), lmbda=float(getattr(args, "lmbda", 0.01)))
+        rd = dict(model=model, unit=unit, cali=cali_data.to(next(model.parameters()).device), lmbda=float(getattr(args, "lmbda", 0.01)),
+                  metric=rd_metric)
     elif getattr(args, "loss_mode", "lp") != "lp":
         raise ValueError(f"unknown loss_mode {args.loss_mode!r} ('lp' or 'rd')")
     # the CLI --lr is ignored by the reference (Adam default 1e-3, layer_opt.py:253-254); kept that way.

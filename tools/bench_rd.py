@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Time one calibration iteration of the opt-in R + lambda*D task-loss mode (`loss_mode='rd'`, main2.py:125-137 through
 layer_opt.py:258-274) on a full-size Cheng2020-anchor (N=192): the captured-graph iteration against the host-driven one
-(RDO_RD_GRAPH=0), next to the default MSE-only iteration of the same unit.
+(RDO_RD_GRAPH=0), next to the default MSE-only iteration of the same unit; `rd-msssim` is the captured-graph iteration with the
+MS-SSIM distortion (rd metric 'ms-ssim', lambda 12).
 
-    python tools/bench_rd.py [--unit g_s.2] [--batch 8] [--size 256] [--iters 60]
+    python tools/bench_rd.py [--unit g_s.2] [--batch 8] [--size 256] [--iters 60] [--modes mse,rd-graph,rd-host,rd-msssim]
 
 Prints one line per path: ms per iteration (HIP events around `iters` iterations after the engine's own warm-up)."""
 import argparse
@@ -32,10 +33,11 @@ def main():
     ap.add_argument("--images", type=int, default=32)
     ap.add_argument("--iters", type=int, default=60)
     ap.add_argument("--N", type=int, default=192)
+    ap.add_argument("--modes", default="mse,rd-graph,rd-host")
     a = ap.parse_args()
     torch.manual_seed(0)
     cali = torch.rand(a.images, 3, a.size, a.size).cuda()
-    for mode in ("mse", "rd-graph", "rd-host"):
+    for mode in a.modes.split(","):
         torch.manual_seed(1)
         qnn = QuantModel(lic.Cheng2020Anchor(N=a.N).eval().cuda(), WQ, AQ, is_cheng=True).cuda().eval()
         qnn.set_quant_state(False, False)
@@ -56,6 +58,8 @@ def main():
         k, mods = _unit_modules(unit)
         warm = 8
         rd = None if mode == "mse" else dict(model=qnn, unit=unit, cali=cali, lmbda=0.0483)
+        if mode == "rd-msssim":
+            rd.update(lmbda=12.0, metric="ms-ssim")
         eng = UnitEngine(k, mods, inp, inp, out, batch_size=a.batch, iters=warm + a.iters, seed=1, rd=rd)
         eng.run(warm)
         torch.cuda.synchronize()
