@@ -10,13 +10,17 @@ layer_opt.py:287-309) of EVERY one of the 29 reconstruction units of the model; 
 wall time.  Caches (cached_inps / cached_outs of every unit, built by the product's `save_inp_oup_data`) are resident in
 HBM before the timed region.
 
-Keys of the JSON line next to the contract's: `value` / `ms_per_step` = the timed loops; `recon_model_images_per_s` (+
-`recon_model_iters_per_unit`, `recon_model_cache_s`) = SURVEY 8d's literal metric, wall of the whole `recon_model` through the public
-API with cache building and plan recording inside; `roofline`, `cpu_baseline` (contract); `kernels` (per kernel family, event
-probe); `extra` (batch 32 / 64 / 256, one number each for BASELINE configs 3-5, `dp_overhead_one_rank`: the data-parallel op
-sequence -- gradient bucket -> RCCL all-reduce -> apply -- on ONE rank, host-driven and captured, against the single-GPU step).
+A plain run does what its headline needs and nothing else: set-up (model, caches, engines), warm-up, the timed steps, the arrays of
+`--dump-outputs`, and the JSON line -- `value` / `ms_per_step` = the timed loops, `config` = the workload, library and tuning.
+`--full` measures everything else after the timed region and adds it to the line: `sustained_*` (1 000 more steps in windows of
+100); `kernels` (per kernel family, event probe) and `roofline`; `dp` (N > 1: wall per iteration and collective time of every unit);
+`recon_model_images_per_s` (+ `recon_model_iters_per_unit`, `recon_model_cache_s`) = SURVEY 8d's literal metric, wall of the whole
+`recon_model` through the public API with cache building and plan recording inside; `extra` (batch 32 / 64 / 256, one number each
+for BASELINE configs 3-5, `dp_overhead_one_rank`: the data-parallel op sequence -- gradient bucket -> RCCL all-reduce -> apply -- on
+ONE rank, host-driven and captured, against the single-GPU step); `cpu_baseline`.  The timed steps are the same in both modes.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--images n] [--no-cpu-baseline] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--images n] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-extras] [--recon-iters n] [--sustain-steps n]]
 
 `--dump-outputs DIR` writes what the timed loops computed in their last step as DIR/*.npy (see `dump_outputs`): with the same
 arguments the inputs are the same from run to run, so two builds can be compared output for output.
@@ -90,6 +94,37 @@ def kernel_row(tag, launches, ms, flops, nbytes):
     return row
 
 
+def roofline_of(per_tag):
+    """The line's `roofline` (the dominant conv kernel against the peak of its pipe) and `kernels` (every family, `kernel_row`) from
+    the event probe's {tag: [launches, ms, flops, bytes]} per step."""
+    conv = {t: v for t, v in per_tag.items() if t.startswith("conv_")}
+    dom = max(conv, key=lambda t: conv[t][1])
+    cnt, ms, fl, _ = conv[dom]
+    achieved = fl / (ms * 1e-3) / 1e12
+    peak, peak_note = kernel_peak(dom)
+    kernels = {t: kernel_row(t, *v) for t, v in sorted(per_tag.items(), key=lambda kv: -kv[1][1])}
+    traffic, traffic_src = None, None
+    for tf in ("r06_traffic.json", "r05_traffic.json", "r04_traffic.json", "r03_traffic.json", "r02_traffic.json", "r01_traffic.json"):   # HBM-side bytes per launch of the dominant kernel, last committed --pmc passes
+        try:
+            tj = json.load(open(os.path.join(ROOT, "profiles", tf)))
+            if dom in tj:
+                traffic = round((2 * tj[dom]["fetch_mib_raw"] + tj[dom]["write_mib"]) * 1048576)
+                traffic_src = f"profiles/{tf} (rocprofv3 --pmc FETCH_SIZE x2 gfx950 correction + WRITE_SIZE, bytes per launch)"
+                break
+        except Exception:
+            pass
+    roofline = {"bound": "mfma", "kernel": dom, "achieved": round(achieved, 2), "peak": round(peak, 1),
+                "peak_note": peak_note, "unit": "TFLOP/s", "frac": round(achieved / peak, 4), "traffic": traffic,
+                "traffic_source": traffic_src,
+                "launches_per_step": cnt, "avg_launch_ms": round(ms / cnt, 4),
+                "algorithmic_gflop_per_launch": round(fl / cnt / 1e9, 3),
+                # what the board's power limit lets nothing-but-MFMA code reach on random fp16 operands (tools/micro/mfma_power.hip,
+                # DESIGN 3): 1709 TFLOP/s of v_mfma_f32_16x16x32_f16 at 1.72 GHz -- informative, `frac` stays against the nominal peak
+                "power_limited_peak_measured": round(MEASURED_F16_MFMA_SUSTAINED_TFLOPS / 3.0, 1) if kernel_peak(dom) is _H2 else None,
+                "frac_of_power_limited_peak": round(achieved / (MEASURED_F16_MFMA_SUSTAINED_TFLOPS / 3.0), 4) if kernel_peak(dom) is _H2 else None}
+    return roofline, kernels
+
+
 def log(*a):
     if os.environ.get("RANK", "0") == "0":
         print(f"[bench {time.strftime('%H:%M:%S')}]", *a, file=sys.stderr, flush=True)
@@ -122,18 +157,22 @@ def parse():
     ap.add_argument("--images", type=int, default=256, help="calibration images per GPU")
     ap.add_argument("--N", type=int, default=192, help="Cheng2020 channel width")
     ap.add_argument("--crop", type=int, default=256)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure everything beyond the headline: sustained rate, per-kernel roofline probe, "
+                         "data-parallel per-unit probe (N > 1), recon_model wall, extra configurations and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without cpu_baseline")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--cpu-iters", type=int, default=20, help="timed oracle iterations per unit for cpu_baseline")
     ap.add_argument("--recon-iters", type=int, default=2000,
-                    help="after the timed region (N = 1 only): wall time of the whole `recon_model` schedule through the public "
+                    help="--full, after the timed region (N = 1 only): wall time of the whole `recon_model` schedule through the public "
                          "layer_/block_reconstruction API with this many iterations per unit (SURVEY 8d's definition of the metric: cache "
                          "building + plan recording + loops); 0: skip")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the extra measurements after the timed region (N = 1 only): batch 32 / 64 throughput of the same workload and "
-                         "one number each for BASELINE configs 3, 4, 5 (tools/bench_configs.py)")
+                    help="--full without the extra measurements after the timed region (N = 1 only): batch 32 / 64 / 256 throughput of the "
+                         "same workload and one number each for BASELINE configs 3, 4, 5 (tools/bench_configs.py)")
     ap.add_argument("--sustain-steps", type=int, default=1000,
-                    help="steps run AFTER the timed region in windows of 100 to report a sustained rate (0: skip)")
+                    help="steps run AFTER the timed region in windows of 100 to report a sustained rate (--full; 0: skip).  The engines "
+                         "are recorded for them in every run: the AdaRound schedule spans all of an engine's iterations")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the timed loops computed in their last step to DIR/<name>.npy (float32, at most 64 MB in all)")
     a = ap.parse_args()
@@ -261,9 +300,11 @@ def gpu_leg(a, rank, world, device):
     t_cache = time.time() - t0
     log(f"caches built in {t_cache:.1f}s; recording engines")
     force_dp = bool(os.environ.get("RDO_BENCH_FORCE_DP"))    # exercise the grad -> RCCL all-reduce -> apply sequence on 1 rank
-    unit_wall = bool(os.environ.get("RDO_BENCH_UNIT_WALL"))   # diagnostic: per-unit wall time of graph replays after the timed region
+    unit_wall = bool(os.environ.get("RDO_BENCH_UNIT_WALL"))   # diagnostic (--full): per-unit wall time of graph replays after the timed region
     sustain = (a.sustain_steps // 100) * 100
     dp_probe = 10 if (world > 1 or force_dp) else 0             # per-unit wall / collective probe after the timed region (N > 1)
+    # The engines have room for everything --full runs after the timed region, in a plain run too: the AdaRound schedule (round-loss
+    # warm-up, temperature decay) is laid out over all `iters`, so the timed steps compute the same with and without --full.
     iters = a.warmup + a.steps + sustain + 1 + (a.steps if unit_wall else 0) + dp_probe   # +1: the event-profiled iteration after the timed region
     gi = torch.Generator().manual_seed(77 + rank)
     engines = []
@@ -302,6 +343,9 @@ def gpu_leg(a, rank, world, device):
     log(f"timed region done: {dt:.3f}s for {a.steps} steps")
     if a.dump_outputs:
         dump_outputs(a.dump_outputs, engines, a.warmup + a.steps - 1, rank)
+    if not a.full:                               # the headline is complete: everything below is --full
+        check_finite(engines, a.warmup + a.steps)
+        return leg_result(engines, dt=dt, t_cache=t_cache)
     # ---- sustained rate: the driver-sized timed region lasts a fraction of a second on a part whose clock moves with load and
     # temperature; run on for `sustain` more steps in windows of 100 (each closed by the same barrier) and report them
     windows = []
@@ -367,12 +411,7 @@ def gpu_leg(a, rank, world, device):
             d = per_tag.setdefault(tag, [0, 0.0, 0.0, 0.0])
             d[0] += 1; d[1] += m; d[2] += fl; d[3] += by
     log("roofline probe done")
-    # sanity: losses finite
-    for name, e in engines:
-        tot, _, _ = e.logs()
-        if not torch.isfinite(tot[:a.warmup + a.steps + sustain]).all():
-            raise RuntimeError(f"non-finite loss in unit {name}")
-    h2_units = [n for n, e in engines if getattr(e, "h2_plan", None)]
+    check_finite(engines, a.warmup + a.steps + sustain)
     # ---- "throughput" configurations of SURVEY 8d (outside the timed region): the same schedule at mini-batch 32 and 64
     batch_extra = {}
     if world == 1 and not force_dp and not a.no_extras:
@@ -432,11 +471,25 @@ def gpu_leg(a, rank, world, device):
             except Exception as ex:      # an extra must never cost the headline
                 batch_extra["batch256_units_in_sequence"] = {"error": repr(ex)[:300]}
                 torch.cuda.empty_cache()
+    return leg_result(engines, dt=dt, t_cache=t_cache, per_tag=per_tag, windows=windows, batch_extra=batch_extra, dp_units=dp_units)
+
+
+def check_finite(engines, n):
+    """sanity: the losses of the first `n` iterations of every unit are finite (collective under data parallelism, like `logs`)"""
+    for name, e in engines:
+        tot, _, _ = e.logs()
+        if not torch.isfinite(tot[:n]).all():
+            raise RuntimeError(f"non-finite loss in unit {name}")
+
+
+def leg_result(engines, *, dt, t_cache, per_tag=None, windows=(), batch_extra=None, dp_units=None):
+    """What `main` reports of the GPU leg; the measurements after the timed region (--full) are empty in a plain run."""
+    h2_units = [n for n, e in engines if getattr(e, "h2_plan", None)]
     # which data-parallel loop ran: "graph" (iteration + collectives replayed from one graph) or "host" (plan / all-reduce / plan)
     dp_paths = sorted({e.dp_path for _, e in engines if e.dp_path is not None})
     dp_fallbacks = sum(e.dp_fallbacks for _, e in engines)
-    return dict(dt=dt, n_units=len(engines), per_tag=per_tag, t_cache=t_cache, windows=windows, h2_units=h2_units, dp_paths=dp_paths, dp_fallbacks=dp_fallbacks,
-                batch_extra=batch_extra, dp_units=dp_units)
+    return dict(dt=dt, n_units=len(engines), per_tag=per_tag or {}, t_cache=t_cache, windows=list(windows), h2_units=h2_units, dp_paths=dp_paths,
+                dp_fallbacks=dp_fallbacks, batch_extra=batch_extra or {}, dp_units=dp_units or {})
 
 
 def dp_overhead_one_rank(a, device, single_ms, steps=12):
@@ -772,22 +825,6 @@ def main():
     n_units, dt = res["n_units"], res["dt"]
     value = n_units * a.batch * a.steps * world / dt
     if rank == 0:
-        conv = {t: v for t, v in res["per_tag"].items() if t.startswith("conv_")}
-        dom = max(conv, key=lambda t: conv[t][1])
-        cnt, ms, fl, _ = conv[dom]
-        achieved = fl / (ms * 1e-3) / 1e12
-        peak, peak_note = kernel_peak(dom)
-        kernels = {t: kernel_row(t, *v) for t, v in sorted(res["per_tag"].items(), key=lambda kv: -kv[1][1])}
-        traffic, traffic_src = None, None
-        for tf in ("r06_traffic.json", "r05_traffic.json", "r04_traffic.json", "r03_traffic.json", "r02_traffic.json", "r01_traffic.json"):   # HBM-side bytes per launch of the dominant kernel, last committed --pmc passes
-            try:
-                tj = json.load(open(os.path.join(ROOT, "profiles", tf)))
-                if dom in tj:
-                    traffic = round((2 * tj[dom]["fetch_mib_raw"] + tj[dom]["write_mib"]) * 1048576)
-                    traffic_src = f"profiles/{tf} (rocprofv3 --pmc FETCH_SIZE x2 gfx950 correction + WRITE_SIZE, bytes per launch)"
-                    break
-            except Exception:
-                pass
         out = {
             "metric": "calibration images/sec (Cheng2020 W8A8 task-oriented RDO-PTQ, image-iterations over all units)",
             "value": round(value, 2), "unit": "images/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -810,17 +847,9 @@ def main():
                                             "measured_vs_fp64": 7.4e-7, "fp32_fma_chain_vs_fp64": 1.5e-6,
                                             "where": "tests/test_gpu_h2.py:80-92 (assert), DESIGN.md section 5 round 3 (measurement)"},
                        "cache_build_s": round(res["t_cache"], 2)},
-            "roofline": {"bound": "mfma", "kernel": dom, "achieved": round(achieved, 2), "peak": round(peak, 1),
-                         "peak_note": peak_note, "unit": "TFLOP/s", "frac": round(achieved / peak, 4), "traffic": traffic,
-                         "traffic_source": traffic_src,
-                         "launches_per_step": cnt, "avg_launch_ms": round(ms / cnt, 4),
-                         "algorithmic_gflop_per_launch": round(fl / cnt / 1e9, 3),
-                         # what the board's power limit lets nothing-but-MFMA code reach on random fp16 operands (tools/micro/mfma_power.hip,
-                         # DESIGN 3): 1709 TFLOP/s of v_mfma_f32_16x16x32_f16 at 1.72 GHz -- informative, `frac` stays against the nominal peak
-                         "power_limited_peak_measured": round(MEASURED_F16_MFMA_SUSTAINED_TFLOPS / 3.0, 1) if kernel_peak(dom) is _H2 else None,
-                         "frac_of_power_limited_peak": round(achieved / (MEASURED_F16_MFMA_SUSTAINED_TFLOPS / 3.0), 4) if kernel_peak(dom) is _H2 else None},
-            "kernels": kernels,
         }
+        if a.full:
+            out["roofline"], out["kernels"] = roofline_of(res["per_tag"])
         if res["windows"]:
             w = res["windows"]
             out["sustained_ms_per_step"] = round(sum(w) / len(w), 3)
@@ -848,7 +877,7 @@ def main():
                          "sum_allreduce_ms": round(sum(d["allreduce_us"] for d in du.values()) / 1e3, 3),
                          "note": "rank 0, after the timed region: wall per iteration of each unit's data-parallel loop and of its collective(s) alone",
                          "units": du}
-        if world == 1 and a.recon_iters > 0 and not os.environ.get("RDO_BENCH_FORCE_DP"):
+        if a.full and world == 1 and a.recon_iters > 0 and not os.environ.get("RDO_BENCH_FORCE_DP"):
             # outside the timed region: the metric by SURVEY 8d's literal definition -- wall time of recon_model (main2.py:227-253)
             sys.path.insert(0, os.path.join(ROOT, "tools"))
             from full_schedule import run_schedule
@@ -865,7 +894,7 @@ def main():
                                   "images_per_s": round(rs["images_per_s"], 1),
                                   "note": "whole schedule through the public API incl. asymmetric cache building and plan recording; the "
                                           "reference's 20000-iteration schedule is timed by tools/full_schedule.py (profiles/)"}
-        if world == 1 and not a.no_extras and not os.environ.get("RDO_BENCH_FORCE_DP"):
+        if a.full and world == 1 and not a.no_extras and not os.environ.get("RDO_BENCH_FORCE_DP"):
             extra = dict(res["batch_extra"])
             sys.path.insert(0, os.path.join(ROOT, "tools"))
             import bench_configs
@@ -883,7 +912,7 @@ def main():
             except Exception as ex:          # an extra must never cost the headline
                 extra["dp_overhead_one_rank"] = {"error": repr(ex)[:300]}
             out["extra"] = extra
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_leg(a)
             out["cpu_baseline"]["value"] = round(out["cpu_baseline"]["value"], 3)
         print(json.dumps(out), file=json_out, flush=True)

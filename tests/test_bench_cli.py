@@ -1,5 +1,6 @@
 """bench.py command-line contract, checked without a GPU except where marked: `--gpus N` must never time
-a smaller world under the label n_gpus = N; `--dump-outputs DIR` writes the last timed step's outputs."""
+a smaller world under the label n_gpus = N; `--dump-outputs DIR` writes the last timed step's outputs; `--full` measures more after the
+same timed steps."""
 import os
 import subprocess
 import sys
@@ -35,6 +36,33 @@ def test_steps_must_be_positive():
     r = _run(["--gpus", "1", "--steps", "0"])
     assert r.returncode != 0 and "--steps must be >= 1" in r.stderr
     assert r.stdout.strip() == ""
+
+
+def test_full_is_off_by_default(monkeypatch):
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--full"])
+    assert bench.parse().full is True
+
+
+def test_roofline_of_the_event_probe():
+    """`roofline` prices the conv family with the most time per step against the peak of its pipe; `kernels` lists every family,
+    longest first."""
+    import bench
+    per_tag = {"conv_fwd_h2_halo": [12, 1.2, 12 * 40e9, 12 * 100e6],        # [launches, ms, flops, bytes] per step
+               "conv_wgrad_64x64": [39, 1.8, 39 * 2e9, 39 * 50e6],
+               "ada_step_gather": [105, 1.5, 0.0, 4e9]}
+    roof, kernels = bench.roofline_of(per_tag)
+    assert list(kernels) == ["conv_wgrad_64x64", "ada_step_gather", "conv_fwd_h2_halo"]
+    assert roof["kernel"] == "conv_wgrad_64x64" and roof["launches_per_step"] == 39 and roof["avg_launch_ms"] == round(1.8 / 39, 4)
+    assert roof["peak"] == bench.PEAK_F32_MFMA_TFLOPS and roof["achieved"] == round(39 * 2e9 / 1.8e-3 / 1e12, 2)
+    assert roof["frac"] == round(39 * 2e9 / 1.8e-3 / 1e12 / bench.PEAK_F32_MFMA_TFLOPS, 4) and roof["power_limited_peak_measured"] is None
+    assert kernels["ada_step_gather"]["bound"] == "hbm" and kernels["conv_fwd_h2_halo"]["bound"] == "mfma"
+    per_tag["conv_fwd_h2_halo"][1] = 2.0
+    roof, _ = bench.roofline_of(per_tag)
+    assert roof["kernel"] == "conv_fwd_h2_halo" and roof["peak"] == round(bench.PEAK_BF16_MFMA_TFLOPS / 3.0, 1)
+    assert roof["power_limited_peak_measured"] == round(bench.MEASURED_F16_MFMA_SUSTAINED_TFLOPS / 3.0, 1)
 
 
 class _StubEngine:
@@ -107,3 +135,33 @@ def test_dump_outputs_of_a_short_run(tmp_path):
     for f in files:
         a = np.load(f)
         assert a.dtype == np.float32 and a.size > 0 and np.isfinite(a).all(), f.name
+
+
+@pytest.mark.gpu
+def test_full_measures_after_the_same_timed_steps(tmp_path):
+    """A plain run reports the headline and nothing of `--full`; `--full` adds its measurements after a timed region that computes
+    the same: on the headline's workload both dump the same outputs of the last timed step.  The engines of both are recorded for the
+    same schedule, so the round loss is off in the same iterations (a schedule recorded for fewer iterations would switch it on
+    within these 21 and change every loss row); float atomics may move the last bits from run to run."""
+    import json
+    import numpy as np
+    args = ["--gpus", "1", "--steps", "20", "--warmup", "1", "--no-extras", "--no-cpu-baseline", "--sustain-steps", "100", "--recon-iters", "0"]
+    lines = {}
+    for mode, extra in (("plain", []), ("full", ["--full"])):
+        r = _run(args + extra + ["--dump-outputs", str(tmp_path / mode)], timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines[mode] = json.loads(r.stdout.strip().splitlines()[-1])
+    plain, full = lines["plain"], lines["full"]
+    for d in (plain, full):
+        assert d["steps"] == 20 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["unit"] == "images/s" and d["higher_is_better"] is True
+        assert d["dtype"] == "f32" and d["metric"].startswith("calibration images/sec")
+    assert not {"roofline", "kernels", "sustained_ms_per_step", "dp", "recon_model_images_per_s", "extra", "cpu_baseline"} & set(plain)
+    assert full["roofline"]["kernel"] in full["kernels"] and full["sustained_steps"] == 100
+    names = sorted(f.name for f in (tmp_path / "plain").iterdir())
+    assert len(names) > 29 and names == sorted(f.name for f in (tmp_path / "full").iterdir())
+    for n in names:
+        a, b = np.load(tmp_path / "plain" / n), np.load(tmp_path / "full" / n)
+        if n.endswith(".loss.npy"):                  # [total, rec+task, round] of the last timed step
+            np.testing.assert_allclose(a, b, rtol=1e-4, atol=1e-9, err_msg=n)
+        else:
+            assert np.linalg.norm(a - b) <= 1e-4 * np.linalg.norm(b), n

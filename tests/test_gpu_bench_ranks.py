@@ -13,8 +13,8 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ARGS = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--images", "8", "--no-extras", "--no-cpu-baseline", "--sustain-steps", "0",
-        "--recon-iters", "0"]
+ARGS = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--images", "8", "--full", "--no-extras", "--no-cpu-baseline", "--sustain-steps", "0",
+        "--recon-iters", "0"]                    # --full: the line's `dp` table comes from the per-unit probe after the timed region
 
 
 def _env(**extra):
@@ -65,6 +65,19 @@ def test_launcher_spawns_ranks_and_reports_one_line():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + ARGS, env=_env(), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     _check_line(r.stdout)
+
+
+def test_plain_run_of_two_ranks_reports_the_headline_only():
+    """Without --full both ranks leave after the timed region (a collective loss check on every rank), rank 0 prints the line."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + [a for a in ARGS if a != "--full"], env=_env(),
+                       capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 2 and d["steps"] == 3 and d["warmup"] == 1 and d["config"]["parallelism"] == "dp2"
+    assert abs(d["value"] - 29 * 4 * 3 * 2 / (d["ms_per_step"] * 3 / 1e3)) <= 1e-3 * d["value"]
+    assert d["config"]["dp_loop"] == "host" and not {"dp", "roofline", "kernels", "sustained_ms_per_step"} & set(d)
 
 
 def test_launcher_stops_everything_when_a_rank_dies():

@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT
 VAR=$1; KER=$2; shift 2
 for v in "$@"; do
-  env $VAR=$v timeout 600 python bench.py --no-extras --no-cpu-baseline 2>/dev/null | tail -1 | python3 -c "
+  env $VAR=$v timeout 600 python bench.py --full --no-extras --no-cpu-baseline 2>/dev/null | tail -1 | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 k=d['kernels'].get('$KER',{})

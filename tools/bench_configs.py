@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The measurement plan beyond the headline ("GPU runs"): one number each for
-BASELINE configs 3, 4 and 5 on one MI355X.  bench.py calls these after its timed region and reports them as EXTRA keys of its JSON
+BASELINE configs 3, 4 and 5 on one MI355X.  `bench.py --full` calls these after its timed region and reports them as EXTRA keys of its JSON
 line; standalone:   python tools/bench_configs.py [attn] [lu2022] [mbt2018]"""
 import os
 import sys

@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/trace_tmp
 mkdir -p $OUT
-timeout 600 rocprofv3 --kernel-trace -d $OUT -o t --output-format csv -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --sustain-steps 0 > $OUT/log.txt 2>&1
+timeout 600 rocprofv3 --kernel-trace -d $OUT -o t --output-format csv -- python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --sustain-steps 0 > $OUT/log.txt 2>&1
 echo rc=$?
 F=$(find $OUT -name "*kernel_trace.csv" | head -1)
 python3 - "$F" "$1" > $R/gpurun_out/trace_$1.txt <<'PY'
