@@ -80,6 +80,33 @@ class IdxStream:
         return torch.stack([torch.randperm(n)[:B] for _ in range(iters)])
 
 
+# Forms of an activation tensor inside a unit (`UnitEngine._forms`): as an fp32 tensor, as H2 planes (two fp16 planes of the scaled
+# tensor), as both, or -- the pre-activation of a conv whose tail runs in the same launch -- not in memory at all
+ABSENT, F32, PLANES, BOTH = 0, 1, 2, 3
+
+
+class Act:
+    """One activation tensor of a unit in the form(s) the unit's table gives it: `f32` (tensor or None) and / or `planes` (ops.H2 or
+    None).  The recording helpers take an `Act` or a bare fp32 tensor and choose the kernel by the form of their operands."""
+    __slots__ = ("name", "shape", "f32", "planes")
+
+    def __init__(self, name, shape, f32=None, planes=None):
+        self.name, self.shape, self.f32, self.planes = name, tuple(shape), f32, planes
+
+
+def _act_of(x):
+    return x if isinstance(x, Act) else Act(None, x.shape, x)
+
+
+def _f32(x):
+    return x.f32 if isinstance(x, Act) else x
+
+
+def _planes_only(x):
+    """the planes of a tensor that has no fp32 form, else None: a reader that can take either takes the fp32 tensor where there is one"""
+    return x.planes if isinstance(x, Act) and x.f32 is None else None
+
+
 class _Op:
     """Device state of one trainable QuantModule inside a unit."""
 
@@ -335,6 +362,7 @@ class UnitEngine:
         with ops.h2_flag(self._ovf[0:2]):
             self._build_ops()
             self._alloc()
+            self.forms = {}                    # activation buffer name -> form, where it is not F32 (`_forms`; set per recording)
             self.scales = {}                   # activation buffer name -> power-of-two scale of its H2 planes
             self._amax = {}                    # ... and the magnitude it was derived from
             self._probing = False
@@ -469,18 +497,19 @@ class UnitEngine:
         if not (self.lin_conv and not self._probing and op.qm.kind == "conv" and op.K == 1 and op.stride == 1 and op.pad == 0 and op.tconv is None):
             return False
         C = x.shape[-1]
-        rows = x.numel() // C
+        rows = math.prod(x.shape[:-1])
         return rows >= self.LIN_GDN_MIN_ROWS and ops.linear_h2_supported(rows, C, op.w4[0])
 
     unit1x1 = int(os.environ.get("RDO_UNIT1X1", "2"))       # 0 off, 1 only 16^2 maps and K = 96, 2 wherever the shape is supported (default)
 
     def _unit1x1_ok(self, op, x):
         """A plain 1 x 1 / stride-1 conv as a LAYER unit with the default objective: rdo_unit1x1 (forward + tail + weight-gradient slabs in
-        one launch, exact fp32) -- the 192 <-> 96 convs of Cheng2020-attn's attention blocks (BASELINE config 3)."""
+        one launch; on split fp16 where Cout is a multiple of 96, else in exact fp32: ops.unit1x1_form) -- the 192 <-> 96 convs of
+        Cheng2020-attn's attention blocks (BASELINE config 3)."""
         if not (self.unit1x1 and self.fused and self.include_act and self.kind == "layer" and op.qm.kind == "conv" and op.K == 1
                 and op.stride == 1 and op.pad == 0 and op.tconv is None and not op.is_gdn):
             return False
-        M, K = x.numel() // x.shape[-1], x.shape[-1]
+        M, K = math.prod(x.shape[:-1]), x.shape[-1]
         # per unit-iteration inside the config-3 schedule (us, three launches -> one): 16^2 maps 31 -> 29 (192 -> 96), 29 -> 22 (96 -> 192),
         # 32 -> 30 (192 -> 192); 64^2 maps 54 -> 47 at K = 96; at K = 192 on the 64^2 maps the first version (serial load / store loops) lost to
         # rdo_linear_h2 + linear_wgrad_h2 (54 -> 58), with its loads batched it wins there too: schedule 9.13 (off) / 8.81 (K = 96 and 16^2
@@ -488,24 +517,49 @@ class UnitEngine:
         return (self.unit1x1 == 2 or M <= 4096 or K <= 96) and ops.unit1x1_supported(M, K, op.w4[0])
 
     def _conv(self, op, x, out, epilogue=L.EPI_NONE, aux=None, residual=None, pre=None, square=False, bias=True):
+        """out = (epilogue of) the conv of x with op's soft weights.  x as planes: the plane-input kernel, which writes `out` as fp32 and /
+        or planes; else the fp32-input kernels (planes of `out` then by a split of their own)."""
+        x, out = _act_of(x), _act_of(out)
         b = (op.beta if op.is_gdn else op.bias) if bias else None
+        if x.planes is not None:
+            op.enable_planes(True, False, h2=True)
+            return ops.conv2d_fwd_h2(x.planes, x.shape, op.w4, op.wq_planes, b, op.stride, op.pad, epilogue=epilogue, aux=_f32(aux),
+                                     residual=_f32(residual), out=out.f32, pre=_f32(pre), out_planes=out.planes)
         if epilogue == L.EPI_NONE and aux is None and residual is None and pre is None and not square and self._lin_conv_ok(op, x):
-            return ops.linear_h2(x.view(-1, x.shape[-1]), op.lin_planes(True), b, out=out.view(-1, out.shape[-1]))
-        if ops.uses_bf16x6(tuple(x.shape), op.w4, op.stride, op.pad):
+            return ops.linear_h2(x.f32.view(-1, x.shape[-1]), op.lin_planes(True), b, out=out.f32.view(-1, out.shape[-1]))
+        if ops.uses_bf16x6(x.shape, op.w4, op.stride, op.pad):
             op.enable_planes(True, False)
-        return ops.conv2d_fwd(x, op.wq4(), b, op.stride, op.pad, epilogue=epilogue, aux=aux, residual=residual,
-                              square_input=square, out=out, pre=pre, wplanes=op.wq_planes)
+        y = ops.conv2d_fwd(x.f32, op.wq4(), b, op.stride, op.pad, epilogue=epilogue, aux=_f32(aux), residual=_f32(residual),
+                           square_input=square, out=out.f32, pre=_f32(pre), wplanes=op.wq_planes)
+        if out.planes is not None:
+            ops.split_h2(out.f32, out.planes)
+        return y
+
+    def _wgrad_into(self, slabs, x, dy, w4, stride, pad, square=False):
+        """weight-gradient slabs of a conv from its input and its output gradient: the plane kernel when both come as planes"""
+        x, dy = _act_of(x), _act_of(dy)
+        if x.planes is not None and dy.planes is not None:
+            ops.conv2d_wgrad_h2(x.planes, x.shape, dy.planes, w4, stride, pad, slabs=slabs)
+        else:
+            ops.conv2d_wgrad(x.f32, dy.f32, w4, stride, pad, square_input=square, slabs=slabs)
 
     def _wgrad(self, op, x, dy, square=False):
         if op.slabs is None:
             self._slabs(op, x.shape)
-        ops.conv2d_wgrad(x, dy, op.w4, op.stride, op.pad, square_input=square, slabs=op.slabs)
+        self._wgrad_into(op.slabs, x, dy, op.w4, op.stride, op.pad, square)
 
     def _dgrad(self, op, dy, out, epilogue=L.EPI_NONE, aux=None):
-        if ops.uses_bf16x6(tuple(dy.shape), tuple(op.wd4().shape), 1, op.K - 1 - op.pad):
+        """out = (epilogue of) the input gradient of op's conv; `aux` (the tensor whose sign the LeakyReLU mask needs) as fp32, else its
+        planes (the sign is read off plane 0)"""
+        dy, out = _act_of(dy), _act_of(out)
+        wd4, pad = tuple(op.wd4().shape), op.K - 1 - op.pad
+        if dy.planes is not None:
+            op.enable_planes(False, True, h2=True)
+            return ops.conv2d_fwd_h2(dy.planes, dy.shape, wd4, op.wd_planes, None, 1, pad, epilogue=epilogue, aux=_f32(aux),
+                                     aux_planes=_planes_only(aux), out=out.f32, out_planes=out.planes)
+        if ops.uses_bf16x6(dy.shape, wd4, 1, pad):
             op.enable_planes(False, True)
-        return ops.conv2d_fwd(dy, op.wd4(), None, 1, op.K - 1 - op.pad, epilogue=epilogue, aux=aux, out=out,
-                              wplanes=op.wd_planes)
+        return ops.conv2d_fwd(dy.f32, op.wd4(), None, 1, pad, epilogue=epilogue, aux=_f32(aux), out=out.f32, wplanes=op.wd_planes)
 
     # ---- the two 1x1 GEMMs of a GDN / IGDN (norm pool beta' + gamma' . x^2 and, backward, t . gamma'): token-matrix Linears over the
     # channels.  From LIN_GDN_MIN_ROWS pixels on they run on rdo_linear_h2 (per-pixel dynamic scale, three fp16 products) instead of the
@@ -515,7 +569,7 @@ class UnitEngine:
 
     def _gdn_lin_ok(self, g, x):
         C = x.shape[-1]
-        rows = x.numel() // C
+        rows = math.prod(x.shape[:-1])
         return (self.lin_gdn and not self._probing and rows >= self.LIN_GDN_MIN_ROWS and g.w4[0] == C and ops.linear_h2_supported(rows, C, C))
 
     def _gdn_pool(self, g, x, norm):
@@ -526,32 +580,37 @@ class UnitEngine:
         return self._conv(g, x, norm, square=True)
 
     def _gdn_acc(self, g, tbuf, acc):
-        """acc = t . gamma'   (wd = gamma'^T as [C][1][1][C])"""
-        if self._gdn_lin_ok(g, tbuf):
+        """acc = t . gamma'   (wd = gamma'^T as [C][1][1][C]): rdo_linear_h2 over the fp32 t where that applies (`_forms` then keeps t
+        off planes), else the 1 x 1 "input gradient" of the pool"""
+        tbuf = _act_of(tbuf)
+        if tbuf.planes is None and self._gdn_lin_ok(g, tbuf):
             C = tbuf.shape[-1]
-            return ops.linear_h2(tbuf.view(-1, C), g.lin_planes(False), None, out=acc.view(-1, C))
-        if ops.uses_bf16x6(tuple(tbuf.shape), tuple(g.wd4().shape), 1, 0):
-            g.enable_planes(False, True)
-        return ops.conv2d_fwd(tbuf, g.wd4(), None, 1, 0, out=acc, wplanes=g.wd_planes)
+            return ops.linear_h2(tbuf.f32.view(-1, C), g.lin_planes(False), None, out=acc.view(-1, C))
+        return self._dgrad(g, tbuf, acc)
 
     def _tconv_forward(self, op, x, y, epilogue=L.EPI_NONE):
         """y [B, sH, sW, Cout] <- (activation of) the transposed conv of x with the soft weights: stride-1 conv with the phase weight,
         then the pixel shuffle (LeakyReLU / ReLU commute with it)."""
-        ph = op.tc_phase
-        if ops.uses_bf16x6(tuple(x.shape), op.wp4, 1, ph.pad) and op.wp_planes is None:
-            op.wp_planes = torch.empty((3,) + tuple(op.wp4), device=self.dev, dtype=torch.int16)
-        ops.conv2d_fwd(x, op.wp, op.bias_p, 1, ph.pad, epilogue=epilogue, out=self.t["yp"], wplanes=op.wp_planes)
+        ph, x = op.tc_phase, _act_of(x)
+        if x.planes is not None:
+            if op.wp_h2 is None:
+                op.wp_h2 = ops.H2(torch.empty((2,) + tuple(op.wp4), device=self.dev, dtype=torch.int16), op.wscale)
+            ops.conv2d_fwd_h2(x.planes, x.shape, op.wp4, op.wp_h2, op.bias_p, 1, ph.pad, epilogue=epilogue, out=self.t["yp"])
+        else:
+            if ops.uses_bf16x6(x.shape, op.wp4, 1, ph.pad) and op.wp_planes is None:
+                op.wp_planes = torch.empty((3,) + tuple(op.wp4), device=self.dev, dtype=torch.int16)
+            ops.conv2d_fwd(x.f32, op.wp, op.bias_p, 1, ph.pad, epilogue=epilogue, out=self.t["yp"], wplanes=op.wp_planes)
         self._shuffle(self.t["yp"], ph.stride, y)
 
     def _tconv_wgrad(self, op, x, dy):
         """slabs of dL/d(kernel-layout weight) from dy [B, sH, sW, Cout]: unshuffle, weight gradient of the phase conv, fold"""
-        ph = op.tc_phase
-        self._unshuffle(dy, ph.stride, self.t["dyp"])
+        ph, dyp = op.tc_phase, self._act("dyp")
+        self._unshuffle(dy, ph.stride, dyp)
         if op.slabs is None:
             ns = ops.wgrad_nsplit(tuple(x.shape), op.wp4, 1, ph.pad)
             op.slabs_p = self._buf(ns, *op.wp4)
             op.slabs = self._buf(ns, *op.w4)
-        ops.conv2d_wgrad(x, self.t["dyp"], op.wp4, 1, ph.pad, slabs=op.slabs_p)
+        self._wgrad_into(op.slabs_p, x, dyp, op.wp4, 1, ph.pad)
         ops.tconv_fold(op.slabs_p, ph, op.rows, op.w4[3], out=op.slabs)
 
     def _after_step(self, lin_done=False):
@@ -574,10 +633,7 @@ class UnitEngine:
             ops.lp2_loss_grad(pred, self.co, self.idx, self.it, 1.0, grad, self.loss_log)
             self._rd_pred = pred
             self.g_task = torch.zeros_like(pred)
-            self._rec_ctx.__exit__(None, None, None)
-            self.plan_rd = Plan()
-            self._rec_ctx = self.plan_rd.record()
-            self._rec_ctx.__enter__()
+            self.plan_rd = self._next_plan()
             ops.add(grad, self.g_task, out=grad)
             return
         # rec_loss + task_loss on the same tensors (fp_out is the identity for these coders)
@@ -593,27 +649,41 @@ class UnitEngine:
         return self.task_p == 2.0 and self.fuse_tail
 
     def _shuffle(self, x, r, out):
-        if r == 2 and x.shape[-1] % 16 == 0:
-            return ops.pixel_shuffle_h2(x, out=out)
-        return ops.pixel_shuffle(x, r, out)
+        out = _act_of(out)
+        if out.planes is not None or (r == 2 and x.shape[-1] % 16 == 0):
+            return ops.pixel_shuffle_h2(x, out=out.f32, out_planes=out.planes)
+        return ops.pixel_shuffle(x, r, out.f32)
 
     def _unshuffle(self, x, r, out):
-        if r == 2 and x.shape[-1] % 4 == 0:
-            return ops.pixel_unshuffle2(x, out)
-        return ops.pixel_unshuffle(x, r, out)
+        x, out = _f32(x), _act_of(out)
+        if out.planes is not None or (r == 2 and x.shape[-1] % 4 == 0):
+            return ops.pixel_unshuffle2(x, out.f32, out_planes=out.planes)
+        return ops.pixel_unshuffle(x, r, out.f32)
 
     def _tail_act(self, pre, res, act, dpre, gout=None):
-        """out = act(pre) + res, rec + task loss against the cached FP output, dL/dout (if wanted) and dL/dpre in one pass."""
+        """out = act(pre) + res, rec + task loss against the cached FP output, dL/dout (if wanted) and dL/dpre in one pass.  A residual
+        that exists as planes only is summed back from them (exactly)."""
+        dpre = _act_of(dpre)
         self._task_is_rec = True
-        ops.loss_act_bwd(pre, res, self.co, self.idx, self.it, 2.0, act, self.loss_log, grad_out=gout, dpre=dpre)
+        ops.loss_act_bwd(_f32(pre), _f32(res), self.co, self.idx, self.it, 2.0, act, self.loss_log, grad_out=gout, dpre=dpre.f32, dpre_planes=dpre.planes,
+                         residual_planes=_planes_only(res))
 
     def _conv_tail(self, op, x, pre, res, act, dpre, gout=None):
-        """Last conv of a unit + its fused tail.  When the conv is split over K, its second pass (sum the partial slabs, add the
-        bias) moves into the tail's first load: one launch and one round trip of the pre-activation tensor less."""
-        if self._lin_conv_ok(op, x):                           # a 1 x 1 conv over a large pixel matrix: rdo_linear_h2, then the tail
+        """Last conv of a unit + its fused tail.  On planes with `pre` None (`_forms`): one launch, the pre-activation never reaches
+        memory.  On fp32, when the conv is split over K, its second pass (sum the partial slabs, add the bias) moves into the tail's
+        first load: one launch and one round trip of the pre-activation tensor less."""
+        x = _act_of(x)
+        if x.planes is not None and pre is None:
+            op.enable_planes(True, False, h2=True)
+            self._task_is_rec = True
+            ops.conv2d_fwd_h2_tail(x.planes, x.shape, op.w4, op.wq_planes, op.bias, op.stride, op.pad, res.planes, self.co, self.idx, self.it,
+                                   2.0, act, dpre.planes, self.loss_log)
+            return
+        if x.planes is not None or self._lin_conv_ok(op, x):   # (or a 1 x 1 conv over a large pixel matrix: rdo_linear_h2, then the tail)
             self._conv(op, x, pre)
             self._tail_act(pre, res, act, dpre, gout=gout)
             return
+        x, res = x.f32, _f32(res)
         if ops.uses_bf16x6(tuple(x.shape), op.w4, op.stride, op.pad):
             op.enable_planes(True, False)
         ks, _ = ops.conv_fwd_ksplit(tuple(x.shape), op.w4, op.stride, op.pad, op.wq_planes is not None, self.dev)
@@ -621,14 +691,15 @@ class UnitEngine:
             ws, ks = ops.conv2d_fwd_partials(x, op.wq4(), op.stride, op.pad, wplanes=op.wq_planes)
             self._task_is_rec = True
             ops.loss_act_bwd_splitk(ws, ks, op.bias, tuple(pre.shape), res, self.co, self.idx, self.it, 2.0, act, self.loss_log,
-                                    grad_out=gout, dpre=dpre)
+                                    grad_out=gout, dpre=_f32(dpre))
             return
         self._conv(op, x, pre)
         self._tail_act(pre, res, act, dpre, gout=gout)
 
     def _tail_gdn(self, x, norm, res, inverse, gout, tbuf):
+        tbuf = _act_of(tbuf)
         self._task_is_rec = True
-        ops.loss_gdn_bwd(x, norm, res, self.co, self.idx, self.it, 2.0, inverse, self.loss_log, gout, t=tbuf)
+        ops.loss_gdn_bwd(x, norm, _f32(res), self.co, self.idx, self.it, 2.0, inverse, self.loss_log, gout, t=tbuf.f32, t_planes=tbuf.planes)
 
     # ------------------------------------------------------------------------------------------------------------------ H2 path
     # FLOPs of the unit's last weight gradient from which the bucket all-reduce is split in two (see _build_ops): 43.5 GFLOP (~200 us)
@@ -642,12 +713,25 @@ class UnitEngine:
 
     OVF_PAIRS = 8
 
-    def _h2(self, name, like):
-        """Planes of activation buffer `name` (H2 form, scale from the probe iterations, its own overflow words)."""
-        if name not in self.P:
-            k = self._ovf_slot.setdefault(name, 1 + len(self._ovf_slot))
-            self.P[name] = ops.h2_empty(like.shape, self.dev, self.scales[name], flag=self._ovf[2 * k:2 * k + 2])
-        return self.P[name]
+    # the planes of dyp (dL/dpre of a phase-form transposed conv, unshuffled) go by the name of dpre: a permutation of the same values,
+    # so the magnitude probed on dpre gives their scale, and their overflow words are dpre's
+    PLANES_AS = {"dyp": "dpre"}
+
+    def _act(self, name):
+        """Activation buffer `name` of this unit in the form(s) `self.forms` gives it (None: not in memory).  Planes are made on first
+        use: scale from the probe iterations, their own overflow words (pairs handed out in that order)."""
+        buf = self.x_in if name == "x" else self.t[name]
+        form = self.forms.get(name, F32)
+        if form == ABSENT:
+            return None
+        planes = None
+        if form & PLANES:
+            pname = self.PLANES_AS.get(name, name)
+            if pname not in self.P:
+                k = self._ovf_slot.setdefault(pname, 1 + len(self._ovf_slot))
+                self.P[pname] = ops.h2_empty(buf.shape, self.dev, self.scales[pname], flag=self._ovf[2 * k:2 * k + 2])
+            planes = self.P[pname]
+        return Act(name, buf.shape, buf if form & F32 else None, planes)
 
     def _conv_ok_h2(self, op, x_shape, dgrad=False):
         if dgrad:
@@ -658,27 +742,6 @@ class UnitEngine:
             return False
         d = ops.conv_desc(tuple(x_shape), w4, stride, pad)
         return d.B * d.Ho * d.Wo * d.Cout >= self.H2_MIN_OUT
-
-    def _conv_h2(self, op, xp, x_shape, out=None, out_planes=None, epilogue=L.EPI_NONE, aux=None, residual=None, pre=None):
-        op.enable_planes(True, False, h2=True)
-        ops.conv2d_fwd_h2(xp, tuple(x_shape), op.w4, op.wq_planes, op.beta if op.is_gdn else op.bias, op.stride, op.pad,
-                          epilogue=epilogue, aux=aux, residual=residual, out=out, pre=pre, out_planes=out_planes)
-
-    def _dgrad_h2(self, op, dyp, dy_shape, out=None, out_planes=None, epilogue=L.EPI_NONE, aux=None, aux_planes=None):
-        op.enable_planes(False, True, h2=True)
-        ops.conv2d_fwd_h2(dyp, tuple(dy_shape), tuple(op.wd4().shape), op.wd_planes, None, 1, op.K - 1 - op.pad, epilogue=epilogue,
-                          aux=aux, aux_planes=aux_planes, out=out, out_planes=out_planes)
-
-    def _wgrad_h2(self, op, xp, x_shape, dyp):
-        if op.slabs is None:
-            self._slabs(op, x_shape)
-        ops.conv2d_wgrad_h2(xp, tuple(x_shape), dyp, op.w4, op.stride, op.pad, slabs=op.slabs)
-
-    def _gdn_backward_h2(self, g, dout, xin, norm, tp, acc, dxp):
-        """GDN / IGDN backward with t given as planes `tp` (written by the fused tail): acc = t . gamma' on the plane kernel, then
-        dx as planes only (its consumers are the plane-input weight gradient and dgrad)."""
-        self._dgrad_h2(g, tp, xin.shape, out=acc)
-        ops.gdn_bwd_dx_h2(dout, xin, norm, acc, g.inverse, dx_planes=dxp)
 
     def _plan_h2(self):
         """Which big convs of this unit run on H2 tensors (decided once, at record time)."""
@@ -712,122 +775,179 @@ class UnitEngine:
                 return k
         return None
 
-    def _fb_rb_h2(self):
-        o, t, x = self.ops, self.t, self.x_in
-        c1, c2 = o["conv1"], o["conv2"]
-        xp, h1p = self._h2("x", x), self._h2("h1", t["h1"])
-        dp2p, dh1p = self._h2("dpre2", t["h1"]), self._h2("dh1", t["h1"])
-        lean = self.h2_lean
-        # lean: x and h1 exist as planes only -- the residual add of the tail sums the three planes back (exactly), the LeakyReLU
-        # mask of the dgrad epilogue reads the sign off plane 0
-        self._gather(None if lean else x, xp)
-        self._conv_h2(c1, xp, x.shape, out=None if lean else t["h1"], out_planes=h1p, epilogue=L.EPI_LRELU)
-        self._task_is_rec = True
-        if self.fuse_h2_tail and ops.conv_h2_tail_supported(tuple(t["h1"].shape), c2.w4, c2.stride, c2.pad):
-            # conv2 + tail in one launch: the pre-activation never reaches memory
-            c2.enable_planes(True, False, h2=True)
-            ops.conv2d_fwd_h2_tail(h1p, tuple(t["h1"].shape), c2.w4, c2.wq_planes, c2.bias, c2.stride, c2.pad, xp, self.co, self.idx, self.it,
-                                   2.0, ops.ACT_LRELU, dp2p, self.loss_log)
-        else:
-            self._conv_h2(c2, h1p, t["h1"].shape, out=t["pre2"])
-            ops.loss_act_bwd(t["pre2"], None if lean else x, self.co, self.idx, self.it, 2.0, ops.ACT_LRELU, self.loss_log, dpre_planes=dp2p,
-                             residual_planes=xp if lean else None)
-        self._wgrad_h2(c2, h1p, t["h1"].shape, dp2p)
-        self._dgrad_h2(c2, dp2p, t["h1"].shape, out_planes=dh1p, epilogue=L.EPI_LRELU_BWD, aux=None if lean else t["h1"],
-                       aux_planes=h1p if lean else None)
-        self._split_point()
-        self._wgrad_h2(c1, xp, x.shape, dh1p)
-
-    def _fb_gdn_block_h2(self):
-        """RBWS / RBU whose second conv runs on H2 tensors: that conv, its weight gradient and dgrad; where the shapes qualify also the
-        gamma'^T GEMM of the GDN backward, the first conv of an RBWS with >= 16 input channels and the two sub-pixel convs of an RBU
-        (each with its weight gradient).  What does not qualify (thin stems, small 1x1 GEMMs) stays on fp32 activations."""
-        o, t, x = self.ops, self.t, self.x_in
-        rbu = self.kind == "rbu"
-        xs = tuple(x.shape)
-        if rbu:
-            sp, cv, g, up = o["subpel_conv"], o["conv"], o["igdn"], o["upsample"]
-            cname, dname = "c", "dc"
-            # the two 192 -> 768 sub-pixel convs and their weight gradients on planes as well when the shapes qualify
-            x_h2 = (x.shape[-1] % 16 == 0 and self._conv_ok_h2(sp, xs) and self._conv_ok_h2(up, xs)
-                    and ops.wgrad_h2_supported(xs, sp.w4, sp.stride, sp.pad) and ops.wgrad_h2_supported(xs, up.w4, up.stride, up.pad))
-        else:
-            c1, cv, g = o["conv1"], o["conv2"], o["gdn"]
-            cname, dname = "c2", "dc2"
-            x_h2 = x.shape[-1] % 16 == 0 and self._conv_ok_h2(c1, xs) and ops.wgrad_h2_supported(xs, c1.w4, c1.stride, c1.pad)
-        hs = tuple(t["h1"].shape)
+    def _forms(self, plan, widest=False):
+        """Which activation tensors of this unit exist as planes, as both, or not at all under the plan `_plan_h2` has chosen: name ->
+        form; every tensor that is not named is F32.  The one place that knows it: `_act` hands the bodies their tensors in these forms
+        and the helpers pick their kernels from them.  widest: with every optional part of the plan on planes -- the tensors
+        `_probe_scales` probes (a scale that is never used costs nothing)."""
+        o, t = self.ops, self.t
+        lean = PLANES if self.h2_lean else BOTH              # tensors whose only readers take planes are not also written as fp32
+        if plan == "layer":                                  # conv, tail and weight gradient on planes
+            return {"x": PLANES, "dpre": PLANES}
+        if plan == "tconv":                                  # the phase conv and its weight gradient on planes
+            return {"x": PLANES, "dyp": PLANES}
+        if plan == "rb":
+            # x and h1: the residual add of the tail sums the planes back (exactly), the LeakyReLU mask of the dgrad epilogue reads the
+            # sign off plane 0.  pre2 only where conv2 and the tail are not one launch
+            c2 = o["conv2"]
+            one = self.fuse_h2_tail and ops.conv_h2_tail_supported(tuple(t["h1"].shape), c2.w4, c2.stride, c2.pad)
+            return {"x": lean, "h1": lean, "pre2": ABSENT if one else F32, "dpre2": PLANES, "dh1": PLANES}
+        # "rbws" / "rbu": the second conv, its weight gradient and dgrad run on planes.  Where the shapes qualify (x_h2, g_h2), so do the
+        # convs that read the unit input -- the first conv of an RBWS with >= 16 input channels, the two sub-pixel convs of an RBU --,
+        # each with its weight gradient, and the gamma'^T GEMM of the GDN backward.  What does not qualify (thin stems, small 1x1 GEMMs)
+        # stays on fp32 activations.
+        rbu = plan == "rbu"
+        xs, hs = tuple(self.x_in.shape), tuple(t["h1"].shape)
+        first, g = ((o["subpel_conv"], o["upsample"]), o["igdn"]) if rbu else ((o["conv1"],), o["gdn"])
+        x_h2 = widest or (xs[-1] % 16 == 0 and all(self._conv_ok_h2(c, xs) and ops.wgrad_h2_supported(xs, c.w4, c.stride, c.pad) for c in first))
         # gamma'^T GEMM: on rdo_linear_h2 over the fp32 t where that applies (then t is not written as planes at all), else on the plane kernel
-        g_h2 = self._conv_ok_h2(g, hs, dgrad=True) and not self._gdn_lin_ok(g, t["h1"])
-        h1p, dcp = self._h2("h1", t["h1"]), self._h2(dname, t["h1"])
-        tp = self._h2("t", t["h1"]) if g_h2 else None
-        xp = self._h2("x", x) if x_h2 else None
-        self._gather(x, xp if x_h2 else None)
-        lean_h1 = self.h2_lean and (rbu or x_h2)          # h1 exists as planes only (its LeakyReLU mask is read off plane 0)
+        g_h2 = widest or (self._conv_ok_h2(g, hs, dgrad=True) and not self._gdn_lin_ok(g, t["h1"]))
+        # h1 (its LeakyReLU mask is read off plane 0): as fp32 too behind an fp32-input first conv, which splits it in a launch of its own
+        f = {"x": BOTH if x_h2 else F32, "h1": lean if (rbu or x_h2) else BOTH, "t": BOTH if g_h2 else F32, "dc" if rbu else "dc2": PLANES}
         if rbu:
-            r = self.r
-            if x_h2:
-                self._conv_h2(sp, xp, xs, out=t["sp"], epilogue=L.EPI_LRELU)
-                self._conv_h2(up, xp, xs, out=t["up"])
+            f.update(dup=PLANES if x_h2 else F32, dsp=PLANES if x_h2 else F32)
+        else:
+            f["dh1"] = PLANES if x_h2 else F32
+        return f
+
+    def _fb_layer(self):
+        op, t = self.ops["layer"], self.t
+        x, dpre = self._act("x"), self._act("dpre")
+        self._gather(x)
+        if op.is_gdn:
+            # a GDN / IGDN that is its own unit (sequential Minnen2018-style coders): only gamma is trained, no dx needed
+            x = x.f32
+            if self.fused:
+                self._gdn_pool(op, x, t["norm"])                                                 # norm pool only
+                self._tail_gdn(x, t["norm"], None, op.inverse, t["dy"], t["t"])
             else:
-                self._conv(sp, x, t["sp"], epilogue=L.EPI_LRELU)
-                self._conv(up, x, t["up"])
-            ops.pixel_shuffle_h2(t["sp"], out=None if lean_h1 else t["h1"], out_planes=h1p)
-            self._shuffle(t["up"], r, t["ups"])
+                self._conv(op, x, t["y"], epilogue=L.EPI_IGDN if op.inverse else L.EPI_GDN, aux=x, pre=t["norm"], square=True)
+                self._loss(t["y"], t["dy"])
+                ops.gdn_bwd_t(t["dy"], x, t["norm"], op.inverse, t["t"])
+            self._wgrad(op, x, t["t"], square=True)
+            return
+        if op.tconv is not None and op.tc_phase is None:
+            s_, q_, Hu, Wu = self.tc_geom
+            x = _act_of(ops.zero_insert(x.f32, s_, q_, q_, Hu, Wu, out=t["xu"]))
+        epi = op.qm.fused_epilogue() if self.include_act else None
+        if epi is None and self.include_act and type(op.qm.activation_function).__name__ != "StraightThrough":
+            raise NotImplementedError("calibration engine: only LeakyReLU(0.01) or ReLU may be fused into a layer unit")
+        act = {None: ops.ACT_NONE, L.EPI_LRELU: ops.ACT_LRELU, L.EPI_RELU: ops.ACT_RELU}[epi]
+        phase = op.tc_phase is not None                      # transposed conv without zero insertion
+        if self._unit1x1_ok(op, x):                          # a 1 x 1 conv: forward, tail and weight-gradient slabs in one launch
+            if op.slabs is None:
+                op.slabs = self._buf(ops.unit1x1_nslab(math.prod(x.shape[:-1]), op.w4[0]), *op.w4)
+            self._task_is_rec = True
+            ops.unit1x1(x.f32, op.wq4(), op.bias, self.co, self.idx, self.it, 2.0, act, self.loss_log, op.slabs)
+        elif self.fused and phase:
+            self._tconv_forward(op, x, t["y"])                                                   # pre-activation
+            self._tail_act(t["y"], None, act, t["dpre"])
+            self._tconv_wgrad(op, x, t["dpre"])
+        elif self.fused:
+            self._conv_tail(op, x, t["y"], None, act, dpre)                                      # t["y"]: pre-activation, if it is stored
+            self._wgrad(op, x, dpre)
+        else:
+            if phase:
+                self._tconv_forward(op, x, t["y"], epilogue=L.EPI_NONE if epi is None else epi)
+            else:
+                self._conv(op, x, t["y"], epilogue=L.EPI_NONE if epi is None else epi)
+            self._loss(t["y"], t["dy"])
+            g = t["dy"]
+            if epi is not None:
+                (ops.lrelu_bwd if epi == L.EPI_LRELU else ops.relu_bwd)(t["dy"], t["y"], t["dpre"])
+                g = t["dpre"]
+            (self._tconv_wgrad if phase else self._wgrad)(op, x, g)
+
+    def _fb_rb(self):
+        o, t = self.ops, self.t
+        c1, c2, skip = o["conv1"], o["conv2"], o.get("skip")
+        x, h1, dpre2, dh1 = self._act("x"), self._act("h1"), self._act("dpre2"), self._act("dh1")
+        self._gather(x)
+        self._conv(c1, x, h1, epilogue=L.EPI_LRELU)
+        res = x
+        if skip is not None:
+            self._conv(skip, x, t["sk"])
+            res = t["sk"]
+        if self.fused:
+            self._conv_tail(c2, h1, self._act("pre2"), res, ops.ACT_LRELU, dpre2, gout=t["dout"] if skip is not None else None)
+        else:
+            self._conv(c2, h1, t["out"], epilogue=L.EPI_LRELU, residual=res, pre=t["pre2"])
+            self._loss(t["out"], t["dout"])
+            ops.lrelu_bwd(t["dout"], t["pre2"], t["dpre2"])
+        if skip is not None:
+            self._wgrad(skip, x, t["dout"])
+        self._wgrad(c2, h1, dpre2)
+        self._dgrad(c2, dpre2, dh1, epilogue=L.EPI_LRELU_BWD, aux=h1)
+        self._split_point()
+        self._wgrad(c1, x, dh1)
+
+    def _fb_gdn_block(self):
+        """RBWS (conv1 -> LeakyReLU -> conv2 -> GDN, + the input or its skip conv) and RBU (sub-pixel conv -> LeakyReLU -> conv -> IGDN,
+        + the sub-pixel upsample conv of the input)."""
+        o, t = self.ops, self.t
+        rbu = self.kind == "rbu"
+        if rbu:
+            first, cv, g, side, r = o["subpel_conv"], o["conv"], o["igdn"], o["upsample"], self.r
+        else:
+            first, cv, g, side = o["conv1"], o["conv2"], o["gdn"], o.get("skip")
+        h1, dc, tt, x = self._act("h1"), self._act("dc" if rbu else "dc2"), self._act("t"), self._act("x")
+        c = t["c" if rbu else "c2"]
+        # the branch beside the two convs (skip conv / upsample conv) is recorded in front of the second conv on planes, behind it on fp32
+        # activations: the launches are independent and either order computes the same values; each form keeps the order its plans
+        # have always had, so that the op list of a unit stays comparable from one version of this file to the next
+        side_first = self.h2_plan is not None
+        self._gather(x)
+        if rbu:
+            self._conv(first, x, t["sp"], epilogue=L.EPI_LRELU)    # LeakyReLU commutes with the pixel shuffle
+            if side_first:
+                self._conv(side, x, t["up"])
+            self._shuffle(t["sp"], r, h1)
+            if side_first:
+                self._shuffle(t["up"], r, t["ups"])
+            self._conv(cv, h1, c)
+            if not side_first:
+                self._conv(side, x, t["up"])
+                self._shuffle(t["up"], r, t["ups"])
             res = t["ups"]
         else:
-            if x_h2:
-                self._conv_h2(c1, xp, xs, out=None if lean_h1 else t["h1"], out_planes=h1p, epilogue=L.EPI_LRELU)
-            else:
-                self._conv(c1, x, t["h1"], epilogue=L.EPI_LRELU)
-                ops.split_h2(t["h1"], h1p)
-            res = x
-            if "skip" in o:
-                self._conv(o["skip"], x, t["sk"])
-                res = t["sk"]
-        self._conv_h2(cv, h1p, hs, out=t[cname])
-        self._gdn_pool(g, t[cname], t["norm"])
-        self._task_is_rec = True
-        ops.loss_gdn_bwd(t[cname], t["norm"], res, self.co, self.idx, self.it, 2.0, rbu, self.loss_log, t["dout"], t=t["t"], t_planes=tp)
+            self._conv(first, x, h1, epilogue=L.EPI_LRELU)         # (fp32 input: the planes of h1 by a split of their own)
+            if side is not None and side_first:
+                self._conv(side, x.f32, t["sk"])
+            self._conv(cv, h1, c)
+            if side is not None and not side_first:
+                self._conv(side, x.f32, t["sk"])
+            res = x if side is None else t["sk"]
+        if self.fused:
+            self._gdn_pool(g, c, t["norm"])
+            self._tail_gdn(c, t["norm"], res, rbu, t["dout"], tt)
+        else:
+            self._conv(g, c, t["out"], epilogue=L.EPI_IGDN if rbu else L.EPI_GDN, aux=c, residual=res, pre=t["norm"], square=True)
+            self._loss(t["out"], t["dout"])
         if rbu:
-            if x_h2:
-                dupp = self._h2("dup", t["dup"])
-                ops.pixel_unshuffle2(t["dout"], out_planes=dupp)
-                self._wgrad_h2(up, xp, xs, dupp)
-            else:
-                self._unshuffle(t["dout"], r, t["dup"])
-                self._wgrad(up, x, t["dup"])
-        elif "skip" in o:
-            self._wgrad(o["skip"], x, t["dout"])
-        if g_h2:
-            self._gdn_backward_h2(g, t["dout"], t[cname], t["norm"], tp, t["acc"], dcp)
-        else:                                             # gamma'^T GEMM on the fp32 t, dx still as planes only
-            self._gdn_acc(g, t["t"], t["acc"])
-            ops.gdn_bwd_dx_h2(t["dout"], t[cname], t["norm"], t["acc"], g.inverse, dx_planes=dcp)
-        self._wgrad(g, t[cname], t["t"], square=True)
-        self._wgrad_h2(cv, h1p, hs, dcp)
-        rbws_h2 = x_h2 and not rbu
-        dh1p = self._h2("dh1", t["h1"]) if rbws_h2 else None
-        self._dgrad_h2(cv, dcp, hs, out=None if rbws_h2 else t["dh1"], out_planes=dh1p, epilogue=L.EPI_LRELU_BWD,
-                       aux=None if lean_h1 else t["h1"], aux_planes=h1p if lean_h1 else None)
+            dup = self._act("dup")
+            self._unshuffle(t["dout"], r, dup)
+            self._wgrad(side, x, dup)
+        elif side is not None:
+            self._wgrad(side, x.f32, t["dout"])
+        if not self.fused:                                            # the fused tail has already written t
+            ops.gdn_bwd_t(t["dout"], c, t["norm"], rbu, tt.f32)
+        self._gdn_acc(g, tt, t["acc"])                                # t . gamma'
+        if dc.planes is not None or c.numel() % 4 == 0:
+            ops.gdn_bwd_dx_h2(t["dout"], c, t["norm"], t["acc"], rbu, dx=dc.f32, dx_planes=dc.planes)   # 16-byte accesses
+        else:
+            ops.gdn_bwd_dx(t["dout"], c, t["norm"], t["acc"], rbu, dc.f32)
+        self._wgrad(g, c, tt.f32, square=True)                        # dgamma'[k][i] = sum_m t_k x_i^2
+        self._wgrad(cv, h1, dc)
+        dh1 = self._act("dh1")
+        self._dgrad(cv, dc, dh1, epilogue=L.EPI_LRELU_BWD, aux=h1)
         if rbu:
-            if x_h2:
-                dspp = self._h2("dsp", t["dsp"])
-                ops.pixel_unshuffle2(t["dh1"], out_planes=dspp)
-                self._split_point()
-                self._wgrad_h2(sp, xp, xs, dspp)
-            else:
-                self._unshuffle(t["dh1"], r, t["dsp"])
-                self._split_point()
-                self._wgrad(sp, x, t["dsp"])
+            dsp = self._act("dsp")
+            self._unshuffle(dh1, r, dsp)
+            self._split_point()
+            self._wgrad(first, x, dsp)
         else:
             self._split_point()
-            if x_h2:
-                self._wgrad_h2(c1, xp, xs, dh1p)
-            else:
-                self._wgrad(c1, x, t["dh1"])
-
-    # activation buffers a plan may keep as planes (all probed: a scale that is never used costs nothing)
-    H2_PROBED = {"tconv": ("x", "dpre"), "layer": ("x", "dpre"), "rb": ("x", "h1", "dpre2", "dh1"), "rbws": ("x", "h1", "t", "dc2", "dh1"), "rbu": ("x", "h1", "t", "dc", "dup", "dsp")}
+            self._wgrad(first, x, dh1)
 
     def _probe_amax(self, names):
         """One eager iteration of the unit on fp32 activations and the plain fp32 kernels (no planes, no AdaRound step) at the CURRENT
@@ -860,7 +980,7 @@ class UnitEngine:
         plan = self._plan_h2()
         if plan is None:
             return
-        names = self.H2_PROBED[plan]
+        names = [self.PLANES_AS.get(n, n) for n, f in self._forms(plan, widest=True).items() if f & PLANES]
         amax = self._probe_amax(names)
         self._set_weights(soft=False)
         try:
@@ -981,160 +1101,10 @@ class UnitEngine:
         self._check_overflow()
 
     def _forward_backward(self):
-        o, t, x = self.ops, self.t, self.x_in
+        """Record (or, probing, run on fp32 activations: no plan, every tensor F32) one iteration's forward and backward pass."""
         self.h2_plan = None if self._probing else self._plan_h2()
-        if self.h2_plan == "rb":
-            return self._fb_rb_h2()
-        if self.h2_plan in ("rbws", "rbu"):
-            return self._fb_gdn_block_h2()
-        if self.h2_plan not in ("tconv", "layer"):            # (those plans gather straight into planes)
-            self._gather(x)
-        if self.kind == "layer" and o["layer"].is_gdn:
-            # a GDN / IGDN that is its own unit (sequential Minnen2018-style coders): only gamma is trained, no dx needed
-            op = o["layer"]
-            if self.fused:
-                self._gdn_pool(op, x, t["norm"])                                                 # norm pool only
-                self._tail_gdn(x, t["norm"], None, op.inverse, t["dy"], t["t"])
-            else:
-                self._conv(op, x, t["y"], epilogue=L.EPI_IGDN if op.inverse else L.EPI_GDN, aux=x, pre=t["norm"], square=True)
-                self._loss(t["y"], t["dy"])
-                ops.gdn_bwd_t(t["dy"], x, t["norm"], op.inverse, t["t"])
-            self._wgrad(op, x, t["t"], square=True)
-        elif self.kind == "layer":
-            op = o["layer"]
-            if op.tconv is not None and op.tc_phase is None:
-                s_, q_, Hu, Wu = self.tc_geom
-                x = ops.zero_insert(x, s_, q_, q_, Hu, Wu, out=t["xu"])
-            epi = op.qm.fused_epilogue() if self.include_act else None
-            if epi is None and self.include_act and type(op.qm.activation_function).__name__ != "StraightThrough":
-                raise NotImplementedError("calibration engine: only LeakyReLU(0.01) or ReLU may be fused into a layer unit")
-            act = {None: ops.ACT_NONE, L.EPI_LRELU: ops.ACT_LRELU, L.EPI_RELU: ops.ACT_RELU}[epi]
-            if self.h2_plan == "layer":                      # conv, tail and weight gradient on H2 tensors (x and dL/dpre exist as planes only)
-                xs = tuple(x.shape)
-                xp, dpp = self._h2("x", x), self._h2("dpre", t["dpre"])
-                self._gather(None, xp)
-                self._conv_h2(op, xp, xs, out=t["y"])                                               # pre-activation
-                self._task_is_rec = True
-                ops.loss_act_bwd(t["y"], None, self.co, self.idx, self.it, 2.0, act, self.loss_log, dpre_planes=dpp)
-                self._wgrad_h2(op, xp, xs, dpp)
-            elif self.h2_plan == "tconv":                    # ... with the phase conv and its weight gradient on H2 tensors
-                ph, xs = op.tc_phase, tuple(x.shape)
-                xp, dypp = self._h2("x", x), self._h2("dpre", t["dyp"])
-                if op.wp_h2 is None:
-                    op.wp_h2 = ops.H2(torch.empty((2,) + tuple(op.wp4), device=self.dev, dtype=torch.int16), op.wscale)
-                self._gather(None, xp)
-                ops.conv2d_fwd_h2(xp, xs, op.wp4, op.wp_h2, op.bias_p, 1, ph.pad, out=t["yp"])
-                self._shuffle(t["yp"], 2, t["y"])
-                self._tail_act(t["y"], None, act, t["dpre"])
-                ops.pixel_unshuffle2(t["dpre"], out_planes=dypp)
-                if op.slabs is None:
-                    ns = ops.wgrad_nsplit(xs, op.wp4, 1, ph.pad)
-                    op.slabs_p = self._buf(ns, *op.wp4)
-                    op.slabs = self._buf(ns, *op.w4)
-                ops.conv2d_wgrad_h2(xp, xs, dypp, op.wp4, 1, ph.pad, slabs=op.slabs_p)
-                ops.tconv_fold(op.slabs_p, ph, op.rows, op.w4[3], out=op.slabs)
-            elif op.tc_phase is not None:                    # transposed conv without zero insertion
-                if self.fused:
-                    self._tconv_forward(op, x, t["y"])                                             # pre-activation
-                    self._tail_act(t["y"], None, act, t["dpre"])
-                    self._tconv_wgrad(op, x, t["dpre"])
-                else:
-                    self._tconv_forward(op, x, t["y"], epilogue=L.EPI_NONE if epi is None else epi)
-                    self._loss(t["y"], t["dy"])
-                    g = t["dy"]
-                    if epi is not None:
-                        (ops.lrelu_bwd if epi == L.EPI_LRELU else ops.relu_bwd)(t["dy"], t["y"], t["dpre"])
-                        g = t["dpre"]
-                    self._tconv_wgrad(op, x, g)
-            elif self._unit1x1_ok(op, x):                    # a 1 x 1 conv: forward, tail and weight-gradient slabs in one launch
-                if op.slabs is None:
-                    op.slabs = self._buf(ops.unit1x1_nslab(x.numel() // x.shape[-1], op.w4[0]), *op.w4)
-                self._task_is_rec = True
-                ops.unit1x1(x, op.wq4(), op.bias, self.co, self.idx, self.it, 2.0, act, self.loss_log, op.slabs)
-            elif self.fused:
-                self._conv_tail(op, x, t["y"], None, act, t["dpre"])                              # t["y"]: pre-activation, if it is stored
-                self._wgrad(op, x, t["dpre"])
-            elif epi is not None:
-                self._conv(op, x, t["y"], epilogue=epi)
-                self._loss(t["y"], t["dy"])
-                (ops.lrelu_bwd if epi == L.EPI_LRELU else ops.relu_bwd)(t["dy"], t["y"], t["dpre"])
-                self._wgrad(op, x, t["dpre"])
-            else:
-                self._conv(op, x, t["y"])
-                self._loss(t["y"], t["dy"])
-                self._wgrad(op, x, t["dy"])
-        elif self.kind == "rb":
-            c1, c2 = o["conv1"], o["conv2"]
-            self._conv(c1, x, t["h1"], epilogue=L.EPI_LRELU)
-            res = x
-            if "skip" in o:
-                self._conv(o["skip"], x, t["sk"])
-                res = t["sk"]
-            if self.fused:
-                self._conv_tail(c2, t["h1"], t["pre2"], res, ops.ACT_LRELU, t["dpre2"], gout=t["dout"] if "skip" in o else None)
-            else:
-                self._conv(c2, t["h1"], t["out"], epilogue=L.EPI_LRELU, residual=res, pre=t["pre2"])
-                self._loss(t["out"], t["dout"])
-                ops.lrelu_bwd(t["dout"], t["pre2"], t["dpre2"])
-            if "skip" in o:
-                self._wgrad(o["skip"], x, t["dout"])
-            self._wgrad(c2, t["h1"], t["dpre2"])
-            self._dgrad(c2, t["dpre2"], t["dh1"], epilogue=L.EPI_LRELU_BWD, aux=t["h1"])
-            self._split_point()
-            self._wgrad(c1, x, t["dh1"])
-        elif self.kind == "rbws":
-            c1, c2, g = o["conv1"], o["conv2"], o["gdn"]
-            self._conv(c1, x, t["h1"], epilogue=L.EPI_LRELU)
-            self._conv(c2, t["h1"], t["c2"])
-            res = x
-            if "skip" in o:
-                self._conv(o["skip"], x, t["sk"])
-                res = t["sk"]
-            if self.fused:
-                self._gdn_pool(g, t["c2"], t["norm"])
-                self._tail_gdn(t["c2"], t["norm"], res, False, t["dout"], t["t"])
-            else:
-                self._conv(g, t["c2"], t["out"], epilogue=L.EPI_GDN, aux=t["c2"], residual=res, pre=t["norm"], square=True)
-                self._loss(t["out"], t["dout"])
-            if "skip" in o:
-                self._wgrad(o["skip"], x, t["dout"])
-            self._gdn_backward(g, t["dout"], t["c2"], t["norm"], t["t"], t["acc"], t["dc2"], inverse=False)
-            self._wgrad(c2, t["h1"], t["dc2"])
-            self._dgrad(c2, t["dc2"], t["dh1"], epilogue=L.EPI_LRELU_BWD, aux=t["h1"])
-            self._split_point()
-            self._wgrad(c1, x, t["dh1"])
-        elif self.kind == "rbu":
-            sp, cv, g, up = o["subpel_conv"], o["conv"], o["igdn"], o["upsample"]
-            r = self.r
-            self._conv(sp, x, t["sp"], epilogue=L.EPI_LRELU)       # LeakyReLU commutes with the pixel shuffle
-            self._shuffle(t["sp"], r, t["h1"])
-            self._conv(cv, t["h1"], t["c"])
-            self._conv(up, x, t["up"])
-            self._shuffle(t["up"], r, t["ups"])
-            if self.fused:
-                self._gdn_pool(g, t["c"], t["norm"])
-                self._tail_gdn(t["c"], t["norm"], t["ups"], True, t["dout"], t["t"])
-            else:
-                self._conv(g, t["c"], t["out"], epilogue=L.EPI_IGDN, aux=t["c"], residual=t["ups"], pre=t["norm"], square=True)
-                self._loss(t["out"], t["dout"])
-            self._unshuffle(t["dout"], r, t["dup"])
-            self._wgrad(up, x, t["dup"])
-            self._gdn_backward(g, t["dout"], t["c"], t["norm"], t["t"], t["acc"], t["dc"], inverse=True)
-            self._wgrad(cv, t["h1"], t["dc"])
-            self._dgrad(cv, t["dc"], t["dh1"], epilogue=L.EPI_LRELU_BWD, aux=t["h1"])
-            self._unshuffle(t["dh1"], r, t["dsp"])
-            self._split_point()
-            self._wgrad(sp, x, t["dsp"])
-
-    def _gdn_backward(self, g, dout, xin, norm, tbuf, acc, dx, inverse):
-        if not self.fused:                                           # the fused tail has already written t
-            ops.gdn_bwd_t(dout, xin, norm, inverse, tbuf)
-        self._gdn_acc(g, tbuf, acc)                                   # t . gamma'
-        if xin.numel() % 4 == 0:
-            ops.gdn_bwd_dx_h2(dout, xin, norm, acc, inverse, dx=dx)   # 16-byte accesses
-        else:
-            ops.gdn_bwd_dx(dout, xin, norm, acc, inverse, dx)
-        self._wgrad(g, xin, tbuf, square=True)                        # dgamma'[k][i] = sum_m t_k x_i^2
+        self.forms = {} if self.h2_plan is None else self._forms(self.h2_plan)
+        {"layer": self._fb_layer, "rb": self._fb_rb, "rbws": self._fb_gdn_block, "rbu": self._fb_gdn_block}[self.kind]()
 
     def _items(self, opl):
         # (lin_fwd / lin_bwd: the fragment-ordered planes of a Linear / GDN gamma on rdo_linear_h2 -- written by the step's own launch)
@@ -1157,14 +1127,12 @@ class UnitEngine:
             last = i + self.STEP_BATCH >= len(opl)
             if self._folded:
                 # every launch of the step reads the published word; the LAST one carries the next mini-batch and moves the real counter
-                ops.adaround_step_batch(self._items(opl[i:i + self.STEP_BATCH]), scale, self.weight, self.sched, self.it_shadow, self.round_log, mode=mode,
-                                        iter_shadow=self.it if last else None, gather=self._next_gather if last else None)
+                it, kw = self.it_shadow, dict(iter_shadow=self.it if last else None, gather=self._next_gather if last else None)
             elif self._handover:
-                ops.adaround_step_batch(self._items(opl[i:i + self.STEP_BATCH]), scale, self.weight, self.sched, self.it, self.round_log, mode=mode,
-                                        iter_shadow=self.it_shadow if i == 0 else None)
+                it, kw = self.it, dict(iter_shadow=self.it_shadow if i == 0 else None)
             else:
-                ops.adaround_step_batch(self._items(opl[i:i + self.STEP_BATCH]), scale, self.weight, self.sched, self.it, self.round_log, mode=mode,
-                                        advance_iter=self.it if last else None)
+                it, kw = self.it, dict(advance_iter=self.it if last else None)
+            ops.adaround_step_batch(self._items(opl[i:i + self.STEP_BATCH]), scale, self.weight, self.sched, it, self.round_log, mode=mode, **kw)
 
     @property
     def _handover(self):
@@ -1184,32 +1152,31 @@ class UnitEngine:
     def _it_pub(self):
         return self.it if (self._handover and not self._folded) else None
 
-    def _gather(self, x, xp=None):
-        """The unit's mini-batch for the current iteration: x_q / x_fp rows mixed by the QDrop mask into `x` (fp32, may be None with
-        planes) and / or the planes `xp`.  Recorded as the iteration's first kernel -- or, folded, handed to the step launch of the
-        PREVIOUS iteration (`_step_batches`) with `_prime` covering iteration 0."""
+    def _gather(self, x):
+        """The unit's mini-batch for the current iteration: x_q / x_fp rows mixed by the QDrop mask into `x`, as fp32 and / or planes.
+        Recorded as the iteration's first kernel -- or, folded, handed to the step launch of the PREVIOUS iteration (`_step_batches`)
+        with `_prime` covering iteration 0."""
+        x = _act_of(x)
+        g = dict(cache_q=self.cq, cache_fp=self.cf, idx_table=self.idx, B=self.B, batch_offset=self.batch_offset,
+                 prob=self.input_prob, seed=self.seed, out=x.f32, out_planes=x.planes)
         if self._folded and not self._probing:
-            self._next_gather = dict(cache_q=self.cq, cache_fp=self.cf, idx_table=self.idx, B=self.B, batch_offset=self.batch_offset,
-                                     prob=self.input_prob, seed=self.seed, out=x, out_planes=xp)
-            return
-        if xp is not None:
-            ops.gather_qdrop_h2(self.cq, self.cf, self.idx, self._it_src(), self.B, self.input_prob, self.seed, x, xp, self.batch_offset,
-                                iter_publish=self._it_pub())
+            self._next_gather = g
         else:
-            ops.gather_qdrop(self.cq, self.cf, self.idx, self._it_src(), self.B, self.input_prob, self.seed, x, self.batch_offset,
-                             iter_publish=self._it_pub())
+            self._gather_now(g, self._it_src(), self._it_pub())
+
+    def _gather_now(self, g, it, publish=None):
+        if g["out_planes"] is not None:
+            ops.gather_qdrop_h2(self.cq, self.cf, self.idx, it, self.B, self.input_prob, self.seed, g["out"], g["out_planes"], self.batch_offset,
+                                iter_publish=publish)
+        else:
+            ops.gather_qdrop(self.cq, self.cf, self.idx, it, self.B, self.input_prob, self.seed, g["out"], self.batch_offset, iter_publish=publish)
 
     def _prime(self):
         """Folded gather: the mini-batch of the iteration the counter stands at, assembled eagerly (before the first iteration of a
         run and after a restart; every later one comes from the previous iteration's step launch)."""
-        g = self._next_gather
-        if g is None:
-            return
-        self.it_shadow.copy_(self.it)
-        if g["out_planes"] is not None:
-            ops.gather_qdrop_h2(self.cq, self.cf, self.idx, self.it, self.B, self.input_prob, self.seed, g["out"], g["out_planes"], self.batch_offset)
-        else:
-            ops.gather_qdrop(self.cq, self.cf, self.idx, self.it, self.B, self.input_prob, self.seed, g["out"], self.batch_offset)
+        if self._next_gather is not None:
+            self.it_shadow.copy_(self.it)
+            self._gather_now(self._next_gather, self.it)
 
     def _grad_ops(self, names):
         opl = [self.ops[n] for n in names]
@@ -1220,19 +1187,30 @@ class UnitEngine:
         for op in opl:
             ops.adaround_grad(op.desc, op.w, op.alpha, op.delta, op.zp, op.slabs, op.dalpha)
 
-    def _step_ops(self):
+    def _step_ops(self, apply=False):
         """AdaRound step of every op of the unit + iteration counter: one batched launch (+ one for the dgrad layouts) when the
-        tensors allow it, else one launch per op.  The bf16 planes of the new weights are written by the same launches."""
+        tensors allow it, else one launch per op.  The bf16 planes of the new weights are written by the same launches.
+        apply (data parallel, plan B): the step from the all-reduced gradient bucket instead of from the weight-gradient slabs."""
         opl = list(self.ops.values())
+        scale = self.bucket.scale if apply else 1.0
         if self._batchable(opl):
-            self._step_batches(opl, 1.0, 0)
+            self._step_batches(opl, scale, 2 if apply else 0)
             self._after_step(lin_done=True)
             return
         for op in opl:
-            ops.adaround_step(op.desc, op.w, op.delta, op.zp, op.slabs, 1.0, self.weight, self.sched, self.it,
-                              op.alpha, op.m, op.v, op.wq, op.wd, self.round_log, op.wq_planes, op.wd_planes)
+            (ops.adaround_apply if apply else ops.adaround_step)(
+                op.desc, op.w, op.delta, op.zp, op.dalpha if apply else op.slabs, scale, self.weight, self.sched, self.it,
+                op.alpha, op.m, op.v, op.wq, op.wd, self.round_log, op.wq_planes, op.wd_planes)
         ops.iter_advance(self.it)
         self._after_step()
+
+    def _next_plan(self):
+        """close the plan being recorded and go on recording into a new one"""
+        self._rec_ctx.__exit__(None, None, None)
+        plan = Plan()
+        self._rec_ctx = plan.record()
+        self._rec_ctx.__enter__()
+        return plan
 
     def _split_point(self):
         """Called by the backward pass right before its last weight-gradient kernel.  Data-parallel recording only: the gradients
@@ -1241,10 +1219,7 @@ class UnitEngine:
         if self._probing or self._late is None or self.plan_a2 is not None:
             return
         self._grad_ops([n for n in self.ops if n != self._late])
-        self._rec_ctx.__exit__(None, None, None)
-        self.plan_a2 = Plan()
-        self._rec_ctx = self.plan_a2.record()
-        self._rec_ctx.__enter__()
+        self.plan_a2 = self._next_plan()
 
     def _record(self):
         self.plan_a = Plan()
@@ -1271,16 +1246,7 @@ class UnitEngine:
         if self.split:
             self.plan_b = Plan()
             with self.plan_b.record():
-                opl = list(self.ops.values())
-                if self._batchable(opl):
-                    self._step_batches(opl, self.bucket.scale, 2)
-                    self._after_step(lin_done=True)
-                else:
-                    for op in opl:
-                        ops.adaround_apply(op.desc, op.w, op.delta, op.zp, op.dalpha, self.bucket.scale, self.weight, self.sched,
-                                           self.it, op.alpha, op.m, op.v, op.wq, op.wd, self.round_log, op.wq_planes, op.wd_planes)
-                    ops.iter_advance(self.it)
-                    self._after_step()
+                self._step_ops(apply=True)
 
     # ------------------------------------------------------------------------------------------------------------------
     def run(self, n_iters=None, idle=None):
