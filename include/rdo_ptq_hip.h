@@ -245,6 +245,25 @@ int rdo_uaq_init_minmax(const float* w, int32_t rows, int64_t inner, int32_t n_l
 int rdo_actquant_perchannel(const float* x, int64_t npix, int32_t C, int32_t n_bits, float* out,
                             float* ws_minmax /* rdo_actquant_workspace(C) floats of scratch, no initial state needed */, void* stream);
 int64_t rdo_actquant_workspace(int32_t C);   /* floats: the 2 C results + the per-workgroup partial minima / maxima */
+/* Static per-channel activation quant-dequant (extension: the reference only has the dynamic form above; the paper it implements fixes
+ * the activation grids from the calibration set).  range = lo[C] | hi[C], frozen; r = max(hi_c - lo_c, 1e-6),
+ * out = round(clamp((x - lo_c)/r, 0, 1) * (2^n_bits - 1)) / (2^n_bits - 1) * r + lo_c -- the expression of rdo_actquant_perchannel with the
+ * tensor's own min / max replaced by the frozen pair (bit-identical to it when range holds exactly that min / max) and the lower clamp
+ * at 0.  One launch, one read and one write of the tensor, no workspace; out == x allowed; a pixel's result does not depend on the
+ * other pixels of the call. */
+int rdo_actquant_static(const float* x, int64_t npix, int32_t C, int32_t n_bits, const float* range /* [2 C] */, float* out,
+                        void* stream);
+/* Observation (extension): folds the min | max that rdo_actquant_perchannel left in the first 2 C floats of its workspace into a running
+ * range: lo = min(lo, min_b), hi = max(hi, max_b).  The caller initialises range to +inf | -inf.  C-sized: the tensor is not read. */
+int rdo_actquant_observe(const float* ws_minmax, int32_t C, float* range /* [2 C], updated */, void* stream);
+/* Range search (extension; the ten candidates of UniformAffineQuantizer._init_search, quantizer.py:260-265, on the activation grid):
+ * err[c][k] += sum over pixels of (x - Q_k(x))^2, k = 0..9, Q_k the static expression with lo_c * s_k | hi_c * s_k, s_k = (float)(1 - 0.05 k).
+ * One read of x; per-workgroup partial sums in ws, folded in a fixed order (no atomics: the same input gives the same bits); no serial
+ * fp32 chain longer than 1024 terms.  err is ACCUMULATED INTO (zero it before the first batch). */
+int rdo_actquant_search(const float* x, int64_t npix, int32_t C, int32_t n_bits, const float* range /* [2 C] */,
+                        float* err /* [C][10] */, float* ws /* rdo_actquant_search_workspace(C) floats, no initial state needed */,
+                        void* stream);
+int64_t rdo_actquant_search_workspace(int32_t C);
 
 /* ---- K7: mini-batch assembly: out[b] = keep ? cache_q[idx[b]] : cache_fp[idx[b]], keep ~ counter RNG(seed, iter, i)
  * replaces cached_inps[..][idx] + torch.where(torch.rand_like(x) < p, x_q, x_fp)                layer_opt.py:289-292
@@ -376,6 +395,13 @@ int rdo_gaussian_likelihood_bwd(const float* yhat, const float* scales, const fl
 int rdo_neg_log2_sum(const float* lik, int64_t n, float scale, float* out /* += */, void* stream);   /* bpp numerator */
 int rdo_sq_diff_sum(const float* a, const float* b, int64_t n, float scale, int32_t clamp01_a, float* out /* += */,
                     void* stream);                                                                    /* MSE numerator */
+/* The same two sums in a fixed order (no atomics: the two above add their per-workgroup sums to out[0] in the order the workgroups
+ * happen to finish, so the last bits change from run to run): per-workgroup sums in ws, folded by one workgroup.  For evaluation, where
+ * a saved model must give the same PSNR / bpp on every run.  ws: rdo_ordered_sum_workspace() floats, no initial state needed. */
+int rdo_neg_log2_sum_ordered(const float* lik, int64_t n, float scale, float* out /* += */, float* ws, void* stream);
+int rdo_sq_diff_sum_ordered(const float* a, const float* b, int64_t n, float scale, int32_t clamp01_a, float* out /* += */, float* ws,
+                            void* stream);
+int64_t rdo_ordered_sum_workspace(void);
 
 /* ---- "H2" tensors and fused unit tails -------------------------------------------------------------------------------------------
  * An H2 tensor is an fp32 NHWC activation [M pixels][C channels] (C % 16 == 0) stored as the exact two-way fp16 split of its

@@ -327,7 +327,17 @@ __global__ __launch_bounds__(256) void aq_fold_kernel(const float* part, int nbl
     if (live && j == 0) ws[i] = r;
 }
 
-template <int W>
+// one element on the per-channel grid [zp, zp + rng] with bit_range steps; `lowest` is the lower clamp of the normalised value: -1 in the
+// dynamic quantiser (the reference's clamp; x - min is never negative there), 0 with a frozen range (x may lie below it).  The dynamic
+// and the static quantiser and the range search all evaluate THIS expression: same numbers in, same bits out.
+__device__ __forceinline__ float aq_quant(float x, float zp, float rng, float bit_range, float lowest) {
+    const float xn = x - zp;
+    const float q = rintf(fminf(fmaxf(xn / rng, lowest), 1.f) * bit_range);
+    return (q / bit_range) * rng + zp;
+}
+
+// STATIC = false: ws = this tensor's own min | max (aq_fold_kernel); true: ws = a frozen lo | hi pair (rdo_actquant_static)
+template <int W, bool STATIC = false>
 __global__ __launch_bounds__(256) void aq_apply_kernel(const float* x, long nvec, int C, const float* ws, float bit_range, float* out) {
     typedef float vec_t __attribute__((ext_vector_type(W)));
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += (long)gridDim.x * blockDim.x) {
@@ -338,12 +348,102 @@ __global__ __launch_bounds__(256) void aq_apply_kernel(const float* x, long nvec
         for (int k = 0; k < W; ++k) {
             const float zp = ws[c + k];
             const float rng = fmaxf(ws[C + c + k] - zp, 1e-6f);
-            const float xn = xv[k] - zp;
-            const float q = rintf(fminf(fmaxf(xn / rng, -1.f), 1.f) * bit_range);
-            o[k] = (q / bit_range) * rng + zp;
+            o[k] = aq_quant(xv[k], zp, rng, bit_range, STATIC ? 0.f : -1.f);
         }
         *reinterpret_cast<vec_t*>(out + i * W) = o;
     }
+}
+
+// observation: fold this batch's min | max (the first 2 C floats the dynamic call leaves in its workspace) into a running lo | hi
+__global__ __launch_bounds__(256) void aq_merge_kernel(const float* ws, int C, float* range) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < 2 * C) range[i] = i < C ? fminf(range[i], ws[i]) : fmaxf(range[i], ws[i]);
+}
+
+// ---- range search: err[c][k] = sum over pixels of (x - Q_k(x))^2 for the ten shrunk ranges lo * s_k | hi * s_k, s_k = 1 - 0.05 k
+// (the candidates of UniformAffineQuantizer._init_search, quantizer.py:260-265 of the reference, on the activation grid).  Same
+// thread map as aq_partial_kernel: thread = (pixel lane, group of W channels), one read of x, W x 10 accumulators in registers.
+// Every serial fp32 chain stays at or below 1024 terms: a thread closes its running sums into a second set every kAqsChain pixels, the
+// LDS fold adds at most 256 pixel lanes, the second kernel at most kAqBlocks / 16 rows per lane and a four-step tree.
+constexpr int kAqsCand = 10;
+constexpr int kAqsChain = 1024;
+
+template <int W>
+__global__ __launch_bounds__(256) void aqs_partial_kernel(const float* x, long npix, int C, const float* range, float bit_range, float* part) {
+    typedef float vec_t __attribute__((ext_vector_type(W)));
+    const int QN = C / W;
+    const int qpb = QN < 256 ? QN : 256;
+    const int PL = 256 / qpb;
+    const int pl = threadIdx.x / qpb, ql = threadIdx.x - pl * qpb;
+    __shared__ float sm[W * kAqsCand * 256];               // [channel of the group][candidate][thread]: conflict-free both ways
+    const long step = (long)gridDim.x * PL;
+    for (int qb = 0; qb < QN; qb += qpb) {
+        const int q = qb + ql;
+        const bool live = pl < PL && q < QN;
+        float acc[W][kAqsCand], tot[W][kAqsCand];
+#pragma unroll
+        for (int k = 0; k < W; ++k)
+#pragma unroll
+            for (int j = 0; j < kAqsCand; ++j) acc[k][j] = tot[k][j] = 0.f;
+        if (live) {
+            float lo[W], hi[W];
+#pragma unroll
+            for (int k = 0; k < W; ++k) { lo[k] = range[q * W + k]; hi[k] = range[C + q * W + k]; }
+            const float* src = x + (long)q * W;
+            int run = 0;
+            for (long p = (long)blockIdx.x * PL + pl; p < npix; p += step) {
+                const vec_t v = *reinterpret_cast<const vec_t*>(src + p * C);
+#pragma unroll
+                for (int j = 0; j < kAqsCand; ++j) {
+                    const float s = (float)(1.0 - 0.05 * j);
+#pragma unroll
+                    for (int k = 0; k < W; ++k) {
+                        const float zp = lo[k] * s;
+                        const float rng = fmaxf(hi[k] * s - zp, 1e-6f);
+                        const float d = v[k] - aq_quant(v[k], zp, rng, bit_range, 0.f);
+                        acc[k][j] += d * d;
+                    }
+                }
+                if (++run == kAqsChain) {
+                    run = 0;
+#pragma unroll
+                    for (int k = 0; k < W; ++k)
+#pragma unroll
+                        for (int j = 0; j < kAqsCand; ++j) { tot[k][j] += acc[k][j]; acc[k][j] = 0.f; }
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < W; ++k)
+#pragma unroll
+                for (int j = 0; j < kAqsCand; ++j) sm[(k * kAqsCand + j) * 256 + threadIdx.x] = tot[k][j] + acc[k][j];
+        }
+        __syncthreads();
+        if (live && pl == 0) {
+            float* dst = part + ((long)blockIdx.x * C + (long)q * W) * kAqsCand;
+#pragma unroll
+            for (int k = 0; k < W; ++k)
+#pragma unroll
+                for (int j = 0; j < kAqsCand; ++j) {
+                    float r = sm[(k * kAqsCand + j) * 256 + ql];
+                    for (int t = 1; t < PL; ++t) r += sm[(k * kAqsCand + j) * 256 + t * qpb + ql];
+                    dst[k * kAqsCand + j] = r;
+                }
+        }
+        __syncthreads();
+    }
+}
+
+// err[i] += sum of the `nblk` partial rows, i over C x 10: sixteen lanes per entry walk the rows, then a tree (fixed order: the same
+// input gives the same bits)
+__global__ __launch_bounds__(256) void aqs_fold_kernel(const float* part, int nblk, int n, float* err) {
+    const int i = blockIdx.x * 16 + (threadIdx.x >> 4), j = threadIdx.x & 15;
+    const bool live = i < n;
+    float r = 0.f;
+    if (live)
+        for (int b = j; b < nblk; b += 16) r += part[(long)b * n + i];
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) r += __shfl_xor(r, o, 16);
+    if (live && j == 0) err[i] += r;
 }
 
 // ---- transposed conv as a sub-pixel conv: phase weights ----------------------------------------------------------------------------
@@ -607,5 +707,52 @@ int rdo_actquant_perchannel(const float* x, int64_t npix, int32_t C, int32_t n_b
 }
 
 int64_t rdo_actquant_workspace(int32_t C) { return C > 0 ? 2 * (int64_t)C * (kAqBlocks + 1) : 0; }
+
+int rdo_actquant_static(const float* x, int64_t npix, int32_t C, int32_t n_bits, const float* range, float* out, void* stream) {
+    RDO_REQUIRE(x && out && range && npix > 0 && C > 0, "rdo_actquant_static: bad argument");
+    RDO_REQUIRE(n_bits >= 2 && n_bits <= 16, "rdo_actquant_static: n_bits %d outside [2, 16]", n_bits);
+    const float bit_range = (float)((1 << n_bits) - 1);
+    const bool vec = C % 4 == 0 && (reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) % 16 == 0;
+    return rdo::dispatch(
+        [=](hipStream_t s) {
+            const long nvec = (long)npix * C / (vec ? 4 : 1);
+            if (vec) hipLaunchKernelGGL((aq_apply_kernel<4, true>), dim3(grid_for(nvec)), dim3(256), 0, s, x, nvec, C, range, bit_range, out);
+            else hipLaunchKernelGGL((aq_apply_kernel<1, true>), dim3(grid_for(nvec)), dim3(256), 0, s, x, nvec, C, range, bit_range, out);
+            return rdo::check_launch("actquant_static");
+        },
+        stream, "actquant_static", 0.0, 8.0 * npix * C);
+}
+
+int rdo_actquant_observe(const float* ws_minmax, int32_t C, float* range, void* stream) {
+    RDO_REQUIRE(ws_minmax && range && C > 0, "rdo_actquant_observe: bad argument");
+    return rdo::dispatch(
+        [=](hipStream_t s) {
+            hipLaunchKernelGGL(aq_merge_kernel, dim3((unsigned)rdo::ceil_div(2 * (long)C, 256)), dim3(256), 0, s, ws_minmax, C, range);
+            return rdo::check_launch("actquant_observe");
+        },
+        stream, "actquant_observe", 0.0, 24.0 * C);
+}
+
+int rdo_actquant_search(const float* x, int64_t npix, int32_t C, int32_t n_bits, const float* range, float* err, float* ws, void* stream) {
+    RDO_REQUIRE(x && range && err && ws && npix > 0 && C > 0, "rdo_actquant_search: bad argument");
+    RDO_REQUIRE(n_bits >= 2 && n_bits <= 16, "rdo_actquant_search: n_bits %d outside [2, 16]", n_bits);
+    const float bit_range = (float)((1 << n_bits) - 1);
+    const bool vec = C % 4 == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0;
+    return rdo::dispatch(
+        [=](hipStream_t s) {
+            const int W = vec ? 4 : 1;
+            const int QN = C / W, qpb = QN < 256 ? QN : 256, PL = 256 / qpb;
+            long g = rdo::ceil_div(npix, (long)PL * 8);
+            const int nblk = (int)(g < 1 ? 1 : (g > kAqBlocks ? kAqBlocks : g));
+            if (vec) hipLaunchKernelGGL(aqs_partial_kernel<4>, dim3(nblk), dim3(256), 0, s, x, (long)npix, C, range, bit_range, ws);
+            else hipLaunchKernelGGL(aqs_partial_kernel<1>, dim3(nblk), dim3(256), 0, s, x, (long)npix, C, range, bit_range, ws);
+            const int n = C * kAqsCand;
+            hipLaunchKernelGGL(aqs_fold_kernel, dim3((unsigned)rdo::ceil_div(n, 16)), dim3(256), 0, s, ws, nblk, n, err);
+            return rdo::check_launch("actquant_search");
+        },
+        stream, "actquant_search", 0.0, 4.0 * npix * C);
+}
+
+int64_t rdo_actquant_search_workspace(int32_t C) { return C > 0 ? (int64_t)C * kAqsCand * kAqBlocks : 0; }
 
 }  // extern "C"

@@ -193,6 +193,39 @@ __global__ __launch_bounds__(256) void sq_diff_sum_kernel(const float* a, const 
     if (threadIdx.x == 0) atomicAdd(out, (red[0] + red[1] + red[2] + red[3]) * scale);
 }
 
+// The same two sums without atomics, for evaluation (PSNR / bpp of a saved model must be the same numbers on every run): every
+// workgroup leaves its partial sum in part[blockIdx.x], one workgroup folds them in a fixed order and adds the total to out[0].
+template <bool LOG2>
+__global__ __launch_bounds__(256) void ordered_part_kernel(const float* a, const float* b, long n, float scale, int clamp01, float* part) {
+    float acc = 0.f;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        if (LOG2) {
+            acc -= log2f(a[i]);
+        } else {
+            float x = a[i];
+            if (clamp01) x = fminf(fmaxf(x, 0.f), 1.f);
+            const float d = x - b[i];
+            acc += d * d;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+    __shared__ float red[4];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1] + red[2] + red[3]) * scale;
+}
+
+__global__ __launch_bounds__(256) void ordered_fold_kernel(const float* part, int nblk, float* out) {
+    float acc = 0.f;
+    for (int i = threadIdx.x; i < nblk; i += 256) acc += part[i];
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+    __shared__ float red[4];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) out[0] += red[0] + red[1] + red[2] + red[3];
+}
+constexpr int kOrderedBlocks = 2048;        // = the cap of grid_for
+
 inline unsigned grid_for(long n) {
     long g = rdo::ceil_div(n, 256);
     return (unsigned)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
@@ -262,6 +295,32 @@ int rdo_sq_diff_sum(const float* a, const float* b, int64_t n, float scale, int3
         [=](hipStream_t s) {
             hipLaunchKernelGGL(sq_diff_sum_kernel, dim3(grid_for(n)), dim3(256), 0, s, a, b, (long)n, scale, clamp01, out);
             return rdo::check_launch("sq_diff_sum");
+        },
+        stream, "entropy", 0.0, 8.0 * n);
+}
+
+int64_t rdo_ordered_sum_workspace(void) { return kOrderedBlocks; }
+
+int rdo_neg_log2_sum_ordered(const float* lik, int64_t n, float scale, float* out, float* ws, void* stream) {
+    RDO_REQUIRE(lik && out && ws && n > 0, "rdo_neg_log2_sum_ordered: bad argument");
+    return rdo::dispatch(
+        [=](hipStream_t s) {
+            const unsigned g = grid_for(n);
+            hipLaunchKernelGGL(ordered_part_kernel<true>, dim3(g), dim3(256), 0, s, lik, (const float*)nullptr, (long)n, scale, 0, ws);
+            hipLaunchKernelGGL(ordered_fold_kernel, dim3(1), dim3(256), 0, s, ws, (int)g, out);
+            return rdo::check_launch("neg_log2_sum_ordered");
+        },
+        stream, "entropy", 0.0, 4.0 * n);
+}
+
+int rdo_sq_diff_sum_ordered(const float* a, const float* b, int64_t n, float scale, int32_t clamp01, float* out, float* ws, void* stream) {
+    RDO_REQUIRE(a && b && out && ws && n > 0, "rdo_sq_diff_sum_ordered: bad argument");
+    return rdo::dispatch(
+        [=](hipStream_t s) {
+            const unsigned g = grid_for(n);
+            hipLaunchKernelGGL(ordered_part_kernel<false>, dim3(g), dim3(256), 0, s, a, b, (long)n, scale, clamp01, ws);
+            hipLaunchKernelGGL(ordered_fold_kernel, dim3(1), dim3(256), 0, s, ws, (int)g, out);
+            return rdo::check_launch("sq_diff_sum_ordered");
         },
         stream, "entropy", 0.0, 8.0 * n);
 }

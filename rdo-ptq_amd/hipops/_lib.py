@@ -78,6 +78,10 @@ _SIGS = {
     "rdo_uaq_init_minmax": (C.c_int, [P, C.c_int32, C.c_int64, C.c_int32, P, P, P]),
     "rdo_actquant_perchannel": (C.c_int, [P, C.c_int64, C.c_int32, C.c_int32, P, P, P]),
     "rdo_actquant_workspace": (C.c_int64, [C.c_int32]),
+    "rdo_actquant_static": (C.c_int, [P, C.c_int64, C.c_int32, C.c_int32, P, P, P]),
+    "rdo_actquant_observe": (C.c_int, [P, C.c_int32, P, P]),
+    "rdo_actquant_search": (C.c_int, [P, C.c_int64, C.c_int32, C.c_int32, P, P, P, P]),
+    "rdo_actquant_search_workspace": (C.c_int64, [C.c_int32]),
     "rdo_gather_qdrop": (C.c_int, [P, P, P, P, C.c_int32, C.c_int32, C.c_int64, C.c_float, C.c_uint32, P, P, P]),
     "rdo_lp2_loss_grad": (C.c_int, [P, P, P, P, C.c_int32, C.c_int64, C.c_int32, C.c_float, P, P, P]),
     "rdo_lp_loss_grad": (C.c_int, [P, P, P, P, C.c_int32, C.c_int64, C.c_int32, C.c_float, C.c_float, C.c_float, P, P, P, P]),
@@ -119,6 +123,9 @@ _SIGS = {
     "rdo_gaussian_likelihood_bwd": (C.c_int, [P, P, P, C.c_int64, C.c_float, C.c_float, P, P, P]),
     "rdo_neg_log2_sum": (C.c_int, [P, C.c_int64, C.c_float, P, P]),
     "rdo_sq_diff_sum": (C.c_int, [P, P, C.c_int64, C.c_float, C.c_int32, P, P]),
+    "rdo_neg_log2_sum_ordered": (C.c_int, [P, C.c_int64, C.c_float, P, P, P]),
+    "rdo_sq_diff_sum_ordered": (C.c_int, [P, P, C.c_int64, C.c_float, C.c_int32, P, P, P]),
+    "rdo_ordered_sum_workspace": (C.c_int64, []),
     "rdo_h2_overflow": (C.c_int, [C.c_int]),
     "rdo_h2_bind_flag": (C.c_int, [C.c_void_p]),
     "rdo_split_h2": (C.c_int, [P, C.c_int64, C.c_int32, C.c_float, P, P]),

@@ -320,6 +320,54 @@ def actquant_perchannel(x, out=None, ws=None, n_bits=8):
     return out
 
 
+ACT_SEARCH_CANDIDATES = 10        # kAqsCand of csrc/elementwise.hip: range * (1 - 0.05 k), k = 0..9
+
+
+def _act_range_check(x, rng, what):
+    Cc = x.shape[-1]
+    if rng.numel() != 2 * Cc:
+        raise ValueError(f"{what}: the range holds {rng.numel() // 2} channels, the tensor has {Cc}")
+    return Cc, x.numel() // Cc
+
+
+def act_range_init(channels, device):
+    """Empty running range lo | hi = +inf | -inf of `channels` channels."""
+    r = torch.empty(2 * int(channels), device=device, dtype=torch.float32)
+    r[:channels] = float("inf")
+    r[channels:] = float("-inf")
+    return r
+
+
+def actquant_observe(x, rng, out=None, n_bits=8):
+    """The dynamic quantiser on x [..., C], whose per-channel min | max is then merged into the running range `rng` [2C] (in place):
+    the activation is read by the dynamic kernels only."""
+    Cc, npix = _act_range_check(x, rng, "actquant_observe")
+    ws = torch.empty(int(L.lib().rdo_actquant_workspace(Cc)), device=x.device, dtype=torch.float32)
+    out = actquant_perchannel(x, out=out, ws=ws, n_bits=n_bits)
+    L.check(L.lib().rdo_actquant_observe(_ptr(ws), Cc, _ptr(rng), _stream()), "rdo_actquant_observe")
+    return out
+
+
+def actquant_static(x, rng, out=None, n_bits=8):
+    """x: [..., C] channels-last; quant-dequant on the frozen per-channel grid rng = lo[C] | hi[C] (one launch; out may be x)."""
+    Cc, npix = _act_range_check(x, rng, "actquant_static")
+    out = torch.empty_like(x) if out is None else out
+    L.check(L.lib().rdo_actquant_static(_ptr(x), npix, Cc, int(n_bits), _ptr(rng), _ptr(out), _stream()), "rdo_actquant_static")
+    return out
+
+
+def actquant_search(x, rng, err, n_bits=8, ws=None):
+    """err [C, 10] += per-channel squared error of x [..., C] on the ten shrunk grids rng * (1 - 0.05 k)."""
+    Cc, npix = _act_range_check(x, rng, "actquant_search")
+    if tuple(err.shape) != (Cc, ACT_SEARCH_CANDIDATES):
+        raise ValueError(f"actquant_search: err must be [{Cc}, {ACT_SEARCH_CANDIDATES}], got {tuple(err.shape)}")
+    need = int(L.lib().rdo_actquant_search_workspace(Cc))
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, device=x.device, dtype=torch.float32)
+    L.check(L.lib().rdo_actquant_search(_ptr(x), npix, Cc, int(n_bits), _ptr(rng), _ptr(err), _ptr(ws), _stream()), "rdo_actquant_search")
+    return err
+
+
 def gather_qdrop(cache_q, cache_fp, idx_table, iter_ptr, B, prob, seed, out, batch_offset=0, iter_publish=None):
     """`batch_offset`: row of the global mini-batch this (data-parallel) rank's first row is -- the QDrop counter runs over the
     global batch, so N ranks with one seed draw the mask a single process would."""
@@ -777,6 +825,34 @@ def neg_log2_sum(lik, scale=1.0, out=None):
 def sq_diff_sum(a, b, scale=1.0, clamp01=False, out=None):
     out = torch.zeros(1, device=a.device, dtype=torch.float32) if out is None else out
     L.check(L.lib().rdo_sq_diff_sum(_ptr(a), _ptr(b), a.numel(), scale, int(clamp01), _ptr(out), _stream()), "rdo_sq_diff_sum")
+    return out
+
+
+_ORDERED_WS = {}    # device -> workspace of the ordered sums (launches are stream-ordered, so one buffer per device suffices)
+
+
+def _ordered_ws(device):
+    device = torch.device(device)
+    device = torch.device("cuda", torch.cuda.current_device()) if device.index is None else device
+    ws = _ORDERED_WS.get(device)
+    if ws is None:
+        ws = _ORDERED_WS[device] = torch.empty(int(L.lib().rdo_ordered_sum_workspace()), device=device, dtype=torch.float32)
+    return ws
+
+
+def neg_log2_sum_ordered(lik, scale=1.0, out=None):
+    """`neg_log2_sum` summed in a fixed order: the same bits on every run (evaluation)."""
+    out = torch.zeros(1, device=lik.device, dtype=torch.float32) if out is None else out
+    L.check(L.lib().rdo_neg_log2_sum_ordered(_ptr(lik), lik.numel(), scale, _ptr(out), _ptr(_ordered_ws(lik.device)), _stream()),
+            "rdo_neg_log2_sum_ordered")
+    return out
+
+
+def sq_diff_sum_ordered(a, b, scale=1.0, clamp01=False, out=None):
+    """`sq_diff_sum` summed in a fixed order: the same bits on every run (evaluation)."""
+    out = torch.zeros(1, device=a.device, dtype=torch.float32) if out is None else out
+    L.check(L.lib().rdo_sq_diff_sum_ordered(_ptr(a), _ptr(b), a.numel(), scale, int(clamp01), _ptr(out), _ptr(_ordered_ws(a.device)),
+                                            _stream()), "rdo_sq_diff_sum_ordered")
     return out
 
 

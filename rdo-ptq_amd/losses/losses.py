@@ -19,17 +19,18 @@ def _flat(t):
     return t.detach().contiguous().reshape(-1)
 
 
-def bpp_of(likelihoods: dict, num_pixels: int) -> torch.Tensor:
+def bpp_of(likelihoods: dict, num_pixels: int, ordered: bool = False) -> torch.Tensor:
+    """`ordered`: sum in a fixed order (the evaluation metrics: the same bits on every run) instead of with float atomics."""
     out = None
     for lik in likelihoods.values():
-        out = ops.neg_log2_sum(_flat(lik), 1.0 / num_pixels, out)
+        out = (ops.neg_log2_sum_ordered if ordered else ops.neg_log2_sum)(_flat(lik), 1.0 / num_pixels, out)
     return out.reshape(())
 
 
-def mse_of(a, b, clamp01=False) -> torch.Tensor:
+def mse_of(a, b, clamp01=False, ordered: bool = False) -> torch.Tensor:
     # both tensors must share one memory layout for the element-wise kernel: use the logical NCHW order
     a, b = a.detach().contiguous(), b.detach().contiguous()
-    return ops.sq_diff_sum(a.reshape(-1), b.reshape(-1), 1.0 / a.numel(), clamp01).reshape(())
+    return (ops.sq_diff_sum_ordered if ordered else ops.sq_diff_sum)(a.reshape(-1), b.reshape(-1), 1.0 / a.numel(), clamp01).reshape(())
 
 
 _MS_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
@@ -163,7 +164,7 @@ class Metrics(nn.Module):
 
 def compute_psnr(a, b):
     """test_datasets.py:21-23"""
-    return -10 * math.log10(float(mse_of(a, b)))
+    return -10 * math.log10(float(mse_of(a, b, ordered=True)))
 
 
 def compute_msssim(a, b):
@@ -174,4 +175,4 @@ def compute_msssim(a, b):
 def compute_bpp(out_net):
     """test_datasets.py:29-33 (num_pixels of the padded reconstruction)"""
     size = out_net["x_hat"].size()
-    return float(bpp_of(out_net["likelihoods"], size[0] * size[2] * size[3]))
+    return float(bpp_of(out_net["likelihoods"], size[0] * size[2] * size[3], ordered=True))

@@ -26,6 +26,24 @@ def shard(cali_data, group=None):
     return cali_data[lo:hi]
 
 
+def reduce_act_stats(ranges=(), sums=(), group=None):
+    """Static activation ranges under data parallelism: every rank observed its shard, every rank must freeze the same grid.  In place:
+    each `ranges` tensor [2C] = lo | hi gets MIN over the ranks on its lo half and MAX on its hi half, each `sums` tensor (the search's
+    error sums) gets SUM.  Works on CPU tensors over gloo and on device tensors over RCCL; without a process group nothing happens.
+    Every rank must pass the same tensors in the same order."""
+    if world(group)[1] <= 1:
+        return
+    for r in ranges:
+        c = r.numel() // 2
+        lo, hi = r[:c].contiguous(), r[c:].contiguous()
+        dist.all_reduce(lo, op=dist.ReduceOp.MIN, group=group)
+        dist.all_reduce(hi, op=dist.ReduceOp.MAX, group=group)
+        r[:c].copy_(lo)
+        r[c:].copy_(hi)
+    for e in sums:
+        dist.all_reduce(e, op=dist.ReduceOp.SUM, group=group)
+
+
 class GradBucket:
     """The flat alpha-gradient bucket of one reconstruction unit and its collective.
 

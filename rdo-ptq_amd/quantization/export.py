@@ -32,5 +32,15 @@ def integer_state(qnn) -> "OrderedDict[str, dict]":
     return out
 
 
+def activation_state(qnn) -> "OrderedDict[str, dict]":
+    """name -> {lo, hi (fp32 [channels], CPU), n_bits, channels} of every frozen static activation quantiser (`QuantModel.act_ranges`):
+    x_q = round(clamp((x - lo) / r, 0, 1) * (2^n_bits - 1)) / (2^n_bits - 1) * r + lo with r = max(hi - lo, 1e-6), per channel.
+    Empty for a model whose activation quantisers are dynamic: there is nothing fixed to write."""
+    out = OrderedDict()
+    for name, (lo, hi, n_bits) in qnn.act_ranges().items():
+        out[name] = {"lo": lo.detach().cpu().clone(), "hi": hi.detach().cpu().clone(), "n_bits": int(n_bits), "channels": int(lo.numel())}
+    return out
+
+
 def dequantize(entry) -> torch.Tensor:
     return (entry["levels"].to(torch.float32) - entry["zero_point"]) * entry["delta"]

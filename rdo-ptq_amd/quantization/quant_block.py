@@ -1,7 +1,7 @@
 """Quantised Cheng2020 blocks (reference surface: quantization/quant_block.py:77-102, 219-328, 645-657).
 
-A block owns `QuantModule`s for its convs / GDN and applies the dynamic activation quantiser after the element-wise
-joins once it is trained.  The Lu2022 Swin wrappers (QuantRSTB & co., quant_block.py:330-641) keep tokens in natural pixel
+A block owns `QuantModule`s for its convs / GDN and applies its activation quantiser (dynamic by default, static per-channel
+ranges when the model was calibrated with `act_mode='static'`) after the element-wise joins once it is trained.  The Lu2022 Swin wrappers (QuantRSTB & co., quant_block.py:330-641) keep tokens in natural pixel
 order end to end: the cyclic shift and the window partition are address arithmetic inside the attention kernel, and every
 activation quantiser on the path is per-channel over the whole tensor, hence order-independent."""
 import torch
@@ -11,7 +11,7 @@ from hipops import ops
 import lic
 
 from .quant_layer import QuantModule, _nhwc, _nchw_view
-from .quantizer import ActQuantizer, StraightThrough, UniformAffineQuantizer
+from .quantizer import StraightThrough, UniformAffineQuantizer
 
 
 class BaseQuantBlock(nn.Module):
@@ -33,8 +33,9 @@ class BaseQuantBlock(nn.Module):
             if isinstance(m, QuantModule):
                 m.set_quant_state(weight_quant, act_quant)
 
-    def _aq(self, x):
-        return ActQuantizer(x, self.act_quantizer.dynamic_bits) if (self.use_act_quant and self.trained) else x
+    def _aq(self, x, site=0):
+        """`site`: which of the block's quantisation points this is -- a static quantiser keeps one frozen range per point."""
+        return self.act_quantizer(x, True, site=site) if (self.use_act_quant and self.trained) else x
 
 
 def _tracked(*ts):
@@ -69,7 +70,7 @@ class QuantRBWS(BaseQuantBlock):
         out = self._aq(_lrelu(self.conv1(x)))
         out = self.gdn(self.conv2(out))
         out = _add(out, x if self.skip is None else self.skip(x))
-        return self._aq(out)
+        return self._aq(out, 1)
 
 
 class QuantRBU(BaseQuantBlock):
@@ -98,7 +99,7 @@ class QuantRBU(BaseQuantBlock):
         out = self._aq(_lrelu(self._subpel(self.subpel_conv, x)))
         out = self.igdn(self.conv(out))
         out = _add(out, self._subpel(self.upsample, x))
-        return self._aq(out)
+        return self._aq(out, 1)
 
 
 class QuantRB(BaseQuantBlock):
@@ -114,9 +115,9 @@ class QuantRB(BaseQuantBlock):
 
     def forward(self, x):
         out = self._aq(_lrelu(self.conv1(x)))
-        out = self._aq(_lrelu(self.conv2(out)))
+        out = self._aq(_lrelu(self.conv2(out)), 1)
         out = _add(out, x if self.skip is None else self.skip(x))
-        return self._aq(out)
+        return self._aq(out, 2)
 
 
 class QuantSC(BaseQuantBlock):
@@ -205,9 +206,10 @@ class QuantWindowAttention(BaseQuantBlock):
             n = window * window
             probs = torch.empty((B * (H // window) * (W // window), n, n, self.num_heads), device=qkv.device, dtype=torch.float32)
             ops.window_attention(d, qkv, bias, probs=probs, compute_out=False)
-            nb = self.act_quantizer.dynamic_bits
-            probs = ops.actquant_perchannel(probs, n_bits=nb)            # per head, as ActQuantizer on [B_, heads, N, N]
-            o = ActQuantizer(ops.window_attention_pv(d, qkv, probs).view(B, H * W, C), nb)
+            # one quantiser object, two tensors: site 0 = the probabilities, per head (as ActQuantizer on [B_, heads, N, N]; the kernel
+            # writes them heads-last), site 1 = attn @ v, per channel
+            probs = self.act_quantizer(probs, True, site=0, channels_last=True)
+            o = self.act_quantizer(ops.window_attention_pv(d, qkv, probs).view(B, H * W, C), True, site=1)
         elif _tracked(qkv):
             from hipops.autograd import WindowAttentionFn
             o = WindowAttentionFn.apply(qkv.view(B, H, W, 3 * C), d, bias).view(B, H * W, C)

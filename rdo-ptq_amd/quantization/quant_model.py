@@ -50,6 +50,31 @@ class QuantModel(nn.Module):
             if isinstance(m, (QuantModule, BaseQuantBlock)):
                 m.set_quant_state(weight_quant, act_quant)
 
+    def act_quantizers(self):
+        """(name, quantiser) of every activation quantiser: one per QuantModule and one per block wrapper."""
+        return [(f"{name}.act_quantizer", m.act_quantizer) for name, m in self.named_modules()
+                if isinstance(m, (QuantModule, BaseQuantBlock))]
+
+    def set_act_mode(self, mode: str):
+        """'dynamic' (default: the grid of every tensor is its own min / max) or 'static' (per-channel ranges frozen by the
+        calibration flow, recon.py with args.act_mode='static'; an unfrozen static quantiser raises when it is applied)."""
+        for _, q in self.act_quantizers():
+            q.set_act_mode(mode)
+
+    def act_ranges(self):
+        """OrderedDict name -> (lo, hi, n_bits) of the frozen static ranges.  A quantiser applied at several places of its block (the
+        joins of a residual block; probabilities and attn @ v of an attention) has one entry per place: 'name', 'name#1', ..."""
+        from collections import OrderedDict
+        out = OrderedDict()
+        for name, q in self.act_quantizers():
+            if not q.act_frozen():
+                continue
+            for site in sorted(q.act_range):
+                r = q.act_range[site]
+                c = r.numel() // 2
+                out[name if site == 0 else f"{name}#{site}"] = (r[:c], r[c:], getattr(q, "dynamic_bits", 8))
+        return out
+
     def forward(self, input):
         return self.model(input)
 

@@ -79,13 +79,28 @@ def ActQuantizer(x: torch.Tensor, n_bits: int = 8):
     return ActQuant(x, n_bits)
 
 
+def _act_rows(x: torch.Tensor, channels_last: bool = False):
+    """x -> (contiguous channels-last tensor the kernels see, function taking a result back to x's layout); the channel rule of
+    `ActQuant`.  `channels_last`: the last dim is the channel whatever the rank (the attention probabilities [B_, N, N, heads])."""
+    x = x.detach()
+    if channels_last or x.dim() in (2, 3):
+        return x.contiguous(), (lambda y: y)
+    if x.dim() == 4:
+        return x.permute(0, 2, 3, 1).contiguous(), (lambda y: y.permute(0, 3, 1, 2))
+    shape = x.shape
+    return x.reshape(-1, 1).contiguous(), (lambda y: y.reshape(shape))
+
+
+ACT_MODES = ("dynamic", "static")
+
+
 # ----------------------------------------------------------------------------- uniform affine quantiser
 class UniformAffineQuantizer(nn.Module):
     """Asymmetric uniform fake-quantiser; scales are initialised lazily on the first weight it sees."""
 
     def __init__(self, n_bits: int = 8, symmetric: bool = False, channel_wise: bool = False, scale_method: str = "max",
                  leaf_param: bool = False, tconv: bool = False, act: bool = False, prob: float = 1.0,
-                 dynamic_bits: int = None):
+                 dynamic_bits: int = None, act_mode: str = "dynamic"):
         super().__init__()
         # width of the dynamic activation grid: None = the reference's fixed 8 bits (its ActQuant ignores n_bits_a,
         # quantizer.py:81,158-159); an explicit value is this build's extension (e.g. 10 for W10A10)
@@ -107,6 +122,15 @@ class UniformAffineQuantizer(nn.Module):
         self.act = act
         self.prob = prob
         self.is_training = False
+        # activation grids: "dynamic" = the reference's ActQuant (min / max of the very tensor being quantised); "static" = per-channel
+        # ranges frozen from the calibration set (an extension; recon.py drives observing -> (searching ->) frozen).  One quantiser
+        # object may sit at several places of its block (`site`): each place has its own range [2C] = lo | hi in `act_range`.
+        if act_mode not in ACT_MODES:
+            raise ValueError(f"unknown act_mode {act_mode!r} {ACT_MODES}")
+        self.act_mode = act_mode
+        self.act_phase = "idle"            # static only: "idle" (no range yet) | "observe" | "search" | "frozen"
+        self.act_range = {}                # site -> fp32 [2C], lo | hi
+        self.act_err = {}                  # site -> fp32 [C, 10] while searching
 
     def _apply(self, fn, *args, **kwargs):
         super()._apply(fn, *args, **kwargs)
@@ -114,7 +138,68 @@ class UniformAffineQuantizer(nn.Module):
             t = getattr(self, name, None)
             if torch.is_tensor(t):
                 setattr(self, name, fn(t))
+        for name in ("act_range", "act_err"):
+            d = getattr(self, name, None)
+            if isinstance(d, dict):
+                setattr(self, name, {k: fn(t) for k, t in d.items()})
         return self
+
+    # -- static activation grids ----------------------------------------------------------------------------------
+    def set_act_mode(self, mode: str):
+        if mode not in ACT_MODES:
+            raise ValueError(f"unknown act_mode {mode!r} {ACT_MODES}")
+        for name, val in (("act_phase", "idle"), ("act_range", {}), ("act_err", {})):      # (an artefact of an earlier version)
+            if not hasattr(self, name):
+                setattr(self, name, val)
+        self.act_mode = mode
+
+    def act_observe(self):
+        """Start observing: every call quantises dynamically and merges the batch's per-channel min / max into the site's range."""
+        self.act_phase, self.act_range, self.act_err = "observe", {}, {}
+
+    def act_search(self):
+        """Start the L2 search over the observed ranges: every call accumulates the ten candidates' squared errors and returns the
+        max-range static output."""
+        if not self.act_range:
+            raise RuntimeError("act_search: nothing was observed")
+        self.act_phase = "search"
+        self.act_err = {k: torch.zeros(r.numel() // 2, ops.ACT_SEARCH_CANDIDATES, device=r.device) for k, r in self.act_range.items()}
+
+    def act_freeze(self):
+        """Fix the ranges.  After a search each channel shrinks to its best candidate lo * s_k | hi * s_k (first minimum, as `_init_search`
+        keeps the first strictly better score).  Scaling towards zero moves an end that does not straddle zero (lo > 0 or hi < 0) OUT of
+        the observed range, where no calibration value lies: such an end stays at the observed one, so a frozen range always lies inside
+        its max range.  A quantiser that was never applied stays without a range ("idle")."""
+        for k, err in self.act_err.items():
+            rng = self.act_range[k]
+            c = rng.numel() // 2
+            table = torch.tensor([1.0 - 0.05 * i for i in range(ops.ACT_SEARCH_CANDIDATES)], dtype=torch.float32, device=rng.device)
+            s = table[err.argmin(dim=1)]                                   # (float)(1 - 0.05 k): the kernel's factors
+            lo, hi = torch.maximum(rng[:c] * s, rng[:c]), torch.minimum(rng[c:] * s, rng[c:])
+            keep = lo > hi                                                 # (a candidate that left the observed range altogether)
+            self.act_range[k] = torch.cat([torch.where(keep, rng[:c], lo), torch.where(keep, rng[c:], hi)])
+        self.act_err = {}
+        self.act_phase = "frozen" if self.act_range else "idle"
+
+    def act_frozen(self):
+        return getattr(self, "act_mode", "dynamic") == "static" and getattr(self, "act_phase", "idle") == "frozen"
+
+    def _act_static(self, x, site, channels_last):
+        xr, back = _act_rows(x, channels_last)
+        bits, Cc, phase = getattr(self, "dynamic_bits", 8), xr.shape[-1], self.act_phase
+        rng = self.act_range.get(site)
+        if rng is not None and rng.numel() != 2 * Cc:
+            raise ValueError(f"static activation quantiser (site {site}): calibrated for {rng.numel() // 2} channels, got {Cc}")
+        if phase == "observe":
+            if rng is None:
+                rng = self.act_range[site] = ops.act_range_init(Cc, xr.device)
+            return back(ops.actquant_observe(xr, rng, n_bits=bits))
+        if rng is None:
+            raise RuntimeError(f"static activation quantiser (site {site}) has no frozen range: calibrate it first "
+                               "(recon.py with args.act_mode='static'); there is no fall-back to the dynamic grid")
+        if phase == "search":
+            ops.actquant_search(xr, rng, self.act_err[site], n_bits=bits)
+        return back(ops.actquant_static(xr, rng, n_bits=bits))
 
     # -- scale initialisation -------------------------------------------------------------------------------------
     def _rows(self, x):
@@ -180,8 +265,12 @@ class UniformAffineQuantizer(nn.Module):
         return delta, zp
 
     # -- forward ---------------------------------------------------------------------------------------------------
-    def forward(self, x: torch.Tensor, act: bool = False):
+    def forward(self, x: torch.Tensor, act: bool = False, site: int = 0, channels_last: bool = False):
         if act:
+            if getattr(self, "act_mode", "dynamic") == "static":
+                return self._act_static(x, site, channels_last)
+            if channels_last:
+                return ops.actquant_perchannel(x.detach().contiguous(), n_bits=getattr(self, "dynamic_bits", 8))
             return ActQuantizer(x, getattr(self, "dynamic_bits", 8))
         if not self.inited:
             if self.leaf_param:

@@ -134,6 +134,57 @@ def _rd_metric(args, cali_data):
     return metric
 
 
+def _act_args(args):
+    """args.act_mode: 'dynamic' (default; the reference's ActQuant) or 'static' (per-channel ranges frozen from the calibration set);
+    args.act_range: how a static range is fixed, 'max' (default: min / max over the calibration set) or 'l2' (each channel then shrinks
+    to the best of ten candidates by squared error).  Checked before any work is done."""
+    mode = getattr(args, "act_mode", "dynamic") if args is not None else "dynamic"
+    how = getattr(args, "act_range", "max") if args is not None else "max"
+    if mode not in ("dynamic", "static"):
+        raise ValueError(f"unknown act_mode {mode!r} ('dynamic' or 'static')")
+    if how not in ("max", "l2"):
+        raise ValueError(f"unknown act_range {how!r} ('max' or 'l2')")
+    return mode, how
+
+
+def calibrate_act_ranges(unit, inp_q, act_range="max", batch=32):
+    """Fix the static activation ranges of a calibrated unit: run it once over its cached quantised inputs in the state the W8A8
+    evaluation uses (the unit, its QuantModules and nested block wrappers with weight and activation quantisation on) with its quantisers
+    observing, then freeze them; with act_range='l2' a second pass over the same inputs accumulates the candidates' squared errors
+    first.  Under data parallelism the observed ranges and the error sums are reduced over the ranks before they are used, so every
+    rank freezes the same grid.  Every quant state flag is left as it was found."""
+    mods = [m for m in unit.modules() if isinstance(m, (QuantModule, BaseQuantBlock))]
+    quants = [m.act_quantizer for m in mods]
+    states = [(m, m.use_weight_quant, m.use_act_quant) for m in mods]
+
+    def run():
+        with torch.no_grad():
+            for i in range(0, inp_q.shape[0], batch):
+                h = inp_q[i:i + batch]
+                unit(h, (h.shape[2], h.shape[3])) if isinstance(unit, QuantRSTB) else unit(h)
+
+    def applied(name):                   # in a fixed order: the collectives of all ranks must line up
+        return [getattr(q, name)[k] for q in quants for k in sorted(getattr(q, name))]
+    try:
+        for m in mods:
+            m.use_weight_quant = m.use_act_quant = True
+        for q in quants:
+            q.act_observe()
+        run()
+        dp.reduce_act_stats(ranges=applied("act_range"))
+        if act_range == "l2":
+            for q in quants:
+                if q.act_range:
+                    q.act_search()
+            run()
+            dp.reduce_act_stats(sums=applied("act_err"))
+        for q in quants:
+            q.act_freeze()
+    finally:
+        for m, w, a_ in states:
+            m.use_weight_quant, m.use_act_quant = w, a_
+
+
 def reconstruct(model, unit, unit_name, cali_data, *a, **kw):
     """`_reconstruct` with the one piece of cross-unit state tidied up on failure: the full-precision cache memo of the schedule
     (quantization/utils.py::_FpMemo) is dropped when a unit raises, so a schedule that dies half-way pins no device memory."""
@@ -160,6 +211,7 @@ def _reconstruct(model, unit, unit_name, cali_data, batch_size=32, iters=20000, 
     if float(task_p) < 1.0:
         raise ValueError("--task_loss < 1 has no finite gradient at zero error")
     rd_metric = _rd_metric(args, cali_data)
+    act_mode, act_range = _act_args(args)
     rank, world_size = dp.world()
     if world_size > 1:                      # data parallel: this rank calibrates on its shard with its share of the batch
         if batch_size % world_size != 0:
@@ -179,8 +231,16 @@ def _reconstruct(model, unit, unit_name, cali_data, batch_size=32, iters=20000, 
             torch.cuda.synchronize()
         return time.time()
     t0 = _mark()
-    # dynamic activation quantisation makes cached values depend on the caching batch: keep the reference's batch of 1 then
-    cache_bs = 1 if act_quant else max(1, min(32, cali_data.size(0)))
+    # dynamic activation quantisation makes cached values depend on the caching batch: keep the reference's batch of 1 then (a static
+    # grid is the same whatever shares the batch)
+    static_act = bool(act_quant) and act_mode == "static"
+    if act_quant:
+        # args decide, in both directions: a model calibrated static earlier and reconstructed again with act_mode='dynamic' (or without
+        # it) runs dynamic grids; frozen ranges stay on the quantisers and come back with QuantModel.set_act_mode('static')
+        for m in model.modules():
+            if isinstance(m, (QuantModule, BaseQuantBlock)) and getattr(m.act_quantizer, "act_mode", "dynamic") != act_mode:
+                m.act_quantizer.set_act_mode(act_mode)
+    cache_bs = 1 if (act_quant and not static_act) else max(1, min(32, cali_data.size(0)))
     (inp_q, inp_fp), out_fp = save_inp_oup_data(model, unit, cali_data, asym, act_quant, batch_size=cache_bs, input_prob=True)
     t1 = _mark()
     logging.info("Cached init time: {}".format(t1 - t0))
@@ -255,4 +315,14 @@ def _reconstruct(model, unit, unit_name, cali_data, batch_size=32, iters=20000, 
     for m in ([unit] if not is_block else unit.modules()):
         if isinstance(m, (QuantModule, BaseQuantBlock)):
             m.trained = True
+    if static_act:
+        # only now does the unit apply its own activation quantisers (`trained`): fix their grids on what the unit will be fed.  Also for
+        # a unit the reference's "last layer" rule above trained without activation quantisation: that rule matches every layer unit whose
+        # name holds a '7' (g_a[7] of Cheng2020-attn, convs inside its attention blocks), and the cache passes of later units and the
+        # W8A8 evaluation apply those quantisers all the same (utils.set_mode).  What decides is whether a later forward applies the
+        # quantiser: one behind `disable_act_quant` is never called, observes nothing and stays without a range.
+        t4 = _mark()
+        calibrate_act_ranges(unit, inp_q, act_range, batch=cache_bs)
+        if timing is not None:
+            timing[-1]["act_s"] = _mark() - t4
     return eng

@@ -1,0 +1,147 @@
+#!/usr/bin/env python3
+"""Dynamic against static per-channel activation quantisation on one MI355X, on the shapes the product meets (NHWC fp32).
+
+Kernel part: device-event timing after warm-up, the two quantisers ALTERNATING in one process (dynamic round, static round, ...; the
+median round is reported), µs per call and GB/s against algorithmic bytes -- static 8 B per element (one read, one write), dynamic 12
+(two reads, one write).  The static call does a strict subset of the dynamic call's work: a shape on which it is slower is flagged.
+The range search (one read, ten candidates) is timed next to them.
+
+Flow part (--flow): the cache-building wall (`args.timing`, `cache_s`) of a W8A8 calibration schedule of a toy Cheng2020 (N = 8, 64^2
+crops) in both modes -- dynamic grids build every unit's caches image by image, static ones in batches.
+
+    python tools/bench_actquant.py [--reps 1000] [--rounds 7] [--flow] [--images 32] [--json out.json]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import types
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "rdo-ptq_amd"))
+sys.path.insert(0, ROOT)
+
+SHAPES = [(4, 128, 128, 192), (4, 64, 64, 192), (4, 16, 16, 192), (1, 32, 48, 192), (1, 512, 768, 3)]
+
+
+def _time_us(fn, reps):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) * 1e3 / reps
+
+
+def bench_kernels(reps, rounds, n_bits=8):
+    from hipops import ops
+    L = ops.L
+    rows = []
+    for shape in SHAPES:
+        g = torch.Generator().manual_seed(sum(shape))
+        x = (torch.randn(*shape, generator=g) * 3).cuda()
+        C, n = shape[-1], x.numel()
+        out = torch.empty_like(x)
+        ws = torch.empty(int(L.lib().rdo_actquant_workspace(C)), device="cuda")
+        sws = torch.empty(int(L.lib().rdo_actquant_search_workspace(C)), device="cuda")
+        rng = ops.act_range_init(C, "cuda")
+        ops.actquant_observe(x, rng, n_bits=n_bits)
+        err = torch.zeros(C, ops.ACT_SEARCH_CANDIDATES, device="cuda")
+        calls = {
+            "dynamic": lambda: ops.actquant_perchannel(x, out=out, ws=ws, n_bits=n_bits),
+            "static": lambda: ops.actquant_static(x, rng, out=out, n_bits=n_bits),
+            "search": lambda: ops.actquant_search(x, rng, err, n_bits=n_bits, ws=sws),
+        }
+        r = reps
+        for fn in calls.values():                              # warm-up: code objects, caches
+            for _ in range(10):
+                fn()
+        torch.cuda.synchronize()
+        t = {k: [] for k in calls}
+        for _ in range(rounds):                                # alternate within one process
+            for k, fn in calls.items():
+                t[k].append(_time_us(fn, r))
+        assert torch.equal(ops.actquant_static(x, rng, n_bits=n_bits), ops.actquant_perchannel(x, n_bits=n_bits))
+        med = {k: statistics.median(v) for k, v in t.items()}
+        row = dict(shape=list(shape), elements=n, reps=r, rounds=rounds,
+                   dynamic_us=round(med["dynamic"], 2), static_us=round(med["static"], 2), search_us=round(med["search"], 2),
+                   dynamic_spread_us=[round(min(t["dynamic"]), 2), round(max(t["dynamic"]), 2)],
+                   static_spread_us=[round(min(t["static"]), 2), round(max(t["static"]), 2)],
+                   dynamic_gbs=round(12.0 * n / med["dynamic"] / 1e3, 1), static_gbs=round(8.0 * n / med["static"] / 1e3, 1),
+                   search_gbs=round(4.0 * n / med["search"] / 1e3, 1),
+                   speedup=round(med["dynamic"] / med["static"], 2), static_slower=bool(med["static"] > med["dynamic"]))
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    return rows
+
+
+def bench_flow(images, iters=6):
+    """cache_s of every unit of the toy W8A8 schedule, dynamic then static (then dynamic and static again: the spread)."""
+    import torch.nn as nn
+    import lic
+    from quantization import BaseQuantBlock, QuantModel, QuantModule, block_reconstruction, layer_reconstruction
+
+    def run(mode):
+        torch.manual_seed(1005)
+        model = lic.Cheng2020Anchor(N=8).cuda().eval()
+        g = torch.Generator().manual_seed(13)
+        cali = torch.rand(images, 3, 64, 64, generator=g).cuda()
+        wq = {"n_bits": 8, "channel_wise": True, "scale_method": "max"}
+        aq = {"n_bits": 8, "channel_wise": True, "scale_method": "max", "leaf_param": False}
+        qnn = QuantModel(model=model, weight_quant_params=wq, act_quant_params=aq, is_cheng=True).cuda().eval()
+        qnn.set_first_last_layer_to_8bit()
+        qnn.disable_network_output_quantization()
+        qnn.set_quant_state(True, False)
+        with torch.no_grad():
+            qnn(cali[:2])
+        timing = []
+        args = types.SimpleNamespace(lmbda=0.0483, task_loss=2.0, arch="Cheng2020", act_mode=mode, timing=timing)
+        kw = dict(cali_data=cali, batch_size=2, iters=iters, weight=0.01, input_prob=0.5, lr=4e-5, asym=True, b_range=(20, 2), warmup=0.2,
+                  act_quant=True, opt_mode="mse", config=None, args=args)
+        qnn.set_quant_state(True, True)
+
+        def walk(m: nn.Module):
+            for name, c in m.named_children():
+                if isinstance(c, QuantModule):
+                    layer_reconstruction(qnn, c, name, **kw)
+                elif isinstance(c, BaseQuantBlock):
+                    block_reconstruction(qnn, c, name, **kw)
+                else:
+                    walk(c)
+        walk(qnn)
+        return dict(mode=mode, images=images, units=len(timing), cache_s=round(sum(t["cache_s"] for t in timing), 4),
+                    act_s=round(sum(t.get("act_s", 0.0) for t in timing), 4), loop_s=round(sum(t["loop_s"] for t in timing), 4))
+    rows = []
+    for mode in ("dynamic", "static", "dynamic", "static"):
+        rows.append(run(mode))
+        print(json.dumps(rows[-1]), flush=True)
+    return rows
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--reps", type=int, default=1000, help="calls per timed window (7-33 us each: windows of 7 ms and more)")
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--flow", action="store_true")
+    ap.add_argument("--images", type=int, default=32)
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_actquant needs a GPU: there is no CPU path to time")
+    res = {"kernels": bench_kernels(a.reps, a.rounds)}
+    slow = [r["shape"] for r in res["kernels"] if r["static_slower"]]
+    if slow:
+        print(f"DEFECT: static slower than dynamic on {slow}", flush=True)
+    if a.flow:
+        res["flow"] = bench_flow(a.images)
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(res, f, indent=1)
+    return 1 if slow else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
