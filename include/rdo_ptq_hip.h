@@ -264,6 +264,24 @@ int rdo_actquant_search(const float* x, int64_t npix, int32_t C, int32_t n_bits,
                         float* err /* [C][10] */, float* ws /* rdo_actquant_search_workspace(C) floats, no initial state needed */,
                         void* stream);
 int64_t rdo_actquant_search_workspace(int32_t C);
+/* Backward of rdo_actquant_static with a straight-through round (extension: learned activation ranges, and the R + lambda*D task loss behind
+ * frozen quantisers).  y = the forward's value (the same expression on the same operands), r = max(hi_c - lo_c, 1e-6); an element is
+ * below if x < lo_c, above if x > hi_c (plain fp32 comparisons), inside otherwise:
+ *   dx       = g inside, 0 elsewhere                                  (dx == g allowed)
+ *   dlo_c   += sum_p g * (below ? 1 : above ? 0 : (x - y) / r)
+ *   dhi_c   += sum_p g * (above ? 1 : below ? 0 : (y - x) / r)
+ * A channel with hi_c - lo_c < 1e-6 receives zero range gradient.  One read of x and of g, one write of dx; per-workgroup partial sums in
+ * ws, folded in a fixed order (no atomics: the same input gives the same bits); no serial fp32 chain longer than 1024 terms.  drange is
+ * ACCUMULATED INTO (zero it before the first batch). */
+int rdo_actquant_static_bwd(const float* x, const float* g, int64_t npix, int32_t C, int32_t n_bits, const float* range /* [2 C] lo | hi */,
+                            float* dx, float* drange /* [2 C] */,
+                            float* ws /* rdo_actquant_static_bwd_workspace(C) floats, no initial state needed */, void* stream);
+int64_t rdo_actquant_static_bwd_workspace(int32_t C);
+/* One Adam step (beta = 0.9, 0.999; `step` = the count of this step, from 1) on a site's range with a per-channel step size relative to the
+ * observed width w_c = hi_obs,c - lo_obs,c: end += -lr * w_c * m^ / (sqrt(v^) + 1e-8); then the projection: both ends inside
+ * [lo_obs,c, hi_obs,c] and hi >= lo + 1e-3 w_c.  m, v [2 C]: the moments, updated.  C-sized. */
+int rdo_act_range_step(float* range /* [2 C], updated */, const float* grad /* [2 C] */, const float* obs /* [2 C] lo_obs | hi_obs */,
+                       float* m, float* v, int32_t C, int32_t step, float lr, void* stream);
 
 /* ---- K7: mini-batch assembly: out[b] = keep ? cache_q[idx[b]] : cache_fp[idx[b]], keep ~ counter RNG(seed, iter, i)
  * replaces cached_inps[..][idx] + torch.where(torch.rand_like(x) < p, x_q, x_fp)                layer_opt.py:289-292

@@ -446,6 +446,122 @@ __global__ __launch_bounds__(256) void aqs_fold_kernel(const float* part, int nb
     if (live && j == 0) err[i] += r;
 }
 
+// ---- backward of the static quantiser (straight-through rint): dx = g inside [lo, hi], 0 outside; per workgroup and channel the partial
+// sums of d/dlo and d/dhi.  With y the forward's value (aq_quant on the forward's operands: the same bits) an inside element contributes
+// g (x - y) / r to lo and g (y - x) / r to hi -- the quantisation residual over the width, which does not cancel on wide grids the way
+// t - q / R does -- an element below the range g to lo, one above it g to hi.  The region is decided by fp32 comparisons of x with the
+// ends, not from the normalised value.  Thread map and chain rule of aqs_partial_kernel: one read of x and of g, one write of dx (dx may
+// be g: every element is read and written by the same thread), four pixels in flight per thread; part = [workgroup][lo[C] | hi[C]],
+// folded by aqs_fold_kernel.  A channel narrower than 1e-6 (the forward's floor on the width) gets no range gradient.
+template <int W>
+__global__ __launch_bounds__(256) void aqb_partial_kernel(const float* x, const float* g, long npix, int C, const float* range, float bit_range,
+                                                          float* dx, float* part) {
+    typedef float vec_t __attribute__((ext_vector_type(W)));
+    const int QN = C / W;
+    const int qpb = QN < 256 ? QN : 256;
+    const int PL = 256 / qpb;
+    const int pl = threadIdx.x / qpb, ql = threadIdx.x - pl * qpb;
+    __shared__ float sm[W * 2 * 256];                      // [channel of the group][lo | hi][thread]
+    const long step = (long)gridDim.x * PL;
+    for (int qb = 0; qb < QN; qb += qpb) {
+        const int q = qb + ql;
+        const bool live = pl < PL && q < QN;
+        float acc[W][2], tot[W][2];
+#pragma unroll
+        for (int k = 0; k < W; ++k) acc[k][0] = acc[k][1] = tot[k][0] = tot[k][1] = 0.f;
+        if (live) {
+            float lo[W], hi[W], rng[W];
+            bool wide[W];
+#pragma unroll
+            for (int k = 0; k < W; ++k) {
+                lo[k] = range[q * W + k];
+                hi[k] = range[C + q * W + k];
+                rng[k] = fmaxf(hi[k] - lo[k], 1e-6f);
+                wide[k] = !(hi[k] - lo[k] < 1e-6f);
+            }
+            const long off = (long)q * W;
+            int run = 0;
+            auto pixel = [&](const vec_t xv, const vec_t gv, long p) {
+                vec_t d;
+#pragma unroll
+                for (int k = 0; k < W; ++k) {
+                    const bool below = xv[k] < lo[k], above = xv[k] > hi[k];
+                    const float y = aq_quant(xv[k], lo[k], rng[k], bit_range, 0.f);
+                    const float res = (xv[k] - y) / rng[k];                 // (y - x) / r is its exact negative
+                    const float tl = below ? 1.f : above ? 0.f : res;
+                    const float th = above ? 1.f : below ? 0.f : -res;
+                    acc[k][0] += wide[k] ? gv[k] * tl : 0.f;
+                    acc[k][1] += wide[k] ? gv[k] * th : 0.f;
+                    d[k] = (below || above) ? 0.f : gv[k];
+                }
+                *reinterpret_cast<vec_t*>(dx + off + p * C) = d;
+                if (++run == kAqsChain) {
+                    run = 0;
+#pragma unroll
+                    for (int k = 0; k < W; ++k) { tot[k][0] += acc[k][0]; tot[k][1] += acc[k][1]; acc[k][0] = acc[k][1] = 0.f; }
+                }
+            };
+            long p = (long)blockIdx.x * PL + pl;
+            for (; p + 3 * step < npix; p += 4 * step) {
+                vec_t xv[4], gv[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    xv[u] = *reinterpret_cast<const vec_t*>(x + off + (p + u * step) * C);
+                    gv[u] = *reinterpret_cast<const vec_t*>(g + off + (p + u * step) * C);
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) pixel(xv[u], gv[u], p + u * step);
+            }
+            for (; p < npix; p += step)
+                pixel(*reinterpret_cast<const vec_t*>(x + off + p * C), *reinterpret_cast<const vec_t*>(g + off + p * C), p);
+#pragma unroll
+            for (int k = 0; k < W; ++k) {
+                sm[(k * 2 + 0) * 256 + threadIdx.x] = tot[k][0] + acc[k][0];
+                sm[(k * 2 + 1) * 256 + threadIdx.x] = tot[k][1] + acc[k][1];
+            }
+        }
+        __syncthreads();
+        if (live && pl == 0) {
+            float* dst = part + (long)blockIdx.x * 2 * C + (long)q * W;
+#pragma unroll
+            for (int k = 0; k < W; ++k)
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    float r = sm[(k * 2 + e) * 256 + ql];
+                    for (int t = 1; t < PL; ++t) r += sm[(k * 2 + e) * 256 + t * qpb + ql];
+                    dst[e * C + k] = r;
+                }
+        }
+        __syncthreads();
+    }
+}
+
+// ---- one Adam step on a site's range [2C] = lo | hi, then the projection: thread = channel (the projection couples its two ends).  The
+// step is relative to the observed width w = hi_obs - lo_obs; both ends stay inside [lo_obs, hi_obs] and at least 1e-3 w apart.
+__global__ __launch_bounds__(256) void act_range_step_kernel(float* range, const float* grad, const float* obs, float* m, float* v, int C,
+                                                             float lr, float bc1, float bc2) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    const float lo0 = obs[c], hi0 = obs[C + c], w = hi0 - lo0;
+    float end[2];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        const int i = e * C + c;
+        const float gr = grad[i];
+        const float mi = 0.9f * m[i] + 0.1f * gr;
+        const float vi = 0.999f * v[i] + 0.001f * (gr * gr);
+        m[i] = mi;
+        v[i] = vi;
+        end[e] = range[i] - lr * w * (mi / bc1) / (sqrtf(vi / bc2) + 1e-8f);
+    }
+    const float gap = 1e-3f * w;
+    float lo = fminf(fmaxf(end[0], lo0), hi0), hi = fminf(fmaxf(end[1], lo0), hi0);
+    hi = fminf(fmaxf(hi, lo + gap), hi0);
+    lo = fmaxf(fminf(lo, hi - gap), lo0);
+    range[c] = lo;
+    range[C + c] = hi;
+}
+
 // ---- transposed conv as a sub-pixel conv: phase weights ----------------------------------------------------------------------------
 // ConvTranspose2d(k, stride s, padding p) with output size s * H is a stride-1 conv with s^2 * Cout output channels followed by a
 // pixel shuffle: output pixel (s i + a, s j + b) only ever meets the taps kh = (a + p) mod s + s t, and those taps read input rows
@@ -754,5 +870,42 @@ int rdo_actquant_search(const float* x, int64_t npix, int32_t C, int32_t n_bits,
 }
 
 int64_t rdo_actquant_search_workspace(int32_t C) { return C > 0 ? (int64_t)C * kAqsCand * kAqBlocks : 0; }
+
+int rdo_actquant_static_bwd(const float* x, const float* g, int64_t npix, int32_t C, int32_t n_bits, const float* range, float* dx,
+                            float* drange, float* ws, void* stream) {
+    RDO_REQUIRE(x && g && range && dx && drange && ws && npix > 0 && C > 0, "rdo_actquant_static_bwd: bad argument");
+    RDO_REQUIRE(n_bits >= 2 && n_bits <= 16, "rdo_actquant_static_bwd: n_bits %d outside [2, 16]", n_bits);
+    RDO_REQUIRE(dx != x, "rdo_actquant_static_bwd: dx may alias g, not x");
+    const float bit_range = (float)((1 << n_bits) - 1);
+    const bool vec = C % 4 == 0 && (reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(dx)) % 16 == 0;
+    return rdo::dispatch(
+        [=](hipStream_t s) {
+            const int W = vec ? 4 : 1;
+            const int QN = C / W, qpb = QN < 256 ? QN : 256, PL = 256 / qpb;
+            long nb = rdo::ceil_div(npix, (long)PL * 8);
+            const int nblk = (int)(nb < 1 ? 1 : (nb > kAqBlocks ? kAqBlocks : nb));
+            if (vec) hipLaunchKernelGGL(aqb_partial_kernel<4>, dim3(nblk), dim3(256), 0, s, x, g, (long)npix, C, range, bit_range, dx, ws);
+            else hipLaunchKernelGGL(aqb_partial_kernel<1>, dim3(nblk), dim3(256), 0, s, x, g, (long)npix, C, range, bit_range, dx, ws);
+            hipLaunchKernelGGL(aqs_fold_kernel, dim3((unsigned)rdo::ceil_div(2 * C, 16)), dim3(256), 0, s, ws, nblk, 2 * C, drange);
+            return rdo::check_launch("actquant_static_bwd");
+        },
+        stream, "actquant_static_bwd", 0.0, 12.0 * npix * C);
+}
+
+int64_t rdo_actquant_static_bwd_workspace(int32_t C) { return C > 0 ? 2 * (int64_t)C * kAqBlocks : 0; }
+
+int rdo_act_range_step(float* range, const float* grad, const float* obs, float* m, float* v, int32_t C, int32_t step, float lr,
+                       void* stream) {
+    RDO_REQUIRE(range && grad && obs && m && v && C > 0, "rdo_act_range_step: bad argument");
+    RDO_REQUIRE(step >= 1, "rdo_act_range_step: step %d (the count of this step, from 1)", step);
+    const float bc1 = (float)(1.0 - pow(0.9, (double)step)), bc2 = (float)(1.0 - pow(0.999, (double)step));
+    return rdo::dispatch(
+        [=](hipStream_t s) {
+            hipLaunchKernelGGL(act_range_step_kernel, dim3((unsigned)rdo::ceil_div((long)C, 256L)), dim3(256), 0, s, range, grad, obs, m, v, C,
+                               lr, bc1, bc2);
+            return rdo::check_launch("act_range_step");
+        },
+        stream, "act_range_step", 0.0, 40.0 * C);
+}
 
 }  // extern "C"

@@ -243,6 +243,31 @@ def round_ste(x):
     return x + (torch.round(x) - x).detach()
 
 
+class ActQuantStaticFn(torch.autograd.Function):
+    """The static per-channel activation quantiser (rdo_actquant_static) on the range rng [2C] = lo | hi with a straight-through round:
+    gradient to x inside the range, and to the two ends of every channel (rdo_actquant_static_bwd).  Layouts as the quantiser's own
+    `_act_rows`: channel = dim 1 of a 4-D / 2-D tensor, the last dim of a 3-D one or with `channels_last`."""
+
+    @staticmethod
+    def forward(ctx, x, rng, n_bits, channels_last):
+        from quantization.quantizer import _act_rows
+        xr, back = _act_rows(x, channels_last)
+        rng = rng.detach()
+        ctx.conf = (int(n_bits), bool(channels_last))
+        ctx.save_for_backward(xr, rng)
+        return back(ops.actquant_static(xr, rng, n_bits=n_bits))
+
+    @staticmethod
+    def backward(ctx, g):
+        from quantization.quantizer import _act_rows
+        xr, rng = ctx.saved_tensors
+        n_bits, channels_last = ctx.conf
+        gr, back = _act_rows(g, channels_last)
+        drange = torch.zeros_like(rng)
+        dx = ops.actquant_static_bwd(xr, gr, rng, drange, n_bits=n_bits)
+        return back(dx), drange, None, None
+
+
 class NegLog2SumFn(torch.autograd.Function):
     """scale * sum(-log2 p): the rate term of losses.RateDistortionLoss (rdo_neg_log2_sum) with its gradient."""
 

@@ -368,6 +368,32 @@ def actquant_search(x, rng, err, n_bits=8, ws=None):
     return err
 
 
+def actquant_static_bwd(x, g, rng, drange, dx=None, n_bits=8, ws=None):
+    """Backward of `actquant_static` with a straight-through round: returns dx (= g inside the range, 0 outside; `dx` may be g) and
+    accumulates the per-channel range gradient into drange [2C] = dlo | dhi.  x, g: [..., C] channels-last, contiguous."""
+    Cc, npix = _act_range_check(x, rng, "actquant_static_bwd")
+    if g.shape != x.shape or drange.numel() != 2 * Cc:
+        raise ValueError(f"actquant_static_bwd: g {tuple(g.shape)} / drange [{drange.numel()}] do not match x {tuple(x.shape)}")
+    dx = torch.empty_like(x) if dx is None else dx
+    need = int(L.lib().rdo_actquant_static_bwd_workspace(Cc))
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, device=x.device, dtype=torch.float32)
+    L.check(L.lib().rdo_actquant_static_bwd(_ptr(x), _ptr(g), npix, Cc, int(n_bits), _ptr(rng), _ptr(dx), _ptr(drange), _ptr(ws), _stream()),
+            "rdo_actquant_static_bwd")
+    return dx
+
+
+def act_range_step(rng, grad, obs, m, v, step, lr):
+    """One projected Adam step on a site's range [2C] (in place; m, v [2C] are its moments, `step` counts from 1, `obs` [2C] is the
+    observed max range the step size is relative to and the range stays inside)."""
+    n = rng.numel()
+    if n % 2 or any(t.numel() != n for t in (grad, obs, m, v)):
+        raise ValueError(f"act_range_step: range, grad, obs, m and v must all hold 2C = {n} floats")
+    L.check(L.lib().rdo_act_range_step(_ptr(rng), _ptr(grad), _ptr(obs), _ptr(m), _ptr(v), n // 2, int(step), float(lr), _stream()),
+            "rdo_act_range_step")
+    return rng
+
+
 def gather_qdrop(cache_q, cache_fp, idx_table, iter_ptr, B, prob, seed, out, batch_offset=0, iter_publish=None):
     """`batch_offset`: row of the global mini-batch this (data-parallel) rank's first row is -- the QDrop counter runs over the
     global batch, so N ranks with one seed draw the mask a single process would."""

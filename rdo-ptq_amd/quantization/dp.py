@@ -44,6 +44,16 @@ def reduce_act_stats(ranges=(), sums=(), group=None):
         dist.all_reduce(e, op=dist.ReduceOp.SUM, group=group)
 
 
+def reduce_act_grads(flat, group=None):
+    """Learned activation ranges under data parallelism: the concatenated range gradients of a unit's sites (every rank in the same
+    order) become their mean over the ranks, in place: SUM all-reduce, then the division by the world size."""
+    w = world(group)[1]
+    if w <= 1:
+        return flat
+    dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)
+    return flat.div_(w)
+
+
 class GradBucket:
     """The flat alpha-gradient bucket of one reconstruction unit and its collective.
 

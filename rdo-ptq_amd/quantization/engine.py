@@ -118,7 +118,7 @@ class _Op:
         if qm.kind not in ("conv", "gdn", "tconv", "linear", "layernorm"):
             raise NotImplementedError(f"calibration engine: QuantModule kind '{qm.kind}' is not supported yet")
         wq = qm.weight_quantizer
-        if not wq.inited:
+        if not getattr(wq, "inited", True):    # (an AdaRoundQuantizer -- a unit calibrated before, in a second pass -- carries its scales)
             wq(qm.weight)                      # lazy scale init, as the reference's first forward would do
         w = qm.org_weight.detach()
         if qm.kind == "linear":
@@ -1621,7 +1621,8 @@ class UnitEngine:
             with torch.enable_grad():
                 out = rd["model"](x)
                 loss = RateDistortionLoss(lmbda=rd["lmbda"], metric=rd.get("metric", "mse"))(out, x)["loss"]
-                (g,) = torch.autograd.grad(loss, [leaf], allow_unused=True)
+                # (a tape cut on EVERY path from the unit's output leaves a loss without a grad_fn: the same finding as a gradient of None)
+                g = torch.autograd.grad(loss, [leaf], allow_unused=True)[0] if loss.requires_grad else None
         finally:
             for m_ in patched:
                 del m_.forward

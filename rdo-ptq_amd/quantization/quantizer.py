@@ -128,9 +128,13 @@ class UniformAffineQuantizer(nn.Module):
         if act_mode not in ACT_MODES:
             raise ValueError(f"unknown act_mode {act_mode!r} {ACT_MODES}")
         self.act_mode = act_mode
-        self.act_phase = "idle"            # static only: "idle" (no range yet) | "observe" | "search" | "frozen"
-        self.act_range = {}                # site -> fp32 [2C], lo | hi
+        self.act_phase = "idle"            # static only: "idle" (no range yet) | "observe" | "search" | "frozen" | "learn"
+        self.act_range = {}                # site -> fp32 [2C], lo | hi (leaf tensors with requires_grad while learning)
         self.act_err = {}                  # site -> fp32 [C, 10] while searching
+        self.act_obs = {}                  # site -> fp32 [2C]: the observed max range, kept for / while learning the ranges
+        # frozen ranges on torch's tape (hipops.autograd.ActQuantStaticFn, straight-through round) when the input is tracked: set by
+        # recon.reconstruct for the duration of an R + lambda*D unit.  Absent on models pickled before it existed: read with getattr
+        self.act_ste = False
 
     def _apply(self, fn, *args, **kwargs):
         super()._apply(fn, *args, **kwargs)
@@ -138,7 +142,7 @@ class UniformAffineQuantizer(nn.Module):
             t = getattr(self, name, None)
             if torch.is_tensor(t):
                 setattr(self, name, fn(t))
-        for name in ("act_range", "act_err"):
+        for name in ("act_range", "act_err", "act_obs"):
             d = getattr(self, name, None)
             if isinstance(d, dict):
                 setattr(self, name, {k: fn(t) for k, t in d.items()})
@@ -148,14 +152,14 @@ class UniformAffineQuantizer(nn.Module):
     def set_act_mode(self, mode: str):
         if mode not in ACT_MODES:
             raise ValueError(f"unknown act_mode {mode!r} {ACT_MODES}")
-        for name, val in (("act_phase", "idle"), ("act_range", {}), ("act_err", {})):      # (an artefact of an earlier version)
+        for name, val in (("act_phase", "idle"), ("act_range", {}), ("act_err", {}), ("act_obs", {})):     # (an artefact of an earlier version)
             if not hasattr(self, name):
                 setattr(self, name, val)
         self.act_mode = mode
 
     def act_observe(self):
         """Start observing: every call quantises dynamically and merges the batch's per-channel min / max into the site's range."""
-        self.act_phase, self.act_range, self.act_err = "observe", {}, {}
+        self.act_phase, self.act_range, self.act_err, self.act_obs = "observe", {}, {}, {}
 
     def act_search(self):
         """Start the L2 search over the observed ranges: every call accumulates the ten candidates' squared errors and returns the
@@ -163,13 +167,28 @@ class UniformAffineQuantizer(nn.Module):
         if not self.act_range:
             raise RuntimeError("act_search: nothing was observed")
         self.act_phase = "search"
+        self.act_obs = {k: r.clone() for k, r in self.act_range.items()}
         self.act_err = {k: torch.zeros(r.numel() // 2, ops.ACT_SEARCH_CANDIDATES, device=r.device) for k, r in self.act_range.items()}
 
-    def act_freeze(self):
+    def act_learn(self):
+        """Start learning the frozen ranges: every site's range becomes a leaf tensor with requires_grad that the tracked forward
+        differentiates to (ActQuantStaticFn) and `ops.act_range_step` updates in place; `act_obs` holds the observed max range of every
+        site -- what a search kept (`act_freeze(keep_obs=True)`), else the frozen range itself (a 'max' range is its own max range).
+        `act_freeze()` ends the phase."""
+        if not self.act_frozen():
+            raise RuntimeError("act_learn: the ranges are not frozen (calibrate them first)")
+        obs = getattr(self, "act_obs", None) or {}
+        self.act_obs = {k: (obs[k] if k in obs else r.detach().clone()) for k, r in self.act_range.items()}
+        self.act_range = {k: r.detach().clone().requires_grad_(True) for k, r in self.act_range.items()}
+        self.act_phase = "learn"
+
+    def act_freeze(self, keep_obs: bool = False):
         """Fix the ranges.  After a search each channel shrinks to its best candidate lo * s_k | hi * s_k (first minimum, as `_init_search`
         keeps the first strictly better score).  Scaling towards zero moves an end that does not straddle zero (lo > 0 or hi < 0) OUT of
         the observed range, where no calibration value lies: such an end stays at the observed one, so a frozen range always lies inside
-        its max range.  A quantiser that was never applied stays without a range ("idle")."""
+        its max range.  A quantiser that was never applied stays without a range ("idle").  After learning the ranges are detached as they
+        stand.  `keep_obs`: keep the observed max ranges for a learning phase that follows (they are not part of a frozen quantiser)."""
+        self.act_range = {k: r.detach() for k, r in self.act_range.items()}
         for k, err in self.act_err.items():
             rng = self.act_range[k]
             c = rng.numel() // 2
@@ -179,6 +198,8 @@ class UniformAffineQuantizer(nn.Module):
             keep = lo > hi                                                 # (a candidate that left the observed range altogether)
             self.act_range[k] = torch.cat([torch.where(keep, rng[:c], lo), torch.where(keep, rng[c:], hi)])
         self.act_err = {}
+        if not keep_obs:
+            self.act_obs = {}
         self.act_phase = "frozen" if self.act_range else "idle"
 
     def act_frozen(self):
@@ -199,7 +220,10 @@ class UniformAffineQuantizer(nn.Module):
                                "(recon.py with args.act_mode='static'); there is no fall-back to the dynamic grid")
         if phase == "search":
             ops.actquant_search(xr, rng, self.act_err[site], n_bits=bits)
-        return back(ops.actquant_static(xr, rng, n_bits=bits))
+        if torch.is_grad_enabled() and (phase == "learn" or (phase == "frozen" and getattr(self, "act_ste", False) and x.requires_grad)):
+            from hipops.autograd import ActQuantStaticFn
+            return ActQuantStaticFn.apply(x, rng, bits, channels_last)
+        return back(ops.actquant_static(xr, rng.detach(), n_bits=bits))
 
     # -- scale initialisation -------------------------------------------------------------------------------------
     def _rows(self, x):

@@ -136,23 +136,46 @@ def _rd_metric(args, cali_data):
 
 def _act_args(args):
     """args.act_mode: 'dynamic' (default; the reference's ActQuant) or 'static' (per-channel ranges frozen from the calibration set);
-    args.act_range: how a static range is fixed, 'max' (default: min / max over the calibration set) or 'l2' (each channel then shrinks
-    to the best of ten candidates by squared error).  Checked before any work is done."""
+    args.act_range: how a static range is fixed, 'max' (default: min / max over the calibration set), 'l2' (each channel then shrinks
+    to the best of ten candidates by squared error) or 'learned' (the 'l2' ranges are then trained on the unit's reconstruction error:
+    `learn_act_ranges`, with args.act_iters steps, default 500, of size args.act_lr, default 1e-3, relative to a channel's observed
+    width).  Checked before any work is done."""
     mode = getattr(args, "act_mode", "dynamic") if args is not None else "dynamic"
     how = getattr(args, "act_range", "max") if args is not None else "max"
     if mode not in ("dynamic", "static"):
         raise ValueError(f"unknown act_mode {mode!r} ('dynamic' or 'static')")
-    if how not in ("max", "l2"):
-        raise ValueError(f"unknown act_range {how!r} ('max' or 'l2')")
+    if how not in ("max", "l2", "learned"):
+        raise ValueError(f"unknown act_range {how!r} ('max', 'l2' or 'learned')")
+    _act_learn_args(args)
     return mode, how
 
 
-def calibrate_act_ranges(unit, inp_q, act_range="max", batch=32):
+def _act_learn_args(args):
+    """(args.act_iters, args.act_lr) of act_range='learned', validated: a positive whole number of steps, a positive finite step size."""
+    iters = getattr(args, "act_iters", 500) if args is not None else 500
+    lr = getattr(args, "act_lr", 1e-3) if args is not None else 1e-3
+    return _check_learn(iters, lr)
+
+
+def _check_learn(iters, lr):
+    if isinstance(iters, bool) or not isinstance(iters, int) or iters < 1:
+        raise ValueError(f"act_iters must be a positive integer, got {iters!r}")
+    if isinstance(lr, bool) or not isinstance(lr, (int, float)) or not (0.0 < float(lr) < float("inf")):
+        raise ValueError(f"act_lr must be a positive finite number, got {lr!r}")
+    return iters, float(lr)
+
+
+def _is_rstb(unit):
+    return isinstance(unit, QuantRSTB) or getattr(unit, "unit_kind", None) == "rstb"
+
+
+def calibrate_act_ranges(unit, inp_q, act_range="max", batch=32, keep_obs=False):
     """Fix the static activation ranges of a calibrated unit: run it once over its cached quantised inputs in the state the W8A8
     evaluation uses (the unit, its QuantModules and nested block wrappers with weight and activation quantisation on) with its quantisers
     observing, then freeze them; with act_range='l2' a second pass over the same inputs accumulates the candidates' squared errors
     first.  Under data parallelism the observed ranges and the error sums are reduced over the ranks before they are used, so every
-    rank freezes the same grid.  Every quant state flag is left as it was found."""
+    rank freezes the same grid.  Every quant state flag is left as it was found.  `keep_obs`: the quantisers keep the observed max ranges
+    next to the frozen ones (`act_obs`) for `learn_act_ranges`."""
     mods = [m for m in unit.modules() if isinstance(m, (QuantModule, BaseQuantBlock))]
     quants = [m.act_quantizer for m in mods]
     states = [(m, m.use_weight_quant, m.use_act_quant) for m in mods]
@@ -179,26 +202,94 @@ def calibrate_act_ranges(unit, inp_q, act_range="max", batch=32):
             run()
             dp.reduce_act_stats(sums=applied("act_err"))
         for q in quants:
-            q.act_freeze()
+            q.act_freeze(keep_obs=keep_obs)
     finally:
         for m, w, a_ in states:
             m.use_weight_quant, m.use_act_quant = w, a_
 
 
-def reconstruct(model, unit, unit_name, cali_data, *a, **kw):
-    """`_reconstruct` with the one piece of cross-unit state tidied up on failure: the full-precision cache memo of the schedule
-    (quantization/utils.py::_FpMemo) is dropped when a unit raises, so a schedule that dies half-way pins no device memory."""
+def learn_act_ranges(unit, inp_q, out_fp, iters=500, lr=1e-3, batch=32, seed=0, idx_table=None):
+    """Train the frozen static activation ranges of a calibrated unit on its reconstruction error (the activation-grid step of BRECQ /
+    QDrop, after the rounding has been learned).  The unit runs in the W8A8 state with its hard-rounded weights under torch's tape (the
+    modules' tape forwards; every frozen quantiser as `ActQuantStaticFn`, straight-through round) on mini-batches inp_q[idx] of `batch`
+    rows (never a ragged one; idx from a generator seeded with `seed`, or the rows of `idx_table` [iters, batch]); the loss is
+    lp_loss(out, out_fp[idx], p=2); every site range the forward reached takes one projected Adam step per iteration
+    (`ops.act_range_step`: step size relative to the observed width, the range stays inside the observed max range).  Under data
+    parallelism the range gradients of all sites, concatenated in the fixed site order of `calibrate_act_ranges`, are summed over the
+    ranks and divided by the world size before the step, so every rank holds the same grids.  The quantisers end frozen; every quant
+    state flag is left as it was found."""
+    from hipops.autograd import SqDiffSumFn
+    if _is_rstb(unit):
+        raise NotImplementedError("learn_act_ranges: a Swin (RSTB) unit's activation-quantised window attention cannot sit on torch's tape "
+                                  "(quant_block.QuantWindowAttention); use act_range='max' or 'l2' for it")
+    iters, lr = _check_learn(iters, lr)
+    mods = [m for m in unit.modules() if isinstance(m, (QuantModule, BaseQuantBlock))]
+    quants = list({id(m.act_quantizer): m.act_quantizer for m in mods if m.act_quantizer.act_frozen()}.values())
+    states = [(m, m.use_weight_quant, m.use_act_quant) for m in mods]
+    n = inp_q.shape[0]
+    B = max(1, min(int(batch), n))
+    if idx_table is None:
+        g = torch.Generator().manual_seed(int(seed))
+        idx_table = torch.stack([torch.randperm(n, generator=g)[:B] for _ in range(iters)])
+    if idx_table.dim() != 2 or idx_table.shape[0] < iters:
+        raise ValueError(f"learn_act_ranges: idx_table must be [iters >= {iters}, batch], got {tuple(idx_table.shape)}")
+    idx_table = idx_table.to(device=inp_q.device, dtype=torch.long)
+    world_size = dp.world()[1]
     try:
-        return _reconstruct(model, unit, unit_name, cali_data, *a, **kw)
+        for m in mods:
+            m.use_weight_quant = m.use_act_quant = True
+        for q in quants:
+            q.act_learn()
+        sites = [(q, k) for q in quants for k in sorted(q.act_range)]          # in a fixed order: the collectives of all ranks must line up
+        moments = [(torch.zeros_like(q.act_obs[k]), torch.zeros_like(q.act_obs[k])) for q, k in sites]
+        steps = [0] * len(sites)
+        for it in range(iters):
+            idx = idx_table[it]
+            x = inp_q.index_select(0, idx).detach().requires_grad_(True)
+            tgt = out_fp.index_select(0, idx)
+            with torch.enable_grad():
+                out = unit(x)
+                loss = SqDiffSumFn.apply(out, tgt, float(out.shape[1]) / out.numel())      # = lp_loss(out, tgt, p=2)
+                grads = torch.autograd.grad(loss, [q.act_range[k] for q, k in sites], allow_unused=True)
+            if world_size > 1:
+                flat = torch.cat([torch.zeros_like(q.act_obs[k]) if g_ is None else g_ for (q, k), g_ in zip(sites, grads)])
+                dp.reduce_act_grads(flat)
+                grads = [None if g_ is None else f for g_, f in zip(grads, flat.split([q.act_obs[k].numel() for q, k in sites]))]
+            for i, ((q, k), g_) in enumerate(zip(sites, grads)):
+                if g_ is None:                        # a site this forward did not reach
+                    continue
+                steps[i] += 1
+                ops.act_range_step(q.act_range[k], g_.contiguous(), q.act_obs[k], moments[i][0], moments[i][1], steps[i], lr)
+    finally:
+        for q in quants:
+            if getattr(q, "act_phase", "idle") == "learn":
+                q.act_freeze()
+            else:
+                q.act_obs = {}
+        for m, w, a_ in states:
+            m.use_weight_quant, m.use_act_quant = w, a_
+
+
+def reconstruct(model, unit, unit_name, cali_data, *a, **kw):
+    """`_reconstruct` with the cross-unit state tidied up: the full-precision cache memo of the schedule
+    (quantization/utils.py::_FpMemo) is dropped when a unit raises, so a schedule that dies half-way pins no device memory; and the
+    quantisers that `_reconstruct` put on torch's tape for the unit (`act_ste`: loss_mode='rd' behind frozen activation quantisers) are
+    taken off it again, whatever happened."""
+    ste = []
+    try:
+        return _reconstruct(model, unit, unit_name, cali_data, *a, _ste=ste, **kw)
     except BaseException:
         from .utils import _FpMemo
         _FpMemo.clear()
         raise
+    finally:
+        for q in ste:
+            q.act_ste = False
 
 
 def _reconstruct(model, unit, unit_name, cali_data, batch_size=32, iters=20000, weight=0.01, opt_mode="mse", asym=False,
                  include_act_func=True, b_range=(20, 2), warmup=0.0, input_prob=1.0, act_quant=False, lr=4e-5, p=2.0,
-                 config=None, args=None, is_block=False):
+                 config=None, args=None, is_block=False, _ste=None):
     if opt_mode != "mse":
         # The reference cannot run these modes on a compression model either: its LossFunction returns None for them whenever a coder
         # tail output is passed (layer_opt.py:146-151, always the case in its loops, so `err.backward()` fails), and GetLayerGrad feeds
@@ -212,6 +303,10 @@ def _reconstruct(model, unit, unit_name, cali_data, batch_size=32, iters=20000, 
         raise ValueError("--task_loss < 1 has no finite gradient at zero error")
     rd_metric = _rd_metric(args, cali_data)
     act_mode, act_range = _act_args(args)
+    act_iters, act_lr = _act_learn_args(args)
+    if act_quant and act_mode == "static" and act_range == "learned" and _is_rstb(unit):
+        raise NotImplementedError("act_range='learned': a Swin (RSTB) unit's activation-quantised window attention cannot sit on torch's "
+                                  "tape (quant_block.QuantWindowAttention); calibrate it with act_range='max' or 'l2'")
     rank, world_size = dp.world()
     if world_size > 1:                      # data parallel: this rank calibrates on its shard with its share of the batch
         if batch_size % world_size != 0:
@@ -240,6 +335,13 @@ def _reconstruct(model, unit, unit_name, cali_data, batch_size=32, iters=20000, 
         for m in model.modules():
             if isinstance(m, (QuantModule, BaseQuantBlock)) and getattr(m.act_quantizer, "act_mode", "dynamic") != act_mode:
                 m.act_quantizer.set_act_mode(act_mode)
+    if static_act and getattr(args, "loss_mode", "lp") == "rd" and _ste is not None:
+        # the R + lambda*D task loss differentiates through the trained modules behind the unit: their frozen quantisers go on torch's tape
+        # (straight-through round) for the duration of this unit; `reconstruct` clears the flag.  The cache passes run without a tape.
+        for m in model.modules():
+            if isinstance(m, (QuantModule, BaseQuantBlock)) and m.act_quantizer.act_frozen() and not getattr(m.act_quantizer, "act_ste", False):
+                m.act_quantizer.act_ste = True
+                _ste.append(m.act_quantizer)
     cache_bs = 1 if (act_quant and not static_act) else max(1, min(32, cali_data.size(0)))
     (inp_q, inp_fp), out_fp = save_inp_oup_data(model, unit, cali_data, asym, act_quant, batch_size=cache_bs, input_prob=True)
     t1 = _mark()
@@ -322,7 +424,11 @@ def _reconstruct(model, unit, unit_name, cali_data, batch_size=32, iters=20000, 
         # W8A8 evaluation apply those quantisers all the same (utils.set_mode).  What decides is whether a later forward applies the
         # quantiser: one behind `disable_act_quant` is never called, observes nothing and stays without a range.
         t4 = _mark()
-        calibrate_act_ranges(unit, inp_q, act_range, batch=cache_bs)
+        if act_range == "learned":
+            calibrate_act_ranges(unit, inp_q, "l2", batch=cache_bs, keep_obs=True)         # the starting ranges
+            learn_act_ranges(unit, inp_q, out_fp, act_iters, act_lr, batch_size, seed=unit_seed(unit_name))
+        else:
+            calibrate_act_ranges(unit, inp_q, act_range, batch=cache_bs)
         if timing is not None:
             timing[-1]["act_s"] = _mark() - t4
     return eng

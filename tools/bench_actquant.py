@@ -4,17 +4,22 @@
 Kernel part: device-event timing after warm-up, the two quantisers ALTERNATING in one process (dynamic round, static round, ...; the
 median round is reported), µs per call and GB/s against algorithmic bytes -- static 8 B per element (one read, one write), dynamic 12
 (two reads, one write).  The static call does a strict subset of the dynamic call's work: a shape on which it is slower is flagged.
-The range search (one read, ten candidates) is timed next to them.
+The range search (one read, ten candidates) is timed next to them; with --bwd also the backward of the static quantiser (two reads, one
+write: 12 B per element), whose share of the static forward's GB/s on the same tensor is reported.
+
+Learning part (--learn): wall time of `recon.learn_act_ranges` on one Cheng2020 block unit at N = 192 (a ResidualBlock on 32^2 inputs, what
+g_a[5] sees for 256^2 crops), after a short warm-up run, device synchronised at both ends.
 
 Flow part (--flow): the cache-building wall (`args.timing`, `cache_s`) of a W8A8 calibration schedule of a toy Cheng2020 (N = 8, 64^2
 crops) in both modes -- dynamic grids build every unit's caches image by image, static ones in batches.
 
-    python tools/bench_actquant.py [--reps 1000] [--rounds 7] [--flow] [--images 32] [--json out.json]"""
+    python tools/bench_actquant.py [--reps 1000] [--rounds 7] [--bwd] [--learn] [--flow] [--images 32] [--json out.json]"""
 import argparse
 import json
 import os
 import statistics
 import sys
+import time
 import types
 
 import torch
@@ -36,7 +41,7 @@ def _time_us(fn, reps):
     return a.elapsed_time(b) * 1e3 / reps
 
 
-def bench_kernels(reps, rounds, n_bits=8):
+def bench_kernels(reps, rounds, n_bits=8, bwd=False):
     from hipops import ops
     L = ops.L
     rows = []
@@ -55,6 +60,11 @@ def bench_kernels(reps, rounds, n_bits=8):
             "static": lambda: ops.actquant_static(x, rng, out=out, n_bits=n_bits),
             "search": lambda: ops.actquant_search(x, rng, err, n_bits=n_bits, ws=sws),
         }
+        if bwd:
+            gx = torch.randn(*shape, generator=g).cuda()
+            dx, dr = torch.empty_like(x), torch.zeros(2 * C, device="cuda")
+            bws = torch.empty(int(L.lib().rdo_actquant_static_bwd_workspace(C)), device="cuda")
+            calls["bwd"] = lambda: ops.actquant_static_bwd(x, gx, rng, dr, dx=dx, n_bits=n_bits, ws=bws)
         r = reps
         for fn in calls.values():                              # warm-up: code objects, caches
             for _ in range(10):
@@ -73,8 +83,45 @@ def bench_kernels(reps, rounds, n_bits=8):
                    dynamic_gbs=round(12.0 * n / med["dynamic"] / 1e3, 1), static_gbs=round(8.0 * n / med["static"] / 1e3, 1),
                    search_gbs=round(4.0 * n / med["search"] / 1e3, 1),
                    speedup=round(med["dynamic"] / med["static"], 2), static_slower=bool(med["static"] > med["dynamic"]))
+        if bwd:
+            bwd_gbs = 12.0 * n / med["bwd"] / 1e3
+            row.update(bwd_us=round(med["bwd"], 2), bwd_spread_us=[round(min(t["bwd"]), 2), round(max(t["bwd"]), 2)], bwd_gbs=round(bwd_gbs, 1),
+                       bwd_share_of_static_gbs=round(bwd_gbs / (8.0 * n / med["static"] / 1e3), 2))
         rows.append(row)
         print(json.dumps(row), flush=True)
+    return rows
+
+
+def bench_learn(iters=100, images=64, batch=32, n=192, side=32, bits=8):
+    """`learn_act_ranges` on a ResidualBlock unit (N = 192, three quantisation points), seconds per `iters` steps and per 500."""
+    import lic
+    from quantization import BaseQuantBlock, QuantModule
+    from quantization.quant_block import QuantRB
+    from quantization.recon import calibrate_act_ranges, learn_act_ranges
+    torch.manual_seed(1005)
+    wq = {"n_bits": 8, "channel_wise": True, "scale_method": "max"}
+    aq = {"n_bits": 8, "channel_wise": True, "scale_method": "max", "leaf_param": False, "dynamic_bits": bits, "act_mode": "static"}
+    unit = QuantRB(lic.ResidualBlock(n, n), wq, aq).cuda().eval()
+    x = torch.randn(images, n, side, side, generator=torch.Generator().manual_seed(3)).cuda()
+    unit.set_quant_state(False, False)
+    with torch.no_grad():
+        out_fp = unit(x).clone()
+    for m in unit.modules():
+        if isinstance(m, (QuantModule, BaseQuantBlock)):
+            m.trained = True
+    rows = []
+    for rep in range(3):
+        calibrate_act_ranges(unit, x, "l2", batch=batch, keep_obs=True)
+        learn_act_ranges(unit, x, out_fp, 10, 1e-3, batch, seed=1)              # warm-up: code objects, weight packs, allocator
+        calibrate_act_ranges(unit, x, "l2", batch=batch, keep_obs=True)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        learn_act_ranges(unit, x, out_fp, iters, 1e-3, batch, seed=1)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        rows.append(dict(unit=f"ResidualBlock N={n}", inputs=[images, n, side, side], batch=batch, iters=iters, wall_s=round(dt, 4),
+                         ms_per_iter=round(1e3 * dt / iters, 3), s_per_500=round(dt / iters * 500, 3)))
+        print(json.dumps(rows[-1]), flush=True)
     return rows
 
 
@@ -125,16 +172,20 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--reps", type=int, default=1000, help="calls per timed window (7-33 us each: windows of 7 ms and more)")
     ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--bwd", action="store_true", help="also time the backward of the static quantiser")
+    ap.add_argument("--learn", action="store_true", help="time learn_act_ranges on one N = 192 block unit")
     ap.add_argument("--flow", action="store_true")
     ap.add_argument("--images", type=int, default=32)
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_actquant needs a GPU: there is no CPU path to time")
-    res = {"kernels": bench_kernels(a.reps, a.rounds)}
+    res = {"kernels": bench_kernels(a.reps, a.rounds, bwd=a.bwd)}
     slow = [r["shape"] for r in res["kernels"] if r["static_slower"]]
     if slow:
         print(f"DEFECT: static slower than dynamic on {slow}", flush=True)
+    if a.learn:
+        res["learn"] = bench_learn()
     if a.flow:
         res["flow"] = bench_flow(a.images)
     if a.json:
