@@ -1,0 +1,432 @@
+// K6 -- per-channel activation quantisers on NHWC fp32 tensors (channel = fastest dim): the dynamic quantiser (min | max of the tensor
+// itself), the static one (a frozen lo | hi pair), the range search, the static backward and the Adam step of learned ranges.
+// Built with -ffp-contract=off (products and sums round separately, like the reference's op chains).
+//
+// Three of them reduce over the pixels per channel, and all three do it the same way, without atomics: up to kAqBlocks workgroups each
+// leave one row of partial values for their share of the pixels (aq_partial below), a small second kernel folds the rows (aq_fold_kernel).
+// (The first version let 1024 workgroups atomicMin / atomicMax into the same 2 C words: 0.4 M contended atomics per call were most of its
+// time.)  The order of the fp32 additions is fixed HERE, once, and frozen ranges depend on it: a thread's running sum over its pixels in
+// ascending order, closed into a second sum every kAqsChain pixels (tot + acc at the end), lane 0 adding the pixel lanes 1 .. PL - 1 in
+// ascending order onto its own, the fold's lane j adding the rows j, j + 16, .. serially, then the xor tree 8, 4, 2, 1.  No serial chain
+// is longer than 1024 terms: kAqsChain pixels, at most 256 pixel lanes, at most kAqBlocks / 16 rows per lane.
+#include <initializer_list>
+#include <type_traits>
+
+#include "rdo_common.h"
+
+namespace {
+
+using rdo::grid_for;
+
+constexpr int kAqBlocks = 256;
+constexpr int kAqsCand = 10;
+constexpr int kAqsChain = 1024;
+
+// thread = (pixel lane, group of W channels): qpb groups side by side, PL pixel lanes of them in a workgroup of 256
+struct AqGeom { int QN, qpb, PL; };
+__host__ __device__ inline AqGeom aq_geom(int C, int W) {
+    const int QN = C / W, qpb = QN < 256 ? QN : 256;
+    return AqGeom{QN, qpb, 256 / qpb};
+}
+// enough workgroups to keep HBM busy, few enough that each has >= 8 pixels per lane to amortise its fold
+inline int aq_blocks(long npix, int C, int W) {
+    const long g = rdo::ceil_div(npix, (long)aq_geom(C, W).PL * 8);
+    return (int)(g < 1 ? 1 : (g > kAqBlocks ? kAqBlocks : g));
+}
+
+// one element on the per-channel grid [zp, zp + rng] with bit_range steps; `lowest` is the lower clamp of the normalised value: -1 in the
+// dynamic quantiser (the reference's clamp; x - min is never negative there), 0 with a frozen range (x may lie below it).  The dynamic
+// and the static quantiser, the range search and the backward all evaluate THIS expression: same numbers in, same bits out.
+__device__ __forceinline__ float aq_quant(float x, float zp, float rng, float bit_range, float lowest) {
+    const float xn = x - zp;
+    const float q = rintf(fminf(fmaxf(xn / rng, lowest), 1.f) * bit_range);
+    return (q / bit_range) * rng + zp;
+}
+
+// ---- the partial skeleton: W-wide loads down the pixels, FLIGHT of them in flight, then an LDS fold over the pixel lanes.  A Body gives
+// what differs: N values per channel, their start value zero(e) and combine(a, b, e), begin(q, C) for a new channel group, load(off) of
+// one pixel's operands and pixel(in, off, acc) on them (off = element offset of the group's first channel in that pixel), kChain
+// (close the running values every kAqsChain pixels: sums only) and the row layout ([channel][N] or [N][channel]).
+template <int W, int FLIGHT, class Body>
+__device__ __forceinline__ void aq_partial(Body b, long npix, int C, float* part) {
+    constexpr int N = Body::N;
+    const AqGeom m = aq_geom(C, W);
+    const int pl = threadIdx.x / m.qpb, ql = threadIdx.x - pl * m.qpb;
+    __shared__ float sm[W * N * 256];                      // [channel of the group][value][thread]: conflict-free both ways
+    const long step = (long)gridDim.x * m.PL;
+    for (int qb = 0; qb < m.QN; qb += m.qpb) {
+        const int q = qb + ql;
+        const bool live = pl < m.PL && q < m.QN;
+        if (live) {
+            float acc[W][N], tot[W][N];
+#pragma unroll
+            for (int k = 0; k < W; ++k)
+#pragma unroll
+                for (int e = 0; e < N; ++e) acc[k][e] = tot[k][e] = Body::zero(e);
+            b.begin(q, C);
+            const long off = (long)q * W;
+            int run = 0;
+            auto one = [&](const typename Body::in_t& v, long p) {
+                b.pixel(v, off + p * C, acc);
+                if (Body::kChain && ++run == kAqsChain) {
+                    run = 0;
+#pragma unroll
+                    for (int k = 0; k < W; ++k)
+#pragma unroll
+                        for (int e = 0; e < N; ++e) { tot[k][e] += acc[k][e]; acc[k][e] = 0.f; }
+                }
+            };
+            long p = (long)blockIdx.x * m.PL + pl;
+            if constexpr (FLIGHT > 1) {
+                for (; p + (FLIGHT - 1) * step < npix; p += FLIGHT * step) {
+                    typename Body::in_t v[FLIGHT];
+#pragma unroll
+                    for (int u = 0; u < FLIGHT; ++u) v[u] = b.load(off + (p + u * step) * C);
+#pragma unroll
+                    for (int u = 0; u < FLIGHT; ++u) one(v[u], p + u * step);
+                }
+            }
+            for (; p < npix; p += step) one(b.load(off + p * C), p);
+#pragma unroll
+            for (int k = 0; k < W; ++k)
+#pragma unroll
+                for (int e = 0; e < N; ++e) sm[(k * N + e) * 256 + threadIdx.x] = Body::kChain ? tot[k][e] + acc[k][e] : acc[k][e];
+        }
+        __syncthreads();
+        if (live && pl == 0) {
+            float* dst = part + (long)blockIdx.x * N * C;
+#pragma unroll
+            for (int k = 0; k < W; ++k)
+#pragma unroll
+                for (int e = 0; e < N; ++e) {
+                    float r = sm[(k * N + e) * 256 + ql];
+                    for (int t = 1; t < m.PL; ++t) r = Body::combine(r, sm[(k * N + e) * 256 + t * m.qpb + ql], e);
+                    dst[Body::kChannelMajor ? (q * W + k) * N + e : e * C + q * W + k] = r;
+                }
+        }
+        __syncthreads();
+    }
+}
+
+// ---- dynamic quantiser: min | max of the tensor, part = [workgroup][min[C] | max[C]] behind the 2 C result floats of the workspace
+template <int W>
+struct AqMinMax {
+    typedef float in_t __attribute__((ext_vector_type(W)));
+    static constexpr int N = 2;
+    static constexpr bool kChain = false, kChannelMajor = false;
+    const float* x;
+    __device__ static float zero(int e) { return e ? -INFINITY : INFINITY; }
+    __device__ static float combine(float a, float v, int e) { return e ? fmaxf(a, v) : fminf(a, v); }
+    __device__ void begin(int, int) {}
+    __device__ in_t load(long off) const { return *reinterpret_cast<const in_t*>(x + off); }
+    __device__ void pixel(const in_t& v, long, float (&acc)[W][N]) const {
+#pragma unroll
+        for (int k = 0; k < W; ++k) { acc[k][0] = fminf(acc[k][0], v[k]); acc[k][1] = fmaxf(acc[k][1], v[k]); }
+    }
+};
+template <int W>
+__global__ __launch_bounds__(256) void aq_partial_kernel(const float* x, long npix, int C, float* part) {
+    aq_partial<W, 4>(AqMinMax<W>{x}, npix, C, part);
+}
+
+// ---- range search: err[c][k] = sum over pixels of (x - Q_k(x))^2 for the ten shrunk ranges lo * s_k | hi * s_k, s_k = 1 - 0.05 k
+// (the candidates of UniformAffineQuantizer._init_search, quantizer.py:260-265 of the reference, on the activation grid): one read of
+// x, W x 10 running sums (and as many closed ones) in registers, so one pixel in flight; part = [workgroup][C][10].
+template <int W>
+struct AqSearch {
+    typedef float in_t __attribute__((ext_vector_type(W)));
+    static constexpr int N = kAqsCand;
+    static constexpr bool kChain = true, kChannelMajor = true;
+    const float* x;
+    const float* range;
+    float bit_range;
+    float lo[W], hi[W];
+    __device__ static float zero(int) { return 0.f; }
+    __device__ static float combine(float a, float v, int) { return a + v; }
+    __device__ void begin(int q, int C) {
+#pragma unroll
+        for (int k = 0; k < W; ++k) { lo[k] = range[q * W + k]; hi[k] = range[C + q * W + k]; }
+    }
+    __device__ in_t load(long off) const { return *reinterpret_cast<const in_t*>(x + off); }
+    __device__ void pixel(const in_t& v, long, float (&acc)[W][N]) const {
+#pragma unroll
+        for (int j = 0; j < kAqsCand; ++j) {
+            const float s = (float)(1.0 - 0.05 * j);
+#pragma unroll
+            for (int k = 0; k < W; ++k) {
+                const float zp = lo[k] * s;
+                const float rng = fmaxf(hi[k] * s - zp, 1e-6f);
+                const float d = v[k] - aq_quant(v[k], zp, rng, bit_range, 0.f);
+                acc[k][j] += d * d;
+            }
+        }
+    }
+};
+template <int W>
+__global__ __launch_bounds__(256) void aqs_partial_kernel(const float* x, long npix, int C, const float* range, float bit_range, float* part) {
+    aq_partial<W, 1>(AqSearch<W>{x, range, bit_range}, npix, C, part);
+}
+
+// ---- backward of the static quantiser (straight-through rint): dx = g inside [lo, hi], 0 outside; per workgroup and channel the partial
+// sums of d/dlo and d/dhi.  With y the forward's value (aq_quant on the forward's operands: the same bits) an inside element contributes
+// g (x - y) / r to lo and g (y - x) / r to hi -- the quantisation residual over the width, which does not cancel on wide grids the way
+// t - q / R does -- an element below the range g to lo, one above it g to hi.  The region is decided by fp32 comparisons of x with the
+// ends, not from the normalised value.  One read of x and of g, one write of dx (dx may be g: every element is read and written by the
+// same thread, and the loads of the pixels in flight come before their stores); part = [workgroup][lo[C] | hi[C]].  A channel narrower
+// than 1e-6 (the forward's floor on the width) gets no range gradient.
+template <int W>
+struct AqBackward {
+    typedef float vec_t __attribute__((ext_vector_type(W)));
+    struct in_t { vec_t x, g; };
+    static constexpr int N = 2;
+    static constexpr bool kChain = true, kChannelMajor = false;
+    const float* x;
+    const float* g;
+    const float* range;
+    float bit_range;
+    float* dx;
+    float lo[W], hi[W], rng[W];
+    bool wide[W];
+    __device__ static float zero(int) { return 0.f; }
+    __device__ static float combine(float a, float v, int) { return a + v; }
+    __device__ void begin(int q, int C) {
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+            lo[k] = range[q * W + k];
+            hi[k] = range[C + q * W + k];
+            rng[k] = fmaxf(hi[k] - lo[k], 1e-6f);
+            wide[k] = !(hi[k] - lo[k] < 1e-6f);
+        }
+    }
+    __device__ in_t load(long off) const { return in_t{*reinterpret_cast<const vec_t*>(x + off), *reinterpret_cast<const vec_t*>(g + off)}; }
+    __device__ void pixel(const in_t& v, long off, float (&acc)[W][N]) const {
+        vec_t d;
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+            const bool below = v.x[k] < lo[k], above = v.x[k] > hi[k];
+            const float y = aq_quant(v.x[k], lo[k], rng[k], bit_range, 0.f);
+            const float res = (v.x[k] - y) / rng[k];                 // (y - x) / r is its exact negative
+            const float tl = below ? 1.f : above ? 0.f : res;
+            const float th = above ? 1.f : below ? 0.f : -res;
+            acc[k][0] += wide[k] ? v.g[k] * tl : 0.f;
+            acc[k][1] += wide[k] ? v.g[k] * th : 0.f;
+            d[k] = (below || above) ? 0.f : v.g[k];
+        }
+        *reinterpret_cast<vec_t*>(dx + off) = d;
+    }
+};
+template <int W>
+__global__ __launch_bounds__(256) void aqb_partial_kernel(const float* x, const float* g, long npix, int C, const float* range, float bit_range,
+                                                          float* dx, float* part) {
+    aq_partial<W, 4>(AqBackward<W>{x, g, range, bit_range, dx}, npix, C, part);
+}
+
+// ---- fold of the `nblk` partial rows of n entries: sixteen lanes per entry walk the rows (independent loads, no serial chain of nblk
+// round trips; the values still combine in row order), then fold across the lanes.  SUM: out[i] += the sum; else out[i] = min (first half
+// of the entries) | max (second half).
+template <bool SUM>
+__global__ __launch_bounds__(256) void aq_fold_kernel(const float* part, int nblk, int n, float* out) {
+    const int i = blockIdx.x * 16 + (threadIdx.x >> 4), j = threadIdx.x & 15;
+    const bool live = i < n;
+    const bool is_max = i >= n / 2;
+    auto combine = [&](float a, float v) { return SUM ? a + v : is_max ? fmaxf(a, v) : fminf(a, v); };
+    float r = SUM ? 0.f : is_max ? -INFINITY : INFINITY;
+    if (live) {
+        const float* src = part + i;
+        int b = j;
+        for (; b + 48 < nblk; b += 64) {
+            float v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) v[u] = src[(long)(b + 16 * u) * n];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) r = combine(r, v[u]);
+        }
+        for (; b < nblk; b += 16) r = combine(r, src[(long)b * n]);
+    }
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) r = combine(r, __shfl_xor(r, o, 16));
+    if (live && j == 0) out[i] = SUM ? out[i] + r : r;
+}
+
+// STATIC = false: ws = this tensor's own min | max (aq_fold_kernel); true: ws = a frozen lo | hi pair (rdo_actquant_static)
+template <int W, bool STATIC = false>
+__global__ __launch_bounds__(256) void aq_apply_kernel(const float* x, long nvec, int C, const float* ws, float bit_range, float* out) {
+    typedef float vec_t __attribute__((ext_vector_type(W)));
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += (long)gridDim.x * blockDim.x) {
+        const int c = (int)((i * W) % C);
+        const vec_t xv = *reinterpret_cast<const vec_t*>(x + i * W);
+        vec_t o;
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+            const float zp = ws[c + k];
+            const float rng = fmaxf(ws[C + c + k] - zp, 1e-6f);
+            o[k] = aq_quant(xv[k], zp, rng, bit_range, STATIC ? 0.f : -1.f);
+        }
+        *reinterpret_cast<vec_t*>(out + i * W) = o;
+    }
+}
+
+// observation: fold this batch's min | max (the first 2 C floats the dynamic call leaves in its workspace) into a running lo | hi
+__global__ __launch_bounds__(256) void aq_merge_kernel(const float* ws, int C, float* range) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < 2 * C) range[i] = i < C ? fminf(range[i], ws[i]) : fmaxf(range[i], ws[i]);
+}
+
+// ---- one Adam step on a site's range [2C] = lo | hi, then the projection: thread = channel (the projection couples its two ends).  The
+// step is relative to the observed width w = hi_obs - lo_obs; both ends stay inside [lo_obs, hi_obs] and at least 1e-3 w apart.
+__global__ __launch_bounds__(256) void act_range_step_kernel(float* range, const float* grad, const float* obs, float* m, float* v, int C,
+                                                             float lr, float bc1, float bc2) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    const float lo0 = obs[c], hi0 = obs[C + c], w = hi0 - lo0;
+    float end[2];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        const int i = e * C + c;
+        const float gr = grad[i];
+        const float mi = 0.9f * m[i] + 0.1f * gr;
+        const float vi = 0.999f * v[i] + 0.001f * (gr * gr);
+        m[i] = mi;
+        v[i] = vi;
+        end[e] = range[i] - lr * w * (mi / bc1) / (sqrtf(vi / bc2) + 1e-8f);
+    }
+    const float gap = 1e-3f * w;
+    float lo = fminf(fmaxf(end[0], lo0), hi0), hi = fminf(fmaxf(end[1], lo0), hi0);
+    hi = fminf(fmaxf(hi, lo + gap), hi0);
+    lo = fmaxf(fminf(lo, hi - gap), lo0);
+    range[c] = lo;
+    range[C + c] = hi;
+}
+
+// ---- host helpers
+int aq_bit_range(int n_bits, const char* who, float* bit_range) {
+    RDO_REQUIRE(n_bits >= 2 && n_bits <= 16, "%s: n_bits %d outside [2, 16]", who, n_bits);
+    *bit_range = (float)((1 << n_bits) - 1);
+    return RDO_OK;
+}
+// the W = 4 kernels need whole float4 groups of channels and 16-byte aligned tensors
+bool aq_vec(int C, std::initializer_list<const void*> tensors) {
+    uintptr_t bits = 0;
+    for (const void* p : tensors) bits |= reinterpret_cast<uintptr_t>(p);
+    return C % 4 == 0 && bits % 16 == 0;
+}
+// launch(W as a compile-time constant) with W = 4 | 1
+template <class F>
+void aq_with_width(bool vec, F launch) {
+    if (vec) launch(std::integral_constant<int, 4>{});
+    else launch(std::integral_constant<int, 1>{});
+}
+inline dim3 aq_fold_grid(int n) { return dim3((unsigned)rdo::ceil_div(n, 16)); }
+
+}  // namespace
+
+extern "C" {
+
+int rdo_actquant_perchannel(const float* x, int64_t npix, int32_t C, int32_t n_bits, float* out, float* ws_minmax, void* stream) {
+    RDO_REQUIRE(x && out && ws_minmax && npix > 0 && C > 0, "rdo_actquant_perchannel: bad argument");
+    float bit_range;
+    if (const int e = aq_bit_range(n_bits, "rdo_actquant_perchannel", &bit_range)) return e;
+    float* ws = ws_minmax;
+    float* part = ws_minmax + 2 * (long)C;
+    const bool vec = aq_vec(C, {x, out});
+    return rdo::dispatch(
+        [=](hipStream_t s) {
+            aq_with_width(vec, [&](auto w) {
+                constexpr int W = decltype(w)::value;
+                const int nblk = aq_blocks(npix, C, W);
+                hipLaunchKernelGGL(aq_partial_kernel<W>, dim3(nblk), dim3(256), 0, s, x, (long)npix, C, part);
+                hipLaunchKernelGGL(aq_fold_kernel<false>, aq_fold_grid(2 * C), dim3(256), 0, s, part, nblk, 2 * C, ws);
+                const long nvec = (long)npix * C / W;
+                hipLaunchKernelGGL(aq_apply_kernel<W>, dim3(grid_for(nvec)), dim3(256), 0, s, x, nvec, C, ws, bit_range, out);
+            });
+            return rdo::check_launch("actquant_perchannel");
+        },
+        stream);
+}
+
+int64_t rdo_actquant_workspace(int32_t C) { return C > 0 ? 2 * (int64_t)C * (kAqBlocks + 1) : 0; }
+
+int rdo_actquant_static(const float* x, int64_t npix, int32_t C, int32_t n_bits, const float* range, float* out, void* stream) {
+    RDO_REQUIRE(x && out && range && npix > 0 && C > 0, "rdo_actquant_static: bad argument");
+    float bit_range;
+    if (const int e = aq_bit_range(n_bits, "rdo_actquant_static", &bit_range)) return e;
+    const bool vec = aq_vec(C, {x, out});
+    return rdo::dispatch(
+        [=](hipStream_t s) {
+            aq_with_width(vec, [&](auto w) {
+                constexpr int W = decltype(w)::value;
+                const long nvec = (long)npix * C / W;
+                hipLaunchKernelGGL((aq_apply_kernel<W, true>), dim3(grid_for(nvec)), dim3(256), 0, s, x, nvec, C, range, bit_range, out);
+            });
+            return rdo::check_launch("actquant_static");
+        },
+        stream, "actquant_static", 0.0, 8.0 * npix * C);
+}
+
+int rdo_actquant_observe(const float* ws_minmax, int32_t C, float* range, void* stream) {
+    RDO_REQUIRE(ws_minmax && range && C > 0, "rdo_actquant_observe: bad argument");
+    return rdo::dispatch(
+        [=](hipStream_t s) {
+            hipLaunchKernelGGL(aq_merge_kernel, dim3((unsigned)rdo::ceil_div(2 * (long)C, 256)), dim3(256), 0, s, ws_minmax, C, range);
+            return rdo::check_launch("actquant_observe");
+        },
+        stream, "actquant_observe", 0.0, 24.0 * C);
+}
+
+int rdo_actquant_search(const float* x, int64_t npix, int32_t C, int32_t n_bits, const float* range, float* err, float* ws, void* stream) {
+    RDO_REQUIRE(x && range && err && ws && npix > 0 && C > 0, "rdo_actquant_search: bad argument");
+    float bit_range;
+    if (const int e = aq_bit_range(n_bits, "rdo_actquant_search", &bit_range)) return e;
+    const bool vec = aq_vec(C, {x});
+    return rdo::dispatch(
+        [=](hipStream_t s) {
+            aq_with_width(vec, [&](auto w) {
+                constexpr int W = decltype(w)::value;
+                const int nblk = aq_blocks(npix, C, W), n = C * kAqsCand;
+                hipLaunchKernelGGL(aqs_partial_kernel<W>, dim3(nblk), dim3(256), 0, s, x, (long)npix, C, range, bit_range, ws);
+                hipLaunchKernelGGL(aq_fold_kernel<true>, aq_fold_grid(n), dim3(256), 0, s, ws, nblk, n, err);
+            });
+            return rdo::check_launch("actquant_search");
+        },
+        stream, "actquant_search", 0.0, 4.0 * npix * C);
+}
+
+int64_t rdo_actquant_search_workspace(int32_t C) { return C > 0 ? (int64_t)C * kAqsCand * kAqBlocks : 0; }
+
+int rdo_actquant_static_bwd(const float* x, const float* g, int64_t npix, int32_t C, int32_t n_bits, const float* range, float* dx,
+                            float* drange, float* ws, void* stream) {
+    RDO_REQUIRE(x && g && range && dx && drange && ws && npix > 0 && C > 0, "rdo_actquant_static_bwd: bad argument");
+    float bit_range;
+    if (const int e = aq_bit_range(n_bits, "rdo_actquant_static_bwd", &bit_range)) return e;
+    RDO_REQUIRE(dx != x, "rdo_actquant_static_bwd: dx may alias g, not x");
+    const bool vec = aq_vec(C, {x, g, dx});
+    return rdo::dispatch(
+        [=](hipStream_t s) {
+            aq_with_width(vec, [&](auto w) {
+                constexpr int W = decltype(w)::value;
+                const int nblk = aq_blocks(npix, C, W);
+                hipLaunchKernelGGL(aqb_partial_kernel<W>, dim3(nblk), dim3(256), 0, s, x, g, (long)npix, C, range, bit_range, dx, ws);
+                hipLaunchKernelGGL(aq_fold_kernel<true>, aq_fold_grid(2 * C), dim3(256), 0, s, ws, nblk, 2 * C, drange);
+            });
+            return rdo::check_launch("actquant_static_bwd");
+        },
+        stream, "actquant_static_bwd", 0.0, 12.0 * npix * C);
+}
+
+int64_t rdo_actquant_static_bwd_workspace(int32_t C) { return C > 0 ? 2 * (int64_t)C * kAqBlocks : 0; }
+
+int rdo_act_range_step(float* range, const float* grad, const float* obs, float* m, float* v, int32_t C, int32_t step, float lr,
+                       void* stream) {
+    RDO_REQUIRE(range && grad && obs && m && v && C > 0, "rdo_act_range_step: bad argument");
+    RDO_REQUIRE(step >= 1, "rdo_act_range_step: step %d (the count of this step, from 1)", step);
+    const float bc1 = (float)(1.0 - pow(0.9, (double)step)), bc2 = (float)(1.0 - pow(0.999, (double)step));
+    return rdo::dispatch(
+        [=](hipStream_t s) {
+            hipLaunchKernelGGL(act_range_step_kernel, dim3((unsigned)rdo::ceil_div((long)C, 256L)), dim3(256), 0, s, range, grad, obs, m, v, C,
+                               lr, bc1, bc2);
+            return rdo::check_launch("act_range_step");
+        },
+        stream, "act_range_step", 0.0, 40.0 * C);
+}
+
+}  // extern "C"

@@ -314,13 +314,8 @@ __device__ __forceinline__ void ada_step_body(const AdaArgs& a, const long bid, 
         }
     }
     if (a.mode != 1 && a.round_loss_out && round_on != 0.f) {
-        __shared__ float red[4];
-        float vsum = rl_local;
-        for (int o = 32; o > 0; o >>= 1) vsum += __shfl_down(vsum, o, 64);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = vsum;
-        __syncthreads();
+        const float t = rdo::block_sum(rl_local);           // the condition holds kernel arguments only: uniform over the workgroup
         if (threadIdx.x == 0) {
-            const float t = red[0] + red[1] + red[2] + red[3];
             if (t != 0.f) atomicAdd(a.round_loss_out + (long)it * RDO_LOG_SLOTS + (bid & (RDO_LOG_SLOTS - 1)), t);
         }
     }
@@ -486,7 +481,6 @@ __device__ __forceinline__ void ada_step_tile_body(const AdaArgs& a, int bid) {
     }
     // ---- dgrad layout: transpose the tile's new soft weights through LDS (wave-uniform condition: the barrier is reached by all or none)
     __shared__ float tile[32][33];
-    __shared__ float red[4];
     if ((a.wd || a.lin_bwd) && !ADA_ABL(16)) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) tile[r][4 * q + k] = o4[k];
@@ -541,12 +535,8 @@ __device__ __forceinline__ void ada_step_tile_body(const AdaArgs& a, int bid) {
         }
     }
     if (a.round_loss_out && round_on != 0.f) {
-        float vsum = rl_local;
-        for (int o = 32; o > 0; o >>= 1) vsum += __shfl_down(vsum, o, 64);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = vsum;
-        __syncthreads();
+        const float t = rdo::block_sum(rl_local);           // as in the flat form: a uniform condition
         if (threadIdx.x == 0) {
-            const float t = red[0] + red[1] + red[2] + red[3];
             if (t != 0.f) atomicAdd(a.round_loss_out + (long)it * RDO_LOG_SLOTS + (bid0 & (RDO_LOG_SLOTS - 1)), t);
         }
     }
@@ -722,10 +712,7 @@ __global__ __launch_bounds__(256) void reduce_slabs_kernel(const float* slabs, i
     }
 }
 
-inline unsigned grid_for(long n) {
-    long g = rdo::ceil_div(n, 256);
-    return (unsigned)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
-}
+using rdo::grid_for;
 
 int check_desc(const rdo_ada_desc* d, const char* who) {
     RDO_REQUIRE(d != nullptr, "%s: null descriptor", who);

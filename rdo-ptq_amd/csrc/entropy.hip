@@ -170,11 +170,8 @@ __global__ __launch_bounds__(256) void gc_bwd_kernel(const float* yhat, const fl
 __global__ __launch_bounds__(256) void neg_log2_sum_kernel(const float* lik, long n, float scale, float* out) {
     float acc = 0.f;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) acc -= log2f(lik[i]);
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
-    __shared__ float red[4];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(out, (red[0] + red[1] + red[2] + red[3]) * scale);
+    acc = rdo::block_sum(acc);
+    if (threadIdx.x == 0) atomicAdd(out, acc * scale);
 }
 
 __global__ __launch_bounds__(256) void sq_diff_sum_kernel(const float* a, const float* b, long n, float scale, int clamp01,
@@ -186,11 +183,8 @@ __global__ __launch_bounds__(256) void sq_diff_sum_kernel(const float* a, const 
         const float d = x - b[i];
         acc += d * d;
     }
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
-    __shared__ float red[4];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(out, (red[0] + red[1] + red[2] + red[3]) * scale);
+    acc = rdo::block_sum(acc);
+    if (threadIdx.x == 0) atomicAdd(out, acc * scale);
 }
 
 // The same two sums without atomics, for evaluation (PSNR / bpp of a saved model must be the same numbers on every run): every
@@ -208,28 +202,18 @@ __global__ __launch_bounds__(256) void ordered_part_kernel(const float* a, const
             acc += d * d;
         }
     }
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
-    __shared__ float red[4];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1] + red[2] + red[3]) * scale;
+    acc = rdo::block_sum(acc);
+    if (threadIdx.x == 0) part[blockIdx.x] = acc * scale;
 }
 
 __global__ __launch_bounds__(256) void ordered_fold_kernel(const float* part, int nblk, float* out) {
     float acc = 0.f;
     for (int i = threadIdx.x; i < nblk; i += 256) acc += part[i];
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
-    __shared__ float red[4];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) out[0] += red[0] + red[1] + red[2] + red[3];
+    acc = rdo::block_sum(acc);
+    if (threadIdx.x == 0) out[0] += acc;
 }
-constexpr int kOrderedBlocks = 2048;        // = the cap of grid_for
-
-inline unsigned grid_for(long n) {
-    long g = rdo::ceil_div(n, 256);
-    return (unsigned)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
-}
+using rdo::grid_for;
+constexpr int kOrderedBlocks = rdo::kGridCap;      // one partial sum per workgroup of grid_for
 
 }  // namespace
 

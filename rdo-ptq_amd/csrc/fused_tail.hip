@@ -28,20 +28,14 @@ inline unsigned loss_grid(long blocks) {
     return (unsigned)(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
 }
 
-inline unsigned grid_for(long n) {
-    long g = rdo::ceil_div(n, 256L);
-    return (unsigned)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
-}
+using rdo::grid_for;
 
 // (pub: rdo_iter_bind_publish -- the launch's first thread leaves the iteration number there for the AdaRound step of the same iteration)
 __device__ __forceinline__ void block_loss_add(float acc, float scale, float* loss_out, int it, int32_t* pub) {
     if (pub && blockIdx.x == 0 && threadIdx.x == 0) *pub = it;
-    __shared__ float red[4];
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
+    acc = rdo::block_sum(acc);
     if (threadIdx.x == 0 && loss_out)
-        atomicAdd(loss_out + (long)it * RDO_LOG_SLOTS + (blockIdx.x & (RDO_LOG_SLOTS - 1)), (red[0] + red[1] + red[2] + red[3]) * scale);
+        atomicAdd(loss_out + (long)it * RDO_LOG_SLOTS + (blockIdx.x & (RDO_LOG_SLOTS - 1)), acc * scale);
 }
 
 // fp32 values of the thread's 8 channels from planes: (h1 + h2) / s -- the sum is exact in fp32, the value is the original to 2^-24

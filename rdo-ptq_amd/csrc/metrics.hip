@@ -26,7 +26,6 @@ struct SsimArgs {
 __global__ __launch_bounds__(256) void ssim_level_kernel(SsimArgs a) {
     __shared__ float sx[HALO][HALO + 1], sy[HALO][HALO + 1];
     __shared__ float r[5][HALO][TILE + 1];
-    __shared__ float red[2][4];
     const int Ho = a.H - WIN + 1, Wo = a.W - WIN + 1;
     const int plane = blockIdx.z, h0 = blockIdx.y * TILE, w0 = blockIdx.x * TILE;
     const float* px = a.x + (long)plane * a.H * a.W;
@@ -64,13 +63,12 @@ __global__ __launch_bounds__(256) void ssim_level_kernel(SsimArgs a) {
         cs = (2.f * s12 + a.c2) / (s11 + s22 + a.c2);
         ssim = ((2.f * m1 * m2 + a.c1) / (m1 * m1 + m2 * m2 + a.c1)) * cs;
     }
-    for (int o = 32; o > 0; o >>= 1) { ssim += __shfl_down(ssim, o, 64); cs += __shfl_down(cs, o, 64); }
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = ssim; red[1][threadIdx.x >> 6] = cs; }
-    __syncthreads();
+    float sum[2] = {ssim, cs};
+    rdo::block_sum(sum);
     if (threadIdx.x == 0) {
         const float inv = 1.0f / ((float)Ho * (float)Wo);
-        atomicAdd(a.ssim_sum + plane, (red[0][0] + red[0][1] + red[0][2] + red[0][3]) * inv);
-        atomicAdd(a.cs_sum + plane, (red[1][0] + red[1][1] + red[1][2] + red[1][3]) * inv);
+        atomicAdd(a.ssim_sum + plane, sum[0] * inv);
+        atomicAdd(a.cs_sum + plane, sum[1] * inv);
     }
 }
 

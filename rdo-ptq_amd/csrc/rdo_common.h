@@ -87,6 +87,13 @@ __host__ __device__ inline long frag_index(long e, int Cout, int KH, int KW, int
 }
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// workgroups of 256 threads for a grid-stride loop over n items: capped at kGridCap (MI355X: 256 CUs x 8), the loop covers the rest
+constexpr int kGridCap = 2048;
+inline unsigned grid_for(long n, int per_thread = 1) {
+    const long g = ceil_div(n, 256L * per_thread);
+    return (unsigned)(g < 1 ? 1 : (g > kGridCap ? kGridCap : g));
+}
+
 // ---- H2 tensors: an fp32 value as an exact two-way fp16 split of its power-of-two-scaled self ---------------------------------------
 //   x * s = h1 + h2 (+ at most 2^-24 |x s|),  h1 = fp16_rne(x s),  h2 = fp16_rne(x s - h1)         (x s - h1 is exact in fp32)
 // A product of two such values needs THREE fp16 MFMA products (h1 g1 + h1 g2 + h2 g1; h2 g2 <= 2^-22 of the product) where the
@@ -99,6 +106,30 @@ int* h2_overflow_flag();                   // device pointer of the sticky flag 
 int32_t* take_iter_publish();              // the word bound by rdo_iter_bind_publish for the next loss / tail launch (and clears the binding)
 
 #if defined(__HIPCC__)
+// Sums over a 256-thread workgroup, N at a time behind ONE barrier, in a fixed order: per wave the 64-lane __shfl_down steps 32 .. 1,
+// the four wave sums through LDS, then ((w0 + w1) + w2) + w3.  The totals are valid on thread 0 only.  Every thread of the workgroup
+// must make the call (it holds the barrier); a second call by the same workgroup needs a barrier of its own in between.
+template <int N>
+__device__ __forceinline__ void block_sum(float (&v)[N]) {
+    __shared__ float red[N][4];
+    for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+        for (int e = 0; e < N; ++e) v[e] += __shfl_down(v[e], o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int e = 0; e < N; ++e) red[e][threadIdx.x >> 6] = v[e];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < N; ++e) v[e] = red[e][0] + red[e][1] + red[e][2] + red[e][3];
+}
+__device__ __forceinline__ float block_sum(float v) {
+    float a[1] = {v};
+    block_sum(a);
+    return a[0];
+}
+
 typedef _Float16 h2_f16x2 __attribute__((ext_vector_type(2)));
 typedef float h2_f32x2 __attribute__((ext_vector_type(2)));
 // two values -> packed h1 pair, packed h2 pair.  `bad` accumulates the LARGEST |x s| met, as the fp32 bit pattern with the sign

@@ -320,7 +320,7 @@ def actquant_perchannel(x, out=None, ws=None, n_bits=8):
     return out
 
 
-ACT_SEARCH_CANDIDATES = 10        # kAqsCand of csrc/elementwise.hip: range * (1 - 0.05 k), k = 0..9
+ACT_SEARCH_CANDIDATES = 10        # kAqsCand of csrc/actquant.hip: range * (1 - 0.05 k), k = 0..9
 
 
 def _act_range_check(x, rng, what):

@@ -153,7 +153,7 @@ def _rel_err(got, ref):
 
 
 @pytest.mark.parametrize("n_bits", [4, 6, 8])
-@pytest.mark.parametrize("npix,C", [(16384, 192), (1122, 24), (1024, 6)])
+@pytest.mark.parametrize("npix,C", [(16384, 192), (1122, 24), (1024, 6), (35, 1280)])
 def test_search_sums_match_float64(npix, C, n_bits):
     """Tolerance 1e-4 relative: the terms are non-negative, so an fp32 sum whose serial chains hold at most 1024 terms, plus the tree,
     is within about (1024 + 20) * 2^-24 = 6.2e-5 of the exact sum."""
