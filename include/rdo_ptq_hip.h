@@ -282,6 +282,25 @@ int64_t rdo_actquant_static_bwd_workspace(int32_t C);
  * [lo_obs,c, hi_obs,c] and hi >= lo + 1e-3 w_c.  m, v [2 C]: the moments, updated.  C-sized. */
 int rdo_act_range_step(float* range /* [2 C], updated */, const float* grad /* [2 C] */, const float* obs /* [2 C] lo_obs | hi_obs */,
                        float* m, float* v, int32_t C, int32_t step, float lr, void* stream);
+/* Per-channel histogram on the observed range (extension: percentile ranges).  hist[C][1024] (int32, row-major) += the counts of
+ * x [npix][C] with, per element of channel c, w = max(hi_c - lo_c, 1e-6), t = ((x - lo_c) / w) * 1024 (each operation rounded on its own in
+ * fp32), bin = 0 if t < 0, 1023 if t >= 1024, else (int)floor(t): a channel's maximum lands in bin 1023, its minimum in bin 0.  Non-finite
+ * values are counted somewhere (not specified where).  One read of x; counts in LDS per workgroup, whose non-zero counters are added to
+ * hist with global integer atomics: integer sums, so the same input gives the same counts from launch to launch, and the counts of
+ * several batches or ranks add up exactly.  hist is ACCUMULATED INTO (zero it before the first batch); the caller keeps a channel's total
+ * below 2^31.  No workspace. */
+int32_t rdo_actquant_hist_bins(void);            /* 1024 */
+int rdo_actquant_hist(const float* x, int64_t npix, int32_t C, const float* range /* [2 C] lo | hi, observed */,
+                      int32_t* hist /* [C][1024] */, void* stream);
+/* Percentile range of every channel from its histogram: with n = sum_b h[b] (64-bit) and k = (int64)floor(tail * (double)n), tail = 1 -
+ * p / 100 in [0, 0.5), whole bins are dropped from each end while the dropped count stays within k: a = the largest a in [0, 1023] with
+ * sum_{b < a} h[b] <= k, d = the largest d in [0, 1023 - a] with sum_{b >= 1024 - d} h[b] <= k; with wr = hi - lo (fp32),
+ *   lo' = a == 0 ? lo : lo + ((float)a / 1024) * wr,    hi' = d == 0 ? hi : lo + ((float)(1024 - d) / 1024) * wr,
+ * product and sum rounded separately.  A channel with hi - lo < 1e-6 or n == 0 keeps lo | hi.  tail = 0 returns the observed range bit
+ * for bit (its ends are counted in bins 0 and 1023); at least one bin remains, so lo' < hi'; both ends lie inside [lo, hi].  out = lo'[C] |
+ * hi'[C]; out == range allowed.  C-sized: one wave per channel. */
+int rdo_act_percentile_select(const int32_t* hist /* [C][1024] */, int32_t C, const float* range /* [2 C] lo | hi, observed */, double tail,
+                              float* out /* [2 C] */, void* stream);
 
 /* ---- K7: mini-batch assembly: out[b] = keep ? cache_q[idx[b]] : cache_fp[idx[b]], keep ~ counter RNG(seed, iter, i)
  * replaces cached_inps[..][idx] + torch.where(torch.rand_like(x) < p, x_q, x_fp)                layer_opt.py:289-292

@@ -1,5 +1,6 @@
 // K6 -- per-channel activation quantisers on NHWC fp32 tensors (channel = fastest dim): the dynamic quantiser (min | max of the tensor
-// itself), the static one (a frozen lo | hi pair), the range search, the static backward and the Adam step of learned ranges.
+// itself), the static one (a frozen lo | hi pair), the range search, the static backward, the Adam step of learned ranges, and the
+// per-channel histogram with its percentile selection.
 // Built with -ffp-contract=off (products and sums round separately, like the reference's op chains).
 //
 // Three of them reduce over the pixels per channel, and all three do it the same way, without atomics: up to kAqBlocks workgroups each
@@ -298,6 +299,127 @@ __global__ __launch_bounds__(256) void act_range_step_kernel(float* range, const
     range[C + c] = hi;
 }
 
+// ---- per-channel histogram of x on the observed range lo | hi: kAqhBins integer counters per channel.  Not a Body of aq_partial (that
+// keeps N running values per channel in REGISTERS): a workgroup owns a tile of up to kAqhTile channels x kAqhBins int counters in LDS
+// (64 KiB: two workgroups per CU), walks its share of the pixels with W-wide loads, FLIGHT of them in flight, and counts with LDS integer
+// atomicAdd; at the end it adds its NON-ZERO counters to hist with global integer atomicAdd.  Integer sums do not depend on the order of
+// the adds: the same input gives the same counts from launch to launch.  thread = (pixel lane, group of W channels of the tile), the
+// channel fastest: a channel whose values all sit in one bin collides on 256 / (channels of the tile) lanes of a workgroup, not on all.
+// A counter sits at [row][(bin + row) & 1023]: the rotation spreads equal bins of different channels (many values at an end of their
+// ranges) over the LDS banks.  grid = (pixel blocks, channel tiles).
+constexpr int kAqhBins = 1024;
+constexpr int kAqhTile = 16;
+static_assert((kAqhBins & (kAqhBins - 1)) == 0, "the rotation masks with kAqhBins - 1");
+
+// groups of W channels side by side in a tile
+__host__ __device__ inline int aqh_qpb(int C, int W) {
+    const int QN = C / W, qt = kAqhTile / W;
+    return QN < qt ? QN : qt;
+}
+
+// bin of an element: the rule of include/rdo_ptq_hip.h, every operation rounded on its own.  (A NaN counts in bin 0.)
+__device__ __forceinline__ int aqh_bin(float x, float lo, float w) {
+    const float t = ((x - lo) / w) * (float)kAqhBins;
+    return (int)fminf(fmaxf(floorf(t), 0.f), (float)(kAqhBins - 1));
+}
+
+template <int W>
+__global__ __launch_bounds__(256) void aqh_kernel(const float* x, long npix, int C, const float* range, int* hist) {
+    typedef float vec_t __attribute__((ext_vector_type(W)));
+    constexpr int FLIGHT = 4;
+    __shared__ int sm[kAqhTile * kAqhBins];
+    const int QN = C / W, qpb = aqh_qpb(C, W), PL = 256 / qpb;
+    const int pl = threadIdx.x / qpb, ql = threadIdx.x - pl * qpb;
+    const int q = blockIdx.y * qpb + ql;                   // this thread's channel group
+    for (int i = threadIdx.x; i < kAqhTile * kAqhBins; i += 256) sm[i] = 0;
+    __syncthreads();
+    if (pl < PL && q < QN) {
+        float lo[W], w[W];
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+            lo[k] = range[q * W + k];
+            w[k] = fmaxf(range[C + q * W + k] - lo[k], 1e-6f);
+        }
+        const float* src = x + (long)q * W;
+        auto count = [&](const vec_t& v) {
+#pragma unroll
+            for (int k = 0; k < W; ++k) {
+                const int row = ql * W + k;
+                atomicAdd(&sm[row * kAqhBins + ((aqh_bin(v[k], lo[k], w[k]) + row) & (kAqhBins - 1))], 1);
+            }
+        };
+        const long step = (long)gridDim.x * PL;
+        long p = (long)blockIdx.x * PL + pl;
+        for (; p + (FLIGHT - 1) * step < npix; p += FLIGHT * step) {
+            vec_t v[FLIGHT];
+#pragma unroll
+            for (int u = 0; u < FLIGHT; ++u) v[u] = *reinterpret_cast<const vec_t*>(src + (p + u * step) * C);
+#pragma unroll
+            for (int u = 0; u < FLIGHT; ++u) count(v[u]);
+        }
+        for (; p < npix; p += step) count(*reinterpret_cast<const vec_t*>(src + p * C));
+    }
+    __syncthreads();
+    const int c0 = blockIdx.y * qpb * W;                    // first channel of the tile
+    const int rows = C - c0 < qpb * W ? C - c0 : qpb * W;
+    for (int i = threadIdx.x; i < rows * kAqhBins; i += 256) {
+        const int n = sm[i];
+        if (n) {
+            const int row = i / kAqhBins, bin = (i - row) & (kAqhBins - 1);
+            atomicAdd(&hist[(long)(c0 + row) * kAqhBins + bin], n);
+        }
+    }
+}
+
+// ---- percentile range of a channel from its histogram: one wave per channel, lane l holds the bins 16 l .. 16 l + 15.  With k =
+// floor(tail * n) whole bins are dropped from each end while the dropped count stays <= k: the prefix sums P(a) = sum of the bins below a
+// grow with a, so the largest a in [0, 1023] with P(a) <= k is the NUMBER of a in [1, 1023] with P(a) <= k; the same from the top for d in
+// [1, 1023 - a].  Integer arithmetic in 64 bits, then two fp32 operations per moved end.
+__global__ __launch_bounds__(256) void aqh_select_kernel(const int* hist, int C, const float* range, double tail, float* out) {
+    constexpr int PER = kAqhBins / 64;
+    const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (c >= C) return;                                    // (a whole wave: the shuffles below stay among live lanes)
+    const int* h = hist + (long)c * kAqhBins + lane * PER;
+    long long cnt[PER], mine = 0;
+#pragma unroll
+    for (int j = 0; j < PER; ++j) { cnt[j] = h[j]; mine += cnt[j]; }
+    long long incl = mine;                                 // inclusive prefix over the lanes
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const long long up = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += up;
+    }
+    const long long n = __shfl(incl, 63, 64);
+    const long long k = (long long)floor(tail * (double)n);
+    auto wave_sum = [](int v) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        return v;
+    };
+    long long run = incl - mine;                           // P(16 lane)
+    int na = 0;
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+        run += cnt[j];                                     // P(a), a = 16 lane + j + 1
+        na += (lane * PER + j + 1 <= kAqhBins - 1 && run <= k) ? 1 : 0;
+    }
+    const int a = wave_sum(na);
+    run = n - incl;                                        // the bins above this lane's
+    int nd = 0;
+#pragma unroll
+    for (int j = PER - 1; j >= 0; --j) {
+        run += cnt[j];                                     // the bins from 16 lane + j up: d = 1024 - (16 lane + j)
+        nd += (kAqhBins - (lane * PER + j) <= kAqhBins - 1 - a && run <= k) ? 1 : 0;
+    }
+    const int d = wave_sum(nd);
+    if (lane == 0) {
+        const float lo = range[c], hi = range[C + c], wr = hi - lo;
+        const bool keep = wr < 1e-6f || n == 0;
+        out[c] = (keep || a == 0) ? lo : lo + ((float)a / (float)kAqhBins) * wr;
+        out[C + c] = (keep || d == 0) ? hi : lo + ((float)(kAqhBins - d) / (float)kAqhBins) * wr;
+    }
+}
+
 // ---- host helpers
 int aq_bit_range(int n_bits, const char* who, float* bit_range) {
     RDO_REQUIRE(n_bits >= 2 && n_bits <= 16, "%s: n_bits %d outside [2, 16]", who, n_bits);
@@ -427,6 +549,41 @@ int rdo_act_range_step(float* range, const float* grad, const float* obs, float*
             return rdo::check_launch("act_range_step");
         },
         stream, "act_range_step", 0.0, 40.0 * C);
+}
+
+int32_t rdo_actquant_hist_bins(void) { return kAqhBins; }
+
+int rdo_actquant_hist(const float* x, int64_t npix, int32_t C, const float* range, int32_t* hist, void* stream) {
+    RDO_REQUIRE(x && range && hist && npix > 0 && C > 0, "rdo_actquant_hist: bad argument");
+    RDO_REQUIRE(npix <= 0x7fffffffLL, "rdo_actquant_hist: %lld pixels do not fit a channel's 32-bit counters", (long long)npix);
+    RDO_REQUIRE(C <= kAqhTile * 65535, "rdo_actquant_hist: %d channels are more than %d tiles of %d", C, 65535, kAqhTile);
+    const bool vec = aq_vec(C, {x});
+    return rdo::dispatch(
+        [=](hipStream_t s) {
+            aq_with_width(vec, [&](auto w) {
+                constexpr int W = decltype(w)::value;
+                const int qpb = aqh_qpb(C, W), PL = 256 / qpb;
+                const long tiles = rdo::ceil_div((long)(C / W), (long)qpb);
+                // as many pixel blocks as give every lane >= 8 pixels, at most two workgroups per CU over all tiles
+                long nblk = rdo::ceil_div((long)npix, (long)PL * 8);
+                const long cap = 512 / tiles < 1 ? 1 : 512 / tiles;
+                nblk = nblk > cap ? cap : nblk;
+                hipLaunchKernelGGL(aqh_kernel<W>, dim3((unsigned)nblk, (unsigned)tiles), dim3(256), 0, s, x, (long)npix, C, range, hist);
+            });
+            return rdo::check_launch("actquant_hist");
+        },
+        stream, "actquant_hist", 0.0, 4.0 * npix * C);
+}
+
+int rdo_act_percentile_select(const int32_t* hist, int32_t C, const float* range, double tail, float* out, void* stream) {
+    RDO_REQUIRE(hist && range && out && C > 0, "rdo_act_percentile_select: bad argument");
+    RDO_REQUIRE(tail >= 0.0 && tail < 0.5, "rdo_act_percentile_select: tail %g outside [0, 0.5)", tail);
+    return rdo::dispatch(
+        [=](hipStream_t s) {
+            hipLaunchKernelGGL(aqh_select_kernel, dim3((unsigned)rdo::ceil_div((long)C, 4L)), dim3(256), 0, s, hist, C, range, tail, out);
+            return rdo::check_launch("act_percentile_select");
+        },
+        stream, "act_percentile_select", 0.0, 4.0 * kAqhBins * C + 16.0 * C);
 }
 
 }  // extern "C"

@@ -394,6 +394,36 @@ def act_range_step(rng, grad, obs, m, v, step, lr):
     return rng
 
 
+ACT_HIST_BINS = 1024              # kAqhBins of csrc/actquant.hip (rdo_actquant_hist_bins)
+
+
+def act_hist_init(channels, device):
+    """Empty per-channel histogram [C, 1024] (int32)."""
+    return torch.zeros(int(channels), ACT_HIST_BINS, device=device, dtype=torch.int32)
+
+
+def actquant_hist(x, rng, hist):
+    """hist [C, 1024] (int32) += the per-channel counts of x [..., C] on the observed range rng = lo[C] | hi[C] (the bin rule of
+    include/rdo_ptq_hip.h).  The caller keeps a channel's total below 2^31."""
+    Cc, npix = _act_range_check(x, rng, "actquant_hist")
+    if tuple(hist.shape) != (Cc, ACT_HIST_BINS) or hist.dtype != torch.int32 or not hist.is_contiguous():
+        raise ValueError(f"actquant_hist: hist must be a contiguous int32 [{Cc}, {ACT_HIST_BINS}], got {hist.dtype} {tuple(hist.shape)}")
+    L.check(L.lib().rdo_actquant_hist(_ptr(x), npix, Cc, _ptr(rng), _ptr(hist), _stream()), "rdo_actquant_hist")
+    return hist
+
+
+def act_percentile_select(hist, rng, tail):
+    """-> a new range [2C]: every channel's observed range rng with whole bins dropped from each end while the dropped count stays within
+    floor(tail * n) (tail = 1 - p / 100; 0 returns rng bit for bit)."""
+    Cc = hist.shape[0]
+    if tuple(hist.shape) != (Cc, ACT_HIST_BINS) or hist.dtype != torch.int32 or not hist.is_contiguous() or rng.numel() != 2 * Cc:
+        raise ValueError(f"act_percentile_select: hist {hist.dtype} {tuple(hist.shape)} / range [{rng.numel()}] are not int32 "
+                         f"[C, {ACT_HIST_BINS}] / [2C]")
+    out = torch.empty_like(rng)
+    L.check(L.lib().rdo_act_percentile_select(_ptr(hist), Cc, _ptr(rng), float(tail), _ptr(out), _stream()), "rdo_act_percentile_select")
+    return out
+
+
 def gather_qdrop(cache_q, cache_fp, idx_table, iter_ptr, B, prob, seed, out, batch_offset=0, iter_publish=None):
     """`batch_offset`: row of the global mini-batch this (data-parallel) rank's first row is -- the QDrop counter runs over the
     global batch, so N ranks with one seed draw the mask a single process would."""

@@ -128,10 +128,15 @@ class UniformAffineQuantizer(nn.Module):
         if act_mode not in ACT_MODES:
             raise ValueError(f"unknown act_mode {act_mode!r} {ACT_MODES}")
         self.act_mode = act_mode
-        self.act_phase = "idle"            # static only: "idle" (no range yet) | "observe" | "search" | "frozen" | "learn"
+        self.act_phase = "idle"            # static only: "idle" (no range yet) | "observe" | "search" | "hist" | "frozen" | "learn"
         self.act_range = {}                # site -> fp32 [2C], lo | hi (leaf tensors with requires_grad while learning)
         self.act_err = {}                  # site -> fp32 [C, 10] while searching
         self.act_obs = {}                  # site -> fp32 [2C]: the observed max range, kept for / while learning the ranges
+        # site -> int32 [C, 1024] while the percentile histograms are taken (`act_tail` = 1 - p / 100; `act_hist_n`: pixels counted per
+        # site, on the host).  Absent on models pickled before they existed: read with getattr
+        self.act_hist = {}
+        self.act_tail = 0.0
+        self.act_hist_n = {}
         # frozen ranges on torch's tape (hipops.autograd.ActQuantStaticFn, straight-through round) when the input is tracked: set by
         # recon.reconstruct for the duration of an R + lambda*D unit.  Absent on models pickled before it existed: read with getattr
         self.act_ste = False
@@ -142,7 +147,7 @@ class UniformAffineQuantizer(nn.Module):
             t = getattr(self, name, None)
             if torch.is_tensor(t):
                 setattr(self, name, fn(t))
-        for name in ("act_range", "act_err", "act_obs"):
+        for name in ("act_range", "act_err", "act_obs", "act_hist"):
             d = getattr(self, name, None)
             if isinstance(d, dict):
                 setattr(self, name, {k: fn(t) for k, t in d.items()})
@@ -152,14 +157,14 @@ class UniformAffineQuantizer(nn.Module):
     def set_act_mode(self, mode: str):
         if mode not in ACT_MODES:
             raise ValueError(f"unknown act_mode {mode!r} {ACT_MODES}")
-        for name, val in (("act_phase", "idle"), ("act_range", {}), ("act_err", {}), ("act_obs", {})):     # (an artefact of an earlier version)
+        for name, val in (("act_phase", "idle"), ("act_range", {}), ("act_err", {}), ("act_obs", {}), ("act_hist", {})):     # (an artefact of an earlier version)
             if not hasattr(self, name):
                 setattr(self, name, val)
         self.act_mode = mode
 
     def act_observe(self):
         """Start observing: every call quantises dynamically and merges the batch's per-channel min / max into the site's range."""
-        self.act_phase, self.act_range, self.act_err, self.act_obs = "observe", {}, {}, {}
+        self.act_phase, self.act_range, self.act_err, self.act_obs, self.act_hist = "observe", {}, {}, {}, {}
 
     def act_search(self):
         """Start the L2 search over the observed ranges: every call accumulates the ten candidates' squared errors and returns the
@@ -169,6 +174,28 @@ class UniformAffineQuantizer(nn.Module):
         self.act_phase = "search"
         self.act_obs = {k: r.clone() for k, r in self.act_range.items()}
         self.act_err = {k: torch.zeros(r.numel() // 2, ops.ACT_SEARCH_CANDIDATES, device=r.device) for k, r in self.act_range.items()}
+
+    def act_histogram(self, percentile: float = 99.99):
+        """Start the histogram pass over the observed ranges: every call counts its values per channel into the site's 1024 bins and
+        returns the max-range static output (what the search phase returns).  `act_freeze()` then clips a share 1 - percentile / 100 of
+        the counted values at each end of every channel, in whole bins."""
+        if not self.act_range:
+            raise RuntimeError("act_histogram: nothing was observed")
+        self.act_phase = "hist"
+        self.act_tail = 1.0 - float(percentile) / 100.0
+        self.act_obs = {k: r.clone() for k, r in self.act_range.items()}
+        self.act_hist = {k: ops.act_hist_init(r.numel() // 2, r.device) for k, r in self.act_range.items()}
+        self.act_hist_n = {k: 0 for k in self.act_range}
+
+    def _act_count(self, xr, rng, site):
+        """one batch into the site's histogram; the counters are 32-bit, and under data parallelism the ranks' histograms are summed"""
+        from . import dp
+        n = self.act_hist_n[site] + xr.numel() // xr.shape[-1]
+        if n * dp.world()[1] > 2 ** 31 - 1:
+            raise OverflowError(f"static activation quantiser (site {site}): {n} values per channel on each of {dp.world()[1]} ranks "
+                                "do not fit the histogram's 32-bit counters")
+        ops.actquant_hist(xr, rng, self.act_hist[site])
+        self.act_hist_n[site] = n
 
     def act_learn(self):
         """Start learning the frozen ranges: every site's range becomes a leaf tensor with requires_grad that the tracked forward
@@ -186,7 +213,8 @@ class UniformAffineQuantizer(nn.Module):
         """Fix the ranges.  After a search each channel shrinks to its best candidate lo * s_k | hi * s_k (first minimum, as `_init_search`
         keeps the first strictly better score).  Scaling towards zero moves an end that does not straddle zero (lo > 0 or hi < 0) OUT of
         the observed range, where no calibration value lies: such an end stays at the observed one, so a frozen range always lies inside
-        its max range.  A quantiser that was never applied stays without a range ("idle").  After learning the ranges are detached as they
+        its max range.  After a histogram pass each site becomes its percentile range (`ops.act_percentile_select`), which lies inside the
+        max range as well.  A quantiser that was never applied stays without a range ("idle").  After learning the ranges are detached as they
         stand.  `keep_obs`: keep the observed max ranges for a learning phase that follows (they are not part of a frozen quantiser)."""
         self.act_range = {k: r.detach() for k, r in self.act_range.items()}
         for k, err in self.act_err.items():
@@ -197,7 +225,9 @@ class UniformAffineQuantizer(nn.Module):
             lo, hi = torch.maximum(rng[:c] * s, rng[:c]), torch.minimum(rng[c:] * s, rng[c:])
             keep = lo > hi                                                 # (a candidate that left the observed range altogether)
             self.act_range[k] = torch.cat([torch.where(keep, rng[:c], lo), torch.where(keep, rng[c:], hi)])
-        self.act_err = {}
+        for k, hist in (getattr(self, "act_hist", None) or {}).items():
+            self.act_range[k] = ops.act_percentile_select(hist, self.act_range[k], getattr(self, "act_tail", 0.0))
+        self.act_err, self.act_hist, self.act_hist_n = {}, {}, {}
         if not keep_obs:
             self.act_obs = {}
         self.act_phase = "frozen" if self.act_range else "idle"
@@ -220,6 +250,8 @@ class UniformAffineQuantizer(nn.Module):
                                "(recon.py with args.act_mode='static'); there is no fall-back to the dynamic grid")
         if phase == "search":
             ops.actquant_search(xr, rng, self.act_err[site], n_bits=bits)
+        if phase == "hist":
+            self._act_count(xr, rng, site)
         if torch.is_grad_enabled() and (phase == "learn" or (phase == "frozen" and getattr(self, "act_ste", False) and x.requires_grad)):
             from hipops.autograd import ActQuantStaticFn
             return ActQuantStaticFn.apply(x, rng, bits, channels_last)

@@ -139,14 +139,17 @@ def _act_args(args):
     args.act_range: how a static range is fixed, 'max' (default: min / max over the calibration set), 'l2' (each channel then shrinks
     to the best of ten candidates by squared error) or 'learned' (the 'l2' ranges are then trained on the unit's reconstruction error:
     `learn_act_ranges`, with args.act_iters steps, default 500, of size args.act_lr, default 1e-3, relative to a channel's observed
-    width).  Checked before any work is done."""
+    width) or 'percentile' (a second pass takes a 1024-bin histogram of every channel on its observed range; each end then gives up whole
+    bins while they hold no more than a share 1 - args.act_percentile / 100, default 99.99, of the channel's values).  Checked before any
+    work is done."""
     mode = getattr(args, "act_mode", "dynamic") if args is not None else "dynamic"
     how = getattr(args, "act_range", "max") if args is not None else "max"
     if mode not in ("dynamic", "static"):
         raise ValueError(f"unknown act_mode {mode!r} ('dynamic' or 'static')")
-    if how not in ("max", "l2", "learned"):
-        raise ValueError(f"unknown act_range {how!r} ('max', 'l2' or 'learned')")
+    if how not in ("max", "l2", "learned", "percentile"):
+        raise ValueError(f"unknown act_range {how!r} ('max', 'l2', 'learned' or 'percentile')")
     _act_learn_args(args)
+    _act_percentile_args(args)
     return mode, how
 
 
@@ -165,17 +168,32 @@ def _check_learn(iters, lr):
     return iters, float(lr)
 
 
+def _act_percentile_args(args):
+    """args.act_percentile of act_range='percentile', validated: a real number p with 50 < p <= 100 (100 = the max range)."""
+    return _check_percentile(getattr(args, "act_percentile", 99.99) if args is not None else 99.99)
+
+
+def _check_percentile(p):
+    if isinstance(p, bool) or not isinstance(p, (int, float)) or not (50.0 < float(p) <= 100.0):
+        raise ValueError(f"act_percentile must be a number p with 50 < p <= 100, got {p!r}")
+    return float(p)
+
+
 def _is_rstb(unit):
     return isinstance(unit, QuantRSTB) or getattr(unit, "unit_kind", None) == "rstb"
 
 
-def calibrate_act_ranges(unit, inp_q, act_range="max", batch=32, keep_obs=False):
+def calibrate_act_ranges(unit, inp_q, act_range="max", batch=32, keep_obs=False, percentile=99.99):
     """Fix the static activation ranges of a calibrated unit: run it once over its cached quantised inputs in the state the W8A8
     evaluation uses (the unit, its QuantModules and nested block wrappers with weight and activation quantisation on) with its quantisers
     observing, then freeze them; with act_range='l2' a second pass over the same inputs accumulates the candidates' squared errors
-    first.  Under data parallelism the observed ranges and the error sums are reduced over the ranks before they are used, so every
-    rank freezes the same grid.  Every quant state flag is left as it was found.  `keep_obs`: the quantisers keep the observed max ranges
+    first; with act_range='percentile' the second pass takes every channel's histogram on its observed range, and freezing clips a
+    share 1 - percentile / 100 of its values at each end.  Under data parallelism the observed ranges and the error sums or histograms
+    are reduced over the ranks before they are used, so every rank freezes the same grid (integer counts: the very grid of one process
+    on all inputs).  Every quant state flag is left as it was found.  `keep_obs`: the quantisers keep the observed max ranges
     next to the frozen ones (`act_obs`) for `learn_act_ranges`."""
+    if act_range == "percentile":
+        percentile = _check_percentile(percentile)
     mods = [m for m in unit.modules() if isinstance(m, (QuantModule, BaseQuantBlock))]
     quants = [m.act_quantizer for m in mods]
     states = [(m, m.use_weight_quant, m.use_act_quant) for m in mods]
@@ -201,6 +219,12 @@ def calibrate_act_ranges(unit, inp_q, act_range="max", batch=32, keep_obs=False)
                     q.act_search()
             run()
             dp.reduce_act_stats(sums=applied("act_err"))
+        elif act_range == "percentile":
+            for q in quants:
+                if q.act_range:
+                    q.act_histogram(percentile)
+            run()
+            dp.reduce_act_stats(sums=applied("act_hist"))
         for q in quants:
             q.act_freeze(keep_obs=keep_obs)
     finally:
@@ -304,6 +328,7 @@ def _reconstruct(model, unit, unit_name, cali_data, batch_size=32, iters=20000, 
     rd_metric = _rd_metric(args, cali_data)
     act_mode, act_range = _act_args(args)
     act_iters, act_lr = _act_learn_args(args)
+    act_percentile = _act_percentile_args(args)
     if act_quant and act_mode == "static" and act_range == "learned" and _is_rstb(unit):
         raise NotImplementedError("act_range='learned': a Swin (RSTB) unit's activation-quantised window attention cannot sit on torch's "
                                   "tape (quant_block.QuantWindowAttention); calibrate it with act_range='max' or 'l2'")
@@ -428,7 +453,7 @@ def _reconstruct(model, unit, unit_name, cali_data, batch_size=32, iters=20000, 
             calibrate_act_ranges(unit, inp_q, "l2", batch=cache_bs, keep_obs=True)         # the starting ranges
             learn_act_ranges(unit, inp_q, out_fp, act_iters, act_lr, batch_size, seed=unit_seed(unit_name))
         else:
-            calibrate_act_ranges(unit, inp_q, act_range, batch=cache_bs)
+            calibrate_act_ranges(unit, inp_q, act_range, batch=cache_bs, percentile=act_percentile)
         if timing is not None:
             timing[-1]["act_s"] = _mark() - t4
     return eng

@@ -5,15 +5,18 @@ Kernel part: device-event timing after warm-up, the two quantisers ALTERNATING i
 median round is reported), µs per call and GB/s against algorithmic bytes -- static 8 B per element (one read, one write), dynamic 12
 (two reads, one write).  The static call does a strict subset of the dynamic call's work: a shape on which it is slower is flagged.
 The range search (one read, ten candidates) is timed next to them; with --bwd also the backward of the static quantiser (two reads, one
-write: 12 B per element), whose share of the static forward's GB/s on the same tensor is reported.
+write: 12 B per element), whose share of the static forward's GB/s on the same tensor is reported; with --hist the per-channel histogram
+pass of act_range='percentile' (one read, 1024 integer bins per channel) and its C-sized selection, in the same alternating windows as
+the search pass they stand in for.
 
 Learning part (--learn): wall time of `recon.learn_act_ranges` on one Cheng2020 block unit at N = 192 (a ResidualBlock on 32^2 inputs, what
 g_a[5] sees for 256^2 crops), after a short warm-up run, device synchronised at both ends.
 
 Flow part (--flow): the cache-building wall (`args.timing`, `cache_s`) of a W8A8 calibration schedule of a toy Cheng2020 (N = 8, 64^2
-crops) in both modes -- dynamic grids build every unit's caches image by image, static ones in batches.
+crops) in both modes -- dynamic grids build every unit's caches image by image, static ones in batches; with --hist also the range
+fixing wall (`act_s`) of the static flow under act_range='l2' against 'percentile'.
 
-    python tools/bench_actquant.py [--reps 1000] [--rounds 7] [--bwd] [--learn] [--flow] [--images 32] [--json out.json]"""
+    python tools/bench_actquant.py [--reps 1000] [--rounds 7] [--bwd] [--hist] [--learn] [--flow] [--images 32] [--json out.json]"""
 import argparse
 import json
 import os
@@ -41,7 +44,7 @@ def _time_us(fn, reps):
     return a.elapsed_time(b) * 1e3 / reps
 
 
-def bench_kernels(reps, rounds, n_bits=8, bwd=False):
+def bench_kernels(reps, rounds, n_bits=8, bwd=False, hist=False):
     from hipops import ops
     L = ops.L
     rows = []
@@ -65,6 +68,16 @@ def bench_kernels(reps, rounds, n_bits=8, bwd=False):
             dx, dr = torch.empty_like(x), torch.zeros(2 * C, device="cuda")
             bws = torch.empty(int(L.lib().rdo_actquant_static_bwd_workspace(C)), device="cuda")
             calls["bwd"] = lambda: ops.actquant_static_bwd(x, gx, rng, dr, dx=dx, n_bits=n_bits, ws=bws)
+        if hist:
+            hh = ops.act_hist_init(C, "cuda")
+            sel = [None]
+
+            def hist_call():
+                ops.actquant_hist(x, rng, hh)
+
+            def select_call():
+                sel[0] = ops.act_percentile_select(hh, rng, 1e-4)
+            calls["hist"], calls["select"] = hist_call, select_call
         r = reps
         for fn in calls.values():                              # warm-up: code objects, caches
             for _ in range(10):
@@ -73,6 +86,8 @@ def bench_kernels(reps, rounds, n_bits=8, bwd=False):
         t = {k: [] for k in calls}
         for _ in range(rounds):                                # alternate within one process
             for k, fn in calls.items():
+                if k == "hist":
+                    hh.zero_()                                     # (the counters are 32-bit: every window starts empty)
                 t[k].append(_time_us(fn, r))
         assert torch.equal(ops.actquant_static(x, rng, n_bits=n_bits), ops.actquant_perchannel(x, n_bits=n_bits))
         med = {k: statistics.median(v) for k, v in t.items()}
@@ -87,6 +102,11 @@ def bench_kernels(reps, rounds, n_bits=8, bwd=False):
             bwd_gbs = 12.0 * n / med["bwd"] / 1e3
             row.update(bwd_us=round(med["bwd"], 2), bwd_spread_us=[round(min(t["bwd"]), 2), round(max(t["bwd"]), 2)], bwd_gbs=round(bwd_gbs, 1),
                        bwd_share_of_static_gbs=round(bwd_gbs / (8.0 * n / med["static"] / 1e3), 2))
+        if hist:
+            assert int(hh.sum()) == r * n and bool((hh.sum(1) == r * (n // C)).all())     # the last window's counts: nothing lost
+            row.update(hist_us=round(med["hist"], 2), hist_spread_us=[round(min(t["hist"]), 2), round(max(t["hist"]), 2)],
+                       hist_gbs=round(4.0 * n / med["hist"] / 1e3, 1), select_us=round(med["select"], 2),
+                       hist_over_search=round(med["hist"] / med["search"], 2))
         rows.append(row)
         print(json.dumps(row), flush=True)
     return rows
@@ -125,13 +145,14 @@ def bench_learn(iters=100, images=64, batch=32, n=192, side=32, bits=8):
     return rows
 
 
-def bench_flow(images, iters=6):
-    """cache_s of every unit of the toy W8A8 schedule, dynamic then static (then dynamic and static again: the spread)."""
+def bench_flow(images, iters=6, hist=False):
+    """cache_s of every unit of the toy W8A8 schedule, dynamic then static (then dynamic and static again: the spread); with `hist`
+    then the static flow with act_range='l2' and 'percentile', twice each: their act_s."""
     import torch.nn as nn
     import lic
     from quantization import BaseQuantBlock, QuantModel, QuantModule, block_reconstruction, layer_reconstruction
 
-    def run(mode):
+    def run(mode, act_range="max"):
         torch.manual_seed(1005)
         model = lic.Cheng2020Anchor(N=8).cuda().eval()
         g = torch.Generator().manual_seed(13)
@@ -145,7 +166,7 @@ def bench_flow(images, iters=6):
         with torch.no_grad():
             qnn(cali[:2])
         timing = []
-        args = types.SimpleNamespace(lmbda=0.0483, task_loss=2.0, arch="Cheng2020", act_mode=mode, timing=timing)
+        args = types.SimpleNamespace(lmbda=0.0483, task_loss=2.0, arch="Cheng2020", act_mode=mode, act_range=act_range, timing=timing)
         kw = dict(cali_data=cali, batch_size=2, iters=iters, weight=0.01, input_prob=0.5, lr=4e-5, asym=True, b_range=(20, 2), warmup=0.2,
                   act_quant=True, opt_mode="mse", config=None, args=args)
         qnn.set_quant_state(True, True)
@@ -159,11 +180,14 @@ def bench_flow(images, iters=6):
                 else:
                     walk(c)
         walk(qnn)
-        return dict(mode=mode, images=images, units=len(timing), cache_s=round(sum(t["cache_s"] for t in timing), 4),
+        return dict(mode=mode, act_range=act_range, images=images, units=len(timing), cache_s=round(sum(t["cache_s"] for t in timing), 4),
                     act_s=round(sum(t.get("act_s", 0.0) for t in timing), 4), loop_s=round(sum(t["loop_s"] for t in timing), 4))
     rows = []
     for mode in ("dynamic", "static", "dynamic", "static"):
         rows.append(run(mode))
+        print(json.dumps(rows[-1]), flush=True)
+    for how in (("l2", "percentile", "l2", "percentile") if hist else ()):
+        rows.append(run("static", how))
         print(json.dumps(rows[-1]), flush=True)
     return rows
 
@@ -173,6 +197,8 @@ def main():
     ap.add_argument("--reps", type=int, default=1000, help="calls per timed window (7-33 us each: windows of 7 ms and more)")
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--bwd", action="store_true", help="also time the backward of the static quantiser")
+    ap.add_argument("--hist", action="store_true", help="also time the histogram pass and the selection of act_range='percentile'; with "
+                    "--flow also act_s of the toy flow under 'l2' against 'percentile'")
     ap.add_argument("--learn", action="store_true", help="time learn_act_ranges on one N = 192 block unit")
     ap.add_argument("--flow", action="store_true")
     ap.add_argument("--images", type=int, default=32)
@@ -180,14 +206,14 @@ def main():
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_actquant needs a GPU: there is no CPU path to time")
-    res = {"kernels": bench_kernels(a.reps, a.rounds, bwd=a.bwd)}
+    res = {"kernels": bench_kernels(a.reps, a.rounds, bwd=a.bwd, hist=a.hist)}
     slow = [r["shape"] for r in res["kernels"] if r["static_slower"]]
     if slow:
         print(f"DEFECT: static slower than dynamic on {slow}", flush=True)
     if a.learn:
         res["learn"] = bench_learn()
     if a.flow:
-        res["flow"] = bench_flow(a.images)
+        res["flow"] = bench_flow(a.images, hist=a.hist)
     if a.json:
         with open(a.json, "w") as f:
             json.dump(res, f, indent=1)
