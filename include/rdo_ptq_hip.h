@@ -282,7 +282,7 @@ int64_t rdo_actquant_static_bwd_workspace(int32_t C);
  * [lo_obs,c, hi_obs,c] and hi >= lo + 1e-3 w_c.  m, v [2 C]: the moments, updated.  C-sized. */
 int rdo_act_range_step(float* range /* [2 C], updated */, const float* grad /* [2 C] */, const float* obs /* [2 C] lo_obs | hi_obs */,
                        float* m, float* v, int32_t C, int32_t step, float lr, void* stream);
-/* Per-channel histogram on the observed range (extension: percentile ranges).  hist[C][1024] (int32, row-major) += the counts of
+/* Per-channel histogram on the observed range (extension: percentile and histogram-MSE ranges). hist[C][1024] (int32, row-major) += the counts of
  * x [npix][C] with, per element of channel c, w = max(hi_c - lo_c, 1e-6), t = ((x - lo_c) / w) * 1024 (each operation rounded on its own in
  * fp32), bin = 0 if t < 0, 1023 if t >= 1024, else (int)floor(t): a channel's maximum lands in bin 1023, its minimum in bin 0.  Non-finite
  * values are counted somewhere (not specified where).  One read of x; counts in LDS per workgroup, whose non-zero counters are added to
@@ -301,6 +301,23 @@ int rdo_actquant_hist(const float* x, int64_t npix, int32_t C, const float* rang
  * hi'[C]; out == range allowed.  C-sized: one wave per channel. */
 int rdo_act_percentile_select(const int32_t* hist /* [C][1024] */, int32_t C, const float* range /* [2 C] lo | hi, observed */, double tail,
                               float* out /* [2 C] */, void* stream);
+/* Histogram-MSE range of every channel from its histogram (extension: act_range = 'hist_mse'): the clip pair that minimises the modelled
+ * squared quantisation error AT THE GRID WIDTH n_bits, found by exhaustive search.  Per channel, with counts n_b (b = 0 .. 1023) on the
+ * observed range lo | hi, N = sum_b n_b (the caller keeps N < 2^31) and L1 = 2^n_bits - 1, the prefix tables (exact 64-bit integers)
+ *   C_lo(a) = sum_{b < a} n_b,            E_lo(a) = sum_{b < a} n_b (3 k^2 - 3 k + 1),  k = a - b,                      a = 0 .. 1023
+ *   C_hi(d) = sum_{b >= 1024 - d} n_b,    E_hi(d) = sum_{b >= 1024 - d} n_b (3 k^2 - 3 k + 1),  k = b - (1024 - d) + 1,  d = 0 .. 1023
+ * (E_lo(a) + E_hi(d) < 2^53) give every candidate (a, d) with a, d >= 0 and a + d <= 1023 (W = 1024 - a - d bins remain) the score
+ *   S(a, d) = (double)(4 L1^2) * (double)(E_lo(a) + E_hi(d))  +  (double)(N - C_lo(a) - C_hi(d)) * (double)(W * W)
+ * in binary64: the conversions are exact, the two products and the sum are each rounded on their own (no fused multiply-add).  S is
+ * 12 L1^2 / (bin width)^2 times the modelled squared error: a value spread uniformly over a clipped bin lies k^2 - k + 1/3 squared bin
+ * widths from the end, a kept value carries step^2 / 12 with step = W / L1 bins.  Chosen is the smallest S over ALL 524 800 candidates;
+ * among equal S the smallest a + d, then the smallest a.  New ends as rdo_act_percentile_select writes them, with wr = hi - lo (fp32):
+ *   lo' = a == 0 ? lo : lo + ((float)a / 1024) * wr,    hi' = d == 0 ? hi : lo + ((float)(1024 - d) / 1024) * wr.
+ * A channel with hi - lo < 1e-6 or N == 0 keeps lo | hi.  out = lo'[C] | hi'[C]; out == range allowed.  score: null, or [C][2] = S of the
+ * choice | S(0, 0) for a channel that searched, 0 | 0 for one that kept its range.  n_bits in [2, 16].  No atomics, no floating-point
+ * reduction: every launch gives the same bits.  C-sized: one workgroup per channel. */
+int rdo_act_hist_mse_select(const int32_t* hist /* [C][1024] */, int32_t C, const float* range /* [2 C] lo | hi, observed */, int32_t n_bits,
+                            float* out /* [2 C] */, double* score /* [C][2] or null */, void* stream);
 
 /* ---- K7: mini-batch assembly: out[b] = keep ? cache_q[idx[b]] : cache_fp[idx[b]], keep ~ counter RNG(seed, iter, i)
  * replaces cached_inps[..][idx] + torch.where(torch.rand_like(x) < p, x_q, x_fp)                layer_opt.py:289-292

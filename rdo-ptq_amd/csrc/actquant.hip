@@ -1,6 +1,6 @@
 // K6 -- per-channel activation quantisers on NHWC fp32 tensors (channel = fastest dim): the dynamic quantiser (min | max of the tensor
 // itself), the static one (a frozen lo | hi pair), the range search, the static backward, the Adam step of learned ranges, and the
-// per-channel histogram with its percentile selection.
+// per-channel histogram with its percentile and its histogram-MSE selection.
 // Built with -ffp-contract=off (products and sums round separately, like the reference's op chains).
 //
 // Three of them reduce over the pixels per channel, and all three do it the same way, without atomics: up to kAqBlocks workgroups each
@@ -420,6 +420,139 @@ __global__ __launch_bounds__(256) void aqh_select_kernel(const int* hist, int C,
     }
 }
 
+// ---- histogram-MSE range of a channel from its histogram (the rule of include/rdo_ptq_hip.h): the exhaustive search over all 524 800 clip
+// pairs (a bins off the bottom, d off the top, a + d <= 1023), one workgroup of 1024 per channel.  Tables in LDS (32 KiB): for every cut the
+// clipped count and the clipped squared distance E.  Both are exact integers below 2^53 and are kept as DOUBLES: the sum of two E and the
+// difference N - C_lo - C_hi are exact in binary64 too, so (double)(E_lo + E_hi) and (double)(N - C_lo - C_hi) of the rule are one fp64 add
+// each, the very values, and the top side's pair is ONE 16-byte LDS read.  A side's table is the exclusive block scan of the three moments
+// sum n, sum n b, sum n b^2 in 64-bit integers, thread t holding bin t (the top side scans the bins reversed); E(p) = (3 p^2 - 3 p + 1) M0
+// - (6 p - 3) M1 + 3 M2.  Thread t then owns ONE a -- t for the first 512 threads, 1023 - (t - 512) for the others, so the waves w, w + 4,
+// w + 8, w + 12 walk 2176 values of d between them for every w: the four SIMDs of the CU carry the same load -- and walks d upwards, four
+// candidates in flight: all lanes read the same hi[d], an LDS broadcast.  Within a thread a + d grows with d, so it keeps the first
+// strictly smaller S; across threads the key (S, a + d, a), a strict total order: a wave xor tree, then sixteen rows in LDS.  No atomics,
+// no floating-point reduction: every launch gives the same bits.
+// What bounds it: the issue of the candidate loop on the CU's four SIMDs -- per candidate a quarter of a 16-byte LDS broadcast
+// instruction's issue, three fp64 adds, two fp64 products, the integer W^2 and its conversion, one fp64 compare and three selects, times
+// 2176 trips of four waves per SIMD.  There is no memory stream (a channel reads its 4 KiB of counts twice); with C below the 256 CUs
+// every channel has a CU of its own, and the call does not grow with the pixels.
+constexpr int kAqmThreads = 1024;
+static_assert(kAqmThreads == kAqhBins, "thread = bin in the scans, thread = a in the search");
+struct AqmBest { double s; int a, d; };
+struct AqmTop { double e, c; };
+__device__ __forceinline__ bool aqm_better(double s, int a, int d, const AqmBest& b) {
+    return s < b.s || (s == b.s && (a + d < b.a + b.d || (a + d == b.a + b.d && a < b.a)));
+}
+
+// exclusive scan of one side: for the cut p = threadIdx.x in [0, 1023], cnt = the values in the p outermost bins, e = their squared
+// distance sum; `tot`: the waves' moment sums
+template <bool TOP>
+__device__ __forceinline__ void aqm_side(const int* h, long long (*tot)[3], long long& cnt, long long& e) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long p = threadIdx.x;                       // position from this side's end
+    const long long n = h[TOP ? kAqhBins - 1 - threadIdx.x : threadIdx.x];
+    const long long m[3] = {n, n * p, n * p * p};
+    long long incl[3] = {m[0], m[1], m[2]};
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const long long up = __shfl_up(incl[j], o, 64);
+            if (lane >= o) incl[j] += up;
+        }
+    }
+    if (lane == 63) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) tot[wave][j] = incl[j];
+    }
+    __syncthreads();
+    long long run[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        run[j] = incl[j] - m[j];
+        for (int w = 0; w < wave; ++w) run[j] += tot[w][j];
+    }
+    cnt = run[0];
+    e = (3 * p * p - 3 * p + 1) * run[0] - (6 * p - 3) * run[1] + 3 * run[2];
+}
+
+__global__ __launch_bounds__(kAqmThreads) void aqm_select_kernel(const int* hist, int C, const float* range, double k4l2, float* out,
+                                                                 double* score) {
+    constexpr int NW = kAqmThreads / 64;
+    __shared__ double c_lo[kAqhBins], e_lo[kAqhBins];
+    __shared__ AqmTop hi_t[kAqhBins];
+    __shared__ long long tot[2][NW][3];
+    __shared__ AqmBest red[NW];
+    const int c = blockIdx.x, t = threadIdx.x;             // grid = C
+    const int* h = hist + (long)c * kAqhBins;
+    long long cnt, e;
+    aqm_side<false>(h, tot[0], cnt, e);
+    c_lo[t] = (double)cnt;
+    e_lo[t] = (double)e;
+    const long long total = t == kAqhBins - 1 ? cnt + h[t] : 0;
+    aqm_side<true>(h, tot[1], cnt, e);
+    hi_t[t] = AqmTop{(double)e, (double)cnt};
+    __shared__ long long total_sm;
+    if (t == kAqhBins - 1) total_sm = total;
+    __syncthreads();
+    const long long n = total_sm;
+    const float lo = range[c], hi = range[C + c], wr = hi - lo;
+    if (wr < 1e-6f || n == 0) {                            // (the whole workgroup: nothing below is skipped by a part of it)
+        if (t == 0) {
+            out[c] = lo;
+            out[C + c] = hi;
+            if (score) score[2 * c] = score[2 * c + 1] = 0.0;
+        }
+        return;
+    }
+    const int a = t < 512 ? t : kAqhBins - 1 - (t - 512);
+    const int nd = kAqhBins - a;                           // d = 0 .. nd - 1
+    const double ea = e_lo[a], keep_a = (double)n - c_lo[a];
+    auto cand = [&](int d) {
+        const AqmTop v = hi_t[d];
+        const int w = nd - d;
+        return k4l2 * (ea + v.e) + (keep_a - v.c) * (double)(w * w);
+    };
+    double bs = INFINITY;
+    int bd = 0;
+    int d = 0;
+    for (; d + 4 <= nd; d += 4) {
+        double s[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) s[u] = cand(d + u);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const bool lt = s[u] < bs;
+            bs = lt ? s[u] : bs;
+            bd = lt ? d + u : bd;
+        }
+    }
+    for (; d < nd; ++d) {
+        const double s = cand(d);
+        const bool lt = s < bs;
+        bs = lt ? s : bs;
+        bd = lt ? d : bd;
+    }
+    AqmBest best{bs, a, bd};
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double s = __shfl_xor(best.s, o, 64);
+        const int a2 = __shfl_xor(best.a, o, 64), d2 = __shfl_xor(best.d, o, 64);
+        if (aqm_better(s, a2, d2, best)) best = AqmBest{s, a2, d2};
+    }
+    if ((t & 63) == 0) red[t >> 6] = best;
+    __syncthreads();
+    if (t == 0) {
+        for (int w = 1; w < NW; ++w)
+            if (aqm_better(red[w].s, red[w].a, red[w].d, best)) best = red[w];
+        out[c] = best.a == 0 ? lo : lo + ((float)best.a / (float)kAqhBins) * wr;
+        out[C + c] = best.d == 0 ? hi : lo + ((float)(kAqhBins - best.d) / (float)kAqhBins) * wr;
+        if (score) {
+            score[2 * c] = best.s;
+            score[2 * c + 1] = k4l2 * (e_lo[0] + hi_t[0].e) + ((double)n - c_lo[0] - hi_t[0].c) * (double)(kAqhBins * kAqhBins);
+        }
+    }
+}
+
 // ---- host helpers
 int aq_bit_range(int n_bits, const char* who, float* bit_range) {
     RDO_REQUIRE(n_bits >= 2 && n_bits <= 16, "%s: n_bits %d outside [2, 16]", who, n_bits);
@@ -573,6 +706,20 @@ int rdo_actquant_hist(const float* x, int64_t npix, int32_t C, const float* rang
             return rdo::check_launch("actquant_hist");
         },
         stream, "actquant_hist", 0.0, 4.0 * npix * C);
+}
+
+int rdo_act_hist_mse_select(const int32_t* hist, int32_t C, const float* range, int32_t n_bits, float* out, double* score, void* stream) {
+    RDO_REQUIRE(hist && range && out && C > 0, "rdo_act_hist_mse_select: bad argument");
+    float bit_range;
+    if (const int e = aq_bit_range(n_bits, "rdo_act_hist_mse_select", &bit_range)) return e;
+    const long long l1 = (1LL << n_bits) - 1;
+    const double k4l2 = (double)(4 * l1 * l1);              // exact: below 2^34
+    return rdo::dispatch(
+        [=](hipStream_t s) {
+            hipLaunchKernelGGL(aqm_select_kernel, dim3((unsigned)C), dim3(kAqmThreads), 0, s, hist, C, range, k4l2, out, score);
+            return rdo::check_launch("act_hist_mse_select");
+        },
+        stream, "act_hist_mse_select", 0.0, 4.0 * kAqhBins * C + 32.0 * C);
 }
 
 int rdo_act_percentile_select(const int32_t* hist, int32_t C, const float* range, double tail, float* out, void* stream) {

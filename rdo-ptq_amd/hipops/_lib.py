@@ -88,6 +88,7 @@ _SIGS = {
     "rdo_actquant_hist_bins": (C.c_int32, []),
     "rdo_actquant_hist": (C.c_int, [P, C.c_int64, C.c_int32, P, P, P]),
     "rdo_act_percentile_select": (C.c_int, [P, C.c_int32, P, C.c_double, P, P]),
+    "rdo_act_hist_mse_select": (C.c_int, [P, C.c_int32, P, C.c_int32, P, P, P]),
     "rdo_gather_qdrop": (C.c_int, [P, P, P, P, C.c_int32, C.c_int32, C.c_int64, C.c_float, C.c_uint32, P, P, P]),
     "rdo_lp2_loss_grad": (C.c_int, [P, P, P, P, C.c_int32, C.c_int64, C.c_int32, C.c_float, P, P, P]),
     "rdo_lp_loss_grad": (C.c_int, [P, P, P, P, C.c_int32, C.c_int64, C.c_int32, C.c_float, C.c_float, C.c_float, P, P, P, P]),

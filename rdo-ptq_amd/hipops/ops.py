@@ -424,6 +424,25 @@ def act_percentile_select(hist, rng, tail):
     return out
 
 
+def act_hist_mse_select(hist, rng, n_bits, score=False):
+    """-> a new range [2C]: every channel's observed range rng with the whole bins dropped from each end that minimise the modelled
+    squared quantisation error on a grid of n_bits (exhaustive search over all clip pairs: the rule of include/rdo_ptq_hip.h).
+    `score`: -> (range, float64 [C, 2] = S of the choice | S(0, 0); 0 | 0 for a channel that kept its range)."""
+    Cc = hist.shape[0]
+    if tuple(hist.shape) != (Cc, ACT_HIST_BINS) or hist.dtype != torch.int32 or not hist.is_contiguous() or rng.numel() != 2 * Cc:
+        raise ValueError(f"act_hist_mse_select: hist {hist.dtype} {tuple(hist.shape)} / range [{rng.numel()}] are not int32 "
+                         f"[C, {ACT_HIST_BINS}] / [2C]")
+    if isinstance(n_bits, bool) or not isinstance(n_bits, int) or not 2 <= n_bits <= 16:
+        raise ValueError(f"act_hist_mse_select: n_bits {n_bits!r} outside [2, 16]")
+    out = torch.empty_like(rng)
+    sc = torch.empty(Cc, 2, device=rng.device, dtype=torch.float64) if score else None
+    # (the scores are the library's only float64 tensor: made here, on rng's device, after _ptr has checked the others)
+    hp, rp, op = _ptr(hist), _ptr(rng), _ptr(out)
+    L.check(L.lib().rdo_act_hist_mse_select(hp, Cc, rp, n_bits, op, C.c_void_p(sc.data_ptr()) if score else None, _stream()),
+            "rdo_act_hist_mse_select")
+    return (out, sc) if score else out
+
+
 def gather_qdrop(cache_q, cache_fp, idx_table, iter_ptr, B, prob, seed, out, batch_offset=0, iter_publish=None):
     """`batch_offset`: row of the global mini-batch this (data-parallel) rank's first row is -- the QDrop counter runs over the
     global batch, so N ranks with one seed draw the mask a single process would."""

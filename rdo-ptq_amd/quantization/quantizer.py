@@ -92,6 +92,7 @@ def _act_rows(x: torch.Tensor, channels_last: bool = False):
 
 
 ACT_MODES = ("dynamic", "static")
+ACT_HIST_RULES = ("percentile", "mse")      # what `act_freeze` selects from a histogram pass
 
 
 # ----------------------------------------------------------------------------- uniform affine quantiser
@@ -137,6 +138,9 @@ class UniformAffineQuantizer(nn.Module):
         self.act_hist = {}
         self.act_tail = 0.0
         self.act_hist_n = {}
+        # which selection follows the histogram pass: "percentile" | "mse" (ACT_HIST_RULES).  Absent on models pickled before it existed:
+        # read with getattr, as "percentile"
+        self.act_hist_rule = "percentile"
         # frozen ranges on torch's tape (hipops.autograd.ActQuantStaticFn, straight-through round) when the input is tracked: set by
         # recon.reconstruct for the duration of an R + lambda*D unit.  Absent on models pickled before it existed: read with getattr
         self.act_ste = False
@@ -175,13 +179,17 @@ class UniformAffineQuantizer(nn.Module):
         self.act_obs = {k: r.clone() for k, r in self.act_range.items()}
         self.act_err = {k: torch.zeros(r.numel() // 2, ops.ACT_SEARCH_CANDIDATES, device=r.device) for k, r in self.act_range.items()}
 
-    def act_histogram(self, percentile: float = 99.99):
+    def act_histogram(self, percentile: float = 99.99, rule: str = "percentile"):
         """Start the histogram pass over the observed ranges: every call counts its values per channel into the site's 1024 bins and
         returns the max-range static output (what the search phase returns).  `act_freeze()` then clips a share 1 - percentile / 100 of
-        the counted values at each end of every channel, in whole bins."""
+        the counted values at each end of every channel, in whole bins (rule "percentile"), or drops the whole bins from each end that
+        minimise the modelled squared error on this quantiser's grid width (rule "mse": `percentile` is not used)."""
+        if rule not in ACT_HIST_RULES:
+            raise ValueError(f"unknown act_histogram rule {rule!r} {ACT_HIST_RULES}")
         if not self.act_range:
             raise RuntimeError("act_histogram: nothing was observed")
         self.act_phase = "hist"
+        self.act_hist_rule = rule
         self.act_tail = 1.0 - float(percentile) / 100.0
         self.act_obs = {k: r.clone() for k, r in self.act_range.items()}
         self.act_hist = {k: ops.act_hist_init(r.numel() // 2, r.device) for k, r in self.act_range.items()}
@@ -214,7 +222,8 @@ class UniformAffineQuantizer(nn.Module):
         keeps the first strictly better score).  Scaling towards zero moves an end that does not straddle zero (lo > 0 or hi < 0) OUT of
         the observed range, where no calibration value lies: such an end stays at the observed one, so a frozen range always lies inside
         its max range.  After a histogram pass each site becomes its percentile range (`ops.act_percentile_select`), which lies inside the
-        max range as well.  A quantiser that was never applied stays without a range ("idle").  After learning the ranges are detached as they
+        max range as well, or, under the rule "mse", its histogram-MSE range on the grid width `dynamic_bits` (`ops.act_hist_mse_select`).
+        A quantiser that was never applied stays without a range ("idle").  After learning the ranges are detached as they
         stand.  `keep_obs`: keep the observed max ranges for a learning phase that follows (they are not part of a frozen quantiser)."""
         self.act_range = {k: r.detach() for k, r in self.act_range.items()}
         for k, err in self.act_err.items():
@@ -226,7 +235,10 @@ class UniformAffineQuantizer(nn.Module):
             keep = lo > hi                                                 # (a candidate that left the observed range altogether)
             self.act_range[k] = torch.cat([torch.where(keep, rng[:c], lo), torch.where(keep, rng[c:], hi)])
         for k, hist in (getattr(self, "act_hist", None) or {}).items():
-            self.act_range[k] = ops.act_percentile_select(hist, self.act_range[k], getattr(self, "act_tail", 0.0))
+            if getattr(self, "act_hist_rule", "percentile") == "mse":
+                self.act_range[k] = ops.act_hist_mse_select(hist, self.act_range[k], int(getattr(self, "dynamic_bits", 8)))
+            else:
+                self.act_range[k] = ops.act_percentile_select(hist, self.act_range[k], getattr(self, "act_tail", 0.0))
         self.act_err, self.act_hist, self.act_hist_n = {}, {}, {}
         if not keep_obs:
             self.act_obs = {}

@@ -140,14 +140,15 @@ def _act_args(args):
     to the best of ten candidates by squared error) or 'learned' (the 'l2' ranges are then trained on the unit's reconstruction error:
     `learn_act_ranges`, with args.act_iters steps, default 500, of size args.act_lr, default 1e-3, relative to a channel's observed
     width) or 'percentile' (a second pass takes a 1024-bin histogram of every channel on its observed range; each end then gives up whole
-    bins while they hold no more than a share 1 - args.act_percentile / 100, default 99.99, of the channel's values).  Checked before any
-    work is done."""
+    bins while they hold no more than a share 1 - args.act_percentile / 100, default 99.99, of the channel's values) or 'hist_mse' (the
+    same histogram pass; each channel then takes the clip pair, out of all 524 800, that minimises the modelled squared error on its
+    grid width: `ops.act_hist_mse_select`).  Checked before any work is done."""
     mode = getattr(args, "act_mode", "dynamic") if args is not None else "dynamic"
     how = getattr(args, "act_range", "max") if args is not None else "max"
     if mode not in ("dynamic", "static"):
         raise ValueError(f"unknown act_mode {mode!r} ('dynamic' or 'static')")
-    if how not in ("max", "l2", "learned", "percentile"):
-        raise ValueError(f"unknown act_range {how!r} ('max', 'l2', 'learned' or 'percentile')")
+    if how not in ("max", "l2", "learned", "percentile", "hist_mse"):
+        raise ValueError(f"unknown act_range {how!r} ('max', 'l2', 'learned', 'percentile' or 'hist_mse')")
     _act_learn_args(args)
     _act_percentile_args(args)
     return mode, how
@@ -188,10 +189,11 @@ def calibrate_act_ranges(unit, inp_q, act_range="max", batch=32, keep_obs=False,
     evaluation uses (the unit, its QuantModules and nested block wrappers with weight and activation quantisation on) with its quantisers
     observing, then freeze them; with act_range='l2' a second pass over the same inputs accumulates the candidates' squared errors
     first; with act_range='percentile' the second pass takes every channel's histogram on its observed range, and freezing clips a
-    share 1 - percentile / 100 of its values at each end.  Under data parallelism the observed ranges and the error sums or histograms
-    are reduced over the ranks before they are used, so every rank freezes the same grid (integer counts: the very grid of one process
-    on all inputs).  Every quant state flag is left as it was found.  `keep_obs`: the quantisers keep the observed max ranges
-    next to the frozen ones (`act_obs`) for `learn_act_ranges`."""
+    share 1 - percentile / 100 of its values at each end; with act_range='hist_mse' the same pass is followed by the exhaustive search
+    for the clip pair of least modelled squared error on the quantiser's grid width.  Under data parallelism the observed ranges and
+    the error sums or histograms are reduced over the ranks before they are used, so every rank freezes the same grid (integer counts:
+    the very grid of one process on all inputs).  Every quant state flag is left as it was found.  `keep_obs`: the quantisers keep the
+    observed max ranges next to the frozen ones (`act_obs`) for `learn_act_ranges`."""
     if act_range == "percentile":
         percentile = _check_percentile(percentile)
     mods = [m for m in unit.modules() if isinstance(m, (QuantModule, BaseQuantBlock))]
@@ -219,10 +221,10 @@ def calibrate_act_ranges(unit, inp_q, act_range="max", batch=32, keep_obs=False,
                     q.act_search()
             run()
             dp.reduce_act_stats(sums=applied("act_err"))
-        elif act_range == "percentile":
+        elif act_range in ("percentile", "hist_mse"):
             for q in quants:
                 if q.act_range:
-                    q.act_histogram(percentile)
+                    q.act_histogram(percentile, rule="mse" if act_range == "hist_mse" else "percentile")
             run()
             dp.reduce_act_stats(sums=applied("act_hist"))
         for q in quants:

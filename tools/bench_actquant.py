@@ -6,15 +6,15 @@ median round is reported), µs per call and GB/s against algorithmic bytes -- st
 (two reads, one write).  The static call does a strict subset of the dynamic call's work: a shape on which it is slower is flagged.
 The range search (one read, ten candidates) is timed next to them; with --bwd also the backward of the static quantiser (two reads, one
 write: 12 B per element), whose share of the static forward's GB/s on the same tensor is reported; with --hist the per-channel histogram
-pass of act_range='percentile' (one read, 1024 integer bins per channel) and its C-sized selection, in the same alternating windows as
-the search pass they stand in for.
+pass of act_range='percentile' and 'hist_mse' (one read, 1024 integer bins per channel) and their C-sized selections (the percentile
+cut and the exhaustive histogram-MSE search), in the same alternating windows as the search pass they stand in for.
 
 Learning part (--learn): wall time of `recon.learn_act_ranges` on one Cheng2020 block unit at N = 192 (a ResidualBlock on 32^2 inputs, what
 g_a[5] sees for 256^2 crops), after a short warm-up run, device synchronised at both ends.
 
 Flow part (--flow): the cache-building wall (`args.timing`, `cache_s`) of a W8A8 calibration schedule of a toy Cheng2020 (N = 8, 64^2
 crops) in both modes -- dynamic grids build every unit's caches image by image, static ones in batches; with --hist also the range
-fixing wall (`act_s`) of the static flow under act_range='l2' against 'percentile'.
+fixing wall (`act_s`) of the static flow under act_range='l2' against 'percentile' and 'hist_mse'.
 
     python tools/bench_actquant.py [--reps 1000] [--rounds 7] [--bwd] [--hist] [--learn] [--flow] [--images 32] [--json out.json]"""
 import argparse
@@ -77,7 +77,10 @@ def bench_kernels(reps, rounds, n_bits=8, bwd=False, hist=False):
 
             def select_call():
                 sel[0] = ops.act_percentile_select(hh, rng, 1e-4)
-            calls["hist"], calls["select"] = hist_call, select_call
+
+            def select_mse_call():
+                sel[0] = ops.act_hist_mse_select(hh, rng, n_bits)
+            calls["hist"], calls["select"], calls["select_mse"] = hist_call, select_call, select_mse_call
         r = reps
         for fn in calls.values():                              # warm-up: code objects, caches
             for _ in range(10):
@@ -106,6 +109,8 @@ def bench_kernels(reps, rounds, n_bits=8, bwd=False, hist=False):
             assert int(hh.sum()) == r * n and bool((hh.sum(1) == r * (n // C)).all())     # the last window's counts: nothing lost
             row.update(hist_us=round(med["hist"], 2), hist_spread_us=[round(min(t["hist"]), 2), round(max(t["hist"]), 2)],
                        hist_gbs=round(4.0 * n / med["hist"] / 1e3, 1), select_us=round(med["select"], 2),
+                       select_mse_us=round(med["select_mse"], 2),
+                       select_mse_spread_us=[round(min(t["select_mse"]), 2), round(max(t["select_mse"]), 2)],
                        hist_over_search=round(med["hist"] / med["search"], 2))
         rows.append(row)
         print(json.dumps(row), flush=True)
@@ -147,7 +152,7 @@ def bench_learn(iters=100, images=64, batch=32, n=192, side=32, bits=8):
 
 def bench_flow(images, iters=6, hist=False):
     """cache_s of every unit of the toy W8A8 schedule, dynamic then static (then dynamic and static again: the spread); with `hist`
-    then the static flow with act_range='l2' and 'percentile', twice each: their act_s."""
+    then the static flow with act_range='l2', 'percentile' and 'hist_mse', twice each: their act_s."""
     import torch.nn as nn
     import lic
     from quantization import BaseQuantBlock, QuantModel, QuantModule, block_reconstruction, layer_reconstruction
@@ -186,7 +191,7 @@ def bench_flow(images, iters=6, hist=False):
     for mode in ("dynamic", "static", "dynamic", "static"):
         rows.append(run(mode))
         print(json.dumps(rows[-1]), flush=True)
-    for how in (("l2", "percentile", "l2", "percentile") if hist else ()):
+    for how in (("l2", "percentile", "hist_mse") * 2 if hist else ()):
         rows.append(run("static", how))
         print(json.dumps(rows[-1]), flush=True)
     return rows
@@ -197,8 +202,8 @@ def main():
     ap.add_argument("--reps", type=int, default=1000, help="calls per timed window (7-33 us each: windows of 7 ms and more)")
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--bwd", action="store_true", help="also time the backward of the static quantiser")
-    ap.add_argument("--hist", action="store_true", help="also time the histogram pass and the selection of act_range='percentile'; with "
-                    "--flow also act_s of the toy flow under 'l2' against 'percentile'")
+    ap.add_argument("--hist", action="store_true", help="also time the histogram pass and the selections of act_range='percentile' and 'hist_mse'; "
+                    "with --flow also act_s of the toy flow under 'l2' against 'percentile' and 'hist_mse'")
     ap.add_argument("--learn", action="store_true", help="time learn_act_ranges on one N = 192 block unit")
     ap.add_argument("--flow", action="store_true")
     ap.add_argument("--images", type=int, default=32)
