@@ -264,6 +264,22 @@ int rdo_actquant_search(const float* x, int64_t npix, int32_t C, int32_t n_bits,
                         float* err /* [C][10] */, float* ws /* rdo_actquant_search_workspace(C) floats, no initial state needed */,
                         void* stream);
 int64_t rdo_actquant_search_workspace(int32_t C);
+/* Range scoring (extension: act_range = 'auto' and the per-site report): the MEASURED squared error of K arbitrary grids per channel.
+ * cand = K rows of lo_k[C] | hi_k[C]; with Q_k the static expression of rdo_actquant_static on lo_k | hi_k (r = max(hi_k - lo_k, 1e-6), lower
+ * clamp 0: the scored grid is the applied grid, bit for bit),
+ *   err[c][k]       += sum_p (x - Q_k(x))^2
+ *   clip[c][k][0|1] += #(x < lo_k,c) | #(x > hi_k,c)        (plain fp32 comparisons, as in rdo_actquant_static_bwd; exact integers)
+ *   energy[c]       += sum_p x^2
+ * clip and energy may be null (err is the same bits with or without them).  One read of x (16-byte accesses when C % 4 == 0 and x is
+ * 16-byte aligned); per-workgroup partial sums in ws, folded in a fixed order (no atomics: the same input gives the same bits); no serial
+ * fp32 chain longer than 1024 terms; the counts are added as 32-bit integers.  All three outputs are ACCUMULATED INTO (zero them before the
+ * first batch); the caller keeps a channel's total pixel count below 2^31.  Refused before any launch: a null x, cand, err or ws, C <= 0,
+ * npix <= 0 or npix >= 2^31, K outside [1, RDO_ACT_SCORE_MAX], n_bits outside [2, 16]. */
+#define RDO_ACT_SCORE_MAX 4
+int rdo_actquant_score(const float* x, int64_t npix, int32_t C, int32_t n_bits, const float* cand /* [K][2 C] */, int32_t K,
+                       float* err /* [C][K] */, int32_t* clip /* [C][K][2] or null */, float* energy /* [C] or null */,
+                       float* ws /* rdo_actquant_score_workspace(C, K) floats, no initial state needed */, void* stream);
+int64_t rdo_actquant_score_workspace(int32_t C, int32_t K);
 /* Backward of rdo_actquant_static with a straight-through round (extension: learned activation ranges, and the R + lambda*D task loss behind
  * frozen quantisers).  y = the forward's value (the same expression on the same operands), r = max(hi_c - lo_c, 1e-6); an element is
  * below if x < lo_c, above if x > hi_c (plain fp32 comparisons), inside otherwise:

@@ -1,9 +1,9 @@
 // K6 -- per-channel activation quantisers on NHWC fp32 tensors (channel = fastest dim): the dynamic quantiser (min | max of the tensor
-// itself), the static one (a frozen lo | hi pair), the range search, the static backward, the Adam step of learned ranges, and the
-// per-channel histogram with its percentile and its histogram-MSE selection.
+// itself), the static one (a frozen lo | hi pair), the range search, the range scoring, the static backward, the Adam step of learned
+// ranges, and the per-channel histogram with its percentile and its histogram-MSE selection.
 // Built with -ffp-contract=off (products and sums round separately, like the reference's op chains).
 //
-// Three of them reduce over the pixels per channel, and all three do it the same way, without atomics: up to kAqBlocks workgroups each
+// Four of them reduce over the pixels per channel, and all four do it the same way, without atomics: up to kAqBlocks workgroups each
 // leave one row of partial values for their share of the pixels (aq_partial below), a small second kernel folds the rows (aq_fold_kernel).
 // (The first version let 1024 workgroups atomicMin / atomicMax into the same 2 C words: 0.4 M contended atomics per call were most of its
 // time.)  The order of the fp32 additions is fixed HERE, once, and frozen ranges depend on it: a thread's running sum over its pixels in
@@ -220,6 +220,99 @@ template <int W>
 __global__ __launch_bounds__(256) void aqb_partial_kernel(const float* x, const float* g, long npix, int C, const float* range, float bit_range,
                                                           float* dx, float* part) {
     aq_partial<W, 4>(AqBackward<W>{x, g, range, bit_range, dx}, npix, C, part);
+}
+
+// ---- range scoring: the measured squared error of K arbitrary grids lo_k | hi_k per channel, err[c][k] = sum over pixels of
+// (x - Q_k(x))^2 with Q_k the static quantiser's own expression (aq_quant on max(hi_k - lo_k, 1e-6), lower clamp 0: the scored grid is the
+// applied grid), next to it the counts of the values below lo_k and above hi_k (fp32 comparisons of x with the ends, as in the backward)
+// and the channel's energy sum x^2.  One read of x, W x (3 K + 1) running values (and as many closed ones) in registers, so one pixel in
+// flight like the search; part = [workgroup][C][err[K] | (below, above)[K] | energy].  A count runs as an integer-valued float: a
+// workgroup sees about npix / workgroups pixels of a channel, and there are kAqBlocks workgroups unless npix < 8 * 256 * kAqBlocks: below
+// 2^24 for every npix < 2^31 the entry admits, so a partial row holds the exact integer, and the fold (aqc_fold_kernel) adds the rows as
+// int32.
+constexpr int kAqcMax = RDO_ACT_SCORE_MAX;
+template <int W, int K>
+struct AqScore {
+    typedef float in_t __attribute__((ext_vector_type(W)));
+    static constexpr int N = 3 * K + 1;
+    static constexpr bool kChain = true, kChannelMajor = true;
+    const float* x;
+    const float* cand;                                     // [K][2C]
+    float bit_range;
+    float lo[K][W], hi[K][W];
+    __device__ static float zero(int) { return 0.f; }
+    __device__ static float combine(float a, float v, int) { return a + v; }
+    __device__ void begin(int q, int C) {
+#pragma unroll
+        for (int j = 0; j < K; ++j)
+#pragma unroll
+            for (int k = 0; k < W; ++k) {
+                lo[j][k] = cand[(long)j * 2 * C + q * W + k];
+                hi[j][k] = cand[(long)j * 2 * C + C + q * W + k];
+            }
+    }
+    __device__ in_t load(long off) const { return *reinterpret_cast<const in_t*>(x + off); }
+    __device__ void pixel(const in_t& v, long, float (&acc)[W][N]) const {
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                const float rng = fmaxf(hi[j][k] - lo[j][k], 1e-6f);
+                const float d = v[k] - aq_quant(v[k], lo[j][k], rng, bit_range, 0.f);
+                acc[k][j] += d * d;
+                acc[k][K + 2 * j] += v[k] < lo[j][k] ? 1.f : 0.f;
+                acc[k][K + 2 * j + 1] += v[k] > hi[j][k] ? 1.f : 0.f;
+            }
+            acc[k][3 * K] += v[k] * v[k];
+        }
+    }
+};
+template <int W, int K>
+__global__ __launch_bounds__(256) void aqc_partial_kernel(const float* x, long npix, int C, const float* cand, float bit_range, float* part) {
+    aq_partial<W, 1>(AqScore<W, K>{x, cand, bit_range}, npix, C, part);
+}
+
+// fold of the score's partial rows [workgroup][C][3 K + 1]: the lanes and the order of aq_fold_kernel<true> (lane j adds the rows j, j + 16,
+// .. serially, then the xor tree 8, 4, 2, 1); an error or energy entry is summed in fp32, a count entry in int32 (every row's value is an
+// exact integer below 2^24).  err and energy += the sum, clip += the count; clip and energy may be null.
+__global__ __launch_bounds__(256) void aqc_fold_kernel(const float* part, int nblk, int C, int K, float* err, int* clip, float* energy) {
+    const int N = 3 * K + 1, n = C * N;
+    const int i = blockIdx.x * 16 + (threadIdx.x >> 4), j = threadIdx.x & 15;
+    const bool live = i < n;
+    const int c = i / N, e = i - c * N;
+    const bool count = e >= K && e < 3 * K;
+    float r = 0.f;
+    int ri = 0;
+    if (live) {
+        const float* src = part + i;
+        int b = j;
+        for (; b + 48 < nblk; b += 64) {
+            float v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) v[u] = src[(long)(b + 16 * u) * n];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                r = r + v[u];
+                ri += count ? (int)v[u] : 0;
+            }
+        }
+        for (; b < nblk; b += 16) {
+            const float v = src[(long)b * n];
+            r = r + v;
+            ri += count ? (int)v : 0;
+        }
+    }
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) {
+        r = r + __shfl_xor(r, o, 16);
+        ri += __shfl_xor(ri, o, 16);
+    }
+    if (live && j == 0) {
+        if (e < K) err[c * K + e] += r;
+        else if (count) {
+            if (clip) clip[c * 2 * K + (e - K)] += ri;
+        } else if (energy) energy[c] += r;
+    }
 }
 
 // ---- fold of the `nblk` partial rows of n entries: sixteen lanes per entry walk the rows (independent loads, no serial chain of nblk
@@ -647,6 +740,41 @@ int rdo_actquant_search(const float* x, int64_t npix, int32_t C, int32_t n_bits,
 }
 
 int64_t rdo_actquant_search_workspace(int32_t C) { return C > 0 ? (int64_t)C * kAqsCand * kAqBlocks : 0; }
+
+int rdo_actquant_score(const float* x, int64_t npix, int32_t C, int32_t n_bits, const float* cand, int32_t K, float* err, int32_t* clip,
+                       float* energy, float* ws, void* stream) {
+    RDO_REQUIRE(x && cand && err && ws && npix > 0 && C > 0, "rdo_actquant_score: bad argument");
+    RDO_REQUIRE(K >= 1 && K <= kAqcMax, "rdo_actquant_score: K %d outside [1, %d]", K, kAqcMax);
+    float bit_range;
+    if (const int e = aq_bit_range(n_bits, "rdo_actquant_score", &bit_range)) return e;
+    RDO_REQUIRE(npix <= 0x7fffffffLL, "rdo_actquant_score: %lld pixels do not fit a channel's 32-bit counts", (long long)npix);
+    RDO_REQUIRE((int64_t)C * (3 * kAqcMax + 1) <= 0x7fffffffLL, "rdo_actquant_score: %d channels are too many for 32-bit entry indices", C);
+    const bool vec = aq_vec(C, {x});
+    return rdo::dispatch(
+        [=](hipStream_t s) {
+            aq_with_width(vec, [&](auto w) {
+                constexpr int W = decltype(w)::value;
+                const int nblk = aq_blocks(npix, C, W);
+                auto launch = [&](auto k) {
+                    hipLaunchKernelGGL((aqc_partial_kernel<W, decltype(k)::value>), dim3(nblk), dim3(256), 0, s, x, (long)npix, C, cand,
+                                       bit_range, ws);
+                };
+                switch (K) {
+                    case 1: launch(std::integral_constant<int, 1>{}); break;
+                    case 2: launch(std::integral_constant<int, 2>{}); break;
+                    case 3: launch(std::integral_constant<int, 3>{}); break;
+                    default: launch(std::integral_constant<int, 4>{}); break;
+                }
+                hipLaunchKernelGGL(aqc_fold_kernel, aq_fold_grid(C * (3 * K + 1)), dim3(256), 0, s, ws, nblk, C, K, err, clip, energy);
+            });
+            return rdo::check_launch("actquant_score");
+        },
+        stream, "actquant_score", 0.0, 4.0 * npix * C);
+}
+
+int64_t rdo_actquant_score_workspace(int32_t C, int32_t K) {
+    return C > 0 && K >= 1 && K <= kAqcMax ? (int64_t)C * (3 * K + 1) * kAqBlocks : 0;
+}
 
 int rdo_actquant_static_bwd(const float* x, const float* g, int64_t npix, int32_t C, int32_t n_bits, const float* range, float* dx,
                             float* drange, float* ws, void* stream) {

@@ -368,6 +368,40 @@ def actquant_search(x, rng, err, n_bits=8, ws=None):
     return err
 
 
+ACT_SCORE_MAX = 4                 # RDO_ACT_SCORE_MAX of include/rdo_ptq_hip.h: grids scored in one read of the tensor
+
+
+def actquant_score(x, cand, err, clip=None, energy=None, n_bits=8, ws=None):
+    """The measured squared error of K grids on x [..., C]: cand [K, 2C] = rows lo_k | hi_k; err [C, K] += sum (x - Q_k(x))^2 with Q_k the
+    expression of `actquant_static` on row k; clip [C, K, 2] (int32) += the counts of x < lo_k | x > hi_k; energy [C] += sum x^2.  `clip`
+    and `energy` may be None (err is the same bits).  Everything is checked on the host before the call."""
+    def bad(t, shape, dtype):
+        return not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous()
+    if not torch.is_tensor(x) or x.dim() < 1 or x.dtype != torch.float32 or not x.is_contiguous() or x.numel() == 0:
+        raise ValueError("actquant_score: x must be a non-empty contiguous fp32 tensor [..., C]")
+    Cc = x.shape[-1]
+    if not torch.is_tensor(cand) or cand.dim() != 2 or not 1 <= cand.shape[0] <= ACT_SCORE_MAX:
+        raise ValueError(f"actquant_score: cand must be [K, 2C] with K in 1..{ACT_SCORE_MAX}, got "
+                         f"{tuple(cand.shape) if torch.is_tensor(cand) else type(cand).__name__}")
+    K = int(cand.shape[0])
+    if bad(cand, (K, 2 * Cc), torch.float32):
+        raise ValueError(f"actquant_score: cand must be a contiguous fp32 [{K}, {2 * Cc}], got {cand.dtype} {tuple(cand.shape)}")
+    if bad(err, (Cc, K), torch.float32):
+        raise ValueError(f"actquant_score: err must be a contiguous fp32 [{Cc}, {K}]")
+    if clip is not None and bad(clip, (Cc, K, 2), torch.int32):
+        raise ValueError(f"actquant_score: clip must be a contiguous int32 [{Cc}, {K}, 2] or None")
+    if energy is not None and bad(energy, (Cc,), torch.float32):
+        raise ValueError(f"actquant_score: energy must be a contiguous fp32 [{Cc}] or None")
+    if isinstance(n_bits, bool) or not isinstance(n_bits, int) or not 2 <= n_bits <= 16:
+        raise ValueError(f"actquant_score: n_bits {n_bits!r} outside [2, 16]")
+    need = int(L.lib().rdo_actquant_score_workspace(Cc, K))
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, device=x.device, dtype=torch.float32)
+    L.check(L.lib().rdo_actquant_score(_ptr(x), x.numel() // Cc, Cc, n_bits, _ptr(cand), K, _ptr(err), _ptr(clip), _ptr(energy), _ptr(ws),
+                                       _stream()), "rdo_actquant_score")
+    return err
+
+
 def actquant_static_bwd(x, g, rng, drange, dx=None, n_bits=8, ws=None):
     """Backward of `actquant_static` with a straight-through round: returns dx (= g inside the range, 0 outside; `dx` may be g) and
     accumulates the per-channel range gradient into drange [2C] = dlo | dhi.  x, g: [..., C] channels-last, contiguous."""

@@ -29,7 +29,8 @@ def shard(cali_data, group=None):
 def reduce_act_stats(ranges=(), sums=(), group=None):
     """Static activation ranges under data parallelism: every rank observed its shard, every rank must freeze the same grid.  In place:
     each `ranges` tensor [2C] = lo | hi gets MIN over the ranks on its lo half and MAX on its hi half, each `sums` tensor (the search's
-    error sums, fp32, or the percentile histograms, int32: whatever dtype it is given) gets SUM.  Works on CPU tensors over gloo and on
+    error sums, fp32, the percentile histograms, int32, or a scoring pass's fp32 error and energy sums and int32 clipped counts: whatever
+    dtype it is given) gets SUM.  Works on CPU tensors over gloo and on
     device tensors over RCCL; without a process group nothing happens.
     Every rank must pass the same tensors in the same order."""
     if world(group)[1] <= 1:

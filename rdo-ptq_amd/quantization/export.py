@@ -42,5 +42,31 @@ def activation_state(qnn) -> "OrderedDict[str, dict]":
     return out
 
 
+def activation_report(qnn) -> "OrderedDict[str, dict]":
+    """name -> {err, energy (fp32 [channels]), clip_lo, clip_hi (int32 [channels]), n, sqnr_db, clipped_share (float64 [channels]), n_bits,
+    channels} of every frozen static activation range whose statistics were recorded (args.act_report; the names of
+    `QuantModel.act_ranges`), on the CPU: the squared error of the frozen grid measured on the calibration inputs, their energy sum x^2,
+    the counts of the values below and above the range, the values seen per channel; sqnr_db = 10 log10(energy / err) in float64 (inf
+    where err == 0), clipped_share = (clip_lo + clip_hi) / n.  Empty for a model without recorded statistics."""
+    out = OrderedDict()
+    for name, q in qnn.act_quantizers():
+        stats = getattr(q, "act_stats", None) or {}
+        if not q.act_frozen():
+            continue
+        for site in sorted(q.act_range):
+            st = stats.get(site)
+            if st is None:
+                continue
+            err, energy = st["err"].detach().cpu().clone(), st["energy"].detach().cpu().clone()
+            lo, hi, n = st["clip_lo"].detach().cpu().clone(), st["clip_hi"].detach().cpu().clone(), int(st["n"])
+            e64, s64 = err.double(), energy.double()
+            sqnr = torch.where(e64 == 0, torch.full_like(e64, float("inf")), 10.0 * torch.log10(s64 / e64))
+            out[name if site == 0 else f"{name}#{site}"] = {
+                "err": err, "energy": energy, "clip_lo": lo, "clip_hi": hi, "n": n, "sqnr_db": sqnr,
+                "clipped_share": (lo.double() + hi.double()) / max(n, 1), "n_bits": int(getattr(q, "dynamic_bits", 8)),
+                "channels": int(err.numel())}
+    return out
+
+
 def dequantize(entry) -> torch.Tensor:
     return (entry["levels"].to(torch.float32) - entry["zero_point"]) * entry["delta"]

@@ -75,6 +75,12 @@ class QuantModel(nn.Module):
                 out[name if site == 0 else f"{name}#{site}"] = (r[:c], r[c:], getattr(q, "dynamic_bits", 8))
         return out
 
+    def act_report(self):
+        """OrderedDict name -> the measured statistics of every frozen static range that was recorded (args.act_report):
+        `export.activation_report`, under the site names of `act_ranges`."""
+        from .export import activation_report
+        return activation_report(self)
+
     def forward(self, input):
         return self.model(input)
 

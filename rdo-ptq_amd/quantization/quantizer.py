@@ -93,6 +93,31 @@ def _act_rows(x: torch.Tensor, channels_last: bool = False):
 
 ACT_MODES = ("dynamic", "static")
 ACT_HIST_RULES = ("percentile", "mse")      # what `act_freeze` selects from a histogram pass
+ACT_AUTO_CANDIDATES = ("max", "l2", "percentile", "hist_mse")      # the rows of `act_candidates`, in the order that breaks ties
+
+
+def act_l2_range(rng, err):
+    """The range an 'l2' search freezes: each channel of the observed rng [2C] shrunk to its best candidate lo * s_k | hi * s_k of err
+    [C, 10] (first minimum), an end that the scaling moved OUT of the observed range put back on it."""
+    c = rng.numel() // 2
+    table = torch.tensor([1.0 - 0.05 * i for i in range(ops.ACT_SEARCH_CANDIDATES)], dtype=torch.float32, device=rng.device)
+    s = table[err.argmin(dim=1)]                                   # (float)(1 - 0.05 k): the kernel's factors
+    lo, hi = torch.maximum(rng[:c] * s, rng[:c]), torch.minimum(rng[c:] * s, rng[c:])
+    keep = lo > hi                                                 # (a candidate that left the observed range altogether)
+    return torch.cat([torch.where(keep, rng[:c], lo), torch.where(keep, rng[c:], hi)])
+
+
+def act_score_winner(err):
+    """err [C, K] (measured error sums) -> long [C]: the row of the smallest sum; among equal sums the earliest row; a NaN sum never
+    wins; a channel whose sums are all NaN gets row 0 (the max range).  Written out: `torch.argmin` does not promise the first index."""
+    best = torch.full((err.shape[0],), float("inf"), dtype=err.dtype, device=err.device)
+    win = torch.zeros(err.shape[0], dtype=torch.long, device=err.device)
+    found = torch.zeros(err.shape[0], dtype=torch.bool, device=err.device)
+    for k in range(err.shape[1]):
+        e = err[:, k]
+        better = ~torch.isnan(e) & (~found | (e < best))
+        best, win, found = torch.where(better, e, best), torch.where(better, torch.full_like(win, k), win), found | better
+    return win
 
 
 # ----------------------------------------------------------------------------- uniform affine quantiser
@@ -129,7 +154,8 @@ class UniformAffineQuantizer(nn.Module):
         if act_mode not in ACT_MODES:
             raise ValueError(f"unknown act_mode {act_mode!r} {ACT_MODES}")
         self.act_mode = act_mode
-        self.act_phase = "idle"            # static only: "idle" (no range yet) | "observe" | "search" | "hist" | "frozen" | "learn"
+        # static only: "idle" (no range yet) | "observe" | "search" | "hist" | "search+hist" | "score" | "frozen" | "learn"
+        self.act_phase = "idle"
         self.act_range = {}                # site -> fp32 [2C], lo | hi (leaf tensors with requires_grad while learning)
         self.act_err = {}                  # site -> fp32 [C, 10] while searching
         self.act_obs = {}                  # site -> fp32 [2C]: the observed max range, kept for / while learning the ranges
@@ -144,6 +170,16 @@ class UniformAffineQuantizer(nn.Module):
         # frozen ranges on torch's tape (hipops.autograd.ActQuantStaticFn, straight-through round) when the input is tracked: set by
         # recon.reconstruct for the duration of an R + lambda*D unit.  Absent on models pickled before it existed: read with getattr
         self.act_ste = False
+        # the scoring pass (`act_score`): site -> candidate grids fp32 [K, 2C], measured error sums `act_err` [C, K], clipped counts int32
+        # [C, K, 2], energies fp32 [C], pixels scored (on the host); `act_score_kind`: "auto" (act_freeze picks each channel's winner) or
+        # "report" (act_freeze records `act_stats` of the frozen range).  act_stats: site -> {err, energy, clip_lo, clip_hi, n}, kept on
+        # the frozen quantiser.  All absent on models pickled before they existed: read with getattr
+        self.act_cand = {}
+        self.act_clip = {}
+        self.act_energy = {}
+        self.act_score_n = {}
+        self.act_score_kind = "auto"
+        self.act_stats = {}
 
     def _apply(self, fn, *args, **kwargs):
         super()._apply(fn, *args, **kwargs)
@@ -151,10 +187,13 @@ class UniformAffineQuantizer(nn.Module):
             t = getattr(self, name, None)
             if torch.is_tensor(t):
                 setattr(self, name, fn(t))
-        for name in ("act_range", "act_err", "act_obs", "act_hist"):
+        for name in ("act_range", "act_err", "act_obs", "act_hist", "act_cand", "act_clip", "act_energy"):
             d = getattr(self, name, None)
             if isinstance(d, dict):
                 setattr(self, name, {k: fn(t) for k, t in d.items()})
+        st = getattr(self, "act_stats", None)
+        if isinstance(st, dict):
+            self.act_stats = {k: {f: (fn(t) if torch.is_tensor(t) else t) for f, t in d.items()} for k, d in st.items()}
         return self
 
     # -- static activation grids ----------------------------------------------------------------------------------
@@ -169,6 +208,7 @@ class UniformAffineQuantizer(nn.Module):
     def act_observe(self):
         """Start observing: every call quantises dynamically and merges the batch's per-channel min / max into the site's range."""
         self.act_phase, self.act_range, self.act_err, self.act_obs, self.act_hist = "observe", {}, {}, {}, {}
+        self.act_cand, self.act_clip, self.act_energy, self.act_score_n, self.act_stats = {}, {}, {}, {}, {}
 
     def act_search(self):
         """Start the L2 search over the observed ranges: every call accumulates the ten candidates' squared errors and returns the
@@ -179,16 +219,20 @@ class UniformAffineQuantizer(nn.Module):
         self.act_obs = {k: r.clone() for k, r in self.act_range.items()}
         self.act_err = {k: torch.zeros(r.numel() // 2, ops.ACT_SEARCH_CANDIDATES, device=r.device) for k, r in self.act_range.items()}
 
-    def act_histogram(self, percentile: float = 99.99, rule: str = "percentile"):
+    def act_histogram(self, percentile: float = 99.99, rule: str = "percentile", search: bool = False):
         """Start the histogram pass over the observed ranges: every call counts its values per channel into the site's 1024 bins and
         returns the max-range static output (what the search phase returns).  `act_freeze()` then clips a share 1 - percentile / 100 of
         the counted values at each end of every channel, in whole bins (rule "percentile"), or drops the whole bins from each end that
-        minimise the modelled squared error on this quantiser's grid width (rule "mse": `percentile` is not used)."""
+        minimise the modelled squared error on this quantiser's grid width (rule "mse": `percentile` is not used).  `search`: the same
+        calls also accumulate the L2 search's error sums (phase "search+hist": both read the same max-range inputs), for
+        `act_candidates`."""
         if rule not in ACT_HIST_RULES:
             raise ValueError(f"unknown act_histogram rule {rule!r} {ACT_HIST_RULES}")
         if not self.act_range:
             raise RuntimeError("act_histogram: nothing was observed")
-        self.act_phase = "hist"
+        self.act_phase = "search+hist" if search else "hist"
+        if search:
+            self.act_err = {k: torch.zeros(r.numel() // 2, ops.ACT_SEARCH_CANDIDATES, device=r.device) for k, r in self.act_range.items()}
         self.act_hist_rule = rule
         self.act_tail = 1.0 - float(percentile) / 100.0
         self.act_obs = {k: r.clone() for k, r in self.act_range.items()}
@@ -204,6 +248,81 @@ class UniformAffineQuantizer(nn.Module):
                                 "do not fit the histogram's 32-bit counters")
         ops.actquant_hist(xr, rng, self.act_hist[site])
         self.act_hist_n[site] = n
+
+    def act_candidates(self):
+        """After a "search+hist" pass: site -> fp32 [4, 2C], the ranges that 'max', 'l2', 'percentile' (with the pass's percentile) and
+        'hist_mse' (on this quantiser's grid width) would freeze, in the order ACT_AUTO_CANDIDATES."""
+        if getattr(self, "act_phase", "idle") != "search+hist":
+            raise RuntimeError("act_candidates: no search and histogram pass was made (act_histogram(search=True))")
+        bits = int(getattr(self, "dynamic_bits", 8))
+        out = {}
+        for k, rng in self.act_range.items():
+            rng = rng.detach()
+            out[k] = torch.stack([rng, act_l2_range(rng, self.act_err[k]),
+                                  ops.act_percentile_select(self.act_hist[k], rng, getattr(self, "act_tail", 0.0)),
+                                  ops.act_hist_mse_select(self.act_hist[k], rng, bits)]).contiguous()
+        return out
+
+    def act_score(self, cands=None):
+        """Start the scoring pass: every call adds, per site, the MEASURED squared error of the site's K candidate grids `cands[site]`
+        [K, 2C] on the values it sees (`ops.actquant_score`: the static quantiser's own expression), the counts of the values clipped at
+        each end and the energy, and returns the static output on the range the site holds.  Before a range is frozen (after observing:
+        `cands` from `act_candidates`) that is the max range, as in the search and histogram phases, and `act_freeze()` then gives each
+        channel the candidate of least measured error.  On a frozen quantiser (`cands` None: every site scores its own frozen range, K =
+        1) the frozen output goes downstream, and `act_freeze()` records `act_stats` and leaves the ranges as they are."""
+        if not getattr(self, "act_range", None):
+            raise RuntimeError("act_score: nothing was observed")
+        report = self.act_frozen()
+        if cands is None:
+            if not report:
+                raise RuntimeError("act_score: candidates are needed until the ranges are frozen")
+            cands = {k: r.detach().reshape(1, -1) for k, r in self.act_range.items()}
+        if sorted(cands) != sorted(self.act_range):
+            raise ValueError(f"act_score: candidates for the sites {sorted(cands)}, ranges for {sorted(self.act_range)}")
+        for k, cnd in cands.items():
+            if cnd.dim() != 2 or not 1 <= cnd.shape[0] <= ops.ACT_SCORE_MAX or cnd.shape[1] != self.act_range[k].numel():
+                raise ValueError(f"act_score (site {k}): candidates must be [1..{ops.ACT_SCORE_MAX}, {self.act_range[k].numel()}], got "
+                                 f"{tuple(cnd.shape)}")
+        self.act_cand = {k: cnd.detach().to(torch.float32).contiguous() for k, cnd in cands.items()}
+        shape = {k: (cnd.shape[1] // 2, cnd.shape[0]) for k, cnd in self.act_cand.items()}
+        dev = {k: cnd.device for k, cnd in self.act_cand.items()}
+        self.act_err = {k: torch.zeros(c, kk, device=dev[k]) for k, (c, kk) in shape.items()}
+        self.act_clip = {k: torch.zeros(c, kk, 2, dtype=torch.int32, device=dev[k]) for k, (c, kk) in shape.items()}
+        self.act_energy = {k: torch.zeros(c, device=dev[k]) for k, (c, kk) in shape.items()}
+        self.act_score_n = {k: 0 for k in shape}
+        self.act_hist, self.act_hist_n = {}, {}
+        if not report:
+            self.act_obs = {k: r.detach().clone() for k, r in self.act_range.items()}
+        self.act_score_kind = "report" if report else "auto"
+        self.act_phase = "score"
+
+    def _act_score_one(self, xr, site, bits):
+        """one batch into the site's score sums; the counts are 32-bit, and under data parallelism the ranks' counts are summed"""
+        from . import dp
+        n = self.act_score_n[site] + xr.numel() // xr.shape[-1]
+        if n * dp.world()[1] > 2 ** 31 - 1:
+            raise OverflowError(f"static activation quantiser (site {site}): {n} values per channel on each of {dp.world()[1]} ranks "
+                                "do not fit the score's 32-bit counts")
+        ops.actquant_score(xr, self.act_cand[site], self.act_err[site], self.act_clip[site], self.act_energy[site], n_bits=int(bits))
+        self.act_score_n[site] = n
+
+    def _act_close_score(self, keep_obs):
+        """the end of a scoring pass: 'auto' assembles each channel's range from its winning candidate; 'report' records the statistics"""
+        for k, err in self.act_err.items():
+            cnd = self.act_cand[k]
+            c = cnd.shape[1] // 2
+            if getattr(self, "act_score_kind", "auto") == "report":
+                clip = self.act_clip[k]
+                self.act_stats[k] = {"err": err[:, 0].clone(), "energy": self.act_energy[k].clone(), "clip_lo": clip[:, 0, 0].clone(),
+                                     "clip_hi": clip[:, 0, 1].clone(), "n": int(self.act_score_n[k])}
+            else:
+                win = act_score_winner(err).unsqueeze(0)
+                self.act_range[k] = torch.cat([cnd[:, :c].gather(0, win).reshape(-1), cnd[:, c:].gather(0, win).reshape(-1)])
+        self.act_err, self.act_cand, self.act_clip, self.act_energy, self.act_score_n = {}, {}, {}, {}, {}
+        self.act_score_kind = "auto"
+        if not keep_obs:
+            self.act_obs = {}
+        self.act_phase = "frozen" if self.act_range else "idle"
 
     def act_learn(self):
         """Start learning the frozen ranges: every site's range becomes a leaf tensor with requires_grad that the tracked forward
@@ -224,16 +343,18 @@ class UniformAffineQuantizer(nn.Module):
         its max range.  After a histogram pass each site becomes its percentile range (`ops.act_percentile_select`), which lies inside the
         max range as well, or, under the rule "mse", its histogram-MSE range on the grid width `dynamic_bits` (`ops.act_hist_mse_select`).
         A quantiser that was never applied stays without a range ("idle").  After learning the ranges are detached as they
-        stand.  `keep_obs`: keep the observed max ranges for a learning phase that follows (they are not part of a frozen quantiser)."""
+        stand.  After a scoring pass (`act_score`) each channel takes the candidate of least measured error (smallest sum; among equal sums
+        the earliest of max, l2, percentile, hist_mse; never a NaN sum; the max range if all are NaN), or, on a quantiser that was frozen
+        already, the ranges stay and `act_stats` is recorded.  `keep_obs`: keep the observed max ranges for a learning phase that follows (they are not part of a frozen quantiser)."""
         self.act_range = {k: r.detach() for k, r in self.act_range.items()}
+        if getattr(self, "act_phase", "idle") == "score":
+            if not hasattr(self, "act_stats"):
+                self.act_stats = {}
+            return self._act_close_score(keep_obs)
+        if getattr(self, "act_phase", "idle") == "search+hist":
+            raise RuntimeError("act_freeze: a search + histogram pass only feeds act_candidates(); score them first (act_score)")
         for k, err in self.act_err.items():
-            rng = self.act_range[k]
-            c = rng.numel() // 2
-            table = torch.tensor([1.0 - 0.05 * i for i in range(ops.ACT_SEARCH_CANDIDATES)], dtype=torch.float32, device=rng.device)
-            s = table[err.argmin(dim=1)]                                   # (float)(1 - 0.05 k): the kernel's factors
-            lo, hi = torch.maximum(rng[:c] * s, rng[:c]), torch.minimum(rng[c:] * s, rng[c:])
-            keep = lo > hi                                                 # (a candidate that left the observed range altogether)
-            self.act_range[k] = torch.cat([torch.where(keep, rng[:c], lo), torch.where(keep, rng[c:], hi)])
+            self.act_range[k] = act_l2_range(self.act_range[k], err)
         for k, hist in (getattr(self, "act_hist", None) or {}).items():
             if getattr(self, "act_hist_rule", "percentile") == "mse":
                 self.act_range[k] = ops.act_hist_mse_select(hist, self.act_range[k], int(getattr(self, "dynamic_bits", 8)))
@@ -260,10 +381,12 @@ class UniformAffineQuantizer(nn.Module):
         if rng is None:
             raise RuntimeError(f"static activation quantiser (site {site}) has no frozen range: calibrate it first "
                                "(recon.py with args.act_mode='static'); there is no fall-back to the dynamic grid")
-        if phase == "search":
+        if phase in ("search", "search+hist"):
             ops.actquant_search(xr, rng, self.act_err[site], n_bits=bits)
-        if phase == "hist":
+        if phase in ("hist", "search+hist"):
             self._act_count(xr, rng, site)
+        if phase == "score":
+            self._act_score_one(xr, site, bits)
         if torch.is_grad_enabled() and (phase == "learn" or (phase == "frozen" and getattr(self, "act_ste", False) and x.requires_grad)):
             from hipops.autograd import ActQuantStaticFn
             return ActQuantStaticFn.apply(x, rng, bits, channels_last)

@@ -142,16 +142,28 @@ def _act_args(args):
     width) or 'percentile' (a second pass takes a 1024-bin histogram of every channel on its observed range; each end then gives up whole
     bins while they hold no more than a share 1 - args.act_percentile / 100, default 99.99, of the channel's values) or 'hist_mse' (the
     same histogram pass; each channel then takes the clip pair, out of all 524 800, that minimises the modelled squared error on its
-    grid width: `ops.act_hist_mse_select`).  Checked before any work is done."""
+    grid width: `ops.act_hist_mse_select`) or 'auto' (one pass takes the 'l2' error sums and the histograms, the ranges that 'max', 'l2',
+    'percentile' and 'hist_mse' would freeze are then SCORED on the same inputs, `ops.actquant_score`, and each channel takes the one of
+    least measured squared error); args.act_report (default False; a bool): after freezing, one more pass records every site's measured
+    error, energy and clipped counts (`export.activation_report`).  Checked before any work is done."""
     mode = getattr(args, "act_mode", "dynamic") if args is not None else "dynamic"
     how = getattr(args, "act_range", "max") if args is not None else "max"
     if mode not in ("dynamic", "static"):
         raise ValueError(f"unknown act_mode {mode!r} ('dynamic' or 'static')")
-    if how not in ("max", "l2", "learned", "percentile", "hist_mse"):
-        raise ValueError(f"unknown act_range {how!r} ('max', 'l2', 'learned', 'percentile' or 'hist_mse')")
+    if how not in ("max", "l2", "learned", "percentile", "hist_mse", "auto"):
+        raise ValueError(f"unknown act_range {how!r} ('max', 'l2', 'learned', 'percentile', 'hist_mse' or 'auto')")
     _act_learn_args(args)
     _act_percentile_args(args)
+    _act_report_args(args)
     return mode, how
+
+
+def _act_report_args(args):
+    """args.act_report, validated: a bool (default False)."""
+    report = getattr(args, "act_report", False) if args is not None else False
+    if not isinstance(report, bool):
+        raise ValueError(f"act_report must be True or False, got {report!r}")
+    return report
 
 
 def _act_learn_args(args):
@@ -193,8 +205,13 @@ def calibrate_act_ranges(unit, inp_q, act_range="max", batch=32, keep_obs=False,
     for the clip pair of least modelled squared error on the quantiser's grid width.  Under data parallelism the observed ranges and
     the error sums or histograms are reduced over the ranks before they are used, so every rank freezes the same grid (integer counts:
     the very grid of one process on all inputs).  Every quant state flag is left as it was found.  `keep_obs`: the quantisers keep the
-    observed max ranges next to the frozen ones (`act_obs`) for `learn_act_ranges`."""
-    if act_range == "percentile":
+    observed max ranges next to the frozen ones (`act_obs`) for `learn_act_ranges`.
+    With act_range='auto' the second pass takes the 'l2' error sums AND the histograms (both read the same max-range inputs); from them
+    every site forms the four ranges that 'max', 'l2', 'percentile' and 'hist_mse' would freeze (`act_candidates`), a third pass measures
+    their squared error on the same inputs (`act_score`: still behind max-range upstream quantisers), and each channel freezes the one of
+    least measured error.  The measured sums and counts are reduced over the ranks like the others, so every rank picks from the same
+    numbers."""
+    if act_range in ("percentile", "auto"):
         percentile = _check_percentile(percentile)
     mods = [m for m in unit.modules() if isinstance(m, (QuantModule, BaseQuantBlock))]
     quants = [m.act_quantizer for m in mods]
@@ -227,9 +244,60 @@ def calibrate_act_ranges(unit, inp_q, act_range="max", batch=32, keep_obs=False,
                     q.act_histogram(percentile, rule="mse" if act_range == "hist_mse" else "percentile")
             run()
             dp.reduce_act_stats(sums=applied("act_hist"))
+        elif act_range == "auto":
+            seen = [q for q in {id(q): q for q in quants}.values() if q.act_range]
+            for q in seen:
+                q.act_histogram(percentile, rule="mse", search=True)
+            run()
+            dp.reduce_act_stats(sums=applied("act_err") + applied("act_hist"))
+            for q in seen:
+                q.act_score(q.act_candidates())
+            run()
+            _reduce_scores(seen)
         for q in quants:
             q.act_freeze(keep_obs=keep_obs)
     finally:
+        for m, w, a_ in states:
+            m.use_weight_quant, m.use_act_quant = w, a_
+
+
+def _reduce_scores(quants):
+    """the sums, counts and pixel counts of a scoring pass over the ranks, in the fixed site order"""
+    def applied(name):
+        return [getattr(q, name)[k] for q in quants for k in sorted(getattr(q, name))]
+    if dp.world()[1] <= 1:
+        return
+    dp.reduce_act_stats(sums=applied("act_err") + applied("act_energy") + applied("act_clip"))
+    sites = [(q, k) for q in quants for k in sorted(q.act_score_n)]
+    if sites:
+        n = torch.tensor([q.act_score_n[k] for q, k in sites], dtype=torch.int32, device=sites[0][0].act_err[sites[0][1]].device)
+        dp.reduce_act_stats(sums=[n])                    # (the guard of the pass keeps the sum inside 32 bits)
+        for (q, k), v in zip(sites, n.tolist()):
+            q.act_score_n[k] = int(v)
+
+
+def report_act_ranges(unit, inp_q, batch=32):
+    """Measure the frozen static activation ranges of a calibrated unit: one pass over its cached quantised inputs in the W8A8 state, every
+    frozen quantiser scoring its own range (K = 1) and passing its frozen output on; the measured squared error, the energy, the counts of
+    the values clipped at each end and the pixel count stay on the quantiser as `act_stats[site]` (summed over the ranks under data
+    parallelism).  The ranges do not change; every quant state flag is left as it was found."""
+    mods = [m for m in unit.modules() if isinstance(m, (QuantModule, BaseQuantBlock))]
+    quants = list({id(m.act_quantizer): m.act_quantizer for m in mods if m.act_quantizer.act_frozen()}.values())
+    states = [(m, m.use_weight_quant, m.use_act_quant) for m in mods]
+    try:
+        for m in mods:
+            m.use_weight_quant = m.use_act_quant = True
+        for q in quants:
+            q.act_score()
+        with torch.no_grad():
+            for i in range(0, inp_q.shape[0], batch):
+                h = inp_q[i:i + batch]
+                unit(h, (h.shape[2], h.shape[3])) if isinstance(unit, QuantRSTB) else unit(h)
+        _reduce_scores(quants)
+    finally:
+        for q in quants:
+            if getattr(q, "act_phase", "idle") == "score":
+                q.act_freeze()
         for m, w, a_ in states:
             m.use_weight_quant, m.use_act_quant = w, a_
 
@@ -331,6 +399,7 @@ def _reconstruct(model, unit, unit_name, cali_data, batch_size=32, iters=20000, 
     act_mode, act_range = _act_args(args)
     act_iters, act_lr = _act_learn_args(args)
     act_percentile = _act_percentile_args(args)
+    act_report = _act_report_args(args)
     if act_quant and act_mode == "static" and act_range == "learned" and _is_rstb(unit):
         raise NotImplementedError("act_range='learned': a Swin (RSTB) unit's activation-quantised window attention cannot sit on torch's "
                                   "tape (quant_block.QuantWindowAttention); calibrate it with act_range='max' or 'l2'")
@@ -456,6 +525,8 @@ def _reconstruct(model, unit, unit_name, cali_data, batch_size=32, iters=20000, 
             learn_act_ranges(unit, inp_q, out_fp, act_iters, act_lr, batch_size, seed=unit_seed(unit_name))
         else:
             calibrate_act_ranges(unit, inp_q, act_range, batch=cache_bs, percentile=act_percentile)
+        if act_report:
+            report_act_ranges(unit, inp_q, batch=cache_bs)
         if timing is not None:
             timing[-1]["act_s"] = _mark() - t4
     return eng

@@ -4,7 +4,8 @@
 Kernel part: device-event timing after warm-up, the two quantisers ALTERNATING in one process (dynamic round, static round, ...; the
 median round is reported), µs per call and GB/s against algorithmic bytes -- static 8 B per element (one read, one write), dynamic 12
 (two reads, one write).  The static call does a strict subset of the dynamic call's work: a shape on which it is slower is flagged.
-The range search (one read, ten candidates) is timed next to them; with --bwd also the backward of the static quantiser (two reads, one
+The range search (one read, ten candidates) and the range scoring of act_range='auto' and act_report (one read, K = 1 and K = 4 arbitrary
+grids with their clipped counts and the energy) are timed next to them; with --bwd also the backward of the static quantiser (two reads, one
 write: 12 B per element), whose share of the static forward's GB/s on the same tensor is reported; with --hist the per-channel histogram
 pass of act_range='percentile' and 'hist_mse' (one read, 1024 integer bins per channel) and their C-sized selections (the percentile
 cut and the exhaustive histogram-MSE search), in the same alternating windows as the search pass they stand in for.
@@ -58,10 +59,24 @@ def bench_kernels(reps, rounds, n_bits=8, bwd=False, hist=False):
         rng = ops.act_range_init(C, "cuda")
         ops.actquant_observe(x, rng, n_bits=n_bits)
         err = torch.zeros(C, ops.ACT_SEARCH_CANDIDATES, device="cuda")
+        # the grids 'auto' would score: the observed range and three shrunk ones (what they are does not change the work per element)
+        cand4 = torch.stack([rng * s for s in (1.0, 0.9, 0.8, 0.7)]).contiguous()
+        cand1 = cand4[1:2].contiguous()
+        cws = torch.empty(int(L.lib().rdo_actquant_score_workspace(C, ops.ACT_SCORE_MAX)), device="cuda")
+        cerr = {k: torch.zeros(C, k, device="cuda") for k in (1, 4)}
+        cclip = {k: torch.zeros(C, k, 2, dtype=torch.int32, device="cuda") for k in (1, 4)}
+        cen = torch.zeros(C, device="cuda")
+
+        def score_call(cand):
+            k = cand.shape[0]
+            cclip[k].zero_()                                       # (32-bit counts: every call starts empty; a C-sized memset)
+            ops.actquant_score(x, cand, cerr[k], cclip[k], cen, n_bits=n_bits, ws=cws)
         calls = {
             "dynamic": lambda: ops.actquant_perchannel(x, out=out, ws=ws, n_bits=n_bits),
             "static": lambda: ops.actquant_static(x, rng, out=out, n_bits=n_bits),
             "search": lambda: ops.actquant_search(x, rng, err, n_bits=n_bits, ws=sws),
+            "score1": lambda: score_call(cand1),
+            "score4": lambda: score_call(cand4),
         }
         if bwd:
             gx = torch.randn(*shape, generator=g).cuda()
@@ -100,6 +115,10 @@ def bench_kernels(reps, rounds, n_bits=8, bwd=False, hist=False):
                    static_spread_us=[round(min(t["static"]), 2), round(max(t["static"]), 2)],
                    dynamic_gbs=round(12.0 * n / med["dynamic"] / 1e3, 1), static_gbs=round(8.0 * n / med["static"] / 1e3, 1),
                    search_gbs=round(4.0 * n / med["search"] / 1e3, 1),
+                   score1_us=round(med["score1"], 2), score4_us=round(med["score4"], 2),
+                   score4_spread_us=[round(min(t["score4"]), 2), round(max(t["score4"]), 2)],
+                   score1_gbs=round(4.0 * n / med["score1"] / 1e3, 1), score4_gbs=round(4.0 * n / med["score4"] / 1e3, 1),
+                   score4_over_search=round(med["score4"] / med["search"], 2),
                    speedup=round(med["dynamic"] / med["static"], 2), static_slower=bool(med["static"] > med["dynamic"]))
         if bwd:
             bwd_gbs = 12.0 * n / med["bwd"] / 1e3
