@@ -181,6 +181,61 @@ def round_loss_term(alpha, b, weight):
     return weight * (1 - ((rv - .5).abs() * 2).pow(b)).sum()
 
 
+def adaround_step_reference(w, delta, zp, alpha, m, v, G, sched_row, *, n_levels, grad_scale, round_weight, reparam=None):
+    """One calibration step of one weight tensor in float64 and closed form: the soft quantiser's backward (quantizer.py:437-452), for a
+    GDN gamma the LowerBound rule of gamma' = max(w~, bound)^2 - pedestal (`reparam=(bound, pedestal)`, quant_layer.py:142-146), the
+    rounding regulariser's gradient (layer_opt.py:159-165), one torch.optim.Adam(betas=(.9, .999), eps=1e-8) step on alpha and the next
+    soft weight.  `tests/test_adaround_step_reference.py` pins it to autograd through `adaround_forward` / `round_loss_term`.
+
+    w, alpha, m, v: tensors of one shape; delta, zp: broadcastable to it; G: the gradient w.r.t. the kernel-layout weight (w~, or gamma'
+    with `reparam`); sched_row = (b, round_on, step_size = lr / (1 - .9^t), bc2_sqrt = sqrt(1 - .999^t)).  floor(w / delta) is taken
+    in fp32 and then promoted, as the reference's fp32 torch.floor does: the grid a weight sits on is not a rounding question.
+    -> dict(dalpha_data, g_total, m, v, alpha, wq, round_loss, masks); `masks` holds hraw, h, xint (and the soft q with `reparam`) of the
+    CURRENT alpha -- the places where the chain has a kink."""
+    f64 = lambda t: torch.as_tensor(t).detach().to(torch.float64)
+    b, round_on, step_size, bc2 = (float(x) for x in sched_row)
+    Lm1 = float(n_levels - 1)
+    xf = torch.floor(torch.as_tensor(w).detach().float() / torch.as_tensor(delta).detach().float()).to(torch.float64)
+    delta, zp, a, m, v, G = f64(delta), f64(zp), f64(alpha), f64(m), f64(v), f64(G)
+
+    def soft(al):
+        sg = torch.sigmoid(al)
+        hraw = sg * (ZETA - GAMMA) + GAMMA
+        return sg, hraw, hraw.clamp(0, 1)
+
+    def emit(h):
+        q = ((xf + h + zp).clamp(0, Lm1) - zp) * delta
+        return q if reparam is None else q.clamp(min=float(reparam[0])) ** 2 - float(reparam[1])
+
+    sg, hraw, h = soft(a)
+    xint = xf + h + zp
+    dh_da = ((hraw >= 0) & (hraw <= 1)).to(torch.float64) * (ZETA - GAMMA) * sg * (1 - sg)
+    masks = dict(hraw=hraw, h=h, xint=xint)
+    g = G
+    if reparam is not None:
+        bound = float(reparam[0])
+        q = (xint.clamp(0, Lm1) - zp) * delta
+        go = G * 2 * q.clamp(min=bound)
+        g = torch.where((q >= bound) | (go < 0), go, torch.zeros_like(go))          # CompressAI LowerBound backward
+        masks["q"] = q
+    pass_q = ((xint >= 0) & (xint <= Lm1)).to(torch.float64)
+    dalpha_data = g * delta * pass_q * dh_da
+    g_total = dalpha_data * float(grad_scale)
+    round_loss = torch.zeros((), dtype=torch.float64)
+    g_round = torch.zeros_like(g_total)
+    if round_on != 0.0:
+        u = (h - 0.5).abs() * 2
+        ub1 = torch.where(u > 0, u.clamp(min=1e-300) ** (b - 1), torch.zeros_like(u))      # u^(b-1), 0 at u = 0 (b > 1)
+        round_loss = float(round_weight) * (1 - u * ub1).sum()
+        g_round = -float(round_weight) * b * ub1 * 2 * torch.sign(h - 0.5) * dh_da
+        g_total = g_total + g_round
+    m1 = m + (g_total - m) * 0.1
+    v1 = v * 0.999 + 0.001 * g_total * g_total
+    a1 = a - step_size * (m1 / (v1.sqrt() / bc2 + 1e-8))
+    return dict(dalpha_data=dalpha_data, g_round=g_round, g_total=g_total, m=m1, v=v1, alpha=a1, wq=emit(soft(a1)[2]), round_loss=round_loss,
+                masks=masks)
+
+
 # ----------------------------------------------------------------------------- GDN
 _GAMMA_REPARAM = NonNegativeParametrizer()
 _BETA_REPARAM = NonNegativeParametrizer(minimum=1e-6)

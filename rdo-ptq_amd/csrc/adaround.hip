@@ -17,7 +17,10 @@ namespace {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr float kGamma = -0.1f, kZeta = 1.1f;
-constexpr float kBeta1 = 0.9f, kBeta2 = 0.999f, kAdamEps = 1e-8f;
+constexpr float kBeta2 = 0.999f, kAdamEps = 1e-8f;
+// 1 - beta as torch.optim.Adam forms it (in double, then one rounding): 1.f - 0.999f is 1.3e-5 below 0.001, and until
+// tests/test_gpu_adaround_step.py read adam_v against float64 every second moment carried that factor.  beta1 = 0.9 enters as 1 - beta1 only.
+constexpr float kOmBeta1 = (float)(1.0 - 0.9), kOmBeta2 = (float)(1.0 - 0.999);
 
 __device__ __forceinline__ float sigmoidf_(float a) { return 1.0f / (1.0f + __expf(-a)); }
 
@@ -223,8 +226,8 @@ __device__ __forceinline__ void ada_step_body(const AdaArgs& a, const long bid, 
             }
             // Adam (torch.optim.Adam defaults; alpha has no weight decay)
             float mm = m4[k], vv = v4[k];
-            mm = mm + (g_total - mm) * (1.f - kBeta1);
-            vv = vv * kBeta2 + (1.f - kBeta2) * g_total * g_total;
+            mm = fmaf(g_total - mm, kOmBeta1, mm);                       // lerp as one fma: a single rounding behind the difference
+            vv = fmaf(vv, kBeta2, kOmBeta2 * g_total * g_total);
             const float denom = sqrtf(vv) / bc2 + kAdamEps;
             al = al - step_size * (mm / denom);
             m4[k] = mm; v4[k] = vv; al4[k] = al;
@@ -419,8 +422,8 @@ __device__ __forceinline__ void ada_step_tile_body(const AdaArgs& a, int bid) {
                 g_total += (-a.round_weight * (b * ub1) * 2.f * sgn) * dh_da;
             }
             float mm = m4[k], vv = v4[k];
-            mm = mm + (g_total - mm) * (1.f - kBeta1);
-            vv = vv * kBeta2 + (1.f - kBeta2) * g_total * g_total;
+            mm = fmaf(g_total - mm, kOmBeta1, mm);                       // lerp as one fma: a single rounding behind the difference
+            vv = fmaf(vv, kBeta2, kOmBeta2 * g_total * g_total);
             const float denom = sqrtf(vv) / bc2 + kAdamEps;
             al = al - step_size * (mm / denom);
             m4[k] = mm; v4[k] = vv; al4[k] = al;
@@ -839,6 +842,7 @@ static int step_batch_impl(const rdo_ada_step_item* items, int32_t n, int32_t mo
     RDO_REQUIRE(mode == 1 || (sched && iter_ptr), "rdo_adaround_step_batch: schedule / iteration counter missing");
     RDO_REQUIRE(!(advance_iter && iter_shadow), "rdo_adaround_step_batch: advance_iter and iter_shadow are alternatives");
     RDO_REQUIRE(!iter_shadow || iter_ptr, "rdo_adaround_step_batch: iter_shadow needs iter_ptr");
+    RDO_REQUIRE(!next || (mode != 1 && iter_ptr), "rdo_adaround_step_batch_gather: the gather rides on a fused step or an apply launch");
     AdaBatch b{}, bw{};
     const int w1_min = rdo::tuning(rdo::T_ADA_W1_MIN);
     b.w1_min = bw.w1_min = w1_min;
@@ -859,7 +863,7 @@ static int step_batch_impl(const rdo_ada_step_item* items, int32_t n, int32_t mo
         a.alpha = it.alpha; a.m = it.adam_m; a.v = it.adam_v; a.wq = it.wq; a.wd = it.wd; a.round_loss_out = round_loss_out; a.mode = mode;
         a.wq_planes = static_cast<unsigned short*>(it.wq_planes);
         a.wd_planes = it.wd ? static_cast<unsigned short*>(it.wd_planes) : nullptr;
-        a.wq_pscale = it.wq_plane_scale; a.wd_pscale = it.wd_plane_scale; a.ovf = rdo::h2_overflow_flag();
+        a.wq_pscale = it.wq_plane_scale; a.wd_pscale = it.wd_plane_scale;
         if (mode != 1 && (it.lin_fwd_planes || it.lin_bwd_planes)) {
             RDO_REQUIRE(it.d.rows % 32 == 0 && (it.d.numel / it.d.rows) % 32 == 0 && it.lin_plane_scale > 0.f,
                         "rdo_adaround_step_batch: item %d: Linear planes need rows and inner in blocks of 32 and a positive scale", i);
@@ -867,6 +871,7 @@ static int step_batch_impl(const rdo_ada_step_item* items, int32_t n, int32_t mo
             a.lin_bwd = static_cast<unsigned short*>(it.lin_bwd_planes);
             a.lin_pscale = it.lin_plane_scale;
         }
+        a.ovf = rdo::h2_overflow_flag();          // behind the item's last argument check: the look-up may allocate the word
         b.tile[i] = tile_ok(it.d, mode) ? 1 : 0;
         blocks += b.tile[i] ? (int)tile_blocks(it.d) : (int)grid_for((it.nsplit >= w1_min && mode != 2) ? it.d.numel : it.d.numel / 4);
         b.blk_end[i] = blocks;
@@ -881,7 +886,6 @@ static int step_batch_impl(const rdo_ada_step_item* items, int32_t n, int32_t mo
     b.iter_shadow = iter_shadow;
     b.gather_beg = blocks;
     if (next) {
-        RDO_REQUIRE(mode != 1 && iter_ptr, "rdo_adaround_step_batch_gather: the gather rides on a fused step or an apply launch");
         RDO_REQUIRE(next->cache_q && next->cache_fp && next->idx_table && (next->out || next->out_planes) && next->n_iters > 0,
                     "rdo_adaround_step_batch_gather: null pointer in the gather descriptor");
         RDO_REQUIRE(next->B > 0 && next->batch_offset >= 0 && next->per_image > 0 && next->per_image % 4 == 0 &&
