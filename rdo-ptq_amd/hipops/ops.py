@@ -894,9 +894,50 @@ def iter_advance(iter_ptr):
     L.check(L.lib().rdo_iter_advance(_ptr(iter_ptr), _stream()), "rdo_iter_advance")
 
 
+def _fp32_operands(what, optional=(), **named):
+    """The entropy / rate kernels index every operand by the first one's element count: refuse, before any pointer is taken, an operand
+    that is not a non-empty fp32 tensor of that count on the same device (the operands named in `optional` may be None).  -> the count"""
+    first = None
+    for name, t in named.items():
+        if t is None and name in optional:
+            continue
+        if not torch.is_tensor(t) or t.dtype != torch.float32:
+            raise ValueError(f"{what}: {name} must be an fp32 tensor, got {t.dtype if torch.is_tensor(t) else type(t).__name__}")
+        if first is None:
+            first = (name, t)
+            if t.numel() == 0:
+                raise ValueError(f"{what}: {name} is empty")
+        elif t.numel() != first[1].numel() or t.device != first[1].device:
+            raise ValueError(f"{what}: {name} holds {t.numel()} elements on {t.device}, {first[0]} {first[1].numel()} on {first[1].device}")
+    return first[1].numel()
+
+
+def _eb_operands(what, z, params, medians=False):
+    """-> C of a channels-last z [..., C] whose params are [C, 58] (and medians [C]) fp32 on z's device"""
+    _fp32_operands(what, z=z)
+    if z.dim() < 1:
+        raise ValueError(f"{what}: z must be channels-last [..., C], got a scalar")
+    Cc = z.shape[-1]
+    for name, t, shape in (("params", params, (Cc, 58)),) + ((("medians", medians, (Cc,)),) if medians is not False else ()):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != shape or t.device != z.device:
+            raise ValueError(f"{what}: {name} must be fp32 {list(shape)} on {z.device} for a tensor of {Cc} channels, got "
+                             f"{(t.dtype, tuple(t.shape), t.device) if torch.is_tensor(t) else type(t).__name__}")
+    return Cc
+
+
+def _sum_out(what, ref, out):
+    """the accumulator of a rate / distortion sum: one fp32 element on the operands' device (made zero when None)"""
+    if out is None:
+        return torch.zeros(1, device=ref.device, dtype=torch.float32)
+    if not torch.is_tensor(out) or out.dtype != torch.float32 or out.numel() != 1 or out.device != ref.device:
+        raise ValueError(f"{what}: out must be one fp32 element on {ref.device}, got "
+                         f"{(out.dtype, tuple(out.shape), out.device) if torch.is_tensor(out) else type(out).__name__}")
+    return out
+
+
 def factorized_likelihood(z_cl, params, medians):
     """z_cl: [..., C] channels-last.  -> (z_hat, likelihood)"""
-    Cc = z_cl.shape[-1]
+    Cc = _eb_operands("factorized_likelihood", z_cl, params, medians)
     zhat, lik = torch.empty_like(z_cl), torch.empty_like(z_cl)
     L.check(L.lib().rdo_factorized_likelihood_fwd(_ptr(z_cl), _ptr(params), _ptr(medians), z_cl.numel(), Cc, _ptr(zhat),
                                                   _ptr(lik), _stream()), "rdo_factorized_likelihood_fwd")
@@ -905,35 +946,40 @@ def factorized_likelihood(z_cl, params, medians):
 
 def factorized_likelihood_bwd(zhat_cl, params, grad_scale=1.0):
     """d(grad_scale * sum(-log2 p)) / dz^ of the factorised prior, element-wise (z^ channels-last)"""
+    Cc = _eb_operands("factorized_likelihood_bwd", zhat_cl, params)
     dz = torch.empty_like(zhat_cl)
-    L.check(L.lib().rdo_factorized_likelihood_bwd(_ptr(zhat_cl), _ptr(params), zhat_cl.numel(), zhat_cl.shape[-1], grad_scale, _ptr(dz), _stream()),
+    L.check(L.lib().rdo_factorized_likelihood_bwd(_ptr(zhat_cl), _ptr(params), zhat_cl.numel(), Cc, grad_scale, _ptr(dz), _stream()),
             "rdo_factorized_likelihood_bwd")
     return dz
 
 
 def gaussian_likelihood(y, scales, means=None, scale_bound=0.11):
+    n = _fp32_operands("gaussian_likelihood", ("means",), y=y, scales=scales, means=means)
     yhat, lik = torch.empty_like(y), torch.empty_like(y)
-    L.check(L.lib().rdo_gaussian_likelihood_fwd(_ptr(y), _ptr(scales), _ptr(means), y.numel(), scale_bound, _ptr(yhat), _ptr(lik),
+    L.check(L.lib().rdo_gaussian_likelihood_fwd(_ptr(y), _ptr(scales), _ptr(means), n, scale_bound, _ptr(yhat), _ptr(lik),
                                                 _stream()), "rdo_gaussian_likelihood_fwd")
     return yhat, lik
 
 
 def gaussian_likelihood_bwd(yhat, scales, means, grad_scale=1.0, scale_bound=0.11):
+    n = _fp32_operands("gaussian_likelihood_bwd", ("means",), yhat=yhat, scales=scales, means=means)
     ds, dm = torch.empty_like(scales), torch.empty_like(scales)
-    L.check(L.lib().rdo_gaussian_likelihood_bwd(_ptr(yhat), _ptr(scales), _ptr(means), yhat.numel(), scale_bound, grad_scale,
+    L.check(L.lib().rdo_gaussian_likelihood_bwd(_ptr(yhat), _ptr(scales), _ptr(means), n, scale_bound, grad_scale,
                                                 _ptr(ds), _ptr(dm), _stream()), "rdo_gaussian_likelihood_bwd")
     return ds, dm
 
 
 def neg_log2_sum(lik, scale=1.0, out=None):
-    out = torch.zeros(1, device=lik.device, dtype=torch.float32) if out is None else out
-    L.check(L.lib().rdo_neg_log2_sum(_ptr(lik), lik.numel(), scale, _ptr(out), _stream()), "rdo_neg_log2_sum")
+    n = _fp32_operands("neg_log2_sum", lik=lik)
+    out = _sum_out("neg_log2_sum", lik, out)
+    L.check(L.lib().rdo_neg_log2_sum(_ptr(lik), n, scale, _ptr(out), _stream()), "rdo_neg_log2_sum")
     return out
 
 
 def sq_diff_sum(a, b, scale=1.0, clamp01=False, out=None):
-    out = torch.zeros(1, device=a.device, dtype=torch.float32) if out is None else out
-    L.check(L.lib().rdo_sq_diff_sum(_ptr(a), _ptr(b), a.numel(), scale, int(clamp01), _ptr(out), _stream()), "rdo_sq_diff_sum")
+    n = _fp32_operands("sq_diff_sum", a=a, b=b)
+    out = _sum_out("sq_diff_sum", a, out)
+    L.check(L.lib().rdo_sq_diff_sum(_ptr(a), _ptr(b), n, scale, int(clamp01), _ptr(out), _stream()), "rdo_sq_diff_sum")
     return out
 
 
@@ -951,16 +997,18 @@ def _ordered_ws(device):
 
 def neg_log2_sum_ordered(lik, scale=1.0, out=None):
     """`neg_log2_sum` summed in a fixed order: the same bits on every run (evaluation)."""
-    out = torch.zeros(1, device=lik.device, dtype=torch.float32) if out is None else out
-    L.check(L.lib().rdo_neg_log2_sum_ordered(_ptr(lik), lik.numel(), scale, _ptr(out), _ptr(_ordered_ws(lik.device)), _stream()),
+    n = _fp32_operands("neg_log2_sum_ordered", lik=lik)
+    out = _sum_out("neg_log2_sum_ordered", lik, out)
+    L.check(L.lib().rdo_neg_log2_sum_ordered(_ptr(lik), n, scale, _ptr(out), _ptr(_ordered_ws(lik.device)), _stream()),
             "rdo_neg_log2_sum_ordered")
     return out
 
 
 def sq_diff_sum_ordered(a, b, scale=1.0, clamp01=False, out=None):
     """`sq_diff_sum` summed in a fixed order: the same bits on every run (evaluation)."""
-    out = torch.zeros(1, device=a.device, dtype=torch.float32) if out is None else out
-    L.check(L.lib().rdo_sq_diff_sum_ordered(_ptr(a), _ptr(b), a.numel(), scale, int(clamp01), _ptr(out), _ptr(_ordered_ws(a.device)),
+    n = _fp32_operands("sq_diff_sum_ordered", a=a, b=b)
+    out = _sum_out("sq_diff_sum_ordered", a, out)
+    L.check(L.lib().rdo_sq_diff_sum_ordered(_ptr(a), _ptr(b), n, scale, int(clamp01), _ptr(out), _ptr(_ordered_ws(a.device)),
                                             _stream()), "rdo_sq_diff_sum_ordered")
     return out
 
