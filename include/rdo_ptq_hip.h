@@ -280,6 +280,18 @@ int rdo_actquant_score(const float* x, int64_t npix, int32_t C, int32_t n_bits, 
                        float* err /* [C][K] */, int32_t* clip /* [C][K][2] or null */, float* energy /* [C] or null */,
                        float* ws /* rdo_actquant_score_workspace(C, K) floats, no initial state needed */, void* stream);
 int64_t rdo_actquant_score_workspace(int32_t C, int32_t K);
+/* Pair moments (extension: the per-unit output error report): a, b = two tensors of the same NHWC storage [npix][C]; with d = a - b formed
+ * in fp32, per channel
+ *   shift[c]  += sum_p d
+ *   err[c]    += sum_p d * d
+ *   energy[c] += sum_p a * a          (a = the reference operand: the report passes the full-precision output as a)
+ * every product and sum rounded on its own.  out = shift[C] | err[C] | energy[C].  One read of a and of b (16-byte accesses when C % 4 == 0
+ * and both are 16-byte aligned); per-workgroup partial sums in ws, folded in the fixed order the head comment of csrc/actquant.hip
+ * states (no atomics: the same input gives the same bits); no serial fp32 chain longer than 1024 terms.  out is ACCUMULATED INTO (zero it
+ * before the first batch).  Refused before any launch: a null a, b, out or ws, npix <= 0, C <= 0. */
+int rdo_pair_moments(const float* a, const float* b, int64_t npix, int32_t C, float* out /* [3][C]: shift | err | energy */,
+                     float* ws /* rdo_pair_moments_workspace(C) floats, no initial state needed */, void* stream);
+int64_t rdo_pair_moments_workspace(int32_t C);   /* floats; 0 for C <= 0 */
 /* Backward of rdo_actquant_static with a straight-through round (extension: learned activation ranges, and the R + lambda*D task loss behind
  * frozen quantisers).  y = the forward's value (the same expression on the same operands), r = max(hi_c - lo_c, 1e-6); an element is
  * below if x < lo_c, above if x > hi_c (plain fp32 comparisons), inside otherwise:

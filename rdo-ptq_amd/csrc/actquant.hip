@@ -1,9 +1,10 @@
 // K6 -- per-channel activation quantisers on NHWC fp32 tensors (channel = fastest dim): the dynamic quantiser (min | max of the tensor
 // itself), the static one (a frozen lo | hi pair), the range search, the range scoring, the static backward, the Adam step of learned
-// ranges, and the per-channel histogram with its percentile and its histogram-MSE selection.
+// ranges, the per-channel histogram with its percentile and its histogram-MSE selection, and the pair moments of two tensors (the
+// per-unit output error report).
 // Built with -ffp-contract=off (products and sums round separately, like the reference's op chains).
 //
-// Four of them reduce over the pixels per channel, and all four do it the same way, without atomics: up to kAqBlocks workgroups each
+// Five of them reduce over the pixels per channel, and all five do it the same way, without atomics: up to kAqBlocks workgroups each
 // leave one row of partial values for their share of the pixels (aq_partial below), a small second kernel folds the rows (aq_fold_kernel).
 // (The first version let 1024 workgroups atomicMin / atomicMax into the same 2 C words: 0.4 M contended atomics per call were most of its
 // time.)  The order of the fp32 additions is fixed HERE, once, and frozen ranges depend on it: a thread's running sum over its pixels in
@@ -270,6 +271,37 @@ struct AqScore {
 template <int W, int K>
 __global__ __launch_bounds__(256) void aqc_partial_kernel(const float* x, long npix, int C, const float* cand, float bit_range, float* part) {
     aq_partial<W, 1>(AqScore<W, K>{x, cand, bit_range}, npix, C, part);
+}
+
+// ---- pair moments: per channel the three sums over the pixels of d = a - b (fp32), d * d and a * a, in one read of both tensors (the
+// per-unit output error report: a = the full-precision output, b = the quantised one, so energy is the full-precision energy).  W x 3
+// running sums (and as many closed ones) in registers, two pixels of both streams in flight; part = [workgroup][shift[C] | err[C] |
+// energy[C]], the layout of the result.
+template <int W>
+struct AqPair {
+    typedef float vec_t __attribute__((ext_vector_type(W)));
+    struct in_t { vec_t a, b; };
+    static constexpr int N = 3;
+    static constexpr bool kChain = true, kChannelMajor = false;
+    const float* a;
+    const float* b;
+    __device__ static float zero(int) { return 0.f; }
+    __device__ static float combine(float r, float v, int) { return r + v; }
+    __device__ void begin(int, int) {}
+    __device__ in_t load(long off) const { return in_t{*reinterpret_cast<const vec_t*>(a + off), *reinterpret_cast<const vec_t*>(b + off)}; }
+    __device__ void pixel(const in_t& v, long, float (&acc)[W][N]) const {
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+            const float d = v.a[k] - v.b[k];
+            acc[k][0] += d;
+            acc[k][1] += d * d;
+            acc[k][2] += v.a[k] * v.a[k];
+        }
+    }
+};
+template <int W>
+__global__ __launch_bounds__(256) void aqp_partial_kernel(const float* a, const float* b, long npix, int C, float* part) {
+    aq_partial<W, 2>(AqPair<W>{a, b}, npix, C, part);
 }
 
 // fold of the score's partial rows [workgroup][C][3 K + 1]: the lanes and the order of aq_fold_kernel<true> (lane j adds the rows j, j + 16,
@@ -775,6 +807,25 @@ int rdo_actquant_score(const float* x, int64_t npix, int32_t C, int32_t n_bits, 
 int64_t rdo_actquant_score_workspace(int32_t C, int32_t K) {
     return C > 0 && K >= 1 && K <= kAqcMax ? (int64_t)C * (3 * K + 1) * kAqBlocks : 0;
 }
+
+int rdo_pair_moments(const float* a, const float* b, int64_t npix, int32_t C, float* out, float* ws, void* stream) {
+    RDO_REQUIRE(a && b && out && ws && npix > 0 && C > 0, "rdo_pair_moments: bad argument");
+    RDO_REQUIRE(3 * (int64_t)C <= 0x7fffffffLL, "rdo_pair_moments: %d channels are too many for 32-bit entry indices", C);
+    const bool vec = aq_vec(C, {a, b});
+    return rdo::dispatch(
+        [=](hipStream_t s) {
+            aq_with_width(vec, [&](auto w) {
+                constexpr int W = decltype(w)::value;
+                const int nblk = aq_blocks(npix, C, W);
+                hipLaunchKernelGGL(aqp_partial_kernel<W>, dim3(nblk), dim3(256), 0, s, a, b, (long)npix, C, ws);
+                hipLaunchKernelGGL(aq_fold_kernel<true>, aq_fold_grid(3 * C), dim3(256), 0, s, ws, nblk, 3 * C, out);
+            });
+            return rdo::check_launch("pair_moments");
+        },
+        stream, "pair_moments", 0.0, 8.0 * npix * C);
+}
+
+int64_t rdo_pair_moments_workspace(int32_t C) { return C > 0 ? 3 * (int64_t)C * kAqBlocks : 0; }
 
 int rdo_actquant_static_bwd(const float* x, const float* g, int64_t npix, int32_t C, int32_t n_bits, const float* range, float* dx,
                             float* drange, float* ws, void* stream) {

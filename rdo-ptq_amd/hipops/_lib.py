@@ -84,6 +84,8 @@ _SIGS = {
     "rdo_actquant_search_workspace": (C.c_int64, [C.c_int32]),
     "rdo_actquant_score": (C.c_int, [P, C.c_int64, C.c_int32, C.c_int32, P, C.c_int32, P, P, P, P, P]),
     "rdo_actquant_score_workspace": (C.c_int64, [C.c_int32, C.c_int32]),
+    "rdo_pair_moments": (C.c_int, [P, P, C.c_int64, C.c_int32, P, P, P]),
+    "rdo_pair_moments_workspace": (C.c_int64, [C.c_int32]),
     "rdo_actquant_static_bwd": (C.c_int, [P, P, C.c_int64, C.c_int32, C.c_int32, P, P, P, P, P]),
     "rdo_actquant_static_bwd_workspace": (C.c_int64, [C.c_int32]),
     "rdo_act_range_step": (C.c_int, [P, P, P, P, P, C.c_int32, C.c_int32, C.c_float, P]),

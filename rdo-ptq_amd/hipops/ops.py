@@ -402,6 +402,41 @@ def actquant_score(x, cand, err, clip=None, energy=None, n_bits=8, ws=None):
     return err
 
 
+_PAIR_WS = {}       # (device, C) -> workspace of pair_moments (launches are stream-ordered, so one buffer per key suffices)
+
+
+def pair_moments(a, b, out=None):
+    """Per-channel moments of two tensors of the same channels-last storage [..., C]: with d = a - b formed in fp32, -> float32 [3, C] =
+    sum d | sum d^2 | sum a^2 over the pixels, in one read of both (a fixed summation order: the same input gives the same bits).  `out`:
+    a contiguous fp32 [3, C] on the operands' device that is ADDED TO; None makes a zero one.  Everything is checked on the host before
+    a pointer is taken."""
+    for name, t in (("a", a), ("b", b)):
+        if not torch.is_tensor(t) or t.dtype != torch.float32:
+            raise ValueError(f"pair_moments: {name} must be an fp32 tensor, got {t.dtype if torch.is_tensor(t) else type(t).__name__}")
+    if a.shape != b.shape:
+        raise ValueError(f"pair_moments: a is {tuple(a.shape)}, b is {tuple(b.shape)}: the shapes differ")
+    if a.dim() < 1 or a.numel() == 0:
+        raise ValueError(f"pair_moments: the operands are empty or scalars: {tuple(a.shape)}")
+    if not a.is_contiguous() or not b.is_contiguous():
+        raise ValueError("pair_moments: a and b must be contiguous")
+    if a.device != b.device:
+        raise ValueError(f"pair_moments: a is on {a.device}, b on {b.device}")
+    Cc = int(a.shape[-1])
+    if out is not None and (not torch.is_tensor(out) or tuple(out.shape) != (3, Cc) or out.dtype != torch.float32 or out.device != a.device
+                            or not out.is_contiguous()):
+        raise ValueError(f"pair_moments: out must be a contiguous fp32 [3, {Cc}] on {a.device}, got "
+                         f"{(out.dtype, tuple(out.shape), out.device) if torch.is_tensor(out) else type(out).__name__}")
+    if not a.is_cuda:
+        raise ValueError(f"pair_moments: the operands are on {a.device}; there is no CPU path")
+    if out is None:
+        out = torch.zeros(3, Cc, device=a.device, dtype=torch.float32)
+    ws = _PAIR_WS.get((a.device, Cc))
+    if ws is None:
+        ws = _PAIR_WS[(a.device, Cc)] = torch.empty(int(L.lib().rdo_pair_moments_workspace(Cc)), device=a.device, dtype=torch.float32)
+    L.check(L.lib().rdo_pair_moments(_ptr(a), _ptr(b), a.numel() // Cc, Cc, _ptr(out), _ptr(ws), _stream()), "rdo_pair_moments")
+    return out
+
+
 def actquant_static_bwd(x, g, rng, drange, dx=None, n_bits=8, ws=None):
     """Backward of `actquant_static` with a straight-through round: returns dx (= g inside the range, 0 outside; `dx` may be g) and
     accumulates the per-channel range gradient into drange [2C] = dlo | dhi.  x, g: [..., C] channels-last, contiguous."""

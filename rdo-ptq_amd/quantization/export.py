@@ -68,5 +68,49 @@ def activation_report(qnn) -> "OrderedDict[str, dict]":
     return out
 
 
+UNIT_REPORT_STATES = ("nearest", "learned")
+
+
+def unit_report(qnn) -> "OrderedDict[str, dict]":
+    """unit name -> the measured output error of every calibrated unit whose statistics were recorded (args.unit_report;
+    `recon.report_unit`), in module order, on the CPU.  With d = full-precision output - quantised output of the unit on its cached
+    calibration inputs, per output channel and for both states 'nearest' (every trained weight rounded to nearest) and 'learned' (the
+    unit as calibrated):
+      channels, n                    channel count; pixels per channel (all ranks)
+      err, shift, energy [state]     float64 [C]: sum d^2, sum d, sum of the squared full-precision output
+      sqnr_db [state]                float64 [C]: 10 log10(energy / err), inf where err == 0
+      gain_db                        float64 [C]: sqnr_db['learned'] - sqnr_db['nearest'] (what the learned rounding gained)
+      shift_share [state]            float64 [C]: shift^2 / (n err), 0 where err == 0: the part of the squared error that a per-channel
+                                     bias would remove (in [0, 1] by Cauchy-Schwarz)
+      total                          {err, shift, energy, sqnr_db [state], gain_db}: the same over the summed channels (Python floats)
+    Empty for a model without recorded statistics."""
+    def sqnr(energy, err):
+        return torch.where(err == 0, torch.full_like(err, float("inf")), 10.0 * torch.log10(energy / err))
+    out = OrderedDict()
+    for _, m in qnn.named_modules():
+        st = getattr(m, "unit_stats", None)
+        if not st:
+            continue
+        n = int(st["n"])
+        row = {"n": n, "total": {}}
+        for f in ("err", "shift", "energy", "sqnr_db", "shift_share"):
+            row[f] = {}
+            if f in ("err", "shift", "energy", "sqnr_db"):
+                row["total"][f] = {}
+        for state in UNIT_REPORT_STATES:
+            shift, err, energy = (st[state][f].detach().to("cpu", torch.float64).clone() for f in ("shift", "err", "energy"))
+            row["err"][state], row["shift"][state], row["energy"][state] = err, shift, energy
+            row["sqnr_db"][state] = sqnr(energy, err)
+            row["shift_share"][state] = torch.where(err == 0, torch.zeros_like(err), shift * shift / (max(n, 1) * err))
+            row["total"]["err"][state], row["total"]["shift"][state] = float(err.sum()), float(shift.sum())
+            row["total"]["energy"][state] = float(energy.sum())
+            row["total"]["sqnr_db"][state] = float(sqnr(energy.sum(), err.sum()))
+        row["channels"] = int(row["err"]["learned"].numel())
+        row["gain_db"] = row["sqnr_db"]["learned"] - row["sqnr_db"]["nearest"]
+        row["total"]["gain_db"] = row["total"]["sqnr_db"]["learned"] - row["total"]["sqnr_db"]["nearest"]
+        out[str(st["name"])] = row
+    return out
+
+
 def dequantize(entry) -> torch.Tensor:
     return (entry["levels"].to(torch.float32) - entry["zero_point"]) * entry["delta"]

@@ -81,6 +81,12 @@ class QuantModel(nn.Module):
         from .export import activation_report
         return activation_report(self)
 
+    def unit_report(self):
+        """OrderedDict unit name -> the measured output error of every calibrated unit that recorded it (args.unit_report): per output
+        channel, learned rounding against round-to-nearest (`export.unit_report`)."""
+        from .export import unit_report
+        return unit_report(self)
+
     def forward(self, input):
         return self.model(input)
 

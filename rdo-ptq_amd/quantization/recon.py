@@ -13,6 +13,7 @@ from .engine import UnitEngine
 from .quant_block import BaseQuantBlock, QuantRSTB
 from .swin_engine import TapeEngine
 from .quant_layer import QuantModule, _nhwc
+from .quantizer import AdaRoundQuantizer
 from .utils import LinearTempDecay, save_inp_oup_data, set_mode
 
 _COOPS = ("g_a", "h_a", "h_s", "g_s")
@@ -145,7 +146,9 @@ def _act_args(args):
     grid width: `ops.act_hist_mse_select`) or 'auto' (one pass takes the 'l2' error sums and the histograms, the ranges that 'max', 'l2',
     'percentile' and 'hist_mse' would freeze are then SCORED on the same inputs, `ops.actquant_score`, and each channel takes the one of
     least measured squared error); args.act_report (default False; a bool): after freezing, one more pass records every site's measured
-    error, energy and clipped counts (`export.activation_report`).  Checked before any work is done."""
+    error, energy and clipped counts (`export.activation_report`); args.unit_report (default False; a bool): a trained unit then measures
+    its own output error on its cached inputs, learned rounding against round-to-nearest (`report_unit`, `export.unit_report`).  Checked
+    before any work is done."""
     mode = getattr(args, "act_mode", "dynamic") if args is not None else "dynamic"
     how = getattr(args, "act_range", "max") if args is not None else "max"
     if mode not in ("dynamic", "static"):
@@ -155,6 +158,7 @@ def _act_args(args):
     _act_learn_args(args)
     _act_percentile_args(args)
     _act_report_args(args)
+    _unit_report_args(args)
     return mode, how
 
 
@@ -163,6 +167,14 @@ def _act_report_args(args):
     report = getattr(args, "act_report", False) if args is not None else False
     if not isinstance(report, bool):
         raise ValueError(f"act_report must be True or False, got {report!r}")
+    return report
+
+
+def _unit_report_args(args):
+    """args.unit_report, validated: a bool (default False)."""
+    report = getattr(args, "unit_report", False) if args is not None else False
+    if not isinstance(report, bool):
+        raise ValueError(f"unit_report must be True or False, got {report!r}")
     return report
 
 
@@ -302,6 +314,68 @@ def report_act_ranges(unit, inp_q, batch=32):
             m.use_weight_quant, m.use_act_quant = w, a_
 
 
+def _nearest_alpha(q, w):
+    """A stand-in for the alpha of the AdaRoundQuantizer `q` of weight `w` whose sign makes the hard forward, floor(w / delta) + (alpha >=
+    0), round to nearest: +1 where frac = w / delta - floor(w / delta) >= 0.5 (fp32, the quantiser's own rows and scales), -1 below."""
+    wr = q._rows(w.detach())
+    d, _ = q._row_scales(wr)
+    r = wr / d.reshape(-1, *([1] * (wr.dim() - 1)))
+    up = (r - torch.floor(r)) >= 0.5
+    return q._unrows(torch.where(up, 1.0, -1.0).to(wr.dtype).contiguous(), w)
+
+
+def report_unit(unit, unit_name, inp_q, out_fp, batch=32):
+    """Measure what calibration gained on a trained unit: two passes over its cached quantised inputs `inp_q`, in the quant state the unit
+    is found in (frozen static activation ranges included), each compared with the cached full-precision outputs `out_fp` per output
+    channel by `ops.pair_moments(out_fp batch, output batch)` on channels-last storage:
+      'nearest'   every trained weight (every AdaRoundQuantizer of the unit) rounded to nearest on the delta | zero point the quantiser
+                  holds, clamp(floor(w / delta) + (frac >= 0.5) + z, 0, n_levels - 1) with frac = w / delta - floor(w / delta) in fp32: A
+                  TIE ROUNDS UP (towards +inf), not to even as torch.round does.  Alpha is swapped for a tensor whose sign encodes frac >=
+                  0.5 for the duration of the pass, then put back (the same Parameter objects) and the weight packs are dropped;
+      'learned'   the unit as calibrated.
+    The fp32 sums of the batches are added in float64 on the device; under data parallelism the two float64 [3, C] tensors are summed
+    over the ranks ('nearest', then 'learned'), then the pixel count.  The result stays on the unit as `unit.unit_stats` = {"name", "n",
+    "nearest": {"shift", "err", "energy"}, "learned": {...}} with float64 [C] CPU tensors (`export.unit_report` reads it).  Nothing else
+    changes: alpha, delta, zero points, ranges, `act_stats` and every flag are left as they were found."""
+    rstb = isinstance(unit, QuantRSTB)
+    adas = [(m, m.weight_quantizer) for m in unit.modules()
+            if isinstance(m, QuantModule) and isinstance(m.weight_quantizer, AdaRoundQuantizer)]
+
+    def run():
+        # (zero sums, not None: a rank with no rows still takes part in the collectives below)
+        acc, n = torch.zeros(3, out_fp.shape[1], dtype=torch.float64, device=out_fp.device), 0
+        with torch.no_grad():
+            for i in range(0, inp_q.shape[0], batch):
+                h = inp_q[i:i + batch]
+                out = _nhwc(unit(h, (h.shape[2], h.shape[3])) if rstb else unit(h))
+                ref = _nhwc(out_fp[i:i + batch])
+                mom = ops.pair_moments(ref, out).double()
+                acc = acc + mom
+                n += ref.numel() // ref.shape[-1]
+        return acc, n
+
+    held = [(q, q.alpha) for _, q in adas]
+    try:
+        for m, q in adas:
+            q.alpha = torch.nn.Parameter(_nearest_alpha(q, m.weight), requires_grad=q.alpha.requires_grad)
+            m.drop_weight_pack()
+        nearest, n = run()
+    finally:
+        for (m, _), (q, alpha) in zip(adas, held):
+            q.alpha = alpha
+            m.drop_weight_pack()
+    learned, _ = run()
+    if dp.world()[1] > 1:
+        count = torch.tensor([n], dtype=torch.int64, device=nearest.device)
+        dp.reduce_act_stats(sums=[nearest, learned, count])
+        n = int(count.item())
+    names = ("shift", "err", "energy")
+    unit.unit_stats = {"name": unit_name, "n": int(n),
+                       "nearest": {f: v for f, v in zip(names, nearest.cpu())},
+                       "learned": {f: v for f, v in zip(names, learned.cpu())}}
+    return unit.unit_stats
+
+
 def learn_act_ranges(unit, inp_q, out_fp, iters=500, lr=1e-3, batch=32, seed=0, idx_table=None):
     """Train the frozen static activation ranges of a calibrated unit on its reconstruction error (the activation-grid step of BRECQ /
     QDrop, after the rounding has been learned).  The unit runs in the W8A8 state with its hard-rounded weights under torch's tape (the
@@ -400,6 +474,7 @@ def _reconstruct(model, unit, unit_name, cali_data, batch_size=32, iters=20000, 
     act_iters, act_lr = _act_learn_args(args)
     act_percentile = _act_percentile_args(args)
     act_report = _act_report_args(args)
+    unit_report = _unit_report_args(args)
     if act_quant and act_mode == "static" and act_range == "learned" and _is_rstb(unit):
         raise NotImplementedError("act_range='learned': a Swin (RSTB) unit's activation-quantised window attention cannot sit on torch's "
                                   "tape (quant_block.QuantWindowAttention); calibrate it with act_range='max' or 'l2'")
@@ -529,4 +604,9 @@ def _reconstruct(model, unit, unit_name, cali_data, batch_size=32, iters=20000, 
             report_act_ranges(unit, inp_q, batch=cache_bs)
         if timing is not None:
             timing[-1]["act_s"] = _mark() - t4
+    if unit_report:
+        t5 = _mark()
+        report_unit(unit, unit_name, inp_q, out_fp, batch=cache_bs)
+        if timing is not None:
+            timing[-1]["report_s"] = _mark() - t5
     return eng

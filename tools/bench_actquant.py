@@ -8,7 +8,8 @@ The range search (one read, ten candidates) and the range scoring of act_range='
 grids with their clipped counts and the energy) are timed next to them; with --bwd also the backward of the static quantiser (two reads, one
 write: 12 B per element), whose share of the static forward's GB/s on the same tensor is reported; with --hist the per-channel histogram
 pass of act_range='percentile' and 'hist_mse' (one read, 1024 integer bins per channel) and their C-sized selections (the percentile
-cut and the exhaustive histogram-MSE search), in the same alternating windows as the search pass they stand in for.
+cut and the exhaustive histogram-MSE search), in the same alternating windows as the search pass they stand in for; with --pair the
+pair moments of the per-unit output error report (two reads: 8 B per element), in the same windows as the K = 1 score.
 
 Learning part (--learn): wall time of `recon.learn_act_ranges` on one Cheng2020 block unit at N = 192 (a ResidualBlock on 32^2 inputs, what
 g_a[5] sees for 256^2 crops), after a short warm-up run, device synchronised at both ends.
@@ -17,7 +18,7 @@ Flow part (--flow): the cache-building wall (`args.timing`, `cache_s`) of a W8A8
 crops) in both modes -- dynamic grids build every unit's caches image by image, static ones in batches; with --hist also the range
 fixing wall (`act_s`) of the static flow under act_range='l2' against 'percentile' and 'hist_mse'.
 
-    python tools/bench_actquant.py [--reps 1000] [--rounds 7] [--bwd] [--hist] [--learn] [--flow] [--images 32] [--json out.json]"""
+    python tools/bench_actquant.py [--reps 1000] [--rounds 7] [--bwd] [--hist] [--pair] [--learn] [--flow] [--images 32] [--json out.json]"""
 import argparse
 import json
 import os
@@ -45,7 +46,7 @@ def _time_us(fn, reps):
     return a.elapsed_time(b) * 1e3 / reps
 
 
-def bench_kernels(reps, rounds, n_bits=8, bwd=False, hist=False):
+def bench_kernels(reps, rounds, n_bits=8, bwd=False, hist=False, pair=False):
     from hipops import ops
     L = ops.L
     rows = []
@@ -96,6 +97,10 @@ def bench_kernels(reps, rounds, n_bits=8, bwd=False, hist=False):
             def select_mse_call():
                 sel[0] = ops.act_hist_mse_select(hh, rng, n_bits)
             calls["hist"], calls["select"], calls["select_mse"] = hist_call, select_call, select_mse_call
+        if pair:
+            y = (x + 0.01 * torch.randn(*shape, generator=g).cuda()).contiguous()
+            pout = torch.zeros(3, C, device="cuda")
+            calls["pair"] = lambda: ops.pair_moments(x, y, out=pout)
         r = reps
         for fn in calls.values():                              # warm-up: code objects, caches
             for _ in range(10):
@@ -131,6 +136,9 @@ def bench_kernels(reps, rounds, n_bits=8, bwd=False, hist=False):
                        select_mse_us=round(med["select_mse"], 2),
                        select_mse_spread_us=[round(min(t["select_mse"]), 2), round(max(t["select_mse"]), 2)],
                        hist_over_search=round(med["hist"] / med["search"], 2))
+        if pair:
+            row.update(pair_us=round(med["pair"], 2), pair_spread_us=[round(min(t["pair"]), 2), round(max(t["pair"]), 2)],
+                       pair_gbs=round(8.0 * n / med["pair"] / 1e3, 1), pair_over_score1=round(med["pair"] / med["score1"], 2))
         rows.append(row)
         print(json.dumps(row), flush=True)
     return rows
@@ -223,6 +231,7 @@ def main():
     ap.add_argument("--bwd", action="store_true", help="also time the backward of the static quantiser")
     ap.add_argument("--hist", action="store_true", help="also time the histogram pass and the selections of act_range='percentile' and 'hist_mse'; "
                     "with --flow also act_s of the toy flow under 'l2' against 'percentile' and 'hist_mse'")
+    ap.add_argument("--pair", action="store_true", help="also time ops.pair_moments (the per-unit output error report) beside the K = 1 score")
     ap.add_argument("--learn", action="store_true", help="time learn_act_ranges on one N = 192 block unit")
     ap.add_argument("--flow", action="store_true")
     ap.add_argument("--images", type=int, default=32)
@@ -230,7 +239,7 @@ def main():
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_actquant needs a GPU: there is no CPU path to time")
-    res = {"kernels": bench_kernels(a.reps, a.rounds, bwd=a.bwd, hist=a.hist)}
+    res = {"kernels": bench_kernels(a.reps, a.rounds, bwd=a.bwd, hist=a.hist, pair=a.pair)}
     slow = [r["shape"] for r in res["kernels"] if r["static_slower"]]
     if slow:
         print(f"DEFECT: static slower than dynamic on {slow}", flush=True)
