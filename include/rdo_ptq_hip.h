@@ -484,6 +484,19 @@ int rdo_neg_log2_sum_ordered(const float* lik, int64_t n, float scale, float* ou
 int rdo_sq_diff_sum_ordered(const float* a, const float* b, int64_t n, float scale, int32_t clamp01_a, float* out /* += */, float* ws,
                             void* stream);
 int64_t rdo_ordered_sum_workspace(void);
+/* Per-channel rate sums (extension: the RD report).  lik = a likelihood tensor [outer][C][inner], element (o, c, i) at
+ * ((o * C) + c) * inner + i:
+ *   out[c] = sum over o, i of -log2f(lik[o, c, i])            (the expression of rdo_neg_log2_sum; out is OVERWRITTEN)
+ * One entry for both storages: NCHW contiguous is outer = B, inner = H * W; channels-last is outer = B * H * W, inner = 1.  One read of
+ * lik, adjacent lanes on adjacent addresses in both (inner > 1: a workgroup walks one channel's runs of `inner` values; inner == 1:
+ * min(C, 64) channels side by side).  No atomics: per-workgroup partial sums in ws are folded in a fixed order (the comment in front of
+ * rate_channel_part_kernel, csrc/entropy.hip, states it), so the bits of out depend on (lik, outer, C, inner) alone, never on what ws
+ * held or on earlier launches.  A NaN in one channel makes that channel NaN and no other.  Refused before any launch: a null lik, out
+ * or ws, outer, C or inner <= 0, C > 65535 or outer * inner >= 2^31 (the index arithmetic: 32-bit positions inside a channel). */
+int rdo_neg_log2_channel_sums(const float* lik, int64_t outer, int32_t C, int64_t inner, float* out /* [C], overwritten */,
+                              float* ws /* rdo_neg_log2_channel_sums_workspace(outer, C, inner) floats, no initial state needed */,
+                              void* stream);
+int64_t rdo_neg_log2_channel_sums_workspace(int64_t outer, int32_t C, int64_t inner);   /* floats; 0 for unsupported arguments */
 
 /* ---- "H2" tensors and fused unit tails -------------------------------------------------------------------------------------------
  * An H2 tensor is an fp32 NHWC activation [M pixels][C channels] (C % 16 == 0) stored as the exact two-way fp16 split of its

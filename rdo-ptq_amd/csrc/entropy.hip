@@ -1,4 +1,5 @@
-// K12 -- entropy-model likelihoods and the rate/distortion reductions, element-wise on NHWC tensors.
+// K12 -- entropy-model likelihoods and the rate/distortion reductions, element-wise on NHWC tensors; the per-channel rate sums of the
+// RD report (rate_channel_part_kernel below) take a likelihood tensor in either storage, [outer][C][inner].
 //
 // Restates (CompressAI 1.2.4 definitions, pinned only against the oracle's restatement -- SURVEY 8c "parity unpinned"):
 //   EntropyBottleneck.forward (eval): z^ = round(z - median) + median ; p(z^) = |sigmoid(s*F(z^+.5)) - sigmoid(s*F(z^-.5))|,
@@ -215,6 +216,74 @@ __global__ __launch_bounds__(256) void ordered_fold_kernel(const float* part, in
 using rdo::grid_for;
 constexpr int kOrderedBlocks = rdo::kGridCap;      // one partial sum per workgroup of grid_for
 
+// ---- per-channel rate sums (the RD report): out[c] = sum over (o, i) of -log2f(lik[((o C) + c) inner + i]), the expression of
+// neg_log2_sum_kernel.  A channel holds n = outer * inner elements, numbered j = o * inner + i.  A thread is (element lane pl, channel):
+// cpb channels side by side and PL = 256 / cpb element lanes of them in a workgroup, S workgroups (blockIdx.x) down a channel's elements,
+// blockIdx.y over the groups of cpb channels; lane pl of workgroup s adds the elements j = s PL + pl, + S PL, .. serially.
+//   inner > 1 (NCHW):          cpb = 1, PL = 256: the 256 threads read 256 consecutive j of ONE channel, i.e. runs of `inner` adjacent
+//                              addresses (one run of 256 when inner >= 256, sixteen 64-byte runs when inner = 16)
+//   inner = 1 (channels-last): cpb = min(C, 64), PL = 256 / cpb: thread t reads channel t % cpb of pixel t / cpb -- adjacent lanes,
+//                              adjacent addresses (for C < 64 the whole workgroup reads one contiguous run of PL C floats)
+// Then the PL lanes of a channel fold through LDS as a binary tree (lane pl += lane pl + h for h = 128, 64, .., 1 while pl + h < PL),
+// part[c][s] = the workgroup's sum, and the fold kernel adds a channel's S partial sums: sixteen lanes, lane j the entries j, j + 16, ..
+// serially, then the xor tree 8, 4, 2, 1.  No atomics, every word of `part` that is read was written by this call, and a thread, an
+// LDS tree and a fold group only ever hold values of ONE channel: a NaN stays in its channel.
+constexpr int kRcSlices = 256;         // most workgroups down one channel
+struct RcGeom { int cpb, PL, S, cblocks; };
+inline RcGeom rc_geom(int64_t outer, int32_t C, int64_t inner) {
+    RcGeom g;
+    g.cpb = inner == 1 ? (C < 64 ? C : 64) : 1;
+    g.PL = 256 / g.cpb;
+    const int64_t s = rdo::ceil_div(outer * inner, (int64_t)g.PL * 8);      // >= 8 elements a lane before a second workgroup pays
+    g.S = (int)(s > kRcSlices ? kRcSlices : s);
+    g.cblocks = (int)rdo::ceil_div(C, g.cpb);
+    return g;
+}
+// the arguments the index arithmetic supports: j and j + S PL in 32 bits unsigned, blockIdx.y <= 65535, addresses in 64 bits
+inline bool rc_supported(int64_t outer, int32_t C, int64_t inner) {
+    return outer > 0 && C > 0 && inner > 0 && C <= 65535 && outer <= 0x7fffffffLL && inner <= 0x7fffffffLL && outer * inner <= 0x7fffffffLL;
+}
+
+template <bool NCHW>
+__global__ __launch_bounds__(256) void rate_channel_part_kernel(const float* lik, unsigned n, int C, unsigned inner, int cpb, int PL,
+                                                                float* part) {
+    __shared__ float sm[256];
+    const int pl = threadIdx.x / cpb, cl = threadIdx.x - pl * cpb;
+    const int c = blockIdx.y * cpb + cl;
+    const bool live = pl < PL && c < C;
+    float acc = 0.f;
+    if (live) {
+        const unsigned step = gridDim.x * PL;
+        for (unsigned j = blockIdx.x * PL + pl; j < n; j += step) {
+            long a;
+            if (NCHW) {
+                const unsigned o = j / inner;
+                a = ((long)o * C + c) * inner + (j - o * inner);
+            } else {
+                a = (long)j * C + c;
+            }
+            acc -= log2f(lik[a]);
+        }
+    }
+    sm[threadIdx.x] = acc;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (live && pl < h && pl + h < PL) sm[threadIdx.x] += sm[threadIdx.x + h * cpb];
+        __syncthreads();
+    }
+    if (live && pl == 0) part[(long)c * gridDim.x + blockIdx.x] = sm[cl];
+}
+
+__global__ __launch_bounds__(256) void rate_channel_fold_kernel(const float* part, int S, int C, float* out) {
+    const int c = blockIdx.x * 16 + (threadIdx.x >> 4), j = threadIdx.x & 15;
+    float r = 0.f;
+    if (c < C)
+        for (int b = j; b < S; b += 16) r += part[(long)c * S + b];
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) r += __shfl_xor(r, o, 16);
+    if (c < C && j == 0) out[c] = r;
+}
+
 }  // namespace
 
 extern "C" {
@@ -307,6 +376,30 @@ int rdo_sq_diff_sum_ordered(const float* a, const float* b, int64_t n, float sca
             return rdo::check_launch("sq_diff_sum_ordered");
         },
         stream, "entropy", 0.0, 8.0 * n);
+}
+
+int64_t rdo_neg_log2_channel_sums_workspace(int64_t outer, int32_t C, int64_t inner) {
+    return rc_supported(outer, C, inner) ? (int64_t)C * rc_geom(outer, C, inner).S : 0;
+}
+
+int rdo_neg_log2_channel_sums(const float* lik, int64_t outer, int32_t C, int64_t inner, float* out, float* ws, void* stream) {
+    RDO_REQUIRE(lik && out && ws && outer > 0 && C > 0 && inner > 0, "rdo_neg_log2_channel_sums: bad argument");
+    RDO_REQUIRE(rc_supported(outer, C, inner),
+                "rdo_neg_log2_channel_sums: outer %lld x C %d x inner %lld is beyond the index arithmetic (C <= 65535, outer * inner < 2^31)",
+                (long long)outer, C, (long long)inner);
+    return rdo::dispatch(
+        [=](hipStream_t s) {
+            const RcGeom g = rc_geom(outer, C, inner);
+            const unsigned n = (unsigned)(outer * inner);
+            if (inner == 1)
+                hipLaunchKernelGGL(rate_channel_part_kernel<false>, dim3(g.S, g.cblocks), dim3(256), 0, s, lik, n, C, 1u, g.cpb, g.PL, ws);
+            else
+                hipLaunchKernelGGL(rate_channel_part_kernel<true>, dim3(g.S, g.cblocks), dim3(256), 0, s, lik, n, C, (unsigned)inner, g.cpb,
+                                   g.PL, ws);
+            hipLaunchKernelGGL(rate_channel_fold_kernel, dim3((unsigned)rdo::ceil_div(C, 16)), dim3(256), 0, s, ws, g.S, C, out);
+            return rdo::check_launch("neg_log2_channel_sums");
+        },
+        stream, "entropy", 0.0, 4.0 * outer * C * inner);
 }
 
 }  // extern "C"

@@ -137,6 +137,8 @@ _SIGS = {
     "rdo_neg_log2_sum_ordered": (C.c_int, [P, C.c_int64, C.c_float, P, P, P]),
     "rdo_sq_diff_sum_ordered": (C.c_int, [P, P, C.c_int64, C.c_float, C.c_int32, P, P, P]),
     "rdo_ordered_sum_workspace": (C.c_int64, []),
+    "rdo_neg_log2_channel_sums": (C.c_int, [P, C.c_int64, C.c_int32, C.c_int64, P, P, P]),
+    "rdo_neg_log2_channel_sums_workspace": (C.c_int64, [C.c_int64, C.c_int32, C.c_int64]),
     "rdo_h2_overflow": (C.c_int, [C.c_int]),
     "rdo_h2_bind_flag": (C.c_int, [C.c_void_p]),
     "rdo_split_h2": (C.c_int, [P, C.c_int64, C.c_int32, C.c_float, P, P]),

@@ -1048,6 +1048,46 @@ def sq_diff_sum_ordered(a, b, scale=1.0, clamp01=False, out=None):
     return out
 
 
+_CHANNEL_WS = {}    # (device, floats) -> workspace of neg_log2_channel_sums (launches are stream-ordered, so one buffer per key suffices)
+
+
+def neg_log2_channel_sums(lik, out=None):
+    """Per-channel rate of a 4-D fp32 likelihood tensor [B, C, H, W] on the GPU: -> float32 [C], out[c] = sum over b, h, w of -log2 lik,
+    in one read and a fixed summation order (the same input gives the same bits; a NaN stays in its channel).  NCHW-contiguous and
+    channels-last-contiguous storage are read as they are (outer, inner = B, H W or B H W, 1); anything else is made contiguous first.
+    `out`: a contiguous fp32 [C] on lik's device that is OVERWRITTEN.  Everything is checked on the host before a pointer is taken."""
+    what = "neg_log2_channel_sums"
+    if not torch.is_tensor(lik) or lik.dtype != torch.float32:
+        raise ValueError(f"{what}: lik must be an fp32 tensor, got {lik.dtype if torch.is_tensor(lik) else type(lik).__name__}")
+    if lik.dim() != 4:
+        raise ValueError(f"{what}: lik must be 4-D [B, C, H, W], got {tuple(lik.shape)}")
+    if lik.numel() == 0:
+        raise ValueError(f"{what}: lik is empty: {tuple(lik.shape)}")
+    B, Cc, H, W = (int(v) for v in lik.shape)
+    if out is not None and (not torch.is_tensor(out) or tuple(out.shape) != (Cc,) or out.dtype != torch.float32 or out.device != lik.device
+                            or not out.is_contiguous()):
+        raise ValueError(f"{what}: out must be a contiguous fp32 [{Cc}] on {lik.device}, got "
+                         f"{(out.dtype, tuple(out.shape), out.device) if torch.is_tensor(out) else type(out).__name__}")
+    if not lik.is_cuda:
+        raise ValueError(f"{what}: lik is on {lik.device}; there is no CPU path")
+    if lik.is_contiguous():
+        outer, inner = B, H * W
+    elif lik.is_contiguous(memory_format=torch.channels_last):
+        lik, outer, inner = lik.permute(0, 2, 3, 1), B * H * W, 1       # the same storage as a contiguous [B, H, W, C] view
+    else:
+        lik, outer, inner = lik.contiguous(), B, H * W
+    if out is None:
+        out = torch.empty(Cc, device=lik.device, dtype=torch.float32)
+    n_ws = int(L.lib().rdo_neg_log2_channel_sums_workspace(outer, Cc, inner))
+    if n_ws <= 0:
+        raise ValueError(f"{what}: {tuple(lik.shape)} is beyond the kernel's index arithmetic (C <= 65535, B H W < 2^31)")
+    ws = _CHANNEL_WS.get((lik.device, n_ws))
+    if ws is None:
+        ws = _CHANNEL_WS[(lik.device, n_ws)] = torch.empty(n_ws, device=lik.device, dtype=torch.float32)
+    L.check(L.lib().rdo_neg_log2_channel_sums(_ptr(lik), outer, Cc, inner, _ptr(out), _ptr(ws), _stream()), "rdo_neg_log2_channel_sums")
+    return out
+
+
 _SCHED_MEMO = {}
 
 

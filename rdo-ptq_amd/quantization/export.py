@@ -2,10 +2,12 @@
 which overwrites weights with uint8 levels): for every trained QuantModule the unsigned integer levels, the per-channel
 scale `delta` and the zero point, such that  w_q = (levels - zero_point) * delta  is exactly the hard-rounded weight the
 module uses at inference (`AdaRoundQuantizer.forward` with soft_targets=False, quantizer.py:441-449)."""
+import math
 from collections import OrderedDict
 
 import torch
 
+from .quant_block import BaseQuantBlock
 from .quant_layer import QuantModule
 from .quantizer import AdaRoundQuantizer
 
@@ -110,6 +112,152 @@ def unit_report(qnn) -> "OrderedDict[str, dict]":
         row["total"]["gain_db"] = row["total"]["sqnr_db"]["learned"] - row["total"]["sqnr_db"]["nearest"]
         out[str(st["name"])] = row
     return out
+
+
+def _rd_report_args(qnn, images, lmbda, act_quant, batch, units):
+    """every argument check of `rd_report`, before any GPU work -> the selected (name, unit) pairs in `units()` order"""
+    if not torch.is_tensor(images) or images.dtype != torch.float32:
+        raise ValueError(f"rd_report: images must be an fp32 tensor [n, 3, H, W], got "
+                         f"{images.dtype if torch.is_tensor(images) else type(images).__name__}")
+    if images.dim() != 4 or images.shape[1] != 3:
+        raise ValueError(f"rd_report: images must be [n, 3, H, W], got {tuple(images.shape)}")
+    if images.numel() == 0:
+        raise ValueError(f"rd_report: images is empty: {tuple(images.shape)}")
+    if images.shape[2] % 64 or images.shape[3] % 64:
+        raise ValueError(f"rd_report: the image sides must be multiples of 64 (the calibration crops; nothing is padded), got "
+                         f"{tuple(images.shape[2:])}")
+    if isinstance(lmbda, bool) or not isinstance(lmbda, (int, float)) or not math.isfinite(lmbda) or lmbda <= 0:
+        raise ValueError(f"rd_report: lmbda must be a positive finite number, got {lmbda!r}")
+    if isinstance(batch, bool) or not isinstance(batch, int) or batch < 1:
+        raise ValueError(f"rd_report: batch must be an integer >= 1, got {batch!r}")
+    if not isinstance(act_quant, bool):
+        raise ValueError(f"rd_report: act_quant must be True or False, got {act_quant!r}")
+    known = qnn.units()
+    if units is None:
+        return list(known.items())
+    if isinstance(units, str) or not all(isinstance(u, str) for u in units):
+        raise ValueError(f"rd_report: units must be None or a list of unit names, got {units!r}")
+    unknown = [u for u in units if u not in known]
+    if unknown:
+        raise ValueError(f"rd_report: unknown unit name(s) {unknown}; QuantModel.units() has {list(known)}")
+    return [(n, u) for n, u in known.items() if n in set(units)]
+
+
+def _dynamic_grids(qnn):
+    """does an activation quantiser that a forward with act_quant=True applies (its module trained, not disabled) follow its own
+    tensor's min | max?"""
+    for _, m in qnn.named_modules():
+        if isinstance(m, (QuantModule, BaseQuantBlock)) and m.trained and not getattr(m, "disable_act_quant", False) \
+                and getattr(m.act_quantizer, "act_mode", "dynamic") != "static":
+            return True
+    return False
+
+
+def rd_report(qnn, images, lmbda=0.01, act_quant=False, batch=8, units=None) -> "OrderedDict":
+    """What each reconstruction unit costs in rate and distortion, measured on `images` (fp32 [n, 3, H, W] in [0, 1] on any device,
+    H and W multiples of 64: the calibration crops, nothing is padded) under torch.no_grad().  Every state runs over the same images:
+      'fp'          qnn.set_quant_state(False, False)
+      'all'         qnn.set_quant_state(True, act_quant): what the W8 / W8A8 evaluation runs (disable_act_quant, `trained` and the
+                    bit-widths as they stand on the model)
+      one per unit  qnn.set_quant_state(False, False); unit.set_quant_state(True, act_quant): only that unit quantised
+    `units`: None for all of `qnn.units()`, or a list of its names (reported in `units()` order).  With P = n H W, per state:
+      bits[k]       float64 [C_k] on the CPU for every key k of out["likelihoods"] in the model's order: each batch's likelihood tensor
+                    goes once through `ops.neg_log2_channel_sums`, the fp32 results are added in float64 on the device
+      bits_total    the float64 sum over the keys of the channel sums
+      sse           sum of ops.sq_diff_sum_ordered(x_hat, x, 1.0, clamp01=True) of the batches, added in float64
+      bpp, mse      bits_total / P, sse / (3 P)
+      psnr_db       -10 log10(mse), inf where mse == 0: the PSNR of the POOLED error, not `evaluate_images`' mean of per-image PSNRs
+      loss          bpp + lmbda 255^2 mse
+    and on every row but 'fp' the differences against 'fp': d_bits[k], d_bpp, d_mse, d_psnr_db, d_loss.
+    -> OrderedDict: 'fp', 'all', 'units' (name -> row), 'n', 'pixels' (= P), 'lmbda', 'act_quant', 'additivity' {'sum_units_d_loss',
+    'all_d_loss'} (unit costs are NOT additive: the pair shows by how much), 'batch' (the batch used).
+
+    Batch: with act_quant=True and an applied activation quantiser on a dynamic grid, a tensor's grid depends on what shares its batch;
+    the batch is then 1 whatever `batch` says (the rule of the calibration's cache batch).
+    State: every module's use_weight_quant | use_act_quant pair is recorded first and restored in a `finally`; alpha, delta, zero points,
+    activation ranges, act_stats, unit_stats and `trained` are not written.  A weight quantiser that has never run initialises its scale
+    on its first use here, as in any forward.
+    Data parallel: with an initialised process group rank r takes the images r, r + world, ..., the float64 sums are all-reduced (SUM)
+    and every rank returns the same report; 'n' and 'pixels' are global (the rule of `evaluate_images`); fewer images than ranks is refused.
+    Cost: len(units) + 2 passes over `images` -- meant for the calibration crops, not for Kodak at full size.
+    Raises ValueError before any GPU work for: images not fp32 4-D with 3 channels, empty, or sides not multiples of 64; lmbda not a
+    positive finite number; batch not an integer >= 1; act_quant not a bool; an unknown unit name."""
+    from hipops import ops
+    from . import dp
+    chosen = _rd_report_args(qnn, images, lmbda, act_quant, batch, units)
+    n, _, H, W = (int(v) for v in images.shape)
+    pixels = n * H * W
+    bs = 1 if (act_quant and _dynamic_grids(qnn)) else batch
+    device = next(qnn.parameters()).device
+    rank, world = dp.world()
+    if n < world:
+        raise ValueError(f"rd_report: {n} image(s) for {world} ranks: every rank needs at least one")
+    mine = images[rank::world]
+    mods = [m for m in qnn.modules() if isinstance(m, (QuantModule, BaseQuantBlock))]
+    held = [(m.use_weight_quant, m.use_act_quant) for m in mods]
+
+    def measure():
+        """one pass over this rank's images in the state the model is in -> (keys, float64 device sums [bits of every key | sse])"""
+        keys, acc, sse = None, None, torch.zeros(1, dtype=torch.float64, device=device)
+        with torch.no_grad():
+            for i in range(0, mine.shape[0], bs):
+                x = mine[i:i + bs].to(device).contiguous()
+                out = qnn(x)
+                liks = out["likelihoods"]
+                if keys is None:
+                    keys = list(liks)
+                    acc = [torch.zeros(liks[k].shape[1], dtype=torch.float64, device=device) for k in keys]
+                for a, k in zip(acc, keys):
+                    a += ops.neg_log2_channel_sums(liks[k]).double()
+                sse += ops.sq_diff_sum_ordered(out["x_hat"].contiguous(), x, 1.0, clamp01=True).double()
+        return keys, acc, sse
+
+    def row(state):
+        keys, acc, sse = state
+        bits = OrderedDict((k, a.cpu()) for k, a in zip(keys, acc))
+        total = float(sum(b.sum() for b in bits.values()))
+        mse = float(sse) / (3 * pixels)
+        r = OrderedDict(bits=bits, bits_total=total, sse=float(sse), bpp=total / pixels, mse=mse,
+                        psnr_db=float("inf") if mse == 0 else -10.0 * math.log10(mse))
+        r["loss"] = r["bpp"] + lmbda * 255.0 ** 2 * mse
+        return r
+
+    def against(r, fp):
+        r["d_bits"] = OrderedDict((k, r["bits"][k] - fp["bits"][k]) for k in r["bits"])
+        for f in ("bpp", "mse", "psnr_db", "loss"):
+            r["d_" + f] = r[f] - fp[f]
+        return r
+
+    states = []
+    try:
+        qnn.set_quant_state(False, False)
+        states.append(measure())
+        qnn.set_quant_state(True, act_quant)
+        states.append(measure())
+        for _, u in chosen:
+            qnn.set_quant_state(False, False)
+            u.set_quant_state(True, act_quant)
+            states.append(measure())
+    finally:
+        for m, (w, a) in zip(mods, held):
+            m.use_weight_quant, m.use_act_quant = w, a
+    if world > 1:
+        flat = torch.cat([t for _, acc, sse in states for t in acc + [sse]])
+        dp.reduce_act_stats(sums=[flat])
+        off = 0
+        for _, acc, sse in states:
+            for t in acc + [sse]:
+                t.copy_(flat[off:off + t.numel()])
+                off += t.numel()
+    fp = row(states[0])
+    full = against(row(states[1]), fp)
+    rows = OrderedDict((name, against(row(st), fp)) for (name, _), st in zip(chosen, states[2:]))
+    rep = OrderedDict()
+    rep["fp"], rep["all"], rep["units"] = fp, full, rows
+    rep["n"], rep["pixels"], rep["lmbda"], rep["act_quant"] = n, pixels, float(lmbda), act_quant
+    rep["additivity"] = {"sum_units_d_loss": float(sum(r["d_loss"] for r in rows.values())), "all_d_loss": full["d_loss"]}
+    rep["batch"] = bs
+    return rep
 
 
 def dequantize(entry) -> torch.Tensor:

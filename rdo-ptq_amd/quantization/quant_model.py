@@ -87,6 +87,29 @@ class QuantModel(nn.Module):
         from .export import unit_report
         return unit_report(self)
 
+    def units(self):
+        """OrderedDict name -> reconstruction unit, in the order the calibration visits them (recon_model of the reference's
+        main2.py:227-253): every child that is a QuantModule or a BaseQuantBlock is a unit under its dotted name, anything else is
+        descended into; QuantModules without a weight (pixel shuffles) are left out."""
+        from collections import OrderedDict
+        out = OrderedDict()
+
+        def walk(mod, prefix):
+            for n, c in mod.named_children():
+                if isinstance(c, (QuantModule, BaseQuantBlock)):
+                    if not (isinstance(c, QuantModule) and c.org_weight is None):
+                        out[prefix + n] = c
+                else:
+                    walk(c, prefix + n + ".")
+        walk(self.model, "")
+        return out
+
+    def rd_report(self, images, lmbda=0.01, act_quant=False, batch=8, units=None):
+        """What every unit costs in rate and distortion when it alone is quantised, next to the full-precision and the fully
+        quantised model, measured on `images` (`export.rd_report`)."""
+        from .export import rd_report
+        return rd_report(self, images, lmbda=lmbda, act_quant=act_quant, batch=batch, units=units)
+
     def forward(self, input):
         return self.model(input)
 
