@@ -194,7 +194,8 @@ __device__ __forceinline__ void stage2_store(const AttnGeom& g, const f32x4s (&a
     if (tok >= g.N) return;
     if (ATTN_ABL(1) && acc[0][0] != 12345.678f) return;
     float* row = dst + (long)pix[tok] * row_stride + ch0;
-    const bool vec = ((g.hd | row_stride | ch0) & 3) == 0;
+    // 16-byte stores need a 16-byte aligned destination as well (a view that starts one float into a buffer: scalar stores)
+    const bool vec = ((g.hd | row_stride | ch0) & 3) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
 #pragma unroll
     for (int db = 0; db < NDB; ++db) {
         const int d0 = 16 * db + 4 * kq;
@@ -243,8 +244,8 @@ __device__ __forceinline__ void zero_lds(float* p, int n) {
 __device__ __forceinline__ void load_tile256(const AttnGeom& g, const float* src, int row_stride, int ch0, const int* pix, float* dst, float mul) {
     // head dims that are multiples of 4 (the Lu2022 models: 32): 16-byte global loads, one token-pixel computation per quad -- with
     // 4-byte loads a thread issued 8 dependent-address loads per tile (three integer divisions each), and the four tiles of the
-    // backward kernel cost more than its five GEMMs
-    if (((g.hd | row_stride | ch0) & 3) == 0) {
+    // backward kernel cost more than its five GEMMs.  (A source that is not 16-byte aligned itself takes the scalar loop below.)
+    if (((g.hd | row_stride | ch0) & 3) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
         typedef float f32x4 __attribute__((ext_vector_type(4)));
         const int qpt = g.hd >> 2, nq = g.N * qpt;
         for (int e = threadIdx.x; e < nq; e += 256) {
@@ -335,8 +336,10 @@ __device__ __forceinline__ void attn_item(int id, int windows, int heads, int& w
 // One tile (Q, K, V or dO of a (window, head) pair) travels global -> registers -> LDS in two steps, so that the loads of the NEXT work
 // item are in flight while the current one is multiplied (`fetch` right behind the barrier that publishes the current tiles, `stash`
 // at the top of the next item).  Vector form only: head dim and channel offsets multiples of 4 (every Lu2022 shape).
-// TILE_IT = ceil(tokens x hd / 4 / 256): quads per thread and tile (hd <= 16: 1, <= 32: 2, <= 48: 3, <= 64: 4) -- a template parameter, the
-// prefetch registers of a kernel are 3 or 4 tiles x TILE_IT x 4
+// TILE_IT = max(ceil(tokens x hd / 4 / 256), ceil(hd / 16)): quads per thread and tile, and at least the number of 16-channel blocks of
+// a head, which the second-stage products take from it (`attn_tile_it`; 64 tokens: both are ceil(hd / 16) -- hd <= 16: 1, <= 32: 2,
+// <= 48: 3, <= 64: 4; smaller windows need fewer quads than blocks, `ok` disarms the surplus) -- a template parameter, the prefetch
+// registers of a kernel are 3 or 4 tiles x TILE_IT x 4
 // The thread's quads of a tile: token, channel offset, LDS offset -- the same for every tile and every item, computed ONCE per kernel
 // (per tile and item they cost two integer divisions by a run-time value each, in `fetch` and again in `stash`: a fifth of the
 // backward kernel went into issuing its twelve loads).
@@ -390,12 +393,12 @@ __device__ __forceinline__ void tile_stash(const TileMap<TILE_IT>& m, const af4 
 template <bool PF, int TILE_IT>
 __global__ __launch_bounds__(256, 3) void win_attn_fwd_mfma_kernel(const float* qkv, const float* bias, AttnGeom g, float* out, float* probs,
                                                                 int no_pv, int windows, int nitems) {
-    constexpr int NDB = PF ? TILE_IT : 4;                     // 16-channel blocks of a head (TILE_IT = ceil(hd / 16) on the vector path)
+    constexpr int NDB = PF ? TILE_IT : 4;                     // 16-channel blocks of a head (TILE_IT >= ceil(hd / 16) on the vector path: `attn_tile_it`)
     extern __shared__ float lds[];
     float* V = lds;
     float* Q = V + 64 * g.hs;
     float* K = Q + 64 * g.hs;
-    float* S = Q;                                             // [64][65] over Q and K (2 x 64 x hs >= 64 x 65 for hs >= 33; else behind V)
+    float* S = Q;                                             // [64][65] over Q and K (2 x 64 x hs >= 64 x 65 for hs >= 33; narrower heads: the allocation runs on to 64 x 65 past K)
     __shared__ int pix[2][NMAX], reg[2][NMAX];               // token -> pixel (roll + window partition) and -> mask region, per item
     const int w = threadIdx.x >> 6, ti = w >> 1, tj = w & 1;
     const int lr = threadIdx.x & 31, ai = 32 * ti + lr, bj = 32 * tj + lr, hs = g.hs;
@@ -816,6 +819,14 @@ int make_geom(const rdo_attn_desc* d, AttnGeom* g, const char* who) {
 
 }  // namespace
 
+// TILE_IT of the vector-path kernels: the quads a thread moves per tile, and not fewer than the 16-channel blocks of a head -- the
+// kernels' NDB.  (ceil(N hd / 4 / 256) alone is ceil(hd / 16) only for 64 tokens: a 16-token window with hd = 32 got one block, and
+// channels 16..31 of `out` and `dqkv` were never computed or stored.)
+static int attn_tile_it(int N, int hd) {
+    const int quads = (int)rdo::ceil_div((long)N * (hd >> 2), 256), blocks = (hd + 15) / 16;
+    return quads > blocks ? quads : blocks;
+}
+
 // persistent grid of an attention kernel: as many workgroups as are RESIDENT at once -- registers count as well as LDS (the forward
 // kernels fit four times into a CU's LDS at hd = 48 but three times into its register file: a grid of 1024 ran as 768 + a second round
 // of 256 on a third of the chip) -- a multiple of 8 so that a workgroup's items stay on one XCD
@@ -845,7 +856,7 @@ int rdo_window_attention_fwd(const rdo_attn_desc* d, const float* qkv, const flo
     if (int rc = make_geom(d, &g, "rdo_window_attention_fwd")) return rc;
     RDO_REQUIRE(qkv && bias && (out || probs), "rdo_window_attention_fwd: null argument");
     const int windows = g.B * (g.H / g.ws) * (g.W / g.ws);
-    // V, then Q and K with the score matrix over them (or behind V where two narrow tiles are smaller than it)
+    // V, then Q and K with the score matrix over them (running on past K where two narrow tiles are smaller than it)
     const size_t qk = (size_t)2 * 64 * g.hs, sm = (size_t)64 * SS;
     const size_t lds = ((size_t)64 * g.hs + (qk > sm ? qk : sm)) * sizeof(float);
     const int no_pv = out == nullptr;
@@ -865,7 +876,7 @@ int rdo_window_attention_fwd(const rdo_attn_desc* d, const float* qkv, const flo
                 return rdo::check_launch("window_attention_fwd");
             };
             if (!pf) return go(win_attn_fwd_mfma_kernel<false, 1>, 0);
-            const int it = (int)rdo::ceil_div((long)g.N * (g.hd >> 2), 256);
+            const int it = attn_tile_it(g.N, g.hd);
             if (it <= 1) return go(win_attn_fwd_mfma_kernel<true, 1>, 1);
             if (it == 2) return go(win_attn_fwd_mfma_kernel<true, 2>, 2);
             if (it == 3) return go(win_attn_fwd_mfma_kernel<true, 3>, 3);
@@ -913,7 +924,7 @@ int rdo_window_attention_bwd(const rdo_attn_desc* d, const float* qkv, const flo
                 return rdo::check_launch("window_attention_bwd");
             };
             if (!pf) return go(win_attn_bwd_mfma_kernel<false, 1>, 0);
-            const int it = (int)rdo::ceil_div((long)g.N * (g.hd >> 2), 256);
+            const int it = attn_tile_it(g.N, g.hd);
             if (it <= 1) return go(win_attn_bwd_mfma_kernel<true, 1>, 1);
             if (it == 2) return go(win_attn_bwd_mfma_kernel<true, 2>, 2);
             if (it == 3) return go(win_attn_bwd_mfma_kernel<true, 3>, 3);

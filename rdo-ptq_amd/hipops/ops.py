@@ -761,10 +761,52 @@ def conv_transpose2d(x, w_iohw_rows, bias, stride, pad, output_padding, epilogue
     return conv2d_fwd_pack(xu, pack.get("zi", lambda: WeightPack(pack.w.flip(1, 2), pack.bias)), 1, 0, epilogue=epilogue)
 
 
-def layer_norm(x, weight, bias, eps=1e-5, out=None):
+def _row_tensor(what, name, t, ref=None, numel=None, shape=None, optional=False):
+    """Argument check of the LayerNorm / GELU / attention wrappers, made before any pointer is taken: `t` is a non-empty fp32 tensor (on
+    `ref`'s device), of `numel` elements or of `shape` when given.  The kernels index every operand by the first one's geometry, so
+    anything else is an out-of-bounds device access."""
+    if t is None and optional:
+        return
+    if not torch.is_tensor(t) or t.dtype != torch.float32:
+        raise ValueError(f"{what}: {name} must be an fp32 tensor, got {t.dtype if torch.is_tensor(t) else type(t).__name__}")
+    if t.numel() == 0:
+        raise ValueError(f"{what}: {name} is empty")
+    if ref is not None and t.device != ref.device:
+        raise ValueError(f"{what}: {name} is on {t.device}, the other operands on {ref.device}")
+    if numel is not None and t.numel() != numel:
+        raise ValueError(f"{what}: {name} holds {t.numel()} elements, expected {numel}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what}: {name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+
+
+def _ln_operands(what, x, weight, bias=None, same=(), slabs=None, max_c=None, vec=False):
+    """-> (rows, C, nslabs) of a LayerNorm call on x [..., C]: weight / bias [C] (or None), every tensor of `same` of x's shape (or None),
+    `slabs` [n >= 1, C]"""
+    _row_tensor(what, "x", x)
+    if x.dim() < 1:
+        raise ValueError(f"{what}: x must be [..., C], got a scalar")
     Cc = x.shape[-1]
+    if max_c is not None and Cc > max_c:
+        raise ValueError(f"{what}: C = {Cc} channels, at most {max_c} are supported")
+    if vec and Cc % 4:
+        raise ValueError(f"{what}: C = {Cc} must be a multiple of 4")
+    _row_tensor(what, "weight", weight, x, shape=(Cc,), optional=True)
+    _row_tensor(what, "bias", bias, x, shape=(Cc,), optional=True)
+    for name, t in same:
+        _row_tensor(what, name, t, x, shape=x.shape, optional=True)
+    ns = 0
+    if slabs is not None:
+        _row_tensor(what, "dgamma_slabs", slabs, x)
+        if slabs.dim() != 2 or slabs.shape[1] != Cc:
+            raise ValueError(f"{what}: dgamma_slabs must be [n >= 1, {Cc}], got {tuple(slabs.shape)}")
+        ns = slabs.shape[0]
+    return x.numel() // Cc, Cc, ns
+
+
+def layer_norm(x, weight, bias, eps=1e-5, out=None):
+    rows, Cc, _ = _ln_operands("layer_norm", x, weight, bias, same=(("out", out),))
     out = torch.empty_like(x) if out is None else out
-    L.check(L.lib().rdo_layer_norm(_ptr(x), _ptr(weight), _ptr(bias), x.numel() // Cc, Cc, eps, _ptr(out), _stream()),
+    L.check(L.lib().rdo_layer_norm(_ptr(x), _ptr(weight), _ptr(bias), rows, Cc, eps, _ptr(out), _stream()),
             "rdo_layer_norm")
     return out
 
@@ -807,24 +849,40 @@ def linear_h2(x, planes, bias=None, out=None, square_input=False, epilogue=L.EPI
 def add_layer_norm(a, b, weight, bias, eps=1e-5, sum_out=None, out=None):
     """s = a + b (b may be None) -> `sum_out` (written when given), LayerNorm(s) -> out: the residual add of a Swin block and the
     LayerNorm that reads it, in one pass."""
-    Cc = a.shape[-1]
+    rows, Cc, _ = _ln_operands("add_layer_norm", a, weight, bias, same=(("b", b), ("sum_out", sum_out), ("out", out)), max_c=512, vec=True)
+    if sum_out is not None and b is None:
+        raise ValueError("add_layer_norm: sum_out without a second addend b")
     out = torch.empty_like(a) if out is None else out
-    L.check(L.lib().rdo_add_layer_norm(_ptr(a), _ptr(b), _ptr(weight), _ptr(bias), a.numel() // Cc, Cc, eps, _ptr(sum_out), _ptr(out),
+    L.check(L.lib().rdo_add_layer_norm(_ptr(a), _ptr(b), _ptr(weight), _ptr(bias), rows, Cc, eps, _ptr(sum_out), _ptr(out),
                                        _stream()), "rdo_add_layer_norm")
     return out
 
 
 def layer_norm_bwd_add(x, weight, dy, add1=None, add2=None, eps=1e-5, dx=None, dgamma_slabs=None):
     """dx = (add1) (+ add2) + LayerNorm-backward(dy); dgamma partial sums as in `layer_norm_bwd`."""
-    Cc = x.shape[-1]
-    ns = 0 if dgamma_slabs is None else dgamma_slabs.shape[0]
-    L.check(L.lib().rdo_layer_norm_bwd_add(_ptr(x), _ptr(weight), _ptr(dy), _ptr(add1), _ptr(add2), x.numel() // Cc, Cc, eps, _ptr(dx),
+    what = "layer_norm_bwd_add"
+    _row_tensor(what, "dy", dy)
+    rows, Cc, ns = _ln_operands(what, x, weight, same=(("dy", dy), ("add1", add1), ("add2", add2), ("dx", dx)), slabs=dgamma_slabs,
+                                max_c=512, vec=True)
+    if add2 is not None and add1 is None:
+        raise ValueError(f"{what}: add2 without add1")
+    if add1 is not None and dx is None:
+        raise ValueError(f"{what}: an addend without dx")
+    if dx is None and dgamma_slabs is None:
+        raise ValueError(f"{what}: nothing to compute (neither dx nor dgamma_slabs)")
+    L.check(L.lib().rdo_layer_norm_bwd_add(_ptr(x), _ptr(weight), _ptr(dy), _ptr(add1), _ptr(add2), rows, Cc, eps, _ptr(dx),
                                            _ptr(dgamma_slabs), ns, _stream()), "rdo_layer_norm_bwd_add")
     return dx
 
 
 def add3(a, b, c, out=None):
     """(a + b) + c"""
+    _row_tensor("add3", "a", a)
+    for name, t in (("b", b), ("c", c)):
+        _row_tensor("add3", name, t, a, numel=a.numel())
+    _row_tensor("add3", "out", out, a, numel=a.numel(), optional=True)
+    if a.numel() % 4:
+        raise ValueError(f"add3: {a.numel()} elements, the count must be a multiple of 4")
     out = torch.empty_like(a) if out is None else out
     L.check(L.lib().rdo_add3(_ptr(a), _ptr(b), _ptr(c), a.numel(), _ptr(out), _stream()), "rdo_add3")
     return out
@@ -832,9 +890,12 @@ def add3(a, b, c, out=None):
 
 def layer_norm_bwd(x, weight, dy, eps=1e-5, dx=None, dgamma_slabs=None):
     """dx (returned) and, when `dgamma_slabs` [nslabs, C] is given, the partial sums of dy * xhat."""
-    Cc = x.shape[-1]
-    ns = 0 if dgamma_slabs is None else dgamma_slabs.shape[0]
-    L.check(L.lib().rdo_layer_norm_bwd(_ptr(x), _ptr(weight), _ptr(dy), x.numel() // Cc, Cc, eps, _ptr(dx), _ptr(dgamma_slabs), ns,
+    what = "layer_norm_bwd"
+    _row_tensor(what, "dy", dy)
+    rows, Cc, ns = _ln_operands(what, x, weight, same=(("dy", dy), ("dx", dx)), slabs=dgamma_slabs, max_c=512)
+    if dx is None and dgamma_slabs is None:
+        raise ValueError(f"{what}: nothing to compute (neither dx nor dgamma_slabs)")
+    L.check(L.lib().rdo_layer_norm_bwd(_ptr(x), _ptr(weight), _ptr(dy), rows, Cc, eps, _ptr(dx), _ptr(dgamma_slabs), ns,
                                        _stream()), "rdo_layer_norm_bwd")
     return dx
 
@@ -843,22 +904,62 @@ def attn_desc(B, H, W, Cc, heads, window, shift, scale=None):
     return L.AttnDesc(B, H, W, Cc, heads, window, shift, float((Cc // heads) ** -0.5 if scale is None else scale))
 
 
+def _attn_geometry(what, d):
+    """-> (pixels, N, windows) of a descriptor the attention kernels accept (make_geom of csrc/swin.hip), ValueError otherwise"""
+    if not isinstance(d, L.AttnDesc):
+        raise ValueError(f"{what}: expected an attn_desc, got {type(d).__name__}")
+    if min(d.B, d.H, d.W, d.C, d.heads, d.window) <= 0:
+        raise ValueError(f"{what}: bad geometry B={d.B} H={d.H} W={d.W} C={d.C} heads={d.heads} window={d.window}")
+    if d.C % d.heads:
+        raise ValueError(f"{what}: C={d.C} is not divisible by heads={d.heads}")
+    if d.H % d.window or d.W % d.window:
+        raise ValueError(f"{what}: {d.H}x{d.W} is not divisible by window {d.window}")
+    if d.window * d.window > 64:
+        raise ValueError(f"{what}: windows of more than 64 tokens are not supported (window={d.window})")
+    if d.C // d.heads > 64:
+        raise ValueError(f"{what}: head dims above 64 are not supported (C={d.C}, heads={d.heads})")
+    if not 0 <= d.shift < d.window:
+        raise ValueError(f"{what}: shift={d.shift} must be in [0, window={d.window})")
+    N = d.window * d.window
+    return d.B * d.H * d.W, N, d.B * (d.H // d.window) * (d.W // d.window)
+
+
 def window_attention(d, qkv, bias, out=None, probs=None, compute_out=True):
     """Fused (S)W-MSA core on [B, H, W, 3C] -> [B, H, W, C]; `probs` [windows, N, N, heads] is filled when given."""
-    if compute_out and out is None:
-        out = torch.empty((d.B, d.H, d.W, d.C), device=qkv.device, dtype=torch.float32)
+    what = "window_attention"
+    pixels, N, windows = _attn_geometry(what, d)
+    _row_tensor(what, "qkv", qkv, numel=pixels * 3 * d.C)
+    _row_tensor(what, "bias", bias, qkv, numel=d.heads * N * N)
+    _row_tensor(what, "probs", probs, qkv, numel=windows * N * N * d.heads, optional=True)
+    if not compute_out and probs is None:
+        raise ValueError(f"{what}: compute_out=False without probs leaves nothing to compute")
+    if compute_out:
+        _row_tensor(what, "out", out, qkv, numel=pixels * d.C, optional=True)
+        if out is None:
+            out = torch.empty((d.B, d.H, d.W, d.C), device=qkv.device, dtype=torch.float32)
     L.check(L.lib().rdo_window_attention_fwd(C.byref(d), _ptr(qkv), _ptr(bias), _ptr(out) if compute_out else None, _ptr(probs),
                                              _stream()), "rdo_window_attention_fwd")
     return out
 
 
 def window_attention_pv(d, qkv, probs, out=None):
+    what = "window_attention_pv"
+    pixels, N, windows = _attn_geometry(what, d)
+    _row_tensor(what, "qkv", qkv, numel=pixels * 3 * d.C)
+    _row_tensor(what, "probs", probs, qkv, numel=windows * N * N * d.heads)
+    _row_tensor(what, "out", out, qkv, numel=pixels * d.C, optional=True)
     out = torch.empty((d.B, d.H, d.W, d.C), device=qkv.device, dtype=torch.float32) if out is None else out
     L.check(L.lib().rdo_window_attention_pv(C.byref(d), _ptr(qkv), _ptr(probs), _ptr(out), _stream()), "rdo_window_attention_pv")
     return out
 
 
 def window_attention_bwd(d, qkv, bias, dout, dqkv=None):
+    what = "window_attention_bwd"
+    pixels, N, windows = _attn_geometry(what, d)
+    _row_tensor(what, "qkv", qkv, numel=pixels * 3 * d.C)
+    _row_tensor(what, "bias", bias, qkv, numel=d.heads * N * N)
+    _row_tensor(what, "dout", dout, qkv, numel=pixels * d.C)
+    _row_tensor(what, "dqkv", dqkv, qkv, numel=qkv.numel(), optional=True)
     dqkv = torch.empty_like(qkv) if dqkv is None else dqkv
     L.check(L.lib().rdo_window_attention_bwd(C.byref(d), _ptr(qkv), _ptr(bias), _ptr(dout), _ptr(dqkv), _stream()),
             "rdo_window_attention_bwd")
@@ -866,18 +967,25 @@ def window_attention_bwd(d, qkv, bias, dout, dqkv=None):
 
 
 def gelu(x, out=None):
+    _row_tensor("gelu", "x", x)
+    _row_tensor("gelu", "out", out, x, numel=x.numel(), optional=True)
     out = torch.empty_like(x) if out is None else out
     L.check(L.lib().rdo_gelu_fwd(_ptr(x), x.numel(), _ptr(out), _stream()), "rdo_gelu_fwd")
     return out
 
 
 def gelu_bwd(dy, x, dx=None):
+    _row_tensor("gelu_bwd", "x", x)
+    _row_tensor("gelu_bwd", "dy", dy, x, numel=x.numel())
+    _row_tensor("gelu_bwd", "dx", dx, x, numel=x.numel(), optional=True)
     dx = torch.empty_like(x) if dx is None else dx
     L.check(L.lib().rdo_gelu_bwd(_ptr(dy), _ptr(x), x.numel(), _ptr(dx), _stream()), "rdo_gelu_bwd")
     return dx
 
 
 def round_(x, out=None):
+    _row_tensor("round_", "x", x)
+    _row_tensor("round_", "out", out, x, numel=x.numel(), optional=True)
     out = torch.empty_like(x) if out is None else out
     L.check(L.lib().rdo_round(_ptr(x), x.numel(), _ptr(out), _stream()), "rdo_round")
     return out
