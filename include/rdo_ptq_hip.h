@@ -203,7 +203,7 @@ int rdo_adaround_step_batch_gather(const rdo_ada_step_item* items, int32_t n, in
                                    const rdo_sched_row* sched, const int32_t* iter_ptr, float* round_loss_out, int32_t* iter_shadow,
                                    const rdo_gather_desc* next, void* stream);
 /* The NEXT loss / tail launch issued (or recorded) on this thread -- rdo_lp2_loss_grad, rdo_lp_loss_grad, rdo_loss_act_bwd(_splitk),
- * rdo_loss_gdn_bwd, rdo_conv2d_fwd_h2_tail -- stores the iteration number it read to *publish (its first thread), then the binding is
+ * rdo_loss_gdn_bwd, rdo_gdn_fwd_bwd, rdo_conv2d_fwd_h2_tail -- stores the iteration number it read to *publish (its first thread), then the binding is
  * gone.  Returns 1 when an earlier binding was still pending (never consumed), else 0; publish = NULL only clears. */
 int rdo_iter_bind_publish(int32_t* publish);
 
@@ -510,7 +510,7 @@ int64_t rdo_neg_log2_channel_sums_workspace(int64_t outer, int32_t C, int64_t in
  * power of two; the engine takes it from a probe iteration so that max |x s| ~ 2^7; anything in [2^-2, 2^15] keeps fp32 accuracy, and
  * fp16 denormals are honoured by the MFMA).  A value with |x s| > 65504 cannot be stored: producers raise the sticky device flag read
  * by rdo_h2_overflow() -- the engine checks it after every run and fails loudly.
- * Producers: rdo_conv2d_fwd_h2 (epilogue), rdo_gather_qdrop_h2, rdo_loss_act_bwd, rdo_loss_gdn_bwd, rdo_gdn_bwd_dx_h2,
+ * Producers: rdo_conv2d_fwd_h2 (epilogue), rdo_gather_qdrop_h2, rdo_loss_act_bwd, rdo_loss_gdn_bwd, rdo_gdn_bwd_dx_h2, rdo_gdn_fwd_bwd,
  * rdo_pixel_shuffle_h2, rdo_pixel_unshuffle2, rdo_split_h2 (from an fp32 tensor); weights: rdo_adaround_step* (plane scale > 0),
  * rdo_split_h2_conv. */
 int rdo_h2_overflow(int reset);   /* 1: some producer met a value outside fp16 range since the last reset (synchronises); -1: error */
@@ -582,6 +582,8 @@ int rdo_loss_gdn_bwd(const float* x, const float* norm, const float* residual, c
                      float* grad_out, float* t, void* t_planes, float t_scale, float* loss_out, void* stream);
 int rdo_gdn_bwd_dx_h2(const float* g, const float* x, const float* norm, const float* acc, int64_t n, int32_t C, int32_t inverse,
                       float* dx, void* dx_planes, float dx_scale, void* stream);   /* rdo_gdn_bwd_dx with fp32 and / or H2 output */
+/* (The whole GDN / IGDN block of a unit in one launch -- these two entries and both rdo_linear_h2 GEMMs -- is rdo_gdn_fwd_bwd,
+ * declared in include/rdo_ptq_gdn.h.) */
 /* F.pixel_shuffle(x, 2) on NHWC: [B,H,W,4C] -> [B,2H,2W,C] as fp32 and / or H2 planes */
 int rdo_pixel_shuffle_h2(const float* x, int32_t B, int32_t H, int32_t W, int32_t C, float* out, void* out_planes, float out_scale,
                          void* stream);

@@ -14,6 +14,7 @@
 // which the loss partial sums are added.
 #include "rdo_common.h"
 #include "gather_body.h"
+#include "gdn_device.h"
 
 namespace {
 
@@ -29,14 +30,9 @@ inline unsigned loss_grid(long blocks) {
 }
 
 using rdo::grid_for;
-
-// (pub: rdo_iter_bind_publish -- the launch's first thread leaves the iteration number there for the AdaRound step of the same iteration)
-__device__ __forceinline__ void block_loss_add(float acc, float scale, float* loss_out, int it, int32_t* pub) {
-    if (pub && blockIdx.x == 0 && threadIdx.x == 0) *pub = it;
-    acc = rdo::block_sum(acc);
-    if (threadIdx.x == 0 && loss_out)
-        atomicAdd(loss_out + (long)it * RDO_LOG_SLOTS + (blockIdx.x & (RDO_LOG_SLOTS - 1)), acc * scale);
-}
+using rdo::gdn::block_loss_add;      // gdn_device.h: shared with gdn_fused.hip
+using rdo::gdn::loss_gdn_quad;
+using rdo::gdn::gdn_dx_quad;
 
 // fp32 values of the thread's 8 channels from planes: (h1 + h2) / s -- the sum is exact in fp32, the value is the original to 2^-24
 __device__ __forceinline__ void load_h2_oct(const H2In& pl, long M, int C, const Oct& o, f32x4& a, f32x4& b) {
@@ -155,23 +151,6 @@ __global__ __launch_bounds__(256) void loss_act_bwd_pix_kernel(const float* pre,
 }
 
 // ---- GDN / IGDN epilogue + loss + gradient + dL/dnorm ----------------------------------------------------------------------------------
-__device__ __forceinline__ float loss_gdn_quad(const f32x4& xv, const f32x4& nv, const f32x4& y, const f32x4* r, int inverse, float gs,
-                                               f32x4& o, f32x4& g, f32x4& tv) {
-    f32x4 rs;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        rs[k] = __frsqrt_rn(nv[k]);
-        o[k] = xv[k] * (inverse ? __fsqrt_rn(nv[k]) : rs[k]);       // the GDN / IGDN epilogue of the norm-pool conv
-    }
-    if (r) o += *r;
-    const f32x4 dd = o - y;
-    g = dd * gs;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)       // GDN: y = x n^-1/2 -> dy/dn = -1/2 x n^-3/2 ; IGDN: y = x n^1/2 -> dy/dn = 1/2 x n^-1/2
-        tv[k] = inverse ? (0.5f * g[k] * xv[k]) * rs[k] : (-0.5f * g[k] * xv[k]) * (rs[k] * rs[k] * rs[k]);
-    return (dd[0] * dd[0] + dd[1] * dd[1]) + (dd[2] * dd[2] + dd[3] * dd[3]);
-}
-
 __global__ __launch_bounds__(256) void loss_gdn_bwd_kernel(const float* x, const float* nrm, const float* res, const float* tgt,
                                                            const int32_t* idx_table, const int32_t* iter_ptr, int B, long per_image,
                                                            float inv_npix, float coef, int inverse, float* out, float* gout, float* tbuf,
@@ -234,16 +213,6 @@ __global__ __launch_bounds__(256) void loss_gdn_bwd_pix_kernel(const float* x, c
 }
 
 // ---- GDN backward: dx -------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ f32x4 gdn_dx_quad(const f32x4& gv, const f32x4& xv, const f32x4& nv, const f32x4& av, int inverse) {
-    f32x4 o;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const float f = inverse ? __fsqrt_rn(nv[k]) : __frsqrt_rn(nv[k]);
-        o[k] = gv[k] * f + 2.f * xv[k] * av[k];
-    }
-    return o;
-}
-
 __global__ __launch_bounds__(256) void gdn_bwd_dx_kernel(const float* g, const float* x, const float* nrm, const float* acc, long n4,
                                                          int inverse, float* dx) {
     for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < n4; q += (long)gridDim.x * blockDim.x) {

@@ -26,8 +26,13 @@
 #include <cstdlib>
 
 #include "rdo_common.h"
+#include "gdn_device.h"
 
 namespace {
+
+using rdo::gdn::amax_quad;          // the per-token scale and split: gdn_device.h, shared with gdn_fused.hip
+using rdo::gdn::token_scale;
+using rdo::gdn::split_quad_store;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -56,8 +61,6 @@ struct LinArgs {
     float* pre;            // epi 1: pre-activation [M][N]
     const float* aux;      // epi 2: the GELU's input [M][N]
 };
-
-__device__ __forceinline__ float pow2f(int e) { return __builtin_bit_cast(float, (unsigned)(e + 127) << 23); }
 
 // PART: K = 96 or N = 96 (half a panel / half a chunk) -- an instantiation of its own, the full shapes keep their register budget
 template <int EPI, bool PART = false>
@@ -121,27 +124,20 @@ __global__ __launch_bounds__(256, 3) void linear_h2_kernel(LinArgs a) {
             const int r = pass * 16 + row_in_pass;
             float amax = 0.f;
 #pragma unroll
-            for (int k = 0; k < 3; ++k)
-                amax = fmaxf(amax, fmaxf(fmaxf(fabsf(v[pass][k][0]), fabsf(v[pass][k][1])), fmaxf(fabsf(v[pass][k][2]), fabsf(v[pass][k][3]))));
+            for (int k = 0; k < 3; ++k) amax = fmaxf(amax, amax_quad(v[pass][k]));
             amax = fmaxf(amax, __shfl_xor(amax, 8, 16));
             amax = fmaxf(amax, __shfl_xor(amax, 4, 16));
             amax = fmaxf(amax, __shfl_xor(amax, 2, 16));
             amax = fmaxf(amax, __shfl_xor(amax, 1, 16));
             // scale 2^(7 - floor(log2 amax)): the token's largest value lands in [2^7, 2^8).  Zero / denormal / non-finite rows: scale 1
             // (zeros stay zeros; inf / NaN propagate through fp16 as they would through fp32)
-            const int e = (int)((__builtin_bit_cast(unsigned, amax) >> 23) & 0xFF) - 127;
-            const bool plain = e < -100 || e > 100;
-            const float s = plain ? 1.f : pow2f(7 - e);
-            if (l16 == 0) scl[(kb & 1) * BM + r] = plain ? 1.f : pow2f(e - 7);
+            float s, inv;
+            token_scale(amax, s, inv);
+            if (l16 == 0) scl[(kb & 1) * BM + r] = inv;
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 const int c4 = l16 + 16 * k;                              // float4 index inside the K block: slice c4 / 4, 8-byte piece c4 % 4
-                const f32x4 xs = v[pass][k] * s;
-                const f16x4 hi = __builtin_convertvector(xs, f16x4);
-                const f16x4 lo = __builtin_convertvector(xs - __builtin_convertvector(hi, f32x4), f16x4);
-                char* dst = smem + (c4 >> 2) * (BM * 32) + r * 32 + (c4 & 3) * 8;
-                *reinterpret_cast<f16x4*>(dst) = hi;
-                *reinterpret_cast<f16x4*>(dst + PLANE) = lo;
+                split_quad_store(v[pass][k], s, smem + (c4 >> 2) * (BM * 32) + r * 32 + (c4 & 3) * 8, PLANE);
             }
         }
     };
@@ -326,25 +322,18 @@ __global__ __launch_bounds__(512, 1) void linear_h2w_kernel(LinArgs a) {
             }
             float amax = 0.f;
 #pragma unroll
-            for (int k = 0; k < 3; ++k)
-                amax = fmaxf(amax, fmaxf(fmaxf(fabsf(v[pass][k][0]), fabsf(v[pass][k][1])), fmaxf(fabsf(v[pass][k][2]), fabsf(v[pass][k][3]))));
+            for (int k = 0; k < 3; ++k) amax = fmaxf(amax, amax_quad(v[pass][k]));
             amax = fmaxf(amax, __shfl_xor(amax, 8, 16));
             amax = fmaxf(amax, __shfl_xor(amax, 4, 16));
             amax = fmaxf(amax, __shfl_xor(amax, 2, 16));
             amax = fmaxf(amax, __shfl_xor(amax, 1, 16));
-            const int e = (int)((__builtin_bit_cast(unsigned, amax) >> 23) & 0xFF) - 127;
-            const bool plain = e < -100 || e > 100;
-            const float sc = plain ? 1.f : pow2f(7 - e);
-            if (l16 == 0) scl[(p & 3) * BM + r] = plain ? 1.f : pow2f(e - 7);
+            float sc, inv;
+            token_scale(amax, sc, inv);
+            if (l16 == 0) scl[(p & 3) * BM + r] = inv;
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 const int c4 = l16 + 16 * k;
-                const f32x4 xs = v[pass][k] * sc;
-                const f16x4 hi = __builtin_convertvector(xs, f16x4);
-                const f16x4 lo = __builtin_convertvector(xs - __builtin_convertvector(hi, f32x4), f16x4);
-                char* dst = buf + (c4 >> 2) * (BM * 32) + r * 32 + (c4 & 3) * 8;
-                *reinterpret_cast<f16x4*>(dst) = hi;
-                *reinterpret_cast<f16x4*>(dst + PLANE) = lo;
+                split_quad_store(v[pass][k], sc, buf + (c4 >> 2) * (BM * 32) + r * 32 + (c4 & 3) * 8, PLANE);
             }
         }
     };

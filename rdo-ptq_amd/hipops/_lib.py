@@ -174,6 +174,12 @@ _SIGS = {
     "rdo_plan_profile": (C.c_int, [P, C.POINTER(C.c_float), P]),
 }
 EXPORTS = tuple(_SIGS)
+# include/rdo_ptq_gdn.h: the GDN / IGDN block of a unit in one launch (EXPORTS is the table of include/rdo_ptq_hip.h, and closed)
+_SIGS_GDN = {
+    "rdo_gdn_fwd_bwd_supported": (C.c_int, [C.c_int64, C.c_int32]),
+    "rdo_gdn_fwd_bwd": (C.c_int, [P, P, P, C.c_float, P, P, P, P, P, C.c_int32, C.c_int64, C.c_int32, C.c_float, C.c_int32, P, P, P, P, P, C.c_float, P, P]),
+}
+EXPORTS_GDN = tuple(_SIGS_GDN)
 
 _lib = None
 
@@ -190,7 +196,7 @@ def lib():
         # "no ROCm-capable device is detected"
         import torch  # noqa: F401
         h = C.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGS.items():
+        for name, (res, args) in list(_SIGS.items()) + list(_SIGS_GDN.items()):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         _lib = h

@@ -1426,6 +1426,24 @@ def gdn_bwd_dx_h2(g, x, norm, acc, inverse, dx=None, dx_planes=None):
                                       _ptr(dx_planes), _oscale(dx_planes), _stream()), "rdo_gdn_bwd_dx_h2")
 
 
+def gdn_fwd_bwd_supported(rows, channels):
+    return bool(L.lib().rdo_gdn_fwd_bwd_supported(int(rows), int(channels)))
+
+
+def gdn_fwd_bwd(c, fwd_planes, bwd_planes, beta, residual, tgt_cache, idx_table, iter_ptr, coef, inverse, loss_log, t, grad_out=None, out=None,
+                dx=None, dx_planes=None):
+    """The GDN / IGDN block of a unit in one launch: linear_h2(square_input) + loss_gdn_bwd + linear_h2 (gamma'^T) + gdn_bwd_dx_h2, bit for
+    bit; `fwd_planes` / `bwd_planes` from split_h2_linear of gamma' and of its transpose (one scale)."""
+    if fwd_planes.scale != bwd_planes.scale:
+        raise ValueError("gdn_fwd_bwd: the planes of gamma' and of its transpose must share one scale")
+    B, per_image = c.shape[0], c[0].numel()
+    _bind_out(dx_planes)
+    L.check(L.lib().rdo_gdn_fwd_bwd(_ptr(c), _ptr(fwd_planes), _ptr(bwd_planes), float(fwd_planes.scale), _ptr(beta), _ptr(residual),
+                                    _ptr(tgt_cache), _ptr(idx_table), _ptr(iter_ptr), B, per_image, c.shape[-1], coef, int(inverse), _ptr(out),
+                                    _ptr(grad_out), _ptr(t), _ptr(dx), _ptr(dx_planes), _oscale(dx_planes), _ptr(loss_log), _stream()),
+            "rdo_gdn_fwd_bwd")
+
+
 def pixel_shuffle_h2(x, out=None, out_planes=None):
     """[B,H,W,4C] -> [B,2H,2W,C] (r = 2) as fp32 and / or planes."""
     B, H, W, CC = x.shape

@@ -297,6 +297,9 @@ class UnitEngine:
         # round 6: the NEXT iteration's mini-batch is assembled by the AdaRound-step launch (rdo_adaround_step_batch_gather) -- one launch
         # less per iteration, the gather's stream under the step's latency; iteration 0's mini-batch by a stand-alone gather (`_prime`)
         self.fold_gather = os.environ.get("RDO_GATHER_IN_STEP", "1") != "0"
+        # the GDN / IGDN block of an RBWS / RBU unit -- norm pool, loss tail, gamma'^T GEMM and dx -- in one launch (ops.gdn_fwd_bwd) where
+        # both GEMMs would run on rdo_linear_h2; 0: the four launches
+        self.gdn_fused = os.environ.get("RDO_GDN_FUSED", "1") != "0"
         self._next_gather = None
         # opt-in R + lambda*D task loss (loss_mode='rd'): dict(model=QuantModel, unit=module, cali=calibration images NCHW on the GPU,
         # lmbda=float, metric='mse' | 'ms-ssim' (optional, default 'mse')).  The unit output of every iteration is pushed through the
@@ -461,7 +464,7 @@ class UnitEngine:
             c1 = o["conv1"]
             Ho, Wo = self._out_hw(c1, H, W)
             C = c1.rows
-            for n_ in ("h1", "c2", "norm", "out", "dout", "t", "acc", "dc2", "dh1"):
+            for n_ in ("h1", "c2", "out", "dout", "t", "dc2", "dh1"):      # (norm, acc: `_tmp`, where the GDN block is not one launch)
                 t[n_] = self._buf(B, Ho, Wo, C)
             if "skip" in o:
                 t["sk"] = self._buf(B, Ho, Wo, C)
@@ -474,7 +477,7 @@ class UnitEngine:
             t["h1"] = self._buf(B, H * r, W * r, C)
             t["up"] = self._buf(B, H, W, C4)
             t["ups"] = self._buf(B, H * r, W * r, C)
-            for n_ in ("c", "norm", "out", "dout", "t", "acc", "dc", "dh1"):
+            for n_ in ("c", "out", "dout", "t", "dc", "dh1"):
                 t[n_] = self._buf(B, H * r, W * r, C)
             t["dsp"] = self._buf(B, H, W, C4)
             t["dup"] = self._buf(B, H, W, C4)
@@ -482,6 +485,16 @@ class UnitEngine:
         self.t = t
         for op in self.ops.values():
             op.slabs = None     # allocated at record time when the activation shapes are known
+
+    GDN_TMP = ("norm", "acc")
+
+    def _tmp(self, name, like):
+        """`norm` / `acc` of an RBWS / RBU unit: they only carry values from one launch of the GDN block to the next, so they are made
+        on first use -- by the probe iterations and by a plan that runs the block as separate launches -- and not at all by a plan
+        that runs it as one (`_fb_gdn_block`)"""
+        if name not in self.t:
+            self.t[name] = self._buf(*like.shape)
+        return self.t[name]
 
     def _slabs(self, op, x_shape):
         ns = ops.wgrad_nsplit(tuple(x_shape), op.w4, op.stride, op.pad)
@@ -917,11 +930,19 @@ class UnitEngine:
             if side is not None and not side_first:
                 self._conv(side, x.f32, t["sk"])
             res = x if side is None else t["sk"]
-        if self.fused:
-            self._gdn_pool(g, c, t["norm"])
+        # norm pool, tail, gamma'^T GEMM and dx in ONE launch where both GEMMs would run on rdo_linear_h2 (same bits; norm and acc do not
+        # exist).  dL/dout is written only where something reads it: the weight gradient of the side branch
+        one = (self.fused and self.gdn_fused and self._gdn_lin_ok(g, c) and tt.planes is None
+               and ops.gdn_fwd_bwd_supported(math.prod(c.shape[:-1]), c.shape[-1]))
+        if one:
+            self._task_is_rec = True
+            ops.gdn_fwd_bwd(c, g.lin_planes(True), g.lin_planes(False), g.beta, _f32(res), self.co, self.idx, self.it, 2.0, rbu, self.loss_log,
+                            tt.f32, grad_out=t["dout"] if (rbu or side is not None) else None, dx=dc.f32, dx_planes=dc.planes)
+        elif self.fused:
+            self._gdn_pool(g, c, self._tmp("norm", c))
             self._tail_gdn(c, t["norm"], res, rbu, t["dout"], tt)
         else:
-            self._conv(g, c, t["out"], epilogue=L.EPI_IGDN if rbu else L.EPI_GDN, aux=c, residual=res, pre=t["norm"], square=True)
+            self._conv(g, c, t["out"], epilogue=L.EPI_IGDN if rbu else L.EPI_GDN, aux=c, residual=res, pre=self._tmp("norm", c), square=True)
             self._loss(t["out"], t["dout"])
         if rbu:
             dup = self._act("dup")
@@ -931,11 +952,12 @@ class UnitEngine:
             self._wgrad(side, x.f32, t["dout"])
         if not self.fused:                                            # the fused tail has already written t
             ops.gdn_bwd_t(t["dout"], c, t["norm"], rbu, tt.f32)
-        self._gdn_acc(g, tt, t["acc"])                                # t . gamma'
-        if dc.planes is not None or c.numel() % 4 == 0:
-            ops.gdn_bwd_dx_h2(t["dout"], c, t["norm"], t["acc"], rbu, dx=dc.f32, dx_planes=dc.planes)   # 16-byte accesses
-        else:
-            ops.gdn_bwd_dx(t["dout"], c, t["norm"], t["acc"], rbu, dc.f32)
+        if not one:
+            self._gdn_acc(g, tt, self._tmp("acc", c))                 # t . gamma'
+            if dc.planes is not None or c.numel() % 4 == 0:
+                ops.gdn_bwd_dx_h2(t["dout"], c, t["norm"], t["acc"], rbu, dx=dc.f32, dx_planes=dc.planes)   # 16-byte accesses
+            else:
+                ops.gdn_bwd_dx(t["dout"], c, t["norm"], t["acc"], rbu, dc.f32)
         self._wgrad(g, c, tt.f32, square=True)                        # dgamma'[k][i] = sum_m t_k x_i^2
         self._wgrad(cv, h1, dc)
         dh1 = self._act("dh1")
@@ -988,6 +1010,9 @@ class UnitEngine:
         finally:
             self._set_weights(soft=True)
         self._clear_probe()
+        for n_ in self.GDN_TMP:                               # (the probe ran the GDN block as separate launches; the plan may not: `_tmp`)
+            if self.kind in ("rbws", "rbu"):
+                self.t.pop(n_, None)
         if self.world > 1:
             # every rank probes its own shard: agree on the magnitudes (MAX) so that all ranks record the same scales, take the same
             # "all-zero tensor" decision below and -- after an overflow, whose words are MAX-reduced too -- re-derive the same new scales
