@@ -180,6 +180,15 @@ _SIGS_GDN = {
     "rdo_gdn_fwd_bwd": (C.c_int, [P, P, P, C.c_float, P, P, P, P, P, C.c_int32, C.c_int64, C.c_int32, C.c_float, C.c_int32, P, P, P, P, P, C.c_float, P, P]),
 }
 EXPORTS_GDN = tuple(_SIGS_GDN)
+# include/rdo_ptq_bias.h: bias correction after calibration (tap sums of a layer input, the float64 bias shift)
+_SIGS_BIAS = {
+    "rdo_tap_sums": (C.c_int, [P] + [C.c_int32] * 10 + [P, P, P]),
+    "rdo_tap_sums_workspace": (C.c_int64, [C.c_int32, C.c_int32]),
+    "rdo_tap_sums_lane_pixels": (C.c_int64, [C.c_int32] * 11),
+    "rdo_bias_shift": (C.c_int, [P, P, P, P, C.c_double, P, C.c_int32, C.c_int32, P, P, P]),
+}
+EXPORTS_BIAS = tuple(_SIGS_BIAS)
+TAP_MAX_K = 7             # RDO_TAP_MAX_K of include/rdo_ptq_bias.h
 
 _lib = None
 
@@ -196,7 +205,7 @@ def lib():
         # "no ROCm-capable device is detected"
         import torch  # noqa: F401
         h = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(_SIGS.items()) + list(_SIGS_GDN.items()):
+        for name, (res, args) in list(_SIGS.items()) + list(_SIGS_GDN.items()) + list(_SIGS_BIAS.items()):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         _lib = h

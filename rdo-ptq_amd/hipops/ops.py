@@ -5,6 +5,7 @@ Conventions: every tensor is a contiguous fp32 CUDA tensor; activations are NHWC
 When a plan is being recorded (hipops.plan.Plan.record()), the same calls are captured instead of launched."""
 import ctypes as C
 import math
+import numbers
 import threading
 
 import torch
@@ -435,6 +436,133 @@ def pair_moments(a, b, out=None):
         ws = _PAIR_WS[(a.device, Cc)] = torch.empty(int(L.lib().rdo_pair_moments_workspace(Cc)), device=a.device, dtype=torch.float32)
     L.check(L.lib().rdo_pair_moments(_ptr(a), _ptr(b), a.numel() // Cc, Cc, _ptr(out), _ptr(ws), _stream()), "rdo_pair_moments")
     return out
+
+
+TAP_MAX_SEGMENTS = 48    # kTapMaxSegs of csrc/bias_correct.hip: index runs per axis the kernel arguments hold
+_TAP_WS = {}        # (device, C, k) -> workspace of tap_sums (launches are stream-ordered, so one buffer per key suffices)
+
+
+def tap_out_size(n, k, stride, pad, transposed=False, output_padding=0):
+    """Output size of one axis of `n` inputs: the conv's, or the transposed conv's with `output_padding`."""
+    if transposed:
+        return (n - 1) * stride - 2 * pad + k + output_padding
+    return (n + 2 * pad - k) // stride + 1
+
+
+def _whole(what, name, v, lo):
+    """an integer (Python's or numpy's; not a bool) >= lo, as an int"""
+    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < lo:
+        raise ValueError(f"{what}: {name} must be a whole number >= {lo}, got {v!r}")
+    return int(v)
+
+
+def tap_sums(x, k, stride, pad, out_hw, transposed=False, out=None):
+    """Tap sums of a layer input (rdo_tap_sums, include/rdo_ptq_bias.h): x channels-last [N, H, W, C] fp32 -> float32 [k * k, C], entry
+    (kh * k + kw, c) = the sum of x[:, h, w, c] over the pixels that tap (kh, kw) of a k x k convolution (stride, pad; `transposed`: of a
+    transposed convolution) with `out_hw` = (Ho, Wo) outputs reads.  For k = 1 (a Linear layer; stride 1, pad 0) x may be of any rank >=
+    2, every leading dimension counted as pixels, and out_hw may be None.  `out`: a contiguous fp32 [k * k, C] on x's device that is
+    ADDED TO; None makes a zero one.  One read of x in a fixed summation order: the same input gives the same bits.  Everything is
+    checked on the host before a pointer is taken."""
+    what = "tap_sums"
+    if not torch.is_tensor(x) or x.dtype != torch.float32:
+        raise ValueError(f"{what}: x must be an fp32 tensor, got {x.dtype if torch.is_tensor(x) else type(x).__name__}")
+    k = _whole(what, "k", k, 1)
+    if k > L.TAP_MAX_K:
+        raise ValueError(f"{what}: k = {k}, at most {L.TAP_MAX_K} is supported")
+    stride, pad = _whole(what, "stride", stride, 1), _whole(what, "pad", pad, 0)
+    if not isinstance(transposed, bool):
+        raise ValueError(f"{what}: transposed must be True or False, got {transposed!r}")
+    if x.dim() != 4 and not (k == 1 and x.dim() >= 2):
+        raise ValueError(f"{what}: x must be channels-last of rank 4 [N, H, W, C] (any rank >= 2 for k = 1), got rank {x.dim()}")
+    if x.numel() == 0:
+        raise ValueError(f"{what}: x is empty: {tuple(x.shape)}")
+    if not x.is_contiguous():
+        raise ValueError(f"{what}: x must be contiguous")
+    Cc = int(x.shape[-1])
+    if x.dim() == 4:
+        N, H, W = (int(v) for v in x.shape[:3])
+    else:
+        N, H, W = 1, 1, x.numel() // Cc
+    if x.dim() != 4 or (k == 1 and out_hw is None):
+        if stride != 1 or pad != 0 or transposed:
+            raise ValueError(f"{what}: a token tensor takes k = 1, stride 1, pad 0, not transposed")
+        if x.dim() != 4 and out_hw is not None:
+            raise ValueError(f"{what}: out_hw must be None for a token tensor of rank {x.dim()}")
+        out_hw = (H, W)
+    if (not isinstance(out_hw, (tuple, list)) or len(out_hw) != 2
+            or any(isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < 1 for v in out_hw)):
+        raise ValueError(f"{what}: out_hw must be a pair of positive whole numbers (Ho, Wo), got {out_hw!r}")
+    for name, n_in, n_out in (("Ho", H, int(out_hw[0])), ("Wo", W, int(out_hw[1]))):
+        if transposed:
+            lo = (n_in - 1) * stride - 2 * pad + k
+            if not lo <= n_out < lo + stride:
+                raise ValueError(f"{what}: geometry: a transposed conv of {n_in} inputs (k {k}, stride {stride}, pad {pad}) gives {lo} .. "
+                                 f"{lo + stride - 1} outputs, {name} = {n_out}")
+        elif n_in + 2 * pad - k < 0 or n_out != (n_in + 2 * pad - k) // stride + 1:
+            raise ValueError(f"{what}: geometry: a conv of {n_in} inputs (k {k}, stride {stride}, pad {pad}) does not give {name} = {n_out}")
+    if N * H * W > 0x7fffffff:
+        raise ValueError(f"{what}: geometry: {N * H * W} pixels are beyond 32-bit pixel indices")
+    if max(k * k, 4 * k + 4) * Cc > 0x7fffffff:
+        raise ValueError(f"{what}: geometry: {Cc} channels are too many for 32-bit entry indices")
+    if transposed and 2 * (-(-pad // stride)) > TAP_MAX_SEGMENTS:
+        # (a conv has at most 2 (k - 1) border indices, and no axis more than 4 k + 4 distinct tap masks: only this one can happen)
+        raise ValueError(f"{what}: geometry: pad {pad} at stride {stride} leaves more than {TAP_MAX_SEGMENTS} border indices on an axis")
+    if out is not None and (not torch.is_tensor(out) or tuple(out.shape) != (k * k, Cc) or out.dtype != torch.float32
+                            or out.device != x.device or not out.is_contiguous()):
+        raise ValueError(f"{what}: out must be a contiguous fp32 [{k * k}, {Cc}] on {x.device}, got "
+                         f"{(out.dtype, tuple(out.shape), out.device) if torch.is_tensor(out) else type(out).__name__}")
+    if not x.is_cuda:
+        raise ValueError(f"{what}: x is on {x.device}; there is no CPU path")
+    if out is None:
+        out = torch.zeros(k * k, Cc, device=x.device, dtype=torch.float32)
+    ws = _TAP_WS.get((x.device, Cc, k))
+    if ws is None:
+        ws = _TAP_WS[(x.device, Cc, k)] = torch.empty(int(L.lib().rdo_tap_sums_workspace(Cc, k)), device=x.device, dtype=torch.float32)
+    L.check(L.lib().rdo_tap_sums(_ptr(x), N, H, W, Cc, k, stride, pad, int(out_hw[0]), int(out_hw[1]), int(transposed), _ptr(out),
+                                 _ptr(ws), _stream()), "rdo_tap_sums")
+    return out
+
+
+def bias_shift(w_ref, w_q, s_ref, s_q, n, org_bias, shift=None, bias_out=None):
+    """The bias shift of one layer from float64 tap sums (rdo_bias_shift): w_ref, w_q contiguous fp32 [O, ...] rows in the `to_rows`
+    order, K = their row length; s_ref, s_q float64 of K elements (`tap_sums` results added up in float64, flattened [kh][kw][c]); n =
+    the number of output pixels; org_bias fp32 [O].  -> (shift float64 [O] = (w_ref . s_ref - w_q . s_q) / n, both products and the
+    difference in float64, and bias_out fp32 [O] = float32(org_bias + shift)).  Everything is checked on the host before a pointer is
+    taken."""
+    what = "bias_shift"
+    for name, t, dt in (("w_ref", w_ref, torch.float32), ("w_q", w_q, torch.float32), ("org_bias", org_bias, torch.float32),
+                        ("s_ref", s_ref, torch.float64), ("s_q", s_q, torch.float64)):
+        if not torch.is_tensor(t) or t.dtype != dt:
+            raise ValueError(f"{what}: {name} must be a {str(dt).split('.')[-1]} tensor, got {t.dtype if torch.is_tensor(t) else type(t).__name__}")
+        if t.numel() == 0:
+            raise ValueError(f"{what}: {name} is empty")
+        if not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be contiguous")
+        if t.device != w_ref.device:
+            raise ValueError(f"{what}: {name} is on {t.device}, w_ref on {w_ref.device}")
+    if w_ref.dim() < 2 or w_q.shape != w_ref.shape:
+        raise ValueError(f"{what}: w_ref {tuple(w_ref.shape)} and w_q {tuple(w_q.shape)} must be the same rows [O, ...] of rank >= 2")
+    O = int(w_ref.shape[0])
+    K = w_ref.numel() // O
+    for name, t in (("s_ref", s_ref), ("s_q", s_q)):
+        if t.numel() != K:
+            raise ValueError(f"{what}: {name} holds {t.numel()} elements, the weight rows {K}")
+    if tuple(org_bias.shape) != (O,):
+        raise ValueError(f"{what}: org_bias has shape {tuple(org_bias.shape)}, expected ({O},)")
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError(f"{what}: n must be a positive whole number of output pixels, got {n!r}")
+    for name, t, dt in (("shift", shift, torch.float64), ("bias_out", bias_out, torch.float32)):
+        if t is not None and (not torch.is_tensor(t) or tuple(t.shape) != (O,) or t.dtype != dt or t.device != w_ref.device
+                              or not t.is_contiguous()):
+            raise ValueError(f"{what}: {name} must be a contiguous {str(dt).split('.')[-1]} [{O}] on {w_ref.device}")
+    if not w_ref.is_cuda:
+        raise ValueError(f"{what}: the operands are on {w_ref.device}; there is no CPU path")
+    shift = torch.empty(O, device=w_ref.device, dtype=torch.float64) if shift is None else shift
+    bias_out = torch.empty(O, device=w_ref.device, dtype=torch.float32) if bias_out is None else bias_out
+    dptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731  (float64 operands: _ptr admits fp32 / int only)
+    L.check(L.lib().rdo_bias_shift(_ptr(w_ref), _ptr(w_q), dptr(s_ref), dptr(s_q), 1.0 / n, _ptr(org_bias), O, K, dptr(shift),
+                                   _ptr(bias_out), _stream()), "rdo_bias_shift")
+    return shift, bias_out
 
 
 def actquant_static_bwd(x, g, rng, drange, dx=None, n_bits=8, ws=None):

@@ -46,6 +46,14 @@ def reduce_act_stats(ranges=(), sums=(), group=None):
         dist.all_reduce(e, op=dist.ReduceOp.SUM, group=group)
 
 
+def reduce_max(t, group=None):
+    """In place: the element-wise MAX of `t` over the ranks (every rank the same shape and dtype); without a process group nothing
+    happens."""
+    if world(group)[1] > 1:
+        dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
+    return t
+
+
 def reduce_act_grads(flat, group=None):
     """Learned activation ranges under data parallelism: the concatenated range gradients of a unit's sites (every rank in the same
     order) become their mean over the ranks, in place: SUM all-reduce, then the division by the world size."""

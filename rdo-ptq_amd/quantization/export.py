@@ -13,7 +13,8 @@ from .quantizer import AdaRoundQuantizer
 
 
 def integer_state(qnn) -> "OrderedDict[str, dict]":
-    """name -> {levels (uint8, or int32 above 8 bits; logical weight shape), delta, zero_point, n_bits, bias, kind}."""
+    """name -> {levels (uint8, or int32 above 8 bits; logical weight shape), delta, zero_point, n_bits, bias, kind}.  `bias` is the one
+    the quantised forward uses (`m.bias`): `org_bias` unless a bias correction moved it (`recon.correct_unit_bias`)."""
     out = OrderedDict()
     for name, m in qnn.named_modules():
         if not isinstance(m, QuantModule) or m.org_weight is None:
@@ -30,7 +31,7 @@ def integer_state(qnn) -> "OrderedDict[str, dict]":
             x_int = torch.round(w / d)
         levels = torch.clamp(x_int + z, 0, q.n_levels - 1)
         out[name] = {"levels": levels.to(torch.uint8 if q.n_bits <= 8 else torch.int32).cpu(), "delta": d.detach().cpu(), "zero_point": z.detach().cpu(),
-                     "n_bits": q.n_bits, "bias": None if m.org_bias is None else m.org_bias.detach().cpu(), "kind": m.kind}
+                     "n_bits": q.n_bits, "bias": None if m.bias is None else m.bias.detach().cpu(), "kind": m.kind}
     return out
 
 
@@ -110,6 +111,52 @@ def unit_report(qnn) -> "OrderedDict[str, dict]":
         row["channels"] = int(row["err"]["learned"].numel())
         row["gain_db"] = row["sqnr_db"]["learned"] - row["sqnr_db"]["nearest"]
         row["total"]["gain_db"] = row["total"]["sqnr_db"]["learned"] - row["total"]["sqnr_db"]["nearest"]
+        out[str(st["name"])] = row
+    return out
+
+
+BIAS_REPORT_STATES = ("before", "after")
+
+
+def bias_report(qnn) -> "OrderedDict[str, dict]":
+    """unit name -> what the bias correction of every unit that ran it did (args.bias_correct; `recon.correct_unit_bias`), in module
+    order, on the CPU.  With d = full-precision output - quantised output of the unit on its cached calibration inputs (the unit's own
+    activation quantisers off), per output channel, 'before' the first and 'after' the last layer was corrected:
+      mode, channels, n              'weight' | 'output'; channel count; output pixels per channel (all ranks)
+      err, shift, energy [state]     float64 [C]: sum d^2, sum d, sum of the squared full-precision output
+      shift_share [state]            float64 [C]: shift^2 / (n err), 0 where err == 0 (as in `unit_report`)
+      removed                        float64 [C]: err['before'] - err['after'], the squared error the correction took out
+      layers                         layer name -> {shift (float64 [O]: bias - org_bias before the fp32 rounding), n (the layer's output
+                                     pixels), kind, max_abs}, in the order the layers were corrected
+      skipped                        layer name -> why it was left alone (GDN, LayerNorm, no bias, weight quantisation off)
+      total                          {err, shift, energy, shift_share [state], removed}: the same over the summed channels (Python floats)
+    Empty for a model without recorded statistics."""
+    out = OrderedDict()
+    for _, m in qnn.named_modules():
+        st = getattr(m, "bias_stats", None)
+        if not st:
+            continue
+        n = int(st["n"])
+        row = {"mode": str(st["mode"]), "n": n, "total": {}}
+        for f in ("err", "shift", "energy", "shift_share"):
+            row[f], row["total"][f] = {}, {}
+        for state in BIAS_REPORT_STATES:
+            shift, err, energy = (st[state][f].detach().to("cpu", torch.float64).clone() for f in ("shift", "err", "energy"))
+            row["err"][state], row["shift"][state], row["energy"][state] = err, shift, energy
+            row["shift_share"][state] = torch.where(err == 0, torch.zeros_like(err), shift * shift / (max(n, 1) * err))
+            row["total"]["err"][state], row["total"]["shift"][state] = float(err.sum()), float(shift.sum())
+            row["total"]["energy"][state] = float(energy.sum())
+            e = float(err.sum())
+            row["total"]["shift_share"][state] = 0.0 if e == 0 else float((shift * shift).sum()) / (max(n, 1) * e)
+        row["channels"] = int(row["err"]["after"].numel())
+        row["removed"] = row["err"]["before"] - row["err"]["after"]
+        row["total"]["removed"] = row["total"]["err"]["before"] - row["total"]["err"]["after"]
+        row["layers"] = OrderedDict()
+        for name, e in st["layers"].items():
+            shift = e["shift"].detach().to("cpu", torch.float64).clone()
+            row["layers"][str(name)] = {"shift": shift, "n": int(e["n"]), "kind": str(e["kind"]),
+                                        "max_abs": float(shift.abs().max()) if shift.numel() else 0.0}
+        row["skipped"] = OrderedDict((str(k), str(v)) for k, v in st["skipped"].items())
         out[str(st["name"])] = row
     return out
 

@@ -87,6 +87,23 @@ class QuantModel(nn.Module):
         from .export import unit_report
         return unit_report(self)
 
+    def bias_report(self):
+        """OrderedDict unit name -> what the bias correction of every unit that ran it did (args.bias_correct): the corrected layers'
+        shifts and the unit's output error before and after (`export.bias_report`)."""
+        from .export import bias_report
+        return bias_report(self)
+
+    def clear_bias_correction(self):
+        """Undo every bias correction: `org_bias` goes back into the bias of each corrected layer (bit for bit), the weight packs made
+        from the corrected biases are dropped, `bias_shift` and the units' `bias_stats` are removed."""
+        for m in self.modules():
+            if isinstance(m, QuantModule) and "bias_shift" in m.__dict__:
+                m.bias.data.copy_(m.org_bias)
+                m.drop_weight_pack()
+                del m.bias_shift
+            if "bias_stats" in m.__dict__:
+                del m.bias_stats
+
     def units(self):
         """OrderedDict name -> reconstruction unit, in the order the calibration visits them (recon_model of the reference's
         main2.py:227-253): every child that is a QuantModule or a BaseQuantBlock is a unit under its dotted name, anything else is

@@ -4,6 +4,7 @@ The choreography around the hot loop is the reference's; the loop itself runs on
 import logging
 import time
 import zlib
+from collections import OrderedDict
 
 import torch
 
@@ -12,11 +13,12 @@ from hipops import ops
 from .engine import UnitEngine
 from .quant_block import BaseQuantBlock, QuantRSTB
 from .swin_engine import TapeEngine
-from .quant_layer import QuantModule, _nhwc
-from .quantizer import AdaRoundQuantizer
+from .quant_layer import QuantModule, _nhwc, _sq
+from .quantizer import AdaRoundQuantizer, to_rows
 from .utils import LinearTempDecay, save_inp_oup_data, set_mode
 
 _COOPS = ("g_a", "h_a", "h_s", "g_s")
+BIAS_CORRECT_MODES = ("weight", "output")
 
 
 def find_unquantized_module(model, _name_="g_a", module_list=None, name_list=None):
@@ -147,8 +149,10 @@ def _act_args(args):
     'percentile' and 'hist_mse' would freeze are then SCORED on the same inputs, `ops.actquant_score`, and each channel takes the one of
     least measured squared error); args.act_report (default False; a bool): after freezing, one more pass records every site's measured
     error, energy and clipped counts (`export.activation_report`); args.unit_report (default False; a bool): a trained unit then measures
-    its own output error on its cached inputs, learned rounding against round-to-nearest (`report_unit`, `export.unit_report`).  Checked
-    before any work is done."""
+    its own output error on its cached inputs, learned rounding against round-to-nearest (`report_unit`, `export.unit_report`);
+    args.bias_correct (default off; 'weight' or 'output'): a trained unit then corrects the biases of its conv, transposed-conv and
+    Linear layers by the mean error of their pre-activations on the calibration set (`correct_unit_bias`, `export.bias_report`).
+    Checked before any work is done."""
     mode = getattr(args, "act_mode", "dynamic") if args is not None else "dynamic"
     how = getattr(args, "act_range", "max") if args is not None else "max"
     if mode not in ("dynamic", "static"):
@@ -159,6 +163,7 @@ def _act_args(args):
     _act_percentile_args(args)
     _act_report_args(args)
     _unit_report_args(args)
+    _bias_correct_args(args)
     return mode, how
 
 
@@ -176,6 +181,17 @@ def _unit_report_args(args):
     if not isinstance(report, bool):
         raise ValueError(f"unit_report must be True or False, got {report!r}")
     return report
+
+
+def _bias_correct_args(args):
+    """args.bias_correct, validated -> None (off: absent, None or False, the default), 'weight' or 'output'.  True is refused like every
+    other value: the mode must be named."""
+    mode = getattr(args, "bias_correct", None) if args is not None else None
+    if mode is None or mode is False:
+        return None
+    if not isinstance(mode, str) or mode not in BIAS_CORRECT_MODES:
+        raise ValueError(f"bias_correct must be 'weight', 'output' or off (None / False), got {mode!r}")
+    return mode
 
 
 def _act_learn_args(args):
@@ -376,6 +392,208 @@ def report_unit(unit, unit_name, inp_q, out_fp, batch=32):
     return unit.unit_stats
 
 
+def _tap_layer(m):
+    """-> (k, stride, pad, output_padding, transposed) of the conv, transposed-conv or Linear QuantModule `m`; what the forward refuses
+    (dilated / grouped convolutions) is refused here, and a kernel that is not square"""
+    if m.kind == "linear":
+        return 1, 1, 0, 0, False
+    kw = m.fwd_kwargs
+    if m.kind == "conv":
+        stride, pad = m.conv_geometry()
+        op = 0
+    else:
+        if _sq(kw["dilation"]) != 1 or kw["groups"] != 1:
+            raise NotImplementedError("dilated / grouped transposed convolutions are not on the supported path")
+        stride, pad, op = _sq(kw["stride"]), _sq(kw["padding"]), _sq(kw["output_padding"])
+    kh, kwid = int(m.org_weight.shape[2]), int(m.org_weight.shape[3])
+    if kh != kwid:
+        raise NotImplementedError(f"bias correction: a {kh} x {kwid} kernel is not square")
+    return kh, stride, pad, op, m.kind == "tconv"
+
+
+def _tap_call(m, x):
+    """-> (channels-last input, k, stride, pad, (Ho, Wo) or None, transposed, output pixels) of one call of `m` on the input `x`"""
+    k, stride, pad, op, tr = _tap_layer(m)
+    if m.kind == "linear":
+        t = x.contiguous()
+        return t, 1, 1, 0, None, False, t.numel() // t.shape[-1]
+    t = _nhwc(x)
+    hw = (ops.tap_out_size(t.shape[1], k, stride, pad, tr, op), ops.tap_out_size(t.shape[2], k, stride, pad, tr, op))
+    return t, k, stride, pad, hw, tr, t.shape[0] * hw[0] * hw[1]
+
+
+class _TapCollector:
+    """Forward pre-hooks on QuantModules that add up the tap sums of what each is fed: per module a float64 [k * k * Cin] device tensor
+    (the fp32 sums of a call, `ops.tap_sums`, are added into it in float64 on the device), the output pixels seen, and the order of
+    the first calls."""
+
+    def __init__(self, mods, device, order_only=False):
+        """order_only: the hooks note the order of the first calls and take no sums"""
+        self.sums, self.n, self.order, self.device, self.order_only = {}, {}, [], device, order_only
+        self.handles = [m.register_forward_pre_hook(self._hook) for m in mods]
+
+    def _hook(self, m, args):
+        if self.order_only:
+            if m not in self.order:
+                self.order.append(m)
+            return
+        t, k, stride, pad, hw, tr, n = _tap_call(m, args[0].detach())
+        s32 = ops.tap_sums(t, k, stride, pad, hw, transposed=tr)
+        if m not in self.sums:
+            self.order.append(m)
+            self.sums[m] = torch.zeros(s32.numel(), dtype=torch.float64, device=s32.device)
+            self.n[m] = 0
+        self.sums[m] += s32.reshape(-1).double()
+        self.n[m] += int(n)
+
+    def get(self, m):
+        """(float64 sums, pixels) of `m`; zeros for a module no call reached (a rank without rows still joins the collectives)"""
+        if m not in self.sums:
+            k = 1 if m.kind == "linear" else int(m.org_weight.shape[2])
+            cin = m.org_weight.shape[1] if m.kind != "tconv" else m.org_weight.shape[0]
+            return torch.zeros(k * k * int(cin), dtype=torch.float64, device=self.device), 0
+        return self.sums[m], self.n[m]
+
+    def close(self):
+        for h in self.handles:
+            h.remove()
+        self.handles = []
+
+
+def _bias_rows(m, quantised):
+    """the effective weight of `m` in one quant state as contiguous fp32 rows [O, k * k * Cin] in the `to_rows` order"""
+    held = m.use_weight_quant
+    try:
+        m.use_weight_quant = bool(quantised)
+        w = m._weights()[0].detach()
+    finally:
+        m.use_weight_quant = held
+    rows = w if m.kind == "linear" else to_rows(w, tconv=m.kind == "tconv")
+    return rows.reshape(rows.shape[0], -1).contiguous().float()
+
+
+def correct_unit_bias(unit, unit_name, inp_q, inp_fp, out_fp, mode="weight", batch=32):
+    """Empirical bias correction of a trained unit (Nagel et al. 2019): every conv, transposed-conv and Linear QuantModule of the unit
+    that has a bias and weight quantisation on gets
+        bias = float32(org_bias + (W_fp . S_ref - W_q . S_q) / n)
+    with S = the tap sums of the layer's INPUT over the calibration set (`ops.tap_sums`: the sum over all n output pixels of the
+    pre-activation of a weight W on that input is n b + W . S, exactly, so the pre-activation itself, which the fused kernels never
+    write, is not needed), W_fp / W_q the full-precision / the hard-rounded weight in the `to_rows` order, and both products and their
+    difference in float64 (`ops.bias_shift`).  S_q is taken on what the layer is fed in the quantised unit on `inp_q`; S_ref is
+      mode 'weight':  S_q -- the mean error of the layer's own rounding is removed;
+      mode 'output':  what the layer is fed in the full-precision unit on `inp_fp` -- the mean pre-activation becomes that of the target
+                      the calibration reconstructed against.
+    The bias is absolute from `org_bias`: correcting twice gives the same bits.  The layers are corrected one after the other in the
+    order of their first call in the forward, each from a pass of its own over `inp_q`, so that a layer sees its corrected
+    predecessors.  All passes run without a tape, batch for batch, the quantised ones with weight quantisation on and the unit's own
+    activation quantisers OFF (in both activation modes: a static quantiser that is not frozen yet cannot run), the full-precision one
+    in the (False, False) state; every flag is put back.  Before the first and after the last layer pass the unit output is compared
+    with `out_fp` (`ops.pair_moments`).  GDN, LayerNorm and bias-less layers are left alone and listed with the reason.  Under data
+    parallelism the tap sums, the pixel counts and the moments are summed over the ranks in the fixed layer order, so every rank
+    writes the same biases.  Left behind: `m.bias_shift` (float64 [O], CPU) on every corrected layer and `unit.bias_stats`
+    (`export.bias_report` reads it); `org_bias`, alpha, delta, zero points and ranges are not written."""
+    if mode not in BIAS_CORRECT_MODES:
+        raise ValueError(f"bias_correct must be 'weight' or 'output', got {mode!r}")
+    rstb = isinstance(unit, QuantRSTB)
+    names = {m: (n or "layer") for n, m in unit.named_modules() if isinstance(m, QuantModule)}
+    mods = [m for m in unit.modules() if isinstance(m, (QuantModule, BaseQuantBlock))]
+    states = [(m, m.use_weight_quant, m.use_act_quant) for m in mods]
+    skipped, layers = OrderedDict(), []
+    for m, name in names.items():
+        if m.org_weight is None:
+            continue                                     # (a PixelShuffle wrapper: nothing to correct, nothing to report)
+        if m.kind in ("gdn", "layernorm"):
+            skipped[name] = f"{m.kind}: its output mean is not linear in the mean of its input"
+        elif m.bias is None or m.org_bias is None:
+            skipped[name] = "no bias"
+        elif not m.use_weight_quant:
+            skipped[name] = "weight quantisation off"
+        else:
+            _tap_layer(m)                     # (raises for a geometry off the supported path, before any pass)
+            layers.append(m)
+    device = out_fp.device
+    world_size = dp.world()[1]
+
+    def run(x, moments=False):
+        # (zero sums, not None: a rank with no rows still takes part in the collectives below)
+        acc, n = torch.zeros(3, out_fp.shape[1], dtype=torch.float64, device=device), 0
+        with torch.no_grad():
+            for i in range(0, x.shape[0], batch):
+                h = x[i:i + batch]
+                out = unit(h, (h.shape[2], h.shape[3])) if rstb else unit(h)
+                if moments:
+                    ref = _nhwc(out_fp[i:i + batch])
+                    acc = acc + ops.pair_moments(ref, _nhwc(out)).double()
+                    n += ref.numel() // ref.shape[-1]
+        return acc, n
+
+    def set_state(w, a_):
+        for m in mods:
+            m.use_weight_quant, m.use_act_quant = w, a_
+
+    ref_sums = {}
+    try:
+        # the full-precision pass ('output'), or a first quantised pass ('weight'), also fixes the order of the layers' first calls
+        col = _TapCollector(layers, device, order_only=mode != "output")
+        try:
+            set_state(mode != "output", False)
+            if mode == "output":
+                run(inp_fp)                   # every S_ref in one pass
+                col.close()
+                set_state(True, False)
+            before, n_out = run(inp_q, moments=True)
+        finally:
+            col.close()
+        order = list(col.order) + [m for m in layers if m not in col.order]         # (no rows here: module order)
+        if world_size > 1:
+            # ranks with rows all saw the same order; a rank without rows takes theirs (MAX over the ranks of each layer's position)
+            pos = torch.full((max(1, len(layers)),), -1, dtype=torch.int32, device=device)
+            for i, m in enumerate(col.order):
+                pos[layers.index(m)] = i
+            dp.reduce_max(pos)
+            got = pos[:len(layers)].tolist()
+            if all(v >= 0 for v in got):
+                order = [m for _, m in sorted(zip(got, layers), key=lambda t: t[0])]
+        if mode == "output":
+            for m in order:
+                ref_sums[m] = col.get(m)[0]
+            if world_size > 1 and order:
+                dp.reduce_act_stats(sums=[ref_sums[m] for m in order])
+        shifts = OrderedDict()
+        for m in order:
+            one = _TapCollector([m], device)
+            try:
+                run(inp_q)
+            finally:
+                one.close()
+            s_q, n = one.get(m)
+            if world_size > 1:
+                count = torch.tensor([n], dtype=torch.int64, device=device)
+                dp.reduce_act_stats(sums=[s_q, count])
+                n = int(count.item())
+            if n < 1:
+                raise ValueError(f"correct_unit_bias: {unit_name}: no calibration rows reached {names[m]}")
+            w_q = _bias_rows(m, True)
+            w_ref = _bias_rows(m, False)
+            shift, bias = ops.bias_shift(w_ref, w_q, ref_sums[m] if mode == "output" else s_q, s_q, n, m.org_bias.detach().float().contiguous())
+            m.bias.data.copy_(bias)
+            m.drop_weight_pack()              # (the memo keys on _version, which a .data write does not bump)
+            m.bias_shift = shift.cpu()
+            shifts[names[m]] = {"shift": m.bias_shift.clone(), "n": int(n), "kind": m.kind}
+        after, _ = run(inp_q, moments=True)
+        if world_size > 1:
+            count = torch.tensor([n_out], dtype=torch.int64, device=device)
+            dp.reduce_act_stats(sums=[before, after, count])
+            n_out = int(count.item())
+    finally:
+        for m, w, a_ in states:
+            m.use_weight_quant, m.use_act_quant = w, a_
+    fields = ("shift", "err", "energy")
+    unit.bias_stats = {"name": unit_name, "mode": mode, "n": int(n_out), "layers": shifts, "skipped": skipped,
+                       "before": {f: v for f, v in zip(fields, before.cpu())}, "after": {f: v for f, v in zip(fields, after.cpu())}}
+    return unit.bias_stats
+
+
 def learn_act_ranges(unit, inp_q, out_fp, iters=500, lr=1e-3, batch=32, seed=0, idx_table=None):
     """Train the frozen static activation ranges of a calibrated unit on its reconstruction error (the activation-grid step of BRECQ /
     QDrop, after the rounding has been learned).  The unit runs in the W8A8 state with its hard-rounded weights under torch's tape (the
@@ -475,6 +693,7 @@ def _reconstruct(model, unit, unit_name, cali_data, batch_size=32, iters=20000, 
     act_percentile = _act_percentile_args(args)
     act_report = _act_report_args(args)
     unit_report = _unit_report_args(args)
+    bias_correct = _bias_correct_args(args)
     if act_quant and act_mode == "static" and act_range == "learned" and _is_rstb(unit):
         raise NotImplementedError("act_range='learned': a Swin (RSTB) unit's activation-quantised window attention cannot sit on torch's "
                                   "tape (quant_block.QuantWindowAttention); calibrate it with act_range='max' or 'l2'")
@@ -588,6 +807,12 @@ def _reconstruct(model, unit, unit_name, cali_data, batch_size=32, iters=20000, 
     for m in ([unit] if not is_block else unit.modules()):
         if isinstance(m, (QuantModule, BaseQuantBlock)):
             m.trained = True
+    if bias_correct is not None:
+        # before the static ranges are fixed: they are then observed on the corrected outputs
+        t6 = _mark()
+        correct_unit_bias(unit, unit_name, inp_q, inp_fp, out_fp, bias_correct, batch=cache_bs)
+        if timing is not None:
+            timing[-1]["bias_s"] = _mark() - t6
     if static_act:
         # only now does the unit apply its own activation quantisers (`trained`): fix their grids on what the unit will be fed.  Also for
         # a unit the reference's "last layer" rule above trained without activation quantisation: that rule matches every layer unit whose

@@ -60,9 +60,10 @@ def schedule_roofline(engines, loop_s, iters, top=8):
 
 
 def run_schedule(images=256, iters=20000, batch=4, eval_hw=(512, 768), n_eval=2, log=print, quality=True, arch="anchor", w_bits=8,
-                 a_bits=8, per_unit_log=True, roofline=False, model=None, cali=None):
+                 a_bits=8, per_unit_log=True, roofline=False, model=None, cali=None, bias_correct=None):
     """arch: "anchor" | "attn" (Cheng2020-attn, BASELINE config 3) | "lu2022" (BASELINE config 4: NIC embed 192 / latent 320, the 25
-    units of main2.py's recon_model on the tape engine); w_bits / a_bits: weight grid and dynamic activation grid."""
+    units of main2.py's recon_model on the tape engine); w_bits / a_bits: weight grid and dynamic activation grid; bias_correct: None |
+    'weight' | 'output' (args.bias_correct; the per-unit wall of the correction is logged as bias_s)."""
     import math
     import bench
     from quantization import BaseQuantBlock, QuantModel, QuantModule, block_reconstruction, layer_reconstruction
@@ -120,6 +121,8 @@ def run_schedule(images=256, iters=20000, batch=4, eval_hw=(512, 768), n_eval=2,
         res["w8_rtn"] = evaluate_images(qnn.eval(), test_imgs) + (fidelity(qnn),)
     timing = []
     args = types.SimpleNamespace(lmbda=0.0483, task_loss=2.0, arch="Lu2022" if lu else "Cheng2020", timing=timing)
+    if bias_correct is not None:
+        args.bias_correct = bias_correct
     kwargs = dict(cali_data=cali, batch_size=batch, iters=iters, weight=0.01, input_prob=0.5, lr=4e-5, asym=True, b_range=(20, 2),
                   warmup=0.2, act_quant=False, opt_mode="mse", config=None, args=args)
     engines = []
@@ -151,6 +154,10 @@ def run_schedule(images=256, iters=20000, batch=4, eval_hw=(512, 768), n_eval=2,
     log(f"recon_model: {n_units} units x {iters} iterations x batch {batch} on {images} images: {wall:.2f} s wall "
         f"(cache building {cache_s:.2f} s, recording + graph capture {record_s:.2f} s, loops {loop_s:.2f} s = {loop_s / iters * 1e3:.3f} ms/step)"
         f" => {res['images_per_s']:.0f} calibration images/s")
+    if bias_correct is not None:
+        res["bias_s"] = sum(t.get("bias_s", 0.0) for t in timing)
+        log(f"bias correction ({bias_correct!r}): {res['bias_s']:.3f} s over {n_units} units beside loops of {loop_s:.2f} s; per unit: "
+            + ", ".join(f"{name} {t.get('bias_s', 0.0):.3f}" for (name, _), t in zip(engines, timing)))
     units = []
     for (name, e), t in zip(engines, timing):
         done = tot = 0
@@ -197,9 +204,11 @@ if __name__ == "__main__":
     ap.add_argument("--no-quality", action="store_true")
     ap.add_argument("--w-bits", type=int, default=8)
     ap.add_argument("--a-bits", type=int, default=8)
+    ap.add_argument("--bias-correct", default=None, choices=["weight", "output"], help="args.bias_correct; logs the correction's wall (bias_s)")
     ap.add_argument("--roofline", action="store_true", help="algorithmic-FLOP table per unit and kernel-family fractions (one more profiled iteration per unit)")
     a = ap.parse_args()
-    r = run_schedule(a.images, a.iters, a.batch, arch=a.arch, quality=not a.no_quality, w_bits=a.w_bits, a_bits=a.a_bits, roofline=a.roofline)
+    r = run_schedule(a.images, a.iters, a.batch, arch=a.arch, quality=not a.no_quality, w_bits=a.w_bits, a_bits=a.a_bits, roofline=a.roofline,
+                     bias_correct=a.bias_correct)
     if a.roofline:
         print("| unit | kind | GFLOP / iteration | ms / iteration | TFLOP/s |\n|---|---|---|---|---|")
         for u in r["roofline"]["units"]:
