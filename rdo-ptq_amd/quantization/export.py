@@ -10,11 +10,12 @@ import torch
 from .quant_block import BaseQuantBlock
 from .quant_layer import QuantModule
 from .quantizer import AdaRoundQuantizer
+from .utils import quant_state
 
 
 def integer_state(qnn) -> "OrderedDict[str, dict]":
     """name -> {levels (uint8, or int32 above 8 bits; logical weight shape), delta, zero_point, n_bits, bias, kind}.  `bias` is the one
-    the quantised forward uses (`m.bias`): `org_bias` unless a bias correction moved it (`recon.correct_unit_bias`)."""
+    the quantised forward uses (`m.bias`): `org_bias` unless a bias correction moved it (`unit_passes.correct_unit_bias`)."""
     out = OrderedDict()
     for name, m in qnn.named_modules():
         if not isinstance(m, QuantModule) or m.org_weight is None:
@@ -71,12 +72,24 @@ def activation_report(qnn) -> "OrderedDict[str, dict]":
     return out
 
 
+def _moment_columns(row, st, states):
+    """What `unit_report` and `bias_report` both derive from recorded pair moments `st[state]` with row["n"] pixels per channel, into the
+    dicts the row already holds: row[f][state] for f = err | shift | energy | shift_share (float64 [C], CPU) and row["total"][f][state]
+    for err | shift | energy (Python floats)."""
+    for state in states:
+        shift, err, energy = (st[state][f].detach().to("cpu", torch.float64).clone() for f in ("shift", "err", "energy"))
+        row["err"][state], row["shift"][state], row["energy"][state] = err, shift, energy
+        row["shift_share"][state] = torch.where(err == 0, torch.zeros_like(err), shift * shift / (max(row["n"], 1) * err))
+        row["total"]["err"][state], row["total"]["shift"][state] = float(err.sum()), float(shift.sum())
+        row["total"]["energy"][state] = float(energy.sum())
+
+
 UNIT_REPORT_STATES = ("nearest", "learned")
 
 
 def unit_report(qnn) -> "OrderedDict[str, dict]":
     """unit name -> the measured output error of every calibrated unit whose statistics were recorded (args.unit_report;
-    `recon.report_unit`), in module order, on the CPU.  With d = full-precision output - quantised output of the unit on its cached
+    `unit_passes.report_unit`), in module order, on the CPU.  With d = full-precision output - quantised output of the unit on its cached
     calibration inputs, per output channel and for both states 'nearest' (every trained weight rounded to nearest) and 'learned' (the
     unit as calibrated):
       channels, n                    channel count; pixels per channel (all ranks)
@@ -94,19 +107,15 @@ def unit_report(qnn) -> "OrderedDict[str, dict]":
         st = getattr(m, "unit_stats", None)
         if not st:
             continue
-        n = int(st["n"])
-        row = {"n": n, "total": {}}
+        row = {"n": int(st["n"]), "total": {}}
         for f in ("err", "shift", "energy", "sqnr_db", "shift_share"):
             row[f] = {}
             if f in ("err", "shift", "energy", "sqnr_db"):
                 row["total"][f] = {}
+        _moment_columns(row, st, UNIT_REPORT_STATES)
         for state in UNIT_REPORT_STATES:
-            shift, err, energy = (st[state][f].detach().to("cpu", torch.float64).clone() for f in ("shift", "err", "energy"))
-            row["err"][state], row["shift"][state], row["energy"][state] = err, shift, energy
+            err, energy = row["err"][state], row["energy"][state]
             row["sqnr_db"][state] = sqnr(energy, err)
-            row["shift_share"][state] = torch.where(err == 0, torch.zeros_like(err), shift * shift / (max(n, 1) * err))
-            row["total"]["err"][state], row["total"]["shift"][state] = float(err.sum()), float(shift.sum())
-            row["total"]["energy"][state] = float(energy.sum())
             row["total"]["sqnr_db"][state] = float(sqnr(energy.sum(), err.sum()))
         row["channels"] = int(row["err"]["learned"].numel())
         row["gain_db"] = row["sqnr_db"]["learned"] - row["sqnr_db"]["nearest"]
@@ -119,7 +128,7 @@ BIAS_REPORT_STATES = ("before", "after")
 
 
 def bias_report(qnn) -> "OrderedDict[str, dict]":
-    """unit name -> what the bias correction of every unit that ran it did (args.bias_correct; `recon.correct_unit_bias`), in module
+    """unit name -> what the bias correction of every unit that ran it did (args.bias_correct; `unit_passes.correct_unit_bias`), in module
     order, on the CPU.  With d = full-precision output - quantised output of the unit on its cached calibration inputs (the unit's own
     activation quantisers off), per output channel, 'before' the first and 'after' the last layer was corrected:
       mode, channels, n              'weight' | 'output'; channel count; output pixels per channel (all ranks)
@@ -136,18 +145,13 @@ def bias_report(qnn) -> "OrderedDict[str, dict]":
         st = getattr(m, "bias_stats", None)
         if not st:
             continue
-        n = int(st["n"])
-        row = {"mode": str(st["mode"]), "n": n, "total": {}}
+        row = {"mode": str(st["mode"]), "n": int(st["n"]), "total": {}}
         for f in ("err", "shift", "energy", "shift_share"):
             row[f], row["total"][f] = {}, {}
+        _moment_columns(row, st, BIAS_REPORT_STATES)
         for state in BIAS_REPORT_STATES:
-            shift, err, energy = (st[state][f].detach().to("cpu", torch.float64).clone() for f in ("shift", "err", "energy"))
-            row["err"][state], row["shift"][state], row["energy"][state] = err, shift, energy
-            row["shift_share"][state] = torch.where(err == 0, torch.zeros_like(err), shift * shift / (max(n, 1) * err))
-            row["total"]["err"][state], row["total"]["shift"][state] = float(err.sum()), float(shift.sum())
-            row["total"]["energy"][state] = float(energy.sum())
-            e = float(err.sum())
-            row["total"]["shift_share"][state] = 0.0 if e == 0 else float((shift * shift).sum()) / (max(n, 1) * e)
+            shift, e = row["shift"][state], row["total"]["err"][state]
+            row["total"]["shift_share"][state] = 0.0 if e == 0 else float((shift * shift).sum()) / (max(row["n"], 1) * e)
         row["channels"] = int(row["err"]["after"].numel())
         row["removed"] = row["err"]["before"] - row["err"]["after"]
         row["total"]["removed"] = row["total"]["err"]["before"] - row["total"]["err"]["after"]
@@ -240,8 +244,6 @@ def rd_report(qnn, images, lmbda=0.01, act_quant=False, batch=8, units=None) -> 
     if n < world:
         raise ValueError(f"rd_report: {n} image(s) for {world} ranks: every rank needs at least one")
     mine = images[rank::world]
-    mods = [m for m in qnn.modules() if isinstance(m, (QuantModule, BaseQuantBlock))]
-    held = [(m.use_weight_quant, m.use_act_quant) for m in mods]
 
     def measure():
         """one pass over this rank's images in the state the model is in -> (keys, float64 device sums [bits of every key | sse])"""
@@ -276,7 +278,7 @@ def rd_report(qnn, images, lmbda=0.01, act_quant=False, batch=8, units=None) -> 
         return r
 
     states = []
-    try:
+    with quant_state(qnn):
         qnn.set_quant_state(False, False)
         states.append(measure())
         qnn.set_quant_state(True, act_quant)
@@ -285,9 +287,6 @@ def rd_report(qnn, images, lmbda=0.01, act_quant=False, batch=8, units=None) -> 
             qnn.set_quant_state(False, False)
             u.set_quant_state(True, act_quant)
             states.append(measure())
-    finally:
-        for m, (w, a) in zip(mods, held):
-            m.use_weight_quant, m.use_act_quant = w, a
     if world > 1:
         flat = torch.cat([t for _, acc, sse in states for t in acc + [sse]])
         dp.reduce_act_stats(sums=[flat])

@@ -1,24 +1,26 @@
 """Shared body of `layer_reconstruction` / `block_reconstruction` (reference: layer_opt.py:175-320, block_opt.py:176-324).
 
-The choreography around the hot loop is the reference's; the loop itself runs on `engine.UnitEngine`."""
+The choreography around the hot loop is the reference's; the loop itself runs on `engine.UnitEngine`.  What runs on a unit after its
+loop, which the reference does not have (activation ranges, reports, bias correction), is in `unit_passes`; its argument checks are here."""
 import logging
 import time
+import types
 import zlib
-from collections import OrderedDict
 
 import torch
 
 from . import dp
 from hipops import ops
 from .engine import UnitEngine
-from .quant_block import BaseQuantBlock, QuantRSTB
+from .quant_block import BaseQuantBlock
 from .swin_engine import TapeEngine
-from .quant_layer import QuantModule, _nhwc, _sq
-from .quantizer import AdaRoundQuantizer, to_rows
+from .quant_layer import QuantModule, _nhwc
+from .unit_passes import (BIAS_CORRECT_MODES, _check_learn, _check_percentile, _is_rstb, calibrate_act_ranges, correct_unit_bias,
+                          learn_act_ranges, report_act_ranges, report_unit)
+from .unit_passes import _TapCollector, _bias_rows, _nearest_alpha, _reduce_scores, _tap_call, _tap_layer  # noqa: F401  (importable from here as before)
 from .utils import LinearTempDecay, save_inp_oup_data, set_mode
 
 _COOPS = ("g_a", "h_a", "h_s", "g_s")
-BIAS_CORRECT_MODES = ("weight", "output")
 
 
 def find_unquantized_module(model, _name_="g_a", module_list=None, name_list=None):
@@ -124,11 +126,16 @@ def _unit_modules(unit):
     raise NotImplementedError(f"reconstruction of {type(unit).__name__} is not built yet")
 
 
+def _arg(args, name, default):
+    """args.name; `default` where `args` is None or does not carry it"""
+    return getattr(args, name, default) if args is not None else default
+
+
 def _rd_metric(args, cali_data):
     """args.rd_metric: the distortion of the loss_mode='rd' task term, 'mse' (default) or 'ms-ssim' (the objective of CompressAI's
     MS-SSIM checkpoints).  Not `args.metric`: LossFunction.metric is the --task_loss exponent.  Checked before any work is done:
     the five MS-SSIM scales of an 11-tap window need crops with both sides above 160 pixels."""
-    metric = getattr(args, "rd_metric", "mse") if args is not None else "mse"
+    metric = _arg(args, "rd_metric", "mse")
     if metric not in ("mse", "ms-ssim"):
         raise ValueError(f"unknown rd_metric {metric!r} ('mse' or 'ms-ssim')")
     if metric == "ms-ssim" and getattr(args, "loss_mode", "lp") == "rd" and min(cali_data.shape[-2:]) <= 160:
@@ -153,40 +160,45 @@ def _act_args(args):
     args.bias_correct (default off; 'weight' or 'output'): a trained unit then corrects the biases of its conv, transposed-conv and
     Linear layers by the mean error of their pre-activations on the calibration set (`correct_unit_bias`, `export.bias_report`).
     Checked before any work is done."""
-    mode = getattr(args, "act_mode", "dynamic") if args is not None else "dynamic"
-    how = getattr(args, "act_range", "max") if args is not None else "max"
+    opt = _pass_options(args)
+    return opt.act_mode, opt.act_range
+
+
+def _pass_options(args):
+    """Every option `_act_args` describes, read and validated once, a bad one reported in this order -> a namespace of act_mode,
+    act_range, act_iters, act_lr, act_percentile, act_report, unit_report and bias_correct."""
+    mode, how = _arg(args, "act_mode", "dynamic"), _arg(args, "act_range", "max")
     if mode not in ("dynamic", "static"):
         raise ValueError(f"unknown act_mode {mode!r} ('dynamic' or 'static')")
     if how not in ("max", "l2", "learned", "percentile", "hist_mse", "auto"):
         raise ValueError(f"unknown act_range {how!r} ('max', 'l2', 'learned', 'percentile', 'hist_mse' or 'auto')")
-    _act_learn_args(args)
-    _act_percentile_args(args)
-    _act_report_args(args)
-    _unit_report_args(args)
-    _bias_correct_args(args)
-    return mode, how
+    iters, lr = _act_learn_args(args)
+    return types.SimpleNamespace(act_mode=mode, act_range=how, act_iters=iters, act_lr=lr, act_percentile=_act_percentile_args(args),
+                                 act_report=_act_report_args(args), unit_report=_unit_report_args(args),
+                                 bias_correct=_bias_correct_args(args))
+
+
+def _bool_arg(args, name):
+    flag = _arg(args, name, False)
+    if not isinstance(flag, bool):
+        raise ValueError(f"{name} must be True or False, got {flag!r}")
+    return flag
 
 
 def _act_report_args(args):
     """args.act_report, validated: a bool (default False)."""
-    report = getattr(args, "act_report", False) if args is not None else False
-    if not isinstance(report, bool):
-        raise ValueError(f"act_report must be True or False, got {report!r}")
-    return report
+    return _bool_arg(args, "act_report")
 
 
 def _unit_report_args(args):
     """args.unit_report, validated: a bool (default False)."""
-    report = getattr(args, "unit_report", False) if args is not None else False
-    if not isinstance(report, bool):
-        raise ValueError(f"unit_report must be True or False, got {report!r}")
-    return report
+    return _bool_arg(args, "unit_report")
 
 
 def _bias_correct_args(args):
     """args.bias_correct, validated -> None (off: absent, None or False, the default), 'weight' or 'output'.  True is refused like every
     other value: the mode must be named."""
-    mode = getattr(args, "bias_correct", None) if args is not None else None
+    mode = _arg(args, "bias_correct", None)
     if mode is None or mode is False:
         return None
     if not isinstance(mode, str) or mode not in BIAS_CORRECT_MODES:
@@ -196,464 +208,12 @@ def _bias_correct_args(args):
 
 def _act_learn_args(args):
     """(args.act_iters, args.act_lr) of act_range='learned', validated: a positive whole number of steps, a positive finite step size."""
-    iters = getattr(args, "act_iters", 500) if args is not None else 500
-    lr = getattr(args, "act_lr", 1e-3) if args is not None else 1e-3
-    return _check_learn(iters, lr)
-
-
-def _check_learn(iters, lr):
-    if isinstance(iters, bool) or not isinstance(iters, int) or iters < 1:
-        raise ValueError(f"act_iters must be a positive integer, got {iters!r}")
-    if isinstance(lr, bool) or not isinstance(lr, (int, float)) or not (0.0 < float(lr) < float("inf")):
-        raise ValueError(f"act_lr must be a positive finite number, got {lr!r}")
-    return iters, float(lr)
+    return _check_learn(_arg(args, "act_iters", 500), _arg(args, "act_lr", 1e-3))
 
 
 def _act_percentile_args(args):
     """args.act_percentile of act_range='percentile', validated: a real number p with 50 < p <= 100 (100 = the max range)."""
-    return _check_percentile(getattr(args, "act_percentile", 99.99) if args is not None else 99.99)
-
-
-def _check_percentile(p):
-    if isinstance(p, bool) or not isinstance(p, (int, float)) or not (50.0 < float(p) <= 100.0):
-        raise ValueError(f"act_percentile must be a number p with 50 < p <= 100, got {p!r}")
-    return float(p)
-
-
-def _is_rstb(unit):
-    return isinstance(unit, QuantRSTB) or getattr(unit, "unit_kind", None) == "rstb"
-
-
-def calibrate_act_ranges(unit, inp_q, act_range="max", batch=32, keep_obs=False, percentile=99.99):
-    """Fix the static activation ranges of a calibrated unit: run it once over its cached quantised inputs in the state the W8A8
-    evaluation uses (the unit, its QuantModules and nested block wrappers with weight and activation quantisation on) with its quantisers
-    observing, then freeze them; with act_range='l2' a second pass over the same inputs accumulates the candidates' squared errors
-    first; with act_range='percentile' the second pass takes every channel's histogram on its observed range, and freezing clips a
-    share 1 - percentile / 100 of its values at each end; with act_range='hist_mse' the same pass is followed by the exhaustive search
-    for the clip pair of least modelled squared error on the quantiser's grid width.  Under data parallelism the observed ranges and
-    the error sums or histograms are reduced over the ranks before they are used, so every rank freezes the same grid (integer counts:
-    the very grid of one process on all inputs).  Every quant state flag is left as it was found.  `keep_obs`: the quantisers keep the
-    observed max ranges next to the frozen ones (`act_obs`) for `learn_act_ranges`.
-    With act_range='auto' the second pass takes the 'l2' error sums AND the histograms (both read the same max-range inputs); from them
-    every site forms the four ranges that 'max', 'l2', 'percentile' and 'hist_mse' would freeze (`act_candidates`), a third pass measures
-    their squared error on the same inputs (`act_score`: still behind max-range upstream quantisers), and each channel freezes the one of
-    least measured error.  The measured sums and counts are reduced over the ranks like the others, so every rank picks from the same
-    numbers."""
-    if act_range in ("percentile", "auto"):
-        percentile = _check_percentile(percentile)
-    mods = [m for m in unit.modules() if isinstance(m, (QuantModule, BaseQuantBlock))]
-    quants = [m.act_quantizer for m in mods]
-    states = [(m, m.use_weight_quant, m.use_act_quant) for m in mods]
-
-    def run():
-        with torch.no_grad():
-            for i in range(0, inp_q.shape[0], batch):
-                h = inp_q[i:i + batch]
-                unit(h, (h.shape[2], h.shape[3])) if isinstance(unit, QuantRSTB) else unit(h)
-
-    def applied(name):                   # in a fixed order: the collectives of all ranks must line up
-        return [getattr(q, name)[k] for q in quants for k in sorted(getattr(q, name))]
-    try:
-        for m in mods:
-            m.use_weight_quant = m.use_act_quant = True
-        for q in quants:
-            q.act_observe()
-        run()
-        dp.reduce_act_stats(ranges=applied("act_range"))
-        if act_range == "l2":
-            for q in quants:
-                if q.act_range:
-                    q.act_search()
-            run()
-            dp.reduce_act_stats(sums=applied("act_err"))
-        elif act_range in ("percentile", "hist_mse"):
-            for q in quants:
-                if q.act_range:
-                    q.act_histogram(percentile, rule="mse" if act_range == "hist_mse" else "percentile")
-            run()
-            dp.reduce_act_stats(sums=applied("act_hist"))
-        elif act_range == "auto":
-            seen = [q for q in {id(q): q for q in quants}.values() if q.act_range]
-            for q in seen:
-                q.act_histogram(percentile, rule="mse", search=True)
-            run()
-            dp.reduce_act_stats(sums=applied("act_err") + applied("act_hist"))
-            for q in seen:
-                q.act_score(q.act_candidates())
-            run()
-            _reduce_scores(seen)
-        for q in quants:
-            q.act_freeze(keep_obs=keep_obs)
-    finally:
-        for m, w, a_ in states:
-            m.use_weight_quant, m.use_act_quant = w, a_
-
-
-def _reduce_scores(quants):
-    """the sums, counts and pixel counts of a scoring pass over the ranks, in the fixed site order"""
-    def applied(name):
-        return [getattr(q, name)[k] for q in quants for k in sorted(getattr(q, name))]
-    if dp.world()[1] <= 1:
-        return
-    dp.reduce_act_stats(sums=applied("act_err") + applied("act_energy") + applied("act_clip"))
-    sites = [(q, k) for q in quants for k in sorted(q.act_score_n)]
-    if sites:
-        n = torch.tensor([q.act_score_n[k] for q, k in sites], dtype=torch.int32, device=sites[0][0].act_err[sites[0][1]].device)
-        dp.reduce_act_stats(sums=[n])                    # (the guard of the pass keeps the sum inside 32 bits)
-        for (q, k), v in zip(sites, n.tolist()):
-            q.act_score_n[k] = int(v)
-
-
-def report_act_ranges(unit, inp_q, batch=32):
-    """Measure the frozen static activation ranges of a calibrated unit: one pass over its cached quantised inputs in the W8A8 state, every
-    frozen quantiser scoring its own range (K = 1) and passing its frozen output on; the measured squared error, the energy, the counts of
-    the values clipped at each end and the pixel count stay on the quantiser as `act_stats[site]` (summed over the ranks under data
-    parallelism).  The ranges do not change; every quant state flag is left as it was found."""
-    mods = [m for m in unit.modules() if isinstance(m, (QuantModule, BaseQuantBlock))]
-    quants = list({id(m.act_quantizer): m.act_quantizer for m in mods if m.act_quantizer.act_frozen()}.values())
-    states = [(m, m.use_weight_quant, m.use_act_quant) for m in mods]
-    try:
-        for m in mods:
-            m.use_weight_quant = m.use_act_quant = True
-        for q in quants:
-            q.act_score()
-        with torch.no_grad():
-            for i in range(0, inp_q.shape[0], batch):
-                h = inp_q[i:i + batch]
-                unit(h, (h.shape[2], h.shape[3])) if isinstance(unit, QuantRSTB) else unit(h)
-        _reduce_scores(quants)
-    finally:
-        for q in quants:
-            if getattr(q, "act_phase", "idle") == "score":
-                q.act_freeze()
-        for m, w, a_ in states:
-            m.use_weight_quant, m.use_act_quant = w, a_
-
-
-def _nearest_alpha(q, w):
-    """A stand-in for the alpha of the AdaRoundQuantizer `q` of weight `w` whose sign makes the hard forward, floor(w / delta) + (alpha >=
-    0), round to nearest: +1 where frac = w / delta - floor(w / delta) >= 0.5 (fp32, the quantiser's own rows and scales), -1 below."""
-    wr = q._rows(w.detach())
-    d, _ = q._row_scales(wr)
-    r = wr / d.reshape(-1, *([1] * (wr.dim() - 1)))
-    up = (r - torch.floor(r)) >= 0.5
-    return q._unrows(torch.where(up, 1.0, -1.0).to(wr.dtype).contiguous(), w)
-
-
-def report_unit(unit, unit_name, inp_q, out_fp, batch=32):
-    """Measure what calibration gained on a trained unit: two passes over its cached quantised inputs `inp_q`, in the quant state the unit
-    is found in (frozen static activation ranges included), each compared with the cached full-precision outputs `out_fp` per output
-    channel by `ops.pair_moments(out_fp batch, output batch)` on channels-last storage:
-      'nearest'   every trained weight (every AdaRoundQuantizer of the unit) rounded to nearest on the delta | zero point the quantiser
-                  holds, clamp(floor(w / delta) + (frac >= 0.5) + z, 0, n_levels - 1) with frac = w / delta - floor(w / delta) in fp32: A
-                  TIE ROUNDS UP (towards +inf), not to even as torch.round does.  Alpha is swapped for a tensor whose sign encodes frac >=
-                  0.5 for the duration of the pass, then put back (the same Parameter objects) and the weight packs are dropped;
-      'learned'   the unit as calibrated.
-    The fp32 sums of the batches are added in float64 on the device; under data parallelism the two float64 [3, C] tensors are summed
-    over the ranks ('nearest', then 'learned'), then the pixel count.  The result stays on the unit as `unit.unit_stats` = {"name", "n",
-    "nearest": {"shift", "err", "energy"}, "learned": {...}} with float64 [C] CPU tensors (`export.unit_report` reads it).  Nothing else
-    changes: alpha, delta, zero points, ranges, `act_stats` and every flag are left as they were found."""
-    rstb = isinstance(unit, QuantRSTB)
-    adas = [(m, m.weight_quantizer) for m in unit.modules()
-            if isinstance(m, QuantModule) and isinstance(m.weight_quantizer, AdaRoundQuantizer)]
-
-    def run():
-        # (zero sums, not None: a rank with no rows still takes part in the collectives below)
-        acc, n = torch.zeros(3, out_fp.shape[1], dtype=torch.float64, device=out_fp.device), 0
-        with torch.no_grad():
-            for i in range(0, inp_q.shape[0], batch):
-                h = inp_q[i:i + batch]
-                out = _nhwc(unit(h, (h.shape[2], h.shape[3])) if rstb else unit(h))
-                ref = _nhwc(out_fp[i:i + batch])
-                mom = ops.pair_moments(ref, out).double()
-                acc = acc + mom
-                n += ref.numel() // ref.shape[-1]
-        return acc, n
-
-    held = [(q, q.alpha) for _, q in adas]
-    try:
-        for m, q in adas:
-            q.alpha = torch.nn.Parameter(_nearest_alpha(q, m.weight), requires_grad=q.alpha.requires_grad)
-            m.drop_weight_pack()
-        nearest, n = run()
-    finally:
-        for (m, _), (q, alpha) in zip(adas, held):
-            q.alpha = alpha
-            m.drop_weight_pack()
-    learned, _ = run()
-    if dp.world()[1] > 1:
-        count = torch.tensor([n], dtype=torch.int64, device=nearest.device)
-        dp.reduce_act_stats(sums=[nearest, learned, count])
-        n = int(count.item())
-    names = ("shift", "err", "energy")
-    unit.unit_stats = {"name": unit_name, "n": int(n),
-                       "nearest": {f: v for f, v in zip(names, nearest.cpu())},
-                       "learned": {f: v for f, v in zip(names, learned.cpu())}}
-    return unit.unit_stats
-
-
-def _tap_layer(m):
-    """-> (k, stride, pad, output_padding, transposed) of the conv, transposed-conv or Linear QuantModule `m`; what the forward refuses
-    (dilated / grouped convolutions) is refused here, and a kernel that is not square"""
-    if m.kind == "linear":
-        return 1, 1, 0, 0, False
-    kw = m.fwd_kwargs
-    if m.kind == "conv":
-        stride, pad = m.conv_geometry()
-        op = 0
-    else:
-        if _sq(kw["dilation"]) != 1 or kw["groups"] != 1:
-            raise NotImplementedError("dilated / grouped transposed convolutions are not on the supported path")
-        stride, pad, op = _sq(kw["stride"]), _sq(kw["padding"]), _sq(kw["output_padding"])
-    kh, kwid = int(m.org_weight.shape[2]), int(m.org_weight.shape[3])
-    if kh != kwid:
-        raise NotImplementedError(f"bias correction: a {kh} x {kwid} kernel is not square")
-    return kh, stride, pad, op, m.kind == "tconv"
-
-
-def _tap_call(m, x):
-    """-> (channels-last input, k, stride, pad, (Ho, Wo) or None, transposed, output pixels) of one call of `m` on the input `x`"""
-    k, stride, pad, op, tr = _tap_layer(m)
-    if m.kind == "linear":
-        t = x.contiguous()
-        return t, 1, 1, 0, None, False, t.numel() // t.shape[-1]
-    t = _nhwc(x)
-    hw = (ops.tap_out_size(t.shape[1], k, stride, pad, tr, op), ops.tap_out_size(t.shape[2], k, stride, pad, tr, op))
-    return t, k, stride, pad, hw, tr, t.shape[0] * hw[0] * hw[1]
-
-
-class _TapCollector:
-    """Forward pre-hooks on QuantModules that add up the tap sums of what each is fed: per module a float64 [k * k * Cin] device tensor
-    (the fp32 sums of a call, `ops.tap_sums`, are added into it in float64 on the device), the output pixels seen, and the order of
-    the first calls."""
-
-    def __init__(self, mods, device, order_only=False):
-        """order_only: the hooks note the order of the first calls and take no sums"""
-        self.sums, self.n, self.order, self.device, self.order_only = {}, {}, [], device, order_only
-        self.handles = [m.register_forward_pre_hook(self._hook) for m in mods]
-
-    def _hook(self, m, args):
-        if self.order_only:
-            if m not in self.order:
-                self.order.append(m)
-            return
-        t, k, stride, pad, hw, tr, n = _tap_call(m, args[0].detach())
-        s32 = ops.tap_sums(t, k, stride, pad, hw, transposed=tr)
-        if m not in self.sums:
-            self.order.append(m)
-            self.sums[m] = torch.zeros(s32.numel(), dtype=torch.float64, device=s32.device)
-            self.n[m] = 0
-        self.sums[m] += s32.reshape(-1).double()
-        self.n[m] += int(n)
-
-    def get(self, m):
-        """(float64 sums, pixels) of `m`; zeros for a module no call reached (a rank without rows still joins the collectives)"""
-        if m not in self.sums:
-            k = 1 if m.kind == "linear" else int(m.org_weight.shape[2])
-            cin = m.org_weight.shape[1] if m.kind != "tconv" else m.org_weight.shape[0]
-            return torch.zeros(k * k * int(cin), dtype=torch.float64, device=self.device), 0
-        return self.sums[m], self.n[m]
-
-    def close(self):
-        for h in self.handles:
-            h.remove()
-        self.handles = []
-
-
-def _bias_rows(m, quantised):
-    """the effective weight of `m` in one quant state as contiguous fp32 rows [O, k * k * Cin] in the `to_rows` order"""
-    held = m.use_weight_quant
-    try:
-        m.use_weight_quant = bool(quantised)
-        w = m._weights()[0].detach()
-    finally:
-        m.use_weight_quant = held
-    rows = w if m.kind == "linear" else to_rows(w, tconv=m.kind == "tconv")
-    return rows.reshape(rows.shape[0], -1).contiguous().float()
-
-
-def correct_unit_bias(unit, unit_name, inp_q, inp_fp, out_fp, mode="weight", batch=32):
-    """Empirical bias correction of a trained unit (Nagel et al. 2019): every conv, transposed-conv and Linear QuantModule of the unit
-    that has a bias and weight quantisation on gets
-        bias = float32(org_bias + (W_fp . S_ref - W_q . S_q) / n)
-    with S = the tap sums of the layer's INPUT over the calibration set (`ops.tap_sums`: the sum over all n output pixels of the
-    pre-activation of a weight W on that input is n b + W . S, exactly, so the pre-activation itself, which the fused kernels never
-    write, is not needed), W_fp / W_q the full-precision / the hard-rounded weight in the `to_rows` order, and both products and their
-    difference in float64 (`ops.bias_shift`).  S_q is taken on what the layer is fed in the quantised unit on `inp_q`; S_ref is
-      mode 'weight':  S_q -- the mean error of the layer's own rounding is removed;
-      mode 'output':  what the layer is fed in the full-precision unit on `inp_fp` -- the mean pre-activation becomes that of the target
-                      the calibration reconstructed against.
-    The bias is absolute from `org_bias`: correcting twice gives the same bits.  The layers are corrected one after the other in the
-    order of their first call in the forward, each from a pass of its own over `inp_q`, so that a layer sees its corrected
-    predecessors.  All passes run without a tape, batch for batch, the quantised ones with weight quantisation on and the unit's own
-    activation quantisers OFF (in both activation modes: a static quantiser that is not frozen yet cannot run), the full-precision one
-    in the (False, False) state; every flag is put back.  Before the first and after the last layer pass the unit output is compared
-    with `out_fp` (`ops.pair_moments`).  GDN, LayerNorm and bias-less layers are left alone and listed with the reason.  Under data
-    parallelism the tap sums, the pixel counts and the moments are summed over the ranks in the fixed layer order, so every rank
-    writes the same biases.  Left behind: `m.bias_shift` (float64 [O], CPU) on every corrected layer and `unit.bias_stats`
-    (`export.bias_report` reads it); `org_bias`, alpha, delta, zero points and ranges are not written."""
-    if mode not in BIAS_CORRECT_MODES:
-        raise ValueError(f"bias_correct must be 'weight' or 'output', got {mode!r}")
-    rstb = isinstance(unit, QuantRSTB)
-    names = {m: (n or "layer") for n, m in unit.named_modules() if isinstance(m, QuantModule)}
-    mods = [m for m in unit.modules() if isinstance(m, (QuantModule, BaseQuantBlock))]
-    states = [(m, m.use_weight_quant, m.use_act_quant) for m in mods]
-    skipped, layers = OrderedDict(), []
-    for m, name in names.items():
-        if m.org_weight is None:
-            continue                                     # (a PixelShuffle wrapper: nothing to correct, nothing to report)
-        if m.kind in ("gdn", "layernorm"):
-            skipped[name] = f"{m.kind}: its output mean is not linear in the mean of its input"
-        elif m.bias is None or m.org_bias is None:
-            skipped[name] = "no bias"
-        elif not m.use_weight_quant:
-            skipped[name] = "weight quantisation off"
-        else:
-            _tap_layer(m)                     # (raises for a geometry off the supported path, before any pass)
-            layers.append(m)
-    device = out_fp.device
-    world_size = dp.world()[1]
-
-    def run(x, moments=False):
-        # (zero sums, not None: a rank with no rows still takes part in the collectives below)
-        acc, n = torch.zeros(3, out_fp.shape[1], dtype=torch.float64, device=device), 0
-        with torch.no_grad():
-            for i in range(0, x.shape[0], batch):
-                h = x[i:i + batch]
-                out = unit(h, (h.shape[2], h.shape[3])) if rstb else unit(h)
-                if moments:
-                    ref = _nhwc(out_fp[i:i + batch])
-                    acc = acc + ops.pair_moments(ref, _nhwc(out)).double()
-                    n += ref.numel() // ref.shape[-1]
-        return acc, n
-
-    def set_state(w, a_):
-        for m in mods:
-            m.use_weight_quant, m.use_act_quant = w, a_
-
-    ref_sums = {}
-    try:
-        # the full-precision pass ('output'), or a first quantised pass ('weight'), also fixes the order of the layers' first calls
-        col = _TapCollector(layers, device, order_only=mode != "output")
-        try:
-            set_state(mode != "output", False)
-            if mode == "output":
-                run(inp_fp)                   # every S_ref in one pass
-                col.close()
-                set_state(True, False)
-            before, n_out = run(inp_q, moments=True)
-        finally:
-            col.close()
-        order = list(col.order) + [m for m in layers if m not in col.order]         # (no rows here: module order)
-        if world_size > 1:
-            # ranks with rows all saw the same order; a rank without rows takes theirs (MAX over the ranks of each layer's position)
-            pos = torch.full((max(1, len(layers)),), -1, dtype=torch.int32, device=device)
-            for i, m in enumerate(col.order):
-                pos[layers.index(m)] = i
-            dp.reduce_max(pos)
-            got = pos[:len(layers)].tolist()
-            if all(v >= 0 for v in got):
-                order = [m for _, m in sorted(zip(got, layers), key=lambda t: t[0])]
-        if mode == "output":
-            for m in order:
-                ref_sums[m] = col.get(m)[0]
-            if world_size > 1 and order:
-                dp.reduce_act_stats(sums=[ref_sums[m] for m in order])
-        shifts = OrderedDict()
-        for m in order:
-            one = _TapCollector([m], device)
-            try:
-                run(inp_q)
-            finally:
-                one.close()
-            s_q, n = one.get(m)
-            if world_size > 1:
-                count = torch.tensor([n], dtype=torch.int64, device=device)
-                dp.reduce_act_stats(sums=[s_q, count])
-                n = int(count.item())
-            if n < 1:
-                raise ValueError(f"correct_unit_bias: {unit_name}: no calibration rows reached {names[m]}")
-            w_q = _bias_rows(m, True)
-            w_ref = _bias_rows(m, False)
-            shift, bias = ops.bias_shift(w_ref, w_q, ref_sums[m] if mode == "output" else s_q, s_q, n, m.org_bias.detach().float().contiguous())
-            m.bias.data.copy_(bias)
-            m.drop_weight_pack()              # (the memo keys on _version, which a .data write does not bump)
-            m.bias_shift = shift.cpu()
-            shifts[names[m]] = {"shift": m.bias_shift.clone(), "n": int(n), "kind": m.kind}
-        after, _ = run(inp_q, moments=True)
-        if world_size > 1:
-            count = torch.tensor([n_out], dtype=torch.int64, device=device)
-            dp.reduce_act_stats(sums=[before, after, count])
-            n_out = int(count.item())
-    finally:
-        for m, w, a_ in states:
-            m.use_weight_quant, m.use_act_quant = w, a_
-    fields = ("shift", "err", "energy")
-    unit.bias_stats = {"name": unit_name, "mode": mode, "n": int(n_out), "layers": shifts, "skipped": skipped,
-                       "before": {f: v for f, v in zip(fields, before.cpu())}, "after": {f: v for f, v in zip(fields, after.cpu())}}
-    return unit.bias_stats
-
-
-def learn_act_ranges(unit, inp_q, out_fp, iters=500, lr=1e-3, batch=32, seed=0, idx_table=None):
-    """Train the frozen static activation ranges of a calibrated unit on its reconstruction error (the activation-grid step of BRECQ /
-    QDrop, after the rounding has been learned).  The unit runs in the W8A8 state with its hard-rounded weights under torch's tape (the
-    modules' tape forwards; every frozen quantiser as `ActQuantStaticFn`, straight-through round) on mini-batches inp_q[idx] of `batch`
-    rows (never a ragged one; idx from a generator seeded with `seed`, or the rows of `idx_table` [iters, batch]); the loss is
-    lp_loss(out, out_fp[idx], p=2); every site range the forward reached takes one projected Adam step per iteration
-    (`ops.act_range_step`: step size relative to the observed width, the range stays inside the observed max range).  Under data
-    parallelism the range gradients of all sites, concatenated in the fixed site order of `calibrate_act_ranges`, are summed over the
-    ranks and divided by the world size before the step, so every rank holds the same grids.  The quantisers end frozen; every quant
-    state flag is left as it was found."""
-    from hipops.autograd import SqDiffSumFn
-    if _is_rstb(unit):
-        raise NotImplementedError("learn_act_ranges: a Swin (RSTB) unit's activation-quantised window attention cannot sit on torch's tape "
-                                  "(quant_block.QuantWindowAttention); use act_range='max' or 'l2' for it")
-    iters, lr = _check_learn(iters, lr)
-    mods = [m for m in unit.modules() if isinstance(m, (QuantModule, BaseQuantBlock))]
-    quants = list({id(m.act_quantizer): m.act_quantizer for m in mods if m.act_quantizer.act_frozen()}.values())
-    states = [(m, m.use_weight_quant, m.use_act_quant) for m in mods]
-    n = inp_q.shape[0]
-    B = max(1, min(int(batch), n))
-    if idx_table is None:
-        g = torch.Generator().manual_seed(int(seed))
-        idx_table = torch.stack([torch.randperm(n, generator=g)[:B] for _ in range(iters)])
-    if idx_table.dim() != 2 or idx_table.shape[0] < iters:
-        raise ValueError(f"learn_act_ranges: idx_table must be [iters >= {iters}, batch], got {tuple(idx_table.shape)}")
-    idx_table = idx_table.to(device=inp_q.device, dtype=torch.long)
-    world_size = dp.world()[1]
-    try:
-        for m in mods:
-            m.use_weight_quant = m.use_act_quant = True
-        for q in quants:
-            q.act_learn()
-        sites = [(q, k) for q in quants for k in sorted(q.act_range)]          # in a fixed order: the collectives of all ranks must line up
-        moments = [(torch.zeros_like(q.act_obs[k]), torch.zeros_like(q.act_obs[k])) for q, k in sites]
-        steps = [0] * len(sites)
-        for it in range(iters):
-            idx = idx_table[it]
-            x = inp_q.index_select(0, idx).detach().requires_grad_(True)
-            tgt = out_fp.index_select(0, idx)
-            with torch.enable_grad():
-                out = unit(x)
-                loss = SqDiffSumFn.apply(out, tgt, float(out.shape[1]) / out.numel())      # = lp_loss(out, tgt, p=2)
-                grads = torch.autograd.grad(loss, [q.act_range[k] for q, k in sites], allow_unused=True)
-            if world_size > 1:
-                flat = torch.cat([torch.zeros_like(q.act_obs[k]) if g_ is None else g_ for (q, k), g_ in zip(sites, grads)])
-                dp.reduce_act_grads(flat)
-                grads = [None if g_ is None else f for g_, f in zip(grads, flat.split([q.act_obs[k].numel() for q, k in sites]))]
-            for i, ((q, k), g_) in enumerate(zip(sites, grads)):
-                if g_ is None:                        # a site this forward did not reach
-                    continue
-                steps[i] += 1
-                ops.act_range_step(q.act_range[k], g_.contiguous(), q.act_obs[k], moments[i][0], moments[i][1], steps[i], lr)
-    finally:
-        for q in quants:
-            if getattr(q, "act_phase", "idle") == "learn":
-                q.act_freeze()
-            else:
-                q.act_obs = {}
-        for m, w, a_ in states:
-            m.use_weight_quant, m.use_act_quant = w, a_
+    return _check_percentile(_arg(args, "act_percentile", 99.99))
 
 
 def reconstruct(model, unit, unit_name, cali_data, *a, **kw):
@@ -682,19 +242,14 @@ def _reconstruct(model, unit, unit_name, cali_data, batch_size=32, iters=20000, 
         # the model's output DICT to log_softmax / kl_div (utils.py:316-321: BRECQ's classification code).
         raise NotImplementedError(f"opt_mode={opt_mode!r}: only 'mse' (the mode main2.py uses) is built -- the Fisher-weighted modes of the "
                                   "reference are classification left-overs that do not run on its compression models")
-    task_p = getattr(args, "task_loss", 2.0) if args is not None else 2.0
+    task_p = _arg(args, "task_loss", 2.0)
     if float(p) != 2.0:
         raise NotImplementedError("rec_loss is built for p = 2 (the value main2.py passes); --task_loss may be any exponent >= 1")
     if float(task_p) < 1.0:
         raise ValueError("--task_loss < 1 has no finite gradient at zero error")
     rd_metric = _rd_metric(args, cali_data)
-    act_mode, act_range = _act_args(args)
-    act_iters, act_lr = _act_learn_args(args)
-    act_percentile = _act_percentile_args(args)
-    act_report = _act_report_args(args)
-    unit_report = _unit_report_args(args)
-    bias_correct = _bias_correct_args(args)
-    if act_quant and act_mode == "static" and act_range == "learned" and _is_rstb(unit):
+    opt = _pass_options(args)
+    if act_quant and opt.act_mode == "static" and opt.act_range == "learned" and _is_rstb(unit):
         raise NotImplementedError("act_range='learned': a Swin (RSTB) unit's activation-quantised window attention cannot sit on torch's "
                                   "tape (quant_block.QuantWindowAttention); calibrate it with act_range='max' or 'l2'")
     rank, world_size = dp.world()
@@ -709,7 +264,7 @@ def _reconstruct(model, unit, unit_name, cali_data, batch_size=32, iters=20000, 
         batch_size = batch_size // world_size
     # args.timing (optional list): the caller wants this unit's wall split -- cache building / plan recording / loop -- which costs
     # three device synchronisations (tools/full_schedule.py, bench.py's recon_model_wall_s)
-    timing = getattr(args, "timing", None) if args is not None else None
+    timing = _arg(args, "timing", None)
 
     def _mark():
         if timing is not None:
@@ -718,13 +273,13 @@ def _reconstruct(model, unit, unit_name, cali_data, batch_size=32, iters=20000, 
     t0 = _mark()
     # dynamic activation quantisation makes cached values depend on the caching batch: keep the reference's batch of 1 then (a static
     # grid is the same whatever shares the batch)
-    static_act = bool(act_quant) and act_mode == "static"
+    static_act = bool(act_quant) and opt.act_mode == "static"
     if act_quant:
         # args decide, in both directions: a model calibrated static earlier and reconstructed again with act_mode='dynamic' (or without
         # it) runs dynamic grids; frozen ranges stay on the quantisers and come back with QuantModel.set_act_mode('static')
         for m in model.modules():
-            if isinstance(m, (QuantModule, BaseQuantBlock)) and getattr(m.act_quantizer, "act_mode", "dynamic") != act_mode:
-                m.act_quantizer.set_act_mode(act_mode)
+            if isinstance(m, (QuantModule, BaseQuantBlock)) and getattr(m.act_quantizer, "act_mode", "dynamic") != opt.act_mode:
+                m.act_quantizer.set_act_mode(opt.act_mode)
     if static_act and getattr(args, "loss_mode", "lp") == "rd" and _ste is not None:
         # the R + lambda*D task loss differentiates through the trained modules behind the unit: their frozen quantisers go on torch's tape
         # (straight-through round) for the duration of this unit; `reconstruct` clears the flag.  The cache passes run without a tape.
@@ -807,10 +362,10 @@ def _reconstruct(model, unit, unit_name, cali_data, batch_size=32, iters=20000, 
     for m in ([unit] if not is_block else unit.modules()):
         if isinstance(m, (QuantModule, BaseQuantBlock)):
             m.trained = True
-    if bias_correct is not None:
+    if opt.bias_correct is not None:
         # before the static ranges are fixed: they are then observed on the corrected outputs
         t6 = _mark()
-        correct_unit_bias(unit, unit_name, inp_q, inp_fp, out_fp, bias_correct, batch=cache_bs)
+        correct_unit_bias(unit, unit_name, inp_q, inp_fp, out_fp, opt.bias_correct, batch=cache_bs)
         if timing is not None:
             timing[-1]["bias_s"] = _mark() - t6
     if static_act:
@@ -820,16 +375,16 @@ def _reconstruct(model, unit, unit_name, cali_data, batch_size=32, iters=20000, 
         # W8A8 evaluation apply those quantisers all the same (utils.set_mode).  What decides is whether a later forward applies the
         # quantiser: one behind `disable_act_quant` is never called, observes nothing and stays without a range.
         t4 = _mark()
-        if act_range == "learned":
+        if opt.act_range == "learned":
             calibrate_act_ranges(unit, inp_q, "l2", batch=cache_bs, keep_obs=True)         # the starting ranges
-            learn_act_ranges(unit, inp_q, out_fp, act_iters, act_lr, batch_size, seed=unit_seed(unit_name))
+            learn_act_ranges(unit, inp_q, out_fp, opt.act_iters, opt.act_lr, batch_size, seed=unit_seed(unit_name))
         else:
-            calibrate_act_ranges(unit, inp_q, act_range, batch=cache_bs, percentile=act_percentile)
-        if act_report:
+            calibrate_act_ranges(unit, inp_q, opt.act_range, batch=cache_bs, percentile=opt.act_percentile)
+        if opt.act_report:
             report_act_ranges(unit, inp_q, batch=cache_bs)
         if timing is not None:
             timing[-1]["act_s"] = _mark() - t4
-    if unit_report:
+    if opt.unit_report:
         t5 = _mark()
         report_unit(unit, unit_name, inp_q, out_fp, batch=cache_bs)
         if timing is not None:

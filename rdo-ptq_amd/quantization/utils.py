@@ -27,6 +27,33 @@ def set_mode(model, act_quant):
             set_mode(module, act_quant)
 
 
+class quant_state:
+    """Context manager over the QuantModule / BaseQuantBlock instances of the module tree `root`: records each one's
+    use_weight_quant | use_act_quant pair, sets the flags that are given on all of them (None: left as found), and puts every recorded
+    pair back on the way out, whatever was raised and whatever the block switched in between (`set`, or a `set_quant_state` of the
+    modules).  The one place of this package that restores quant flags."""
+
+    def __init__(self, root, weight=None, act=None):
+        self.mods = [m for m in root.modules() if isinstance(m, (QuantModule, BaseQuantBlock))]
+        self.held = [(m.use_weight_quant, m.use_act_quant) for m in self.mods]
+        self.first = (weight, act)
+
+    def set(self, weight=None, act=None):
+        for m in self.mods:
+            if weight is not None:
+                m.use_weight_quant = weight
+            if act is not None:
+                m.use_act_quant = act
+
+    def __enter__(self):
+        self.set(*self.first)
+        return self
+
+    def __exit__(self, *exc):
+        for m, (w, a) in zip(self.mods, self.held):
+            m.use_weight_quant, m.use_act_quant = w, a
+
+
 class LinearTempDecay:
     """Temperature b of the rounding regulariser: start_b during warm-up, then linear to end_b (utils.py:37-54)."""
 
@@ -204,39 +231,37 @@ class _FpMemo:
             return None
         hooks = [u.register_forward_hook(hook) for u in units]
         was_training = model.training
-        states = [(m, m.use_weight_quant, m.use_act_quant) for m in model.modules() if isinstance(m, (QuantModule, BaseQuantBlock))]
         budget = min(float(os.environ.get("RDO_FP_MEMO_GIB", "64")) * 2 ** 30, 0.5 * torch.cuda.mem_get_info(device)[0])
         ok = True
-        try:
-            model.eval()
-            model.set_quant_state(False, False)
-            with torch.no_grad():
-                n = cali_data.size(0)
-                for i in range(0, n, batch_size):
-                    for k in calls:
-                        calls[k] = 0
-                    model(cali_data[i:i + batch_size].to(device))
-                    for k, c in calls.items():
-                        if c != 1:                               # shared / looped / unreached module: its rows are not one per image
-                            bad.add(k)
-                    for k, (a, b) in store.items():              # a later op of this forward wrote into a captured tensor in place
-                        if k not in bad and any(t._version != v for t, v in (a[-1:] + b[-1:])):
-                            bad.add(k)
-                    for k in bad:
-                        store[k][0].clear(); store[k][1].clear()
-                    if i == 0:                                   # extrapolate from the first batch
-                        per = sum(t.numel() * t.element_size() for a, b in store.values() for t, _ in a + b) / min(batch_size, n)
-                        if per * n > budget:
-                            ok = False
-                            break
-        except Exception:                                        # a model whose full forward cannot run here: per-unit passes
-            ok = False
-        finally:
-            for h in hooks:
-                h.remove()
-            for m, w, a_ in states:                              # leave every quant state as it was found
-                m.use_weight_quant, m.use_act_quant = w, a_
-            model.train(was_training)
+        with quant_state(model):                                     # leave every quant state as it was found
+            try:
+                model.eval()
+                model.set_quant_state(False, False)
+                with torch.no_grad():
+                    n = cali_data.size(0)
+                    for i in range(0, n, batch_size):
+                        for k in calls:
+                            calls[k] = 0
+                        model(cali_data[i:i + batch_size].to(device))
+                        for k, c in calls.items():
+                            if c != 1:                               # shared / looped / unreached module: its rows are not one per image
+                                bad.add(k)
+                        for k, (a, b) in store.items():              # a later op of this forward wrote into a captured tensor in place
+                            if k not in bad and any(t._version != v for t, v in (a[-1:] + b[-1:])):
+                                bad.add(k)
+                        for k in bad:
+                            store[k][0].clear(); store[k][1].clear()
+                        if i == 0:                                   # extrapolate from the first batch
+                            per = sum(t.numel() * t.element_size() for a, b in store.values() for t, _ in a + b) / min(batch_size, n)
+                            if per * n > budget:
+                                ok = False
+                                break
+            except Exception:                                        # a model whose full forward cannot run here: per-unit passes
+                ok = False
+            finally:
+                for h in hooks:
+                    h.remove()
+                model.train(was_training)
         if not ok:
             return None
         memo = cls(model, cali_data, batch_size)

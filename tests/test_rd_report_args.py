@@ -267,6 +267,44 @@ def test_rd_report_on_the_cpu_fails_loudly_and_restores_the_flags():
     assert before == [(m.use_weight_quant, m.use_act_quant, m.trained) for m in mods]
 
 
+def test_quant_state_puts_back_what_it_found_whatever_the_block_did():
+    """`utils.quant_state` on mixed flags: restored after a normal exit and after an exception, to the recorded pairs and not to a state
+    the block switched to (through `set`, one flag or both, or through the modules' own `set_quant_state`)"""
+    from quantization import BaseQuantBlock, QuantModule
+    from quantization.utils import quant_state
+    qnn = _toy("cheng")
+    mods = [m for m in qnn.modules() if isinstance(m, (QuantModule, BaseQuantBlock))]
+    for k, m in enumerate(mods):
+        m.use_weight_quant, m.use_act_quant = k % 2 == 0, k % 3 == 0
+    before = [(m.use_weight_quant, m.use_act_quant) for m in mods]
+    assert len(set(before)) == 4                                         # (every combination is among them)
+
+    def flags():
+        return [(m.use_weight_quant, m.use_act_quant) for m in mods]
+    with quant_state(qnn) as state:                                      # nothing given: nothing set
+        assert state.mods == mods and flags() == before
+    assert flags() == before
+    with quant_state(qnn, True, False) as state:
+        assert flags() == [(True, False)] * len(mods)
+        state.set(False, True)
+        assert flags() == [(False, True)] * len(mods)
+        state.set(weight=True)                                           # one flag: the other stays
+        assert flags() == [(True, True)] * len(mods)
+    assert flags() == before
+    with pytest.raises(KeyError, match="inside"):
+        with quant_state(qnn, weight=True):
+            assert flags() == [(True, a) for _, a in before]
+            qnn.set_quant_state(False, False)
+            raise KeyError("inside")
+    assert flags() == before
+    unit = mods[1]                                                       # a sub-tree: the rest of the model is not its business
+    inside = [m for m in unit.modules() if isinstance(m, (QuantModule, BaseQuantBlock))]
+    with quant_state(unit, True, True) as state:
+        assert state.mods == inside
+        assert [f for m, f in zip(mods, flags()) if m not in inside] == [f for m, f in zip(mods, before) if m not in inside]
+    assert flags() == before
+
+
 def test_product_still_never_imports_the_oracle():
     for base, _, files in os.walk(os.path.join(ROOT, "rdo-ptq_amd")):
         for f in files:
