@@ -13,6 +13,10 @@ inside the loop.  Units: a single `QuantModule` ('layer': conv, transposed conv,
 Cheng2020 blocks QuantRB / QuantRBWS / QuantRBU; the Lu2022 RSTB blocks and every unit whose task loss runs through the rest of
 its sub-coder are handled by `swin_engine.TapeEngine`, a subclass that reuses the ops, buffers and plans defined here.
 
+This file holds what one iteration IS (weight holders, buffers, forms, the `_fb_*` bodies, step and record) and the fp16 range of
+the planes (probe, poll, restart).  How the recorded plans are DRIVEN where one `Plan.run` does not do is in two base classes of
+`UnitEngine`: `engine_dp.DpLoop` (data parallel) and `engine_rd.RdTask` (the opt-in R + lambda*D task loss).
+
 Loss = round + rec + task exactly as the reference computes it for Sequential-indexed CompressAI models, where the task
 term degenerates to a second copy of the reconstruction term: `coef = 2`.
 
@@ -30,14 +34,12 @@ from hipops import ops
 from hipops.plan import Plan
 
 from . import dp
+from .engine_dp import DpLoop, DpStallError  # noqa: F401  (DpStallError: re-exported)
+from .engine_rd import RdTask
 from .quant_layer import QuantModule
 from .quantizer import AdaRoundQuantizer, from_rows, to_rows
 
 UNIT_KINDS = ("layer", "rb", "rbws", "rbu", "rstb")
-
-
-class DpStallError(RuntimeError):
-    """The captured data-parallel loop stopped making progress (`UnitEngine._hb_wait`): a collective inside the graph hangs."""
 
 
 class IdxStream:
@@ -107,68 +109,183 @@ def _planes_only(x):
     return x.planes if isinstance(x, Act) and x.f32 is None else None
 
 
-class _Op:
-    """Device state of one trainable QuantModule inside a unit."""
+def conv_out_hw(H, W, K, stride, pad):
+    """output size of a K x K conv over an H x W map"""
+    return ops.tap_out_size(H, K, stride, pad), ops.tap_out_size(W, K, stride, pad)
+
+
+def zero_insert_hw(H, W, K, stride, pad, opad=0):
+    """(q, Hu, Wu): a transposed conv (K, stride, pad, output_padding `opad`) of an H x W map -- or the input gradient of the strided conv
+    with that geometry from its H x W output gradient -- is the stride-1 / pad-0 conv, taps flipped, of the map with stride - 1 zeros
+    between its elements, q = K - 1 - pad around it and `opad` more behind it: Hu x Wu."""
+    q = K - 1 - pad
+    if q < 0:
+        raise NotImplementedError("calibration engine: transposed conv with padding > kernel_size - 1")
+    return q, ops.tap_out_size(H, K, stride, pad, True, opad) + K - 1, ops.tap_out_size(W, K, stride, pad, True, opad) + K - 1
+
+
+def _split_lin(w, planes):
+    ops.split_h2_linear(w, planes=planes)
+
+
+def _split_conv(w, planes):
+    """by the format the buffer was allocated in: ops.H2 for the plane-input kernels, bf16 three-way for the fp32-input ones"""
+    if isinstance(planes, ops.H2):
+        ops.split_h2_conv(w, planes=planes)
+    else:
+        ops.split_bf16x3(w, planes)
+
+
+class _Weights:
+    """One module's weight in the kernels' layouts, with every plane buffer the kernels may want of it: what the trainable `_Op` and
+    the frozen `swin_engine._FpOp` share, so that `UnitEngine._conv` / `._dgrad` take either.  A subclass provides `wq` and, where
+    it has an input gradient, `wd` (the weights the kernels read now, as `wq4()` / `wd4()`) and `plane_scale()`."""
+    is_gdn = False
+    name = None                                # (a trainable op has one: its key in `UnitEngine.ops`)
+    # plane buffer -> (the weight it is split from: an attribute or a method, how), in the order `split_planes` issues its launches; the
+    # buffers are made on first use while a plan is being recorded
+    PLANE_BUFFERS = {"lin_fwd": ("wq4", _split_lin),          # fragment-ordered fp16 planes of a Linear / 1 x 1 conv for rdo_linear_h2
+                     "lin_bwd": ("wd4", _split_lin),          # (large token matrices)
+                     "wp_planes": ("wp", _split_conv),        # of the phase weight of a transposed conv: bf16 three-way ...
+                     "wp_h2": ("wp", _split_conv),            # ... and fp16 two-way
+                     "wbp_planes": ("wbp", _split_conv),      # of the phase weight of a frozen strided conv's input gradient (bf16)
+                     "wq_planes": ("wq4", _split_conv),       # of the weight ...
+                     "wd_planes": ("wd4", _split_conv)}       # ... and of its dgrad layout
+
+    def __init__(self, qm: QuantModule):
+        self.qm = qm
+        self.tconv = None                     # (stride, padding, output_padding) of a ConvTranspose2d
+        self.tc_phase = self.wp = self.bias_p = self.wbp = self.wd = None
+        self.drop_planes()
+
+    def drop_planes(self):
+        for n in self.PLANE_BUFFERS:
+            setattr(self, n, None)
+
+    def _layout(self, bias):
+        """w [co][kh][kw][ci], w4, rows, K, stride, pad, tconv, bias of a conv, a transposed conv or a Linear"""
+        qm = self.qm
+        w = qm.org_weight.detach()
+        self.stride, self.pad = 1, 0
+        if qm.kind == "linear":
+            self.w = w.reshape(w.shape[0], 1, 1, w.shape[1]).contiguous()      # a Linear is a 1x1 conv over the token matrix
+        elif qm.kind == "tconv":
+            kw = qm.fwd_kwargs
+            if kw["groups"] != 1 or tuple(kw["dilation"]) != (1, 1):
+                raise NotImplementedError("calibration engine: grouped / dilated transposed convolutions")
+            self.tconv = (int(kw["stride"][0]), int(kw["padding"][0]), int(kw["output_padding"][0]))
+            # a transposed conv is the forward conv kernel (stride 1, pad 0) on the zero-inserted input with the taps
+            # flipped: keep every per-weight tensor of the engine in that flipped [co][kh'][kw'][ci] layout
+            self.w = to_rows(w, tconv=True).flip(1, 2).contiguous()
+        else:
+            self.w = to_rows(w)                # OHWI
+            self.stride, self.pad = qm.conv_geometry()
+        self.rows, self.K, self.w4 = self.w.shape[0], self.w.shape[1], tuple(self.w.shape)
+        self.bias = None if bias is None else bias.detach().contiguous()
+
+    def _init_phase(self):
+        """Transposed conv whose output is stride x the input: run as a stride-1 conv with the "phase weight" [Cout * s^2][K'][K'][Cin]
+        + pixel shuffle (include/rdo_ptq_hip.h, rdo_tconv_expand) instead of zero insertion + dense conv: `tc_phase` (None where the
+        geometry does not allow it), `wp` from the current weights, `bias_p`."""
+        self.tc_phase = ops.TconvPhase.get(self.K, *self.tconv, True, self.w.device)
+        if self.tc_phase is not None:
+            self.wp4 = self.tc_phase.w_shape(self.rows, self.w4[3])
+            self.wp = torch.empty(self.wp4, device=self.w.device, dtype=torch.float32)
+            self.bias_p = None if self.bias is None else self.bias.repeat_interleave(self.tc_phase.S2).contiguous()
+            self.expand_phase()
+
+    def expand_phase(self):
+        """phase weight of a transposed conv (and its planes) from the current weights"""
+        ops.tconv_expand(self.wq4(), self.tc_phase, out=self.wp)
+        self.split_planes(("wp_planes", "wp_h2"))
+
+    def split_planes(self, names=PLANE_BUFFERS):
+        """split the current weights into every plane buffer of `names` that exists"""
+        for n in names:
+            planes = getattr(self, n)
+            if planes is None:
+                continue
+            src, split = self.PLANE_BUFFERS[n]
+            w = getattr(self, src)
+            split(w() if callable(w) else w, planes)
+
+    def lin_planes(self, fwd: bool):
+        """Planes of this Linear's weight (fwd) / of its transpose (input gradient) for rdo_linear_h2: allocated on first use -- while
+        the plan is being recorded --, filled by `split_planes` (eagerly after the recording; a trainable op's then inside the plan behind
+        every step)."""
+        if self.qm.kind not in ("linear", "gdn") and not (self.qm.kind == "conv" and self.K == 1):
+            raise RuntimeError("lin_planes: a Linear, a 1x1 conv or the 1x1 pool of a GDN")
+        co, _, _, ci = self.w4
+        scale = self.plane_scale()
+        if fwd:
+            if self.lin_fwd is None:
+                self.lin_fwd = ops.H2(torch.empty((2, ci // 32, co // 16, 64, 8), device=self.w.device, dtype=torch.int16), scale)
+            return self.lin_fwd
+        if self.lin_bwd is None:
+            self.lin_bwd = ops.H2(torch.empty((2, co // 32, ci // 16, 64, 8), device=self.w.device, dtype=torch.int16), scale)
+        return self.lin_bwd
+
+    def enable_planes(self, fwd: bool, dgrad: bool, h2: bool = False):
+        """Allocate the plane buffers (called while the plan is being recorded: no kernel may run here; `split_planes` fills them once
+        eagerly after the recording, and a trainable op's again inside the plan after every AdaRound step).  h2: fp16 two-way planes of
+        w * plane_scale() for the plane-input kernels (conv_fwd_h2.hip); else the bf16 three-way planes of the fp32-input kernels."""
+        def alloc(like, cur):
+            if cur is not None:
+                if isinstance(cur, ops.H2) != h2:
+                    raise RuntimeError(f"calibration engine: op '{self.name}' needs its weight planes in two formats")
+                return cur
+            if h2:
+                return ops.H2(torch.empty((2,) + tuple(like.shape), device=like.device, dtype=torch.int16), self.plane_scale())
+            return torch.empty((3,) + tuple(like.shape), device=like.device, dtype=torch.int16)
+        if fwd:
+            self.wq_planes = alloc(self.wq, self.wq_planes)
+        if dgrad and self.wd is not None:
+            self.wd_planes = alloc(self.wd, self.wd_planes)
+
+    def wq4(self):
+        return self.wq.reshape(self.w4)
+
+    def wd4(self):
+        # [ci][kh][kw][co] for convs, gamma'^T viewed [C][1][1][C]
+        co, kh, kw, ci = self.w4
+        return self.wd.reshape(ci, kh, kw, co)
+
+
+class _Op(_Weights):
+    """Device state of one trainable QuantModule inside a unit: the AdaRound state in the kernel layout of its weight."""
 
     def __init__(self, name, qm: QuantModule, need_dgrad: bool):
-        self.name, self.qm, self.need_dgrad = name, qm, need_dgrad
+        super().__init__(qm)
+        self.name, self.need_dgrad = name, need_dgrad
         self.is_gdn = qm.kind == "gdn"
-        self.tconv = None                     # (stride, padding, output_padding) of a ConvTranspose2d unit
         self.is_ln = qm.kind == "layernorm"
         if qm.kind not in ("conv", "gdn", "tconv", "linear", "layernorm"):
             raise NotImplementedError(f"calibration engine: QuantModule kind '{qm.kind}' is not supported yet")
         wq = qm.weight_quantizer
         if not getattr(wq, "inited", True):    # (an AdaRoundQuantizer -- a unit calibrated before, in a second pass -- carries its scales)
             wq(qm.weight)                      # lazy scale init, as the reference's first forward would do
-        w = qm.org_weight.detach()
-        if qm.kind == "linear":
-            self.w = w.reshape(w.shape[0], 1, 1, w.shape[1]).contiguous()      # a Linear is a 1x1 conv over the token matrix
-        elif qm.kind == "layernorm":
-            self.w = w.reshape(1, -1).contiguous()                              # gamma: one quantisation "channel" (per tensor)
-        elif qm.kind == "tconv":
-            # a transposed conv is the forward conv kernel (stride 1, pad 0) on the zero-inserted input with the taps
-            # flipped: keep every per-weight tensor of the engine in that flipped [co][kh'][kw'][ci] layout
-            self.w = to_rows(w, tconv=True).flip(1, 2).contiguous()
+        if self.is_ln or self.is_gdn:
+            w = qm.org_weight.detach()
+            self.w = w.reshape(1, -1).contiguous() if self.is_ln else to_rows(w)     # gamma: one quantisation "channel" (per tensor) / [C,C]
+            self.rows = self.w.shape[0]
+            self.stride, self.pad, self.K = 1, 0, 1
+            self.w4 = tuple(self.w.shape) if self.is_ln else (self.rows, 1, 1, self.rows)
+            self.bias = None if (self.is_gdn or qm.bias is None) else qm.bias.detach().contiguous()
         else:
-            self.w = to_rows(w)                # OHWI or [C,C]
+            self._layout(qm.bias)
         dev = self.w.device
-        self.rows = self.w.shape[0]
         # layer-wise scales (main2.py without --channel_wise): one (delta, zero_point) repeated over the rows
         self.channel_wise = bool(wq.channel_wise)
         self.delta = wq.delta.reshape(-1).to(dev).expand(self.rows).contiguous()
         self.zp = wq.zero_point.reshape(-1).to(dev).expand(self.rows).contiguous()
         self.n_levels = wq.n_levels
-        if self.is_ln:
-            self.desc = ops.ada_desc(self.w, self.n_levels, conv_layout=False)
-            self.stride, self.pad, self.K = 1, 0, 1
-            self.w4 = tuple(self.w.shape)
-            self.bias = None if qm.bias is None else qm.bias.detach().contiguous()
-        elif qm.kind == "linear":
-            self.stride, self.pad, self.K = 1, 0, 1
-            self.desc = ops.ada_desc(self.w, self.n_levels)
-            self.w4 = tuple(self.w.shape)
-            self.bias = None if qm.bias is None else qm.bias.detach().contiguous()
-        elif self.is_gdn:
+        if self.is_gdn:
             self.inverse = bool(qm.fwd_kwargs["inverse"])
             self.beta, reparam = qm.gdn_constants()
             self.beta = self.beta.to(dev).contiguous()
             self.desc = ops.ada_desc(self.w, self.n_levels, reparam=reparam)
-            self.stride, self.pad, self.K = 1, 0, 1
-            self.w4 = (self.rows, 1, 1, self.rows)
-            self.bias = None
         else:
-            if qm.kind == "tconv":
-                kw = qm.fwd_kwargs
-                if kw["groups"] != 1 or tuple(kw["dilation"]) != (1, 1):
-                    raise NotImplementedError("calibration engine: grouped / dilated transposed convolutions")
-                self.tconv = (int(kw["stride"][0]), int(kw["padding"][0]), int(kw["output_padding"][0]))
-                self.stride, self.pad = 1, 0
-            else:
-                self.stride, self.pad = qm.conv_geometry()
-            self.K = self.w.shape[1]
-            self.desc = ops.ada_desc(self.w, self.n_levels)
-            self.w4 = tuple(self.w.shape)
-            self.bias = None if qm.bias is None else qm.bias.detach().contiguous()
+            self.desc = ops.ada_desc(self.w, self.n_levels, conv_layout=False) if self.is_ln else ops.ada_desc(self.w, self.n_levels)
         # bound of |soft-quantised weight| over the whole run (every level of every row's grid; through the GDN re-parametrisation
         # where there is one) -> the power-of-two scale of this op's fp16 weight planes
         lv = torch.maximum(self.zp.abs(), (self.n_levels - 1 - self.zp).abs()) * self.delta
@@ -184,91 +301,26 @@ class _Op:
         self.wd = torch.empty_like(self.w) if (need_dgrad or self.is_gdn) else None
         ops.adaround_init_alpha(self.desc, self.w, self.delta, self.alpha)
         ops.adaround_fwd(self.desc, self.w, self.alpha, self.delta, self.zp, True, self.wq, self.wd)
-        self.slabs = None
-        # transposed conv whose output is stride x the input: run as a stride-1 conv with the "phase weight" [Cout * s^2][K'][K'][Cin]
-        # + pixel shuffle (include/rdo_ptq_hip.h, rdo_tconv_expand) instead of zero insertion + dense conv.  The AdaRound state stays in
-        # the kernel layout of the transposed conv; the phase weight is re-expanded after every step, its gradient folded back.
-        self.tc_phase = self.wp = self.wp_planes = self.wp_h2 = self.slabs_p = self.bias_p = None
-        if self.tconv is not None:
-            s_, p_, op_ = self.tconv
-            self.tc_phase = ops.TconvPhase.get(self.K, s_, p_, op_, True, dev) if os.environ.get("RDO_TCONV_PHASE", "1") != "0" else None
-            if self.tc_phase is not None:
-                self.wp4 = self.tc_phase.w_shape(self.rows, self.w4[3])
-                self.wp = torch.empty(self.wp4, device=dev, dtype=torch.float32)
-                self.bias_p = None if self.bias is None else self.bias.repeat_interleave(self.tc_phase.S2).contiguous()
-                self.expand_phase()
-        # exact bf16 three-way splits of the kernel-layout weights, (re)made after every update for the convs that run on
-        # the split-bf16 MFMA path (large problems only; decided by the library from the activation shape)
-        self.wq_planes = self.wd_planes = None
-        self.lin_fwd = self.lin_bwd = None     # fragment-ordered fp16 planes of a Linear for rdo_linear_h2 (large token matrices)
+        self.slabs = self.slabs_p = None
+        self.dalpha = None                     # data parallel: this op's view of the unit's gradient bucket (`UnitEngine._build_ops`)
+        # phase form of a transposed conv: the AdaRound state stays in the kernel layout of the transposed conv; the phase weight is
+        # re-expanded after every step, its gradient folded back
+        if self.tconv is not None and os.environ.get("RDO_TCONV_PHASE", "1") != "0":
+            self._init_phase()
 
-    def lin_planes(self, fwd: bool):
-        """Planes of this Linear's soft weight (fwd) / of its transpose (input gradient) for rdo_linear_h2: allocated on first use -- while
-        the plan is being recorded --, filled by `refresh_planes` (eagerly after the recording, then inside the plan behind every step)."""
-        if self.qm.kind not in ("linear", "gdn") and not (self.qm.kind == "conv" and self.K == 1):
-            raise RuntimeError("lin_planes: a Linear, a 1x1 conv or the 1x1 pool of a GDN")
-        co, _, _, ci = self.w4
-        if fwd:
-            if self.lin_fwd is None:
-                self.lin_fwd = ops.H2(torch.empty((2, ci // 32, co // 16, 64, 8), device=self.w.device, dtype=torch.int16), self.wscale)
-            return self.lin_fwd
-        if self.lin_bwd is None:
-            self.lin_bwd = ops.H2(torch.empty((2, co // 32, ci // 16, 64, 8), device=self.w.device, dtype=torch.int16), self.wscale)
-        return self.lin_bwd
-
-    def enable_planes(self, fwd: bool, dgrad: bool, h2: bool = False):
-        """Allocate the plane buffers (called while the plan is being recorded: no kernel may run here; the engine fills them
-        once eagerly after recording and re-fills them inside the plan after every AdaRound step).  h2: fp16 two-way planes of
-        w * wscale for the plane-input kernels (conv_fwd_h2.hip); else the bf16 three-way planes of the fp32-input kernels."""
-        def alloc(like, cur):
-            if cur is not None:
-                if isinstance(cur, ops.H2) != h2:
-                    raise RuntimeError(f"calibration engine: op '{self.name}' needs its weight planes in two formats")
-                return cur
-            if h2:
-                return ops.H2(torch.empty((2,) + tuple(like.shape), device=like.device, dtype=torch.int16), self.wscale)
-            return torch.empty((3,) + tuple(like.shape), device=like.device, dtype=torch.int16)
-        if fwd:
-            self.wq_planes = alloc(self.wq, self.wq_planes)
-        if dgrad and self.wd is not None:
-            self.wd_planes = alloc(self.wd, self.wd_planes)
-
-    def expand_phase(self):
-        """phase weight of a transposed conv (and its bf16 planes) from the current soft weights"""
-        ops.tconv_expand(self.wq4(), self.tc_phase, out=self.wp)
-        if self.wp_planes is not None:
-            ops.split_bf16x3(self.wp, self.wp_planes)
-        if self.wp_h2 is not None:
-            ops.split_h2_conv(self.wp, planes=self.wp_h2)
+    def plane_scale(self):
+        return self.wscale
 
     def refresh_planes(self):
-        if self.lin_fwd is not None:
-            ops.split_h2_linear(self.wq4(), planes=self.lin_fwd)
-        if self.lin_bwd is not None:
-            ops.split_h2_linear(self.wd4(), planes=self.lin_bwd)
-        if self.wp_planes is not None:
-            ops.split_bf16x3(self.wp, self.wp_planes)
-        if self.wp_h2 is not None:
-            ops.split_h2_conv(self.wp, planes=self.wp_h2)
-        for planes, w4 in ((self.wq_planes, self.wq4), (self.wd_planes, self.wd4)):
-            if isinstance(planes, ops.H2):
-                ops.split_h2_conv(w4(), planes=planes)
-            elif planes is not None:
-                ops.split_bf16x3(w4(), planes)
-
-    def wq4(self):
-        return self.wq.reshape(self.w4)
-
-    def wd4(self):
-        # [ci][kh][kw][co] for convs, gamma'^T viewed [C][1][1][C]
-        co, kh, kw, ci = self.w4
-        return self.wd.reshape(ci, kh, kw, co)
+        """soft weights -> every plane buffer the recorded kernels read (the exact bf16 three-way splits of the split-bf16 MFMA path,
+        the fp16 planes of the plane-input kernels): eagerly after the recording, then inside the plan behind every step"""
+        self.split_planes()
 
     def numel(self):
         return self.w.numel()
 
 
-class UnitEngine:
+class UnitEngine(DpLoop, RdTask):
     def __init__(self, kind, modules, cache_q, cache_fp, cache_out, *, batch_size, iters, weight=0.01, b_range=(20, 2),
                  warmup=0.2, input_prob=0.5, lr=1e-3, seed=0, idx_table=None, include_act_func=True, group=None,
                  use_graph=True, force_dp_split=False, task_p=2.0, batch_offset=0, dp_overlap=None, fuse_tail=True, batch_step=True, use_h2=True, rd=None):
@@ -301,23 +353,9 @@ class UnitEngine:
         # both GEMMs would run on rdo_linear_h2; 0: the four launches
         self.gdn_fused = os.environ.get("RDO_GDN_FUSED", "1") != "0"
         self._next_gather = None
-        # opt-in R + lambda*D task loss (loss_mode='rd'): dict(model=QuantModel, unit=module, cali=calibration images NCHW on the GPU,
-        # lmbda=float, metric='mse' | 'ms-ssim' (optional, default 'mse')).  The unit output of every iteration is pushed through the
-        # REST of the wrapped model on torch's tape (hipops.autograd) and losses.RateDistortionLoss is differentiated back to it;
-        # rec_loss stays the lp term.
-        self.rd = rd
+        self._rd_init(rd, include_act_func)    # opt-in R + lambda*D task loss (loss_mode='rd', engine_rd.RdTask): separate kernels, fp32
         if rd is not None:
-            metric = rd.get("metric", "mse")
-            if metric not in ("mse", "ms-ssim"):
-                raise ValueError(f"loss_mode='rd': unknown metric {metric!r} ('mse' or 'ms-ssim')")
-            if metric == "ms-ssim" and min(rd["cali"].shape[-2:]) <= 160:
-                raise ValueError(f"loss_mode='rd' with metric 'ms-ssim' needs calibration crops with both sides above 160 pixels (five "
-                                 f"scales of an 11-tap window); got {tuple(rd['cali'].shape[-2:])}")
-            if not include_act_func:
-                raise NotImplementedError("calibration engine: loss_mode='rd' substitutes the unit's module OUTPUT (after its fused "
-                                          "activation); include_act_func=False optimises the pre-activation and cannot be combined with it")
-            fuse_tail = use_h2 = False
-            self.use_h2 = False
+            fuse_tail = self.use_h2 = False
         self.fuse_tail = bool(fuse_tail)       # False: the separate epilogue / loss / activation-backward kernels (A/B, tests)
         self.dev = cache_q.device
         n = cache_q.shape[0]
@@ -348,13 +386,7 @@ class UnitEngine:
             self.world = torch.distributed.get_world_size(group)
         # the data-parallel op sequence (grad -> all-reduce -> apply) can be forced on a single rank to test it
         self.split = self.world > 1 or force_dp_split
-        self.dp_path = None                    # "graph" | "host" once a data-parallel run has started (_run_dp)
-        self._dp_graph, self._dp_graph_failed = None, False
-        self.dp_fallbacks = 0                  # captures the ranks agreed to drop (this unit then runs the host loop on every rank)
-        self._hb_dev = self._hb_host = None    # heartbeat of the captured loop (`_dp_capture`)
-        self._hb_issued = 0
-        self.rd_path = None                    # "graph" | "host" once an R + lambda*D run has started (_run_rd)
-        self._rd_graph, self._rd_graph_failed = None, False
+        self._dp_init()
         # this unit's own fp16-overflow word (rdo_h2_bind_flag): raised by every H2 producer of its plans, polled during long runs
         # (pairs: finite magnitude, non-finite mark; pair 0 for the weight planes, one pair per activation tensor kept as planes)
         self._ovf = torch.zeros(2 * self.OVF_PAIRS, dtype=torch.int32, device=self.dev)
@@ -370,10 +402,14 @@ class UnitEngine:
             self._amax = {}                    # ... and the magnitude it was derived from
             self._probing = False
             self._probe_scales()
-            self._record()
-            for op in self.ops.values():
-                op.refresh_planes()      # initial soft weights -> bf16 planes (eager, before the first iteration)
-            self._prime()                # folded gather: the mini-batch of iteration 0
+            self._start()
+
+    def _start(self):
+        """record the plans at the current scales and make the unit ready for the iteration its counter stands at"""
+        self._record()
+        for op in self.ops.values():
+            op.refresh_planes()          # current soft weights -> planes (eager, before the first iteration)
+        self._prime()                    # folded gather: the mini-batch of that iteration
 
     # ------------------------------------------------------------------------------------------------------------------
     def _build_ops(self):
@@ -422,7 +458,7 @@ class UnitEngine:
         return torch.empty(shape, device=self.dev, dtype=torch.float32)
 
     def _out_hw(self, op, H, W):
-        return (H + 2 * op.pad - op.K) // op.stride + 1, (W + 2 * op.pad - op.K) // op.stride + 1
+        return conv_out_hw(H, W, op.K, op.stride, op.pad)
 
     def _alloc(self):
         B = self.B
@@ -437,13 +473,9 @@ class UnitEngine:
                 t["yp"] = self._buf(B, H, W, op.wp4[0])
                 t["dyp"] = self._buf(B, H, W, op.wp4[0])
             elif op.tconv is not None:
-                s_, p_, op_ = op.tconv
-                q_ = op.K - 1 - p_
-                if q_ < 0:
-                    raise NotImplementedError("calibration engine: transposed conv with padding > kernel_size - 1")
-                Hu, Wu = (H - 1) * s_ + 1 + 2 * q_ + op_, (W - 1) * s_ + 1 + 2 * q_ + op_
+                q_, Hu, Wu = zero_insert_hw(H, W, op.K, *op.tconv)
                 t["xu"] = self._buf(B, Hu, Wu, Cin)
-                self.tc_geom = (s_, q_, Hu, Wu)
+                self.tc_geom = (op.tconv[0], q_, Hu, Wu)
                 Ho, Wo = Hu - op.K + 1, Wu - op.K + 1
             elif op.is_gdn:
                 Ho, Wo = H, W
@@ -632,12 +664,8 @@ class UnitEngine:
         for op in self.ops.values():
             if op.tc_phase is not None:
                 op.expand_phase()
-            if lin_done:
-                continue
-            if op.lin_fwd is not None:                     # Linears on rdo_linear_h2: fragment-ordered planes of the new soft weights
-                ops.split_h2_linear(op.wq4(), planes=op.lin_fwd)
-            if op.lin_bwd is not None:
-                ops.split_h2_linear(op.wd4(), planes=op.lin_bwd)
+            if not lin_done:
+                op.split_planes(("lin_fwd", "lin_bwd"))    # Linears on rdo_linear_h2: fragment-ordered planes of the new soft weights
 
     def _loss(self, pred, grad):
         if self.rd is not None:
@@ -1086,7 +1114,7 @@ class UnitEngine:
         for op in self.ops.values():
             ops.adaround_init_alpha(op.desc, op.w, op.delta, op.alpha)
             op.m.zero_(); op.v.zero_()
-            op.wq_planes = op.wd_planes = op.wp_h2 = op.wp_planes = op.lin_fwd = op.lin_bwd = None
+            op.drop_planes()
         self._set_weights(soft=True)
         self.P, self._ovf_slot = {}, {}
         self._clear_probe()
@@ -1094,10 +1122,7 @@ class UnitEngine:
         self._done = 0
         self._ovf_checked = -1
         self._dp_graph = self._rd_graph = None
-        self._record()
-        for op in self.ops.values():
-            op.refresh_planes()
-        self._prime()
+        self._start()
 
     def _check_overflow(self):
         """Where results leave the engine: an overflow not yet seen by the polls of `run` is handled here.  COLLECTIVE under data
@@ -1134,7 +1159,7 @@ class UnitEngine:
     def _items(self, opl):
         # (lin_fwd / lin_bwd: the fragment-ordered planes of a Linear / GDN gamma on rdo_linear_h2 -- written by the step's own launch)
         return [dict(d=op.desc, w=op.w, delta=op.delta, zp=op.zp, slabs=op.slabs, alpha=op.alpha, m=op.m, v=op.v, wq=op.wq, wd=op.wd,
-                     wq_planes=op.wq_planes, wd_planes=op.wd_planes, dalpha=getattr(op, "dalpha", None),
+                     wq_planes=op.wq_planes, wd_planes=op.wd_planes, dalpha=op.dalpha,
                      lin_fwd=op.lin_fwd, lin_bwd=op.lin_bwd) for op in opl]
 
     STEP_BATCH = 8          # weight tensors per rdo_adaround_step_batch launch (kMaxBatch of adaround.hip)
@@ -1317,346 +1342,6 @@ class UnitEngine:
             self.plan_a.prepare(k)
             if n % k:
                 self.plan_a.prepare(n % k)
-
-    def _dp_iteration(self, graph, first=True, last=True):
-        """One data-parallel iteration on the current stream: plan A -> all-reduce of the front of the bucket (asynchronous, on the
-        process group's stream) overlapped with plan A2 = the last weight gradient -> all-reduce of the rest -> plan B.
-        Inside a host-driven run of several iterations plan B of iteration i and plan A of iteration i + 1 go out as ONE graph launch
-        (`first=False`: plan A was enqueued with the previous iteration's plan B; `last=False`: enqueue the next plan A with this
-        plan B): two host enqueues per iteration and collective instead of three -- the small units are host-bound in this loop."""
-        if first:
-            self.plan_a.run(1, graph=graph)
-        self.bucket.reduce(between=None if self.plan_a2 is None else (lambda: self.plan_a2.run(1, graph=graph)))
-        if last:
-            self.plan_b.run(1, graph=graph)
-        else:
-            self.plan_b.run_then(self.plan_a, graph=graph)
-
-    # backends whose collectives can be captured into a graph (torch's "nccl" = RCCL on ROCm); a test adds "gloo" to exercise the agreement
-    DP_GRAPH_BACKENDS = ("nccl",)
-    DP_HB_BATCH = 32                                                   # captured replays between two looks at the heartbeat
-    DP_STALL_S = float(os.environ.get("RDO_DP_STALL_S", 120))          # no heartbeat for this long = the captured loop hangs
-
-    def _dp_capture(self):
-        """One data-parallel iteration -- the recorded kernels of the plans AND the collectives -- as one graph, closed by the heartbeat:
-        a device counter incremented and copied to pinned host memory by the graph's last two nodes.  torch's NCCL watchdog does not see
-        collectives replayed from a graph; the heartbeat is what tells the host that replays still complete (`_hb_wait`)."""
-        if self._hb_dev is None:
-            self._hb_dev = torch.zeros(1, dtype=torch.int64, device=self.dev)
-            self._hb_host = torch.zeros(1, dtype=torch.int64).pin_memory()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self._dp_iteration(False)
-            self._hb_dev.add_(1)
-            self._hb_host.copy_(self._hb_dev, non_blocking=True)
-        return g
-
-    def _hb_wait(self, target):
-        """Block until `target` captured replays have completed (heartbeat in pinned memory: no device synchronisation, which would hang
-        with the loop).  No progress for DP_STALL_S seconds -> `DpStallError`: the process cannot recover a hung collective; the
-        application decides (bench.py exits with status 86 and its launcher / supervisor starts FRESH children on the host loop)."""
-        import time
-        if self._hb_host is None or target <= 0:
-            return
-        seen, t_last = int(self._hb_host[0]), time.monotonic()
-        while seen < target:
-            time.sleep(0.0005)
-            now = int(self._hb_host[0])
-            if now != seen:
-                seen, t_last = now, time.monotonic()
-            elif time.monotonic() - t_last > self.DP_STALL_S:
-                raise DpStallError(f"rank {self._rank()}: the captured data-parallel loop made no progress for {self.DP_STALL_S:.0f} s "
-                                   f"({seen} of {self._hb_issued} replays completed) -- a collective inside the graph hangs")
-
-    def dp_drain(self):
-        """Wait (heartbeat, with the stall deadline) for every captured replay issued so far: call it before anything that synchronises
-        the device behind a data-parallel run -- a plain synchronisation behind a hung graph would never return."""
-        if self._dp_graph is not None:
-            self._hb_wait(self._hb_issued)
-
-    def _run_dp(self, n):
-        """n data-parallel iterations.  With the RCCL backend (round 5: the DEFAULT; `RDO_DP_GRAPH=0` keeps the host loop) the whole
-        iteration -- the recorded kernels of the three plans AND the collectives -- is captured once per unit into ONE graph
-        (torch.cuda.graph) and replayed with no host work in between: the host-driven loop (plan A -> all-reduce -> plan B, each plan
-        a graph replay, the collective enqueued by torch.distributed in between) costs two to three enqueues per unit-iteration, which
-        the sixteen <= 50-us units cannot hide (+13 % on one rank against +5 % captured, `extra.dp_overhead_one_rank` of the bench
-        line re-measures both on every run).  The ranks AGREE on the outcome of the capture (MIN all-reduce of an "ok" flag) before
-        anyone replays: a rank never replays a graph with collectives while another runs the host loop; a unit whose capture fails
-        on any rank runs the host loop on every rank (`dp_fallbacks` counts them).  The eager iteration in front of the capture is
-        OUTSIDE the try: it is an ordinary iteration on every rank whatever the capture does afterwards, so all ranks run the same
-        number of iterations (an exception in it is a real failure and propagates).  Replays are watched through a heartbeat
-        (`_dp_capture`, `_hb_wait`).  Other backends (gloo in the CPU / one-GPU tests): host loop.  `self.dp_path` says which loop
-        ran ("graph" / "host"); every rank logs it, the bench line carries it per unit."""
-        import logging
-        dist = torch.distributed
-        comm = self.world > 1 or (dist.is_available() and dist.is_initialized())
-        want = (self.use_graph and os.environ.get("RDO_DP_GRAPH", "1") == "1" and comm
-                and dist.get_backend(self.group) in self.DP_GRAPH_BACKENDS)
-        if want and self._dp_graph is None and not self._dp_graph_failed and n > 1:
-            self._dp_iteration(False)                               # one eager iteration: warms RCCL and every lazy initialisation
-            n -= 1
-            ok, g = 1, None
-            try:
-                g = self._dp_capture()
-            except Exception as e:      # pragma: no cover - depends on the RCCL / driver stack
-                logging.warning("rank %s: data-parallel iteration could not be captured into a graph (%s)", self._rank(), e)
-                ok = 0
-                torch.cuda.synchronize()
-            if comm:
-                flag = torch.tensor([ok], device=self.dev, dtype=torch.int32)
-                dist.all_reduce(flag, op=dist.ReduceOp.MIN, group=self.group)
-                ok = int(flag.item())
-            if ok:
-                self._dp_graph, self._hb_issued = g, 0
-                self._hb_dev.zero_()
-                self._hb_host.zero_()
-            else:
-                self._dp_graph_failed = True
-                self.dp_fallbacks += 1
-                del g
-        path = "graph" if self._dp_graph is not None else "host"
-        if self.dp_path != path:
-            self.dp_path = path
-            logging.getLogger("rdo_ptq.dp").info("rank %s: data-parallel loop = %s (world %d)", self._rank(), path, self.world)
-        if self._dp_graph is not None:
-            for _ in range(n):
-                self._dp_graph.replay()
-                self._hb_issued += 1
-                if self._hb_issued % self.DP_HB_BATCH == 0:         # at most two batches queued: the GPU stays fed, a hang is seen
-                    self._hb_wait(self._hb_issued - self.DP_HB_BATCH)
-            return
-        merge = self.use_graph and os.environ.get("RDO_DP_MERGE", "1") != "0"
-        for i in range(n):
-            self._dp_iteration(self.use_graph, first=(i == 0 or not merge), last=(i == n - 1 or not merge))
-
-    def _rank(self):
-        dist = torch.distributed
-        return dist.get_rank(self.group) if (dist.is_available() and dist.is_initialized()) else 0
-
-    def _rd_iteration(self, graph):
-        """One iteration of the R + lambda*D mode on the current stream: plan A (gather, unit forward, rec_loss and its gradient) ->
-        the task term (the whole model behind the unit, `_rd_tail`) -> plan RD (+ g_task, backward, AdaRound step -- or, data
-        parallel, the gradient bucket) [-> all-reduce -> plan B]."""
-        self.plan_a.run(1, graph=graph)
-        self._rd_tail()
-        self.plan_rd.run(1, graph=graph)
-        if self.split:
-            self.bucket.reduce()
-            self.plan_b.run(1, graph=graph)
-
-    def _run_rd(self, n):
-        """n iterations of the R + lambda*D mode.  Single process with graphs on: the WHOLE iteration -- the recorded kernels of both
-        plans and the model tail with its autograd backward (every op of which is a device-side kernel: the mini-batch rows are
-        selected with the device iteration counter) -- is captured once into one graph (torch.cuda.graph) and replayed, no host work
-        per iteration.  `RDO_RD_GRAPH=0`, a refused capture, or the data-parallel split (a collective per iteration): host-driven."""
-        import logging
-        want = self.use_graph and not self.split and os.environ.get("RDO_RD_GRAPH", "1") != "0"
-        if want and self._rd_graph is None and not self._rd_graph_failed and n > 2:
-            self._rd_iteration(False)                 # eager: every lazy initialisation (scratch buffers, kernel attributes, autograd)
-            n -= 1
-            torch.cuda.synchronize()
-            try:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self._rd_iteration(False)
-                self._rd_graph = g
-            except Exception as e:      # pragma: no cover - depends on the driver stack
-                logging.warning("R + lambda*D iteration could not be captured into a graph (%s): host-driven loop", e)
-                self._rd_graph_failed = True
-                torch.cuda.synchronize()
-        self.rd_path = "graph" if self._rd_graph is not None else "host"
-        if self._rd_graph is not None:
-            for _ in range(n):
-                self._rd_graph.replay()
-            return
-        for _ in range(n):
-            self._rd_iteration(self.use_graph)
-
-    # ---- R + lambda*D: what does not depend on this unit is computed once per calibration image -----------------------------------
-    RD_CACHE_LIMIT = 8 << 30            # bytes of cached module outputs per unit (a coder's latent for 256 images is 50-100 MB)
-
-    @staticmethod
-    def _tree(fn, t):
-        if torch.is_tensor(t):
-            return fn(t)
-        if isinstance(t, dict):
-            return {k: UnitEngine._tree(fn, v) for k, v in t.items()}
-        if isinstance(t, (tuple, list)):
-            return type(t)(UnitEngine._tree(fn, v) for v in t)
-        return t
-
-    def _rd_prepare(self):
-        """Modules of the wrapped model whose INPUTS do not depend on this unit's output produce the same output for an image in every
-        iteration (weights behind and before the unit are fixed for the unit's run): found by running the model twice on one
-        mini-batch with two different random tensors in place of the unit's output, on torch's tape: a candidate is independent when
-        its inputs are bit-equal in both runs AND none of them carries a grad_fn back to the substituted tensor (values alone are not
-        enough: two different hyper-latents can round to the same z^; the tape alone is not either: a detached activation
-        quantiser cuts it).  Independent modules are evaluated ONCE per calibration image (in mini-batches of B, the shape the iterations run at) and looked up by row afterwards.
-        Candidates: the children of the model (the coders and entropy models) that do not contain the unit.  Inside the coder that
-        does, the modules in front of the unit in an nn.Sequential only feed the unit, whose forward is replaced: they are skipped.
-        A candidate holding a live dynamic activation quantiser (statistics over the mini-batch) is left alone.  `RDO_RD_CACHE=0`
-        turns all of this off."""
-        rd = self.rd
-        rd["memo"], rd["skip"] = {}, []
-        if os.environ.get("RDO_RD_CACHE", "1") == "0":
-            return
-        from .quant_block import BaseQuantBlock
-        from .quant_layer import QuantModule
-        model, unit, cali = rd["model"], rd["unit"], rd["cali"]
-        root = model.model if isinstance(getattr(model, "model", None), torch.nn.Module) else model
-        holds = lambda m: any(c is unit for c in m.modules())
-        cands = []
-        for _, child in root.named_children():
-            if not holds(child):
-                cands.append(child)
-                continue
-            box = child
-            while box is not unit and isinstance(box, torch.nn.Sequential):       # descend to the unit: skip what only feeds it
-                kids = list(box.children())
-                k = next(i for i, c in enumerate(kids) if holds(c))
-                rd["skip"] += kids[:k]
-                box = kids[k]
-        live_aq = lambda m: any(isinstance(c, (QuantModule, BaseQuantBlock)) and c.use_act_quant and c.trained
-                                and not getattr(c, "disable_act_quant", False) for c in m.modules())
-        cands = [c for c in cands if not live_aq(c)]
-        if not cands:
-            return
-        was_training = model.training
-        model.eval()
-        B = self.B
-        shape = tuple(self._rd_pred.permute(0, 3, 1, 2).shape)
-        seen = [{}, {}]
-        try:
-            tainted = set()
-
-            def note(m, a, k, run):
-                flag = [False]
-                self._tree(lambda t: flag.__setitem__(0, flag[0] or t.requires_grad), (a, k))
-                if flag[0] or id(m) in seen[run]:
-                    # depends on the unit -- or is called more than once per model forward (a shared / looped module): its outputs
-                    # could not be told apart by image row, so it is never memoised
-                    tainted.add(id(m))
-                seen[run][id(m)] = self._tree(lambda t: t.detach().clone(), (a, k))
-            for run in range(2):
-                fake = torch.randn(shape, device=self.dev, generator=torch.Generator(device=self.dev).manual_seed(17 + run)).requires_grad_(True)
-                hooks = [c.register_forward_pre_hook(lambda m, a, k, run=run: note(m, a, k, run), with_kwargs=True) for c in cands]
-                unit.forward = lambda *a, fake=fake, **k: fake
-                for s_ in rd["skip"]:
-                    s_.forward = lambda x, *a, **k: x
-                try:
-                    with torch.enable_grad():
-                        model(cali[:B])
-                finally:
-                    for h in hooks:
-                        h.remove()
-                    del unit.forward
-                    for s_ in rd["skip"]:
-                        del s_.forward
-            with torch.no_grad():
-
-                def same(a, b):
-                    if torch.is_tensor(a):
-                        return torch.is_tensor(b) and a.shape == b.shape and bool(torch.equal(a, b))
-                    if isinstance(a, dict):
-                        return isinstance(b, dict) and a.keys() == b.keys() and all(same(a[k], b[k]) for k in a)
-                    if isinstance(a, (tuple, list)):
-                        return isinstance(b, (tuple, list)) and len(a) == len(b) and all(same(x, y) for x, y in zip(a, b))
-                    return a == b
-                free = [c for c in cands if id(c) in seen[0] and id(c) in seen[1] and id(c) not in tainted and same(seen[0][id(c)], seen[1][id(c)])]
-                seen = None
-                if not free:
-                    return
-                # one pass over the calibration images: outputs of the unit-independent modules, image-major
-                parts = {id(c): [] for c in free}
-                hooks = [c.register_forward_hook(lambda m, a, o: parts[id(m)].append(self._tree(lambda t: t.detach().clone(), o))) for c in free]
-                unit.forward = lambda *a, **k: torch.zeros(shape, device=self.dev)
-                for s_ in rd["skip"]:
-                    s_.forward = lambda x, *a, **k: x
-                try:
-                    n = cali.shape[0]
-                    n_fwd = 0
-                    for i in range(0, n, B):
-                        xb = cali[i:i + B]
-                        if xb.shape[0] < B:                                   # ragged end: pad the mini-batch with the first images
-                            xb = torch.cat([xb, cali[:B - xb.shape[0]]])
-                        model(xb)
-                        n_fwd += 1
-                finally:
-                    for h in hooks:
-                        h.remove()
-                    del unit.forward
-                    for s_ in rd["skip"]:
-                        del s_.forward
-
-                def cat(chunks):
-                    first = chunks[0]
-                    if torch.is_tensor(first):
-                        return torch.cat(chunks)[:n] if first.dim() > 0 and first.shape[0] == B else None
-                    if isinstance(first, dict):
-                        out = {k: cat([c[k] for c in chunks]) for k in first}
-                        return None if any(v is None for v in out.values()) else out
-                    if isinstance(first, (tuple, list)):
-                        out = [cat([c[j] for c in chunks]) for j in range(len(first))]
-                        return None if any(v is None for v in out) else type(first)(out)
-                    return None
-                total = 0
-                for c in free:
-                    chunks = parts.pop(id(c))
-                    if len(chunks) != n_fwd:                                  # exactly one call per model forward, or the rows of the
-                        continue                                              # concatenation would not be the calibration images
-                    memo = cat(chunks)
-                    if memo is None:
-                        continue                                              # an output that is not per-image: leave the module alone
-                    nbytes = [0]
-                    self._tree(lambda v: nbytes.__setitem__(0, nbytes[0] + v.numel() * v.element_size()), memo)
-                    if total + nbytes[0] > self.RD_CACHE_LIMIT:
-                        continue
-                    total += nbytes[0]
-                    rd["memo"][c] = memo
-        finally:
-            model.train(was_training)
-
-    def _rd_tail(self):
-        """The current iteration's task loss: the images of the mini-batch through the wrapped model with this unit's output replaced
-        by the engine's soft-quantised output, `RateDistortionLoss` (lambda * 255^2 * MSE + bpp, or lambda * (1 - MS-SSIM) + bpp with
-        rd['metric'] = 'ms-ssim') on the result, gradient back to that
-        output (HIP kernels under torch's tape: hipops.autograd; the factorised prior and the Gaussian conditional included).  The
-        modules behind the unit are whatever the calibration flow left them: trained ones hard-quantised, the others full precision
-        (layer_opt.py:15-43).  Device-side throughout (capturable): the mini-batch rows come from the index table through the device
-        iteration counter."""
-        from losses.losses import RateDistortionLoss
-        rd = self.rd
-        it = self.it.long()                                                   # [1], published by this iteration's gather
-        rows = self.idx.index_select(0, it).view(-1).long()
-        x = rd["cali"].index_select(0, rows)
-        leaf = self._rd_pred.permute(0, 3, 1, 2).detach().requires_grad_(True)
-        if "memo" not in rd:
-            self._rd_prepare()
-        was_training = rd["model"].training
-        rd["model"].eval()
-        patched = [rd["unit"]]
-        rd["unit"].forward = lambda *a, **k: leaf      # the unit itself is not run: its output is the engine's
-        for m_ in rd["skip"]:                          # ... nor what only feeds it
-            m_.forward = lambda x_, *a, **k: x_
-            patched.append(m_)
-        for m_, memo in rd["memo"].items():            # ... and what does not depend on it is looked up per image
-            m_.forward = lambda *a, memo=memo, **k: self._tree(lambda t: t.index_select(0, rows), memo)
-            patched.append(m_)
-        try:
-            with torch.enable_grad():
-                out = rd["model"](x)
-                loss = RateDistortionLoss(lmbda=rd["lmbda"], metric=rd.get("metric", "mse"))(out, x)["loss"]
-                # (a tape cut on EVERY path from the unit's output leaves a loss without a grad_fn: the same finding as a gradient of None)
-                g = torch.autograd.grad(loss, [leaf], allow_unused=True)[0] if loss.requires_grad else None
-        finally:
-            for m_ in patched:
-                del m_.forward
-            rd["model"].train(was_training)
-        if g is None:
-            raise RuntimeError("loss_mode='rd': no gradient reached the unit's output -- a module behind it detaches the tape (dynamic "
-                               "activation quantisers of trained modules do); run the RD task loss with act_quant=False")
-        self.g_task.copy_(g.permute(0, 2, 3, 1))
-        self.task_log.view(-1).index_add_(0, it * L.LOG_SLOTS, loss.detach().reshape(1))
 
     def _data_terms(self):
         """(rec, task) per iteration on the device, averaged over the data-parallel ranks."""

@@ -13,7 +13,8 @@ that issues its backward kernels; the closures run in reverse after the two loss
 the tensor they belong to; a second contribution to the same tensor goes through a temporary and `rdo_add`.
 
 Tokens stay in natural pixel order ([B, H, W, C] == [B, L, C]); Linears run on the conv kernels as 1x1 convolutions (bf16x6
-split-precision path for the large ones), the attention core / LayerNorm / GELU on csrc/swin.hip."""
+split-precision path for the large ones), the attention core / LayerNorm / GELU on csrc/swin.hip.  The frozen weights of the tail
+(`_FpOp`) take their kernel layouts, plane buffers and geometry from the same `engine._Weights` as the trainable ops."""
 import os
 from collections import OrderedDict
 
@@ -25,104 +26,49 @@ from hipops.autograd import LIN_H2_MIN_ROWS
 from hipops.plan import Plan
 
 from . import dp
-from .engine import UnitEngine, _Op
+from .engine import UnitEngine, _Op, _Weights, conv_out_hw, zero_insert_hw
 from .quant_layer import QuantModule
-from .quantizer import to_rows
 
 
-class _FpOp:
-    """Frozen full-precision parameters of one conv / transposed conv / linear of the tail, in the kernels' layouts.
-    Quacks like `_Op` for UnitEngine._conv / ._dgrad (wq4, wd4, bias, stride, pad, K, plane buffers)."""
-    is_gdn = False
+class _FpOp(_Weights):
+    """Frozen full-precision parameters of one conv / transposed conv / linear of the tail, in the kernels' layouts: what
+    UnitEngine._conv / ._dgrad take in place of an `_Op`, plus the layouts of its input gradient where that is not a 'same' conv."""
     slabs = None
 
     def __init__(self, qm: QuantModule):
-        self.qm, self.kind = qm, qm.kind
-        w = qm.org_weight.detach()
-        self.bias = None if qm.org_bias is None else qm.org_bias.detach().contiguous()
-        self.tconv = self.tc_phase = None
-        if qm.kind == "linear":
-            self.w = w.reshape(w.shape[0], 1, 1, w.shape[1]).contiguous()
-            self.stride, self.pad = 1, 0
-        elif qm.kind == "conv":
-            self.w = to_rows(w)
-            self.stride, self.pad = qm.conv_geometry()
-        elif qm.kind == "tconv":
-            kw = qm.fwd_kwargs
-            self.tconv = (int(kw["stride"][0]), int(kw["padding"][0]), int(kw["output_padding"][0]))
-            self.w = to_rows(w, tconv=True).flip(1, 2).contiguous()      # forward = stride-1 conv on the zero-inserted input
-            self.stride, self.pad = 1, 0
-            self.w_bwd = w.permute(0, 2, 3, 1).contiguous()              # dgrad = strided conv of dy with [Cin_t][kh][kw][Cout_t]
-            # forward without zero insertion where the geometry allows: stride-1 conv with the phase weight + pixel shuffle
-            self.tc_phase = ops.TconvPhase.get(self.w.shape[1], *self.tconv, True, self.w.device)
-            if self.tc_phase is not None:
-                # (a tail op is built while the engine's plan is being RECORDED: the derived weight must exist before `fill_planes`
-                # splits it, i.e. be computed now and not as a recorded op of every iteration)
-                with Plan.eager():
-                    self.wp = ops.tconv_expand(self.w, self.tc_phase)
-                self.bias_p = None if self.bias is None else self.bias.repeat_interleave(self.tc_phase.S2).contiguous()
-        else:
+        if qm.kind not in ("linear", "conv", "tconv"):
             raise NotImplementedError(f"tail stage of kind '{qm.kind}'")
-        self.K = self.w.shape[1]
-        self.w4 = tuple(self.w.shape)
+        super().__init__(qm)
+        self.kind = qm.kind
+        self._layout(qm.org_bias)
+        self.wq = self.w                                                     # frozen: the weight the kernels read is the weight
+        self._lin_scale = None
         self.same = self.tconv is None and self.stride == 1 and 2 * self.pad == self.K - 1
-        if self.same:
+        if self.tconv is not None:
+            self.w_bwd = qm.org_weight.detach().permute(0, 2, 3, 1).contiguous()  # dgrad = strided conv of dy with [Cin_t][kh][kw][Cout_t]
+            # forward without zero insertion where the geometry allows.  (A tail op is built while the engine's plan is being RECORDED:
+            # the derived weight must exist before `fill_planes` splits it, i.e. be computed now and not as a recorded op of every iteration)
+            with Plan.eager():
+                self._init_phase()
+        elif self.same:
             self.wd = self.w.flip(1, 2).permute(3, 1, 2, 0).contiguous()         # [ci][kh'][kw'][co], taps flipped
-        elif self.tconv is None:
+        else:
             # dgrad of a strided conv = transposed conv of dy: stride-1 conv of the zero-inserted dy with this layout
             self.w_bwd = self.w.permute(3, 1, 2, 0).flip(1, 2).contiguous()       # [ci][kh'][kw'][co]
             # ... or, where that transposed conv's output is stride x its input (k = 3 / s = 2 / p = 1 of models/nic_cvt.py on even
-            # sizes), its phase form: a stride-1 conv of dy itself with the phase weight + pixel shuffle -- no zero insertion, a quarter
-            # of the multiply-adds, and a shape the split-precision kernel takes (decided per problem in `_fp_conv`)
+            # sizes), its phase form: a stride-1 conv of dy itself with the phase weight `wbp` + pixel shuffle -- no zero insertion, a
+            # quarter of the multiply-adds, and a shape the split-precision kernel takes (decided per problem in `_fp_conv`)
             self.bw_phase_of = lambda opad: ops.TconvPhase.get(self.K, self.stride, self.pad, opad, False, self.w.device)
-            self.wbp = self.wbp_planes = None
-        self.wq_planes = self.wd_planes = None
-        self.lin_fwd = self.lin_bwd = None
 
-    def lin_planes(self, fwd: bool):
-        """Frozen Linear for rdo_linear_h2: planes of W (fwd) / W^T (input gradient), allocated here (possibly inside a recording),
-        filled by `fill_planes` once the recording is over.  Scale: a power of two from the weight's own magnitude (a torch reduction:
-        not a recorded op)."""
-        co, _, _, ci = self.w4
-        if getattr(self, "_lin_scale", None) is None:
+    def plane_scale(self):
+        """a power of two from the weight's own magnitude, on first use (a torch reduction: it synchronises, and is not a recorded op)"""
+        if self._lin_scale is None:
             self._lin_scale = ops.pow2_scale(self.w.abs().max())
-        if fwd:
-            if self.lin_fwd is None:
-                self.lin_fwd = ops.H2(torch.empty((2, ci // 32, co // 16, 64, 8), device=self.w.device, dtype=torch.int16), self._lin_scale)
-            return self.lin_fwd
-        if self.lin_bwd is None:
-            self.lin_bwd = ops.H2(torch.empty((2, co // 32, ci // 16, 64, 8), device=self.w.device, dtype=torch.int16), self._lin_scale)
-        return self.lin_bwd
-
-    def wq4(self):
-        return self.w
-
-    def wd4(self):
-        return self.wd
-
-    def enable_planes(self, fwd, dgrad):
-        """Called while the plan is being recorded: allocate only; `fill_planes` runs eagerly afterwards (weights are frozen)."""
-        if fwd and self.wq_planes is None:
-            self.wq_planes = torch.empty((3,) + tuple(self.w.shape), device=self.w.device, dtype=torch.int16)
-        if dgrad and self.wd_planes is None and getattr(self, "wd", None) is not None:
-            self.wd_planes = torch.empty((3,) + tuple(self.wd.shape), device=self.wd.device, dtype=torch.int16)
+        return self._lin_scale
 
     def fill_planes(self):
-        if self.lin_fwd is not None:
-            ops.split_h2_linear(self.w, planes=self.lin_fwd)
-        if self.lin_bwd is not None:
-            ops.split_h2_linear(self.wd, planes=self.lin_bwd)
-        if getattr(self, "wp_planes", None) is not None:
-            ops.split_bf16x3(self.wp, self.wp_planes)
-        if getattr(self, "wbp_planes", None) is not None:
-            ops.split_bf16x3(self.wbp, self.wbp_planes)
-        if self.wq_planes is not None:
-            ops.split_bf16x3(self.w, self.wq_planes)
-        if self.wd_planes is not None:
-            ops.split_bf16x3(self.wd, self.wd_planes)
-
-    def refresh_planes(self):
-        pass
+        """the plane buffers the recording allocated, filled once it is over (the weights are frozen)"""
+        self.split_planes()
 
 
 class _Ln:
@@ -397,7 +343,7 @@ class TapeEngine(UnitEngine):
         self._fp.append(p)
         B, H, W, _ = x.shape
         if p.tconv is None:
-            Ho, Wo = (H + 2 * p.pad - p.K) // p.stride + 1, (W + 2 * p.pad - p.K) // p.stride + 1
+            Ho, Wo = conv_out_hw(H, W, p.K, p.stride, p.pad)
             y = self._buf(B, Ho, Wo, p.w4[0])
             self._conv(p, x, y)
 
@@ -407,8 +353,7 @@ class TapeEngine(UnitEngine):
                 if p.same:
                     self._dgrad(p, dy, dx)
                 else:
-                    q = p.K - 1 - p.pad
-                    opad = H - ((Ho - 1) * p.stride - 2 * p.pad + p.K)
+                    opad = H - ops.tap_out_size(Ho, p.K, p.stride, p.pad, True)
                     ph = p.bw_phase_of(opad) if H == Ho * p.stride and W == Wo * p.stride else None
                     if ph is not None:
                         if p.wbp is None:                    # [s^2 Cin][K'][K'][Cout] from the weight read as a transposed conv's
@@ -420,7 +365,7 @@ class TapeEngine(UnitEngine):
                         ops.conv2d_fwd(dy, p.wbp, None, 1, ph.pad, out=dp, wplanes=p.wbp_planes)
                         self._shuffle(dp, p.stride, dx)
                     else:
-                        Hu, Wu = (Ho - 1) * p.stride + 1 + 2 * q + opad, (Wo - 1) * p.stride + 1 + 2 * q + opad
+                        q, Hu, Wu = zero_insert_hw(Ho, Wo, p.K, p.stride, p.pad, opad)
                         du = self._buf(B, Hu, Wu, p.w4[0])
                         ops.zero_insert(dy, p.stride, q, q, Hu, Wu, out=du)
                         ops.conv2d_fwd(du, p.w_bwd, None, 1, 0, out=dx)
@@ -430,14 +375,13 @@ class TapeEngine(UnitEngine):
         if p.tc_phase is not None:
             ph = p.tc_phase
             yp = self._buf(B, H, W, p.wp.shape[0])
-            if ops.uses_bf16x6(tuple(x.shape), tuple(p.wp.shape), 1, ph.pad) and getattr(p, "wp_planes", None) is None:
+            if ops.uses_bf16x6(tuple(x.shape), tuple(p.wp.shape), 1, ph.pad) and p.wp_planes is None:
                 p.wp_planes = torch.empty((3,) + tuple(p.wp.shape), device=self.dev, dtype=torch.int16)
-            ops.conv2d_fwd(x, p.wp, p.bias_p, 1, ph.pad, out=yp, wplanes=getattr(p, "wp_planes", None))
+            ops.conv2d_fwd(x, p.wp, p.bias_p, 1, ph.pad, out=yp, wplanes=p.wp_planes)
             y = self._buf(B, H * s_, W * s_, p.w4[0])
             self._shuffle(yp, s_, y)
         else:
-            q = p.K - 1 - p_
-            Hu, Wu = (H - 1) * s_ + 1 + 2 * q + op_, (W - 1) * s_ + 1 + 2 * q + op_
+            q, Hu, Wu = zero_insert_hw(H, W, p.K, s_, p_, op_)
             xu = self._buf(B, Hu, Wu, x.shape[-1])
             ops.zero_insert(x, s_, q, q, Hu, Wu, out=xu)
             y = self._buf(B, Hu - p.K + 1, Wu - p.K + 1, p.w4[0])
