@@ -11,6 +11,7 @@
 // This file is built with -ffp-contract=off so products and sums round separately, as the reference's op chain does.
 #include "rdo_common.h"
 #include "gather_body.h"
+#include "uaq_device.h"
 
 namespace {
 
@@ -651,19 +652,18 @@ __global__ __launch_bounds__(256) void ada_fwd_kernel(rdo_ada_desc d, const floa
     for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < d.numel; e += (long)gridDim.x * blockDim.x) {
         const int row = (int)(e / inner);
         const float dl = delta[row], z = zp[row], wv = w[e];
-        float xint;
         if (mode == 2) {
-            xint = rintf(wv / dl) + z;
-        } else {
-            const float xf = floorf(wv / dl);
-            float h;
-            if (mode == 1) {
-                h = fminf(fmaxf(sigmoidf_(alpha[e]) * (kZeta - kGamma) + kGamma, 0.f), 1.f);
-            } else {
-                h = alpha[e] >= 0.f ? 1.f : 0.f;
-            }
-            xint = xf + h + z;
+            emit(d, e, rdo::uaq_nearest(wv, dl, z, Lm1), wq, wd);
+            continue;
         }
+        const float xf = floorf(wv / dl);
+        float h;
+        if (mode == 1) {
+            h = fminf(fmaxf(sigmoidf_(alpha[e]) * (kZeta - kGamma) + kGamma, 0.f), 1.f);
+        } else {
+            h = alpha[e] >= 0.f ? 1.f : 0.f;
+        }
+        const float xint = xf + h + z;
         emit(d, e, (fminf(fmaxf(xint, 0.f), Lm1) - z) * dl, wq, wd);
     }
 }
@@ -688,23 +688,8 @@ __global__ __launch_bounds__(256) void uaq_minmax_kernel(const float* w, long in
         mn = fminf(mn, v);
         mx = fmaxf(mx, v);
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        mn = fminf(mn, __shfl_down(mn, o, 64));
-        mx = fmaxf(mx, __shfl_down(mx, o, 64));
-    }
-    __shared__ float smn[4], smx[4];
-    if ((threadIdx.x & 63) == 0) { smn[threadIdx.x >> 6] = mn; smx[threadIdx.x >> 6] = mx; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        mn = fminf(fminf(smn[0], smn[1]), fminf(smn[2], smn[3]));
-        mx = fmaxf(fmaxf(smx[0], smx[1]), fmaxf(smx[2], smx[3]));
-        float dl = (float)(((double)mx - (double)mn) / (double)(n_levels - 1));
-        dl = fmaxf(dl, 1e-8f);
-        delta[blockIdx.x] = dl;
-        // the reference writes (-x_min / delta) with a Python float on the left: torch evaluates that as delta.reciprocal() * (-x_min)
-        // in fp32 (Tensor.__rdiv__), one rounding more than a division -- it decides the ties at x.5 (symmetric weight ranges)
-        zp[blockIdx.x] = rintf(__fmul_rn(__frcp_rn(dl), -mn));
-    }
+    rdo::uaq_block_minmax(mn, mx);
+    if (threadIdx.x == 0) rdo::uaq_minmax_grid(mn, mx, n_levels, delta[blockIdx.x], zp[blockIdx.x]);
 }
 
 __global__ __launch_bounds__(256) void reduce_slabs_kernel(const float* slabs, int nsplit, long numel, float* out) {

@@ -189,6 +189,15 @@ _SIGS_BIAS = {
 }
 EXPORTS_BIAS = tuple(_SIGS_BIAS)
 TAP_MAX_K = 7             # RDO_TAP_MAX_K of include/rdo_ptq_bias.h
+# include/rdo_ptq_bits.h: mixed-precision weight widths (grids and round-to-nearest error of a weight at K widths in one call)
+_SIGS_BITS = {
+    "rdo_uaq_width_scan": (C.c_int, [P, C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_int32, P, P, P, P, P, P, P, P]),
+    "rdo_uaq_width_scan_workspace": (C.c_int64, [C.c_int32, C.c_int64, C.c_int32]),
+}
+EXPORTS_BITS = tuple(_SIGS_BITS)
+WIDTH_SCAN_MAX_K = 8      # RDO_WIDTH_SCAN_MAX_K, _MIN_BITS, _MAX_BITS, _LDS_ROW and _CHUNK of include/rdo_ptq_bits.h
+WIDTH_SCAN_MIN_BITS, WIDTH_SCAN_MAX_BITS = 2, 16
+WIDTH_SCAN_LDS_ROW, WIDTH_SCAN_CHUNK = 8192, 4096
 
 _lib = None
 
@@ -205,7 +214,7 @@ def lib():
         # "no ROCm-capable device is detected"
         import torch  # noqa: F401
         h = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(_SIGS.items()) + list(_SIGS_GDN.items()) + list(_SIGS_BIAS.items()):
+        for name, (res, args) in list(_SIGS.items()) + list(_SIGS_GDN.items()) + list(_SIGS_BIAS.items()) + list(_SIGS_BITS.items()):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         _lib = h

@@ -565,6 +565,70 @@ def bias_shift(w_ref, w_q, s_ref, s_q, n, org_bias, shift=None, bias_out=None):
     return shift, bias_out
 
 
+_SCAN_WS = {}       # device -> workspace of uaq_width_scan (launches are stream-ordered, so one growing buffer per device suffices)
+
+
+def width_list(what, widths, max_bits=L.WIDTH_SCAN_MAX_BITS):
+    """`widths` as a list of ints: a non-empty sequence of at most 8 distinct whole numbers in 2 .. max_bits, else ValueError"""
+    if isinstance(widths, (str, bytes)) or torch.is_tensor(widths) or not hasattr(widths, "__len__") or not hasattr(widths, "__iter__"):
+        raise ValueError(f"{what}: widths must be a sequence of whole numbers, got {widths!r}")
+    widths = list(widths)
+    if not 1 <= len(widths) <= L.WIDTH_SCAN_MAX_K:
+        raise ValueError(f"{what}: widths must hold 1 .. {L.WIDTH_SCAN_MAX_K} entries, got {len(widths)}")
+    for b in widths:
+        if isinstance(b, bool) or not isinstance(b, numbers.Integral) or not L.WIDTH_SCAN_MIN_BITS <= b <= max_bits:
+            raise ValueError(f"{what}: every width must be a whole number in {L.WIDTH_SCAN_MIN_BITS} .. {max_bits}, got {b!r}")
+    widths = [int(b) for b in widths]
+    if len(set(widths)) != len(widths):
+        raise ValueError(f"{what}: widths must be distinct, got {widths}")
+    return widths
+
+
+def uaq_width_scan(w_rows, widths, delta=None, zp=None):
+    """What round-to-nearest costs a weight at several widths, in one call (rdo_uaq_width_scan, include/rdo_ptq_bits.h): w_rows contiguous
+    fp32 [rows, inner] (what `UniformAffineQuantizer._rows` gives, flattened to rank 2), widths: 1 .. 8 distinct whole numbers in 2 .. 16.
+    -> (delta, zp fp32 [K, rows]; err float64 [K, rows] = sum (w - wq)^2 per row with wq the expression of `uaq_fakequant` on the grid of
+    n_levels = 2^width; energy float64 [rows] = sum w^2).  With delta and zp None the grids are those of `uaq_init_minmax(w_rows, 2^width)`
+    bit for bit; with both given (fp32 [K, rows] on w_rows' device) they are copied through and scored.  Float64 sums in a fixed order:
+    the same input gives the same bits.  Everything is checked on the host before a pointer is taken."""
+    what = "uaq_width_scan"
+    if not torch.is_tensor(w_rows) or w_rows.dtype != torch.float32:
+        raise ValueError(f"{what}: w_rows must be an fp32 tensor, got {w_rows.dtype if torch.is_tensor(w_rows) else type(w_rows).__name__}")
+    if w_rows.dim() != 2:
+        raise ValueError(f"{what}: w_rows must be of rank 2 [rows, inner], got rank {w_rows.dim()}")
+    if w_rows.numel() == 0:
+        raise ValueError(f"{what}: w_rows is empty: {tuple(w_rows.shape)}")
+    if not w_rows.is_contiguous():
+        raise ValueError(f"{what}: w_rows must be contiguous")
+    widths = width_list(what, widths)
+    rows, inner, K = int(w_rows.shape[0]), int(w_rows.shape[1]), len(widths)
+    if rows > 0x7fffffff:
+        raise ValueError(f"{what}: {rows} rows are beyond 32-bit row indices")
+    if (delta is None) != (zp is None):
+        raise ValueError(f"{what}: delta and zp must be given together or not at all")
+    for name, t in (("delta", delta), ("zp", zp)):
+        if t is not None and (not torch.is_tensor(t) or tuple(t.shape) != (K, rows) or t.dtype != torch.float32 or t.device != w_rows.device
+                              or not t.is_contiguous()):
+            raise ValueError(f"{what}: {name} must be a contiguous fp32 [{K}, {rows}] on {w_rows.device}, got "
+                             f"{(t.dtype, tuple(t.shape), t.device) if torch.is_tensor(t) else type(t).__name__}")
+    if inner > L.WIDTH_SCAN_LDS_ROW and rows * -(-inner // L.WIDTH_SCAN_CHUNK) > 0x7fffffff:
+        raise ValueError(f"{what}: [{rows}, {inner}] splits into more shares than 32-bit workgroup indices hold")
+    if not w_rows.is_cuda:
+        raise ValueError(f"{what}: w_rows is on {w_rows.device}; there is no CPU path")
+    need = int(L.lib().rdo_uaq_width_scan_workspace(rows, inner, K))
+    ws = _SCAN_WS.get(w_rows.device)
+    if ws is None or ws.numel() * 8 < need:
+        ws = _SCAN_WS[w_rows.device] = torch.empty(-(-need // 8), device=w_rows.device, dtype=torch.float64)
+    out_d = torch.empty(K, rows, device=w_rows.device, dtype=torch.float32)
+    out_z = torch.empty_like(out_d)
+    err = torch.empty(K, rows, device=w_rows.device, dtype=torch.float64)
+    energy = torch.empty(rows, device=w_rows.device, dtype=torch.float64)
+    dptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731  (float64 operands: _ptr admits fp32 / int only)
+    L.check(L.lib().rdo_uaq_width_scan(_ptr(w_rows), rows, inner, (C.c_int32 * K)(*widths), K, _ptr(delta), _ptr(zp), _ptr(out_d), _ptr(out_z),
+                                       dptr(err), dptr(energy), dptr(ws), _stream()), "rdo_uaq_width_scan")
+    return out_d, out_z, err, energy
+
+
 def actquant_static_bwd(x, g, rng, drange, dx=None, n_bits=8, ws=None):
     """Backward of `actquant_static` with a straight-through round: returns dx (= g inside the range, 0 outside; `dx` may be g) and
     accumulates the per-channel range gradient into drange [2C] = dlo | dhi.  x, g: [..., C] channels-last, contiguous."""

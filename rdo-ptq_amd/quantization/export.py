@@ -165,32 +165,33 @@ def bias_report(qnn) -> "OrderedDict[str, dict]":
     return out
 
 
-def _rd_report_args(qnn, images, lmbda, act_quant, batch, units):
-    """every argument check of `rd_report`, before any GPU work -> the selected (name, unit) pairs in `units()` order"""
+def _rd_report_args(qnn, images, lmbda, act_quant, batch, units, what="rd_report"):
+    """every argument check of `rd_report` (and, under its own name, of `bit_report`), before any GPU work -> the selected (name, unit)
+    pairs in `units()` order"""
     if not torch.is_tensor(images) or images.dtype != torch.float32:
-        raise ValueError(f"rd_report: images must be an fp32 tensor [n, 3, H, W], got "
+        raise ValueError(f"{what}: images must be an fp32 tensor [n, 3, H, W], got "
                          f"{images.dtype if torch.is_tensor(images) else type(images).__name__}")
     if images.dim() != 4 or images.shape[1] != 3:
-        raise ValueError(f"rd_report: images must be [n, 3, H, W], got {tuple(images.shape)}")
+        raise ValueError(f"{what}: images must be [n, 3, H, W], got {tuple(images.shape)}")
     if images.numel() == 0:
-        raise ValueError(f"rd_report: images is empty: {tuple(images.shape)}")
+        raise ValueError(f"{what}: images is empty: {tuple(images.shape)}")
     if images.shape[2] % 64 or images.shape[3] % 64:
-        raise ValueError(f"rd_report: the image sides must be multiples of 64 (the calibration crops; nothing is padded), got "
+        raise ValueError(f"{what}: the image sides must be multiples of 64 (the calibration crops; nothing is padded), got "
                          f"{tuple(images.shape[2:])}")
     if isinstance(lmbda, bool) or not isinstance(lmbda, (int, float)) or not math.isfinite(lmbda) or lmbda <= 0:
-        raise ValueError(f"rd_report: lmbda must be a positive finite number, got {lmbda!r}")
+        raise ValueError(f"{what}: lmbda must be a positive finite number, got {lmbda!r}")
     if isinstance(batch, bool) or not isinstance(batch, int) or batch < 1:
-        raise ValueError(f"rd_report: batch must be an integer >= 1, got {batch!r}")
+        raise ValueError(f"{what}: batch must be an integer >= 1, got {batch!r}")
     if not isinstance(act_quant, bool):
-        raise ValueError(f"rd_report: act_quant must be True or False, got {act_quant!r}")
+        raise ValueError(f"{what}: act_quant must be True or False, got {act_quant!r}")
     known = qnn.units()
     if units is None:
         return list(known.items())
     if isinstance(units, str) or not all(isinstance(u, str) for u in units):
-        raise ValueError(f"rd_report: units must be None or a list of unit names, got {units!r}")
+        raise ValueError(f"{what}: units must be None or a list of unit names, got {units!r}")
     unknown = [u for u in units if u not in known]
     if unknown:
-        raise ValueError(f"rd_report: unknown unit name(s) {unknown}; QuantModel.units() has {list(known)}")
+        raise ValueError(f"{what}: unknown unit name(s) {unknown}; QuantModel.units() has {list(known)}")
     return [(n, u) for n, u in known.items() if n in set(units)]
 
 
@@ -202,6 +203,70 @@ def _dynamic_grids(qnn):
                 and getattr(m.act_quantizer, "act_mode", "dynamic") != "static":
             return True
     return False
+
+
+class _StateRunner:
+    """The state runner of `rd_report` and `bit_report`: passes over this rank's share of `images` in whatever state the model is in, the
+    data-parallel reduction of the passes' float64 sums, and the rows made of them (the columns `rd_report` documents)."""
+
+    def __init__(self, qnn, images, lmbda, bs, what):
+        from . import dp
+        self.qnn, self.lmbda, self.bs = qnn, lmbda, bs
+        self.n, _, H, W = (int(v) for v in images.shape)
+        self.pixels = self.n * H * W
+        self.device = next(qnn.parameters()).device
+        rank, self.world = dp.world()
+        if self.n < self.world:
+            raise ValueError(f"{what}: {self.n} image(s) for {self.world} ranks: every rank needs at least one")
+        self.mine = images[rank::self.world]
+
+    def measure(self):
+        """one pass over this rank's images in the state the model is in -> (keys, float64 device sums [bits of every key | sse])"""
+        from hipops import ops
+        device, mine, bs = self.device, self.mine, self.bs
+        keys, acc, sse = None, None, torch.zeros(1, dtype=torch.float64, device=device)
+        with torch.no_grad():
+            for i in range(0, mine.shape[0], bs):
+                x = mine[i:i + bs].to(device).contiguous()
+                out = self.qnn(x)
+                liks = out["likelihoods"]
+                if keys is None:
+                    keys = list(liks)
+                    acc = [torch.zeros(liks[k].shape[1], dtype=torch.float64, device=device) for k in keys]
+                for a, k in zip(acc, keys):
+                    a += ops.neg_log2_channel_sums(liks[k]).double()
+                sse += ops.sq_diff_sum_ordered(out["x_hat"].contiguous(), x, 1.0, clamp01=True).double()
+        return keys, acc, sse
+
+    def reduce(self, states):
+        """all-reduce (SUM) the sums of every measured state in place; nothing to do for one rank"""
+        from . import dp
+        if self.world <= 1:
+            return
+        flat = torch.cat([t for _, acc, sse in states for t in acc + [sse]])
+        dp.reduce_act_stats(sums=[flat])
+        off = 0
+        for _, acc, sse in states:
+            for t in acc + [sse]:
+                t.copy_(flat[off:off + t.numel()])
+                off += t.numel()
+
+    def row(self, state):
+        keys, acc, sse = state
+        bits = OrderedDict((k, a.cpu()) for k, a in zip(keys, acc))
+        total = float(sum(b.sum() for b in bits.values()))
+        mse = float(sse) / (3 * self.pixels)
+        r = OrderedDict(bits=bits, bits_total=total, sse=float(sse), bpp=total / self.pixels, mse=mse,
+                        psnr_db=float("inf") if mse == 0 else -10.0 * math.log10(mse))
+        r["loss"] = r["bpp"] + self.lmbda * 255.0 ** 2 * mse
+        return r
+
+    @staticmethod
+    def against(r, fp):
+        r["d_bits"] = OrderedDict((k, r["bits"][k] - fp["bits"][k]) for k in r["bits"])
+        for f in ("bpp", "mse", "psnr_db", "loss"):
+            r["d_" + f] = r[f] - fp[f]
+        return r
 
 
 def rd_report(qnn, images, lmbda=0.01, act_quant=False, batch=8, units=None) -> "OrderedDict":
@@ -233,77 +298,241 @@ def rd_report(qnn, images, lmbda=0.01, act_quant=False, batch=8, units=None) -> 
     Cost: len(units) + 2 passes over `images` -- meant for the calibration crops, not for Kodak at full size.
     Raises ValueError before any GPU work for: images not fp32 4-D with 3 channels, empty, or sides not multiples of 64; lmbda not a
     positive finite number; batch not an integer >= 1; act_quant not a bool; an unknown unit name."""
-    from hipops import ops
-    from . import dp
     chosen = _rd_report_args(qnn, images, lmbda, act_quant, batch, units)
-    n, _, H, W = (int(v) for v in images.shape)
-    pixels = n * H * W
     bs = 1 if (act_quant and _dynamic_grids(qnn)) else batch
-    device = next(qnn.parameters()).device
-    rank, world = dp.world()
-    if n < world:
-        raise ValueError(f"rd_report: {n} image(s) for {world} ranks: every rank needs at least one")
-    mine = images[rank::world]
-
-    def measure():
-        """one pass over this rank's images in the state the model is in -> (keys, float64 device sums [bits of every key | sse])"""
-        keys, acc, sse = None, None, torch.zeros(1, dtype=torch.float64, device=device)
-        with torch.no_grad():
-            for i in range(0, mine.shape[0], bs):
-                x = mine[i:i + bs].to(device).contiguous()
-                out = qnn(x)
-                liks = out["likelihoods"]
-                if keys is None:
-                    keys = list(liks)
-                    acc = [torch.zeros(liks[k].shape[1], dtype=torch.float64, device=device) for k in keys]
-                for a, k in zip(acc, keys):
-                    a += ops.neg_log2_channel_sums(liks[k]).double()
-                sse += ops.sq_diff_sum_ordered(out["x_hat"].contiguous(), x, 1.0, clamp01=True).double()
-        return keys, acc, sse
-
-    def row(state):
-        keys, acc, sse = state
-        bits = OrderedDict((k, a.cpu()) for k, a in zip(keys, acc))
-        total = float(sum(b.sum() for b in bits.values()))
-        mse = float(sse) / (3 * pixels)
-        r = OrderedDict(bits=bits, bits_total=total, sse=float(sse), bpp=total / pixels, mse=mse,
-                        psnr_db=float("inf") if mse == 0 else -10.0 * math.log10(mse))
-        r["loss"] = r["bpp"] + lmbda * 255.0 ** 2 * mse
-        return r
-
-    def against(r, fp):
-        r["d_bits"] = OrderedDict((k, r["bits"][k] - fp["bits"][k]) for k in r["bits"])
-        for f in ("bpp", "mse", "psnr_db", "loss"):
-            r["d_" + f] = r[f] - fp[f]
-        return r
-
+    run = _StateRunner(qnn, images, lmbda, bs, "rd_report")
     states = []
     with quant_state(qnn):
         qnn.set_quant_state(False, False)
-        states.append(measure())
+        states.append(run.measure())
         qnn.set_quant_state(True, act_quant)
-        states.append(measure())
+        states.append(run.measure())
         for _, u in chosen:
             qnn.set_quant_state(False, False)
             u.set_quant_state(True, act_quant)
-            states.append(measure())
-    if world > 1:
-        flat = torch.cat([t for _, acc, sse in states for t in acc + [sse]])
-        dp.reduce_act_stats(sums=[flat])
-        off = 0
-        for _, acc, sse in states:
-            for t in acc + [sse]:
-                t.copy_(flat[off:off + t.numel()])
-                off += t.numel()
-    fp = row(states[0])
-    full = against(row(states[1]), fp)
-    rows = OrderedDict((name, against(row(st), fp)) for (name, _), st in zip(chosen, states[2:]))
+            states.append(run.measure())
+    run.reduce(states)
+    fp = run.row(states[0])
+    full = run.against(run.row(states[1]), fp)
+    rows = OrderedDict((name, run.against(run.row(st), fp)) for (name, _), st in zip(chosen, states[2:]))
     rep = OrderedDict()
     rep["fp"], rep["all"], rep["units"] = fp, full, rows
-    rep["n"], rep["pixels"], rep["lmbda"], rep["act_quant"] = n, pixels, float(lmbda), act_quant
+    rep["n"], rep["pixels"], rep["lmbda"], rep["act_quant"] = run.n, run.pixels, float(lmbda), act_quant
     rep["additivity"] = {"sum_units_d_loss": float(sum(r["d_loss"] for r in rows.values())), "all_d_loss": full["d_loss"]}
     rep["batch"] = bs
     return rep
+
+
+def weighted_modules(unit):
+    """the QuantModules of a unit that hold a weight (pixel shuffles do not), in module order"""
+    return [m for m in unit.modules() if isinstance(m, QuantModule) and m.org_weight is not None]
+
+
+def is_trained(m):
+    """has this QuantModule been calibrated?  Its AdaRoundQuantizer's alpha belongs to the delta it was trained on: no other width fits it"""
+    return bool(m.trained) or isinstance(m.weight_quantizer, AdaRoundQuantizer)
+
+
+_QUANTIZER_FIELDS = ("n_bits", "n_levels", "delta", "zero_point", "inited")
+
+
+def _width_grids(m, widths):
+    """the grids of one weighted module at every width, scored by `ops.uaq_width_scan` -> (delta, zp fp32 [K, rows], err float64 [K, rows],
+    energy float64 [rows]).  Plain asymmetric 'max': one min-max scan.  Any other scale_method: the quantiser's own
+    `init_quantization_scale` after `bitwidth_refactor(b)` (the caller restores the width), scored by a scan in given mode."""
+    from hipops import ops
+    q = m.weight_quantizer
+    w = m.weight.detach()
+    wr = q._rows(w)
+    flat = wr.reshape(wr.shape[0], -1)
+    if "max" in q.scale_method and "scale" not in q.scale_method and not q.sym:
+        return ops.uaq_width_scan(flat, widths)
+    ds, zs = [], []
+    for b in widths:
+        q.bitwidth_refactor(b)
+        d, z = q.init_quantization_scale(w, q.channel_wise)
+        ds.append(d.reshape(-1).expand(flat.shape[0]))
+        zs.append(z.reshape(-1).expand(flat.shape[0]))
+    return ops.uaq_width_scan(flat, widths, torch.stack(ds).float().contiguous(), torch.stack(zs).float().contiguous())
+
+
+def bit_report(qnn, images, widths=(4, 6, 8), lmbda=0.01, batch=8, units=None) -> "OrderedDict":
+    """What each reconstruction unit costs in rate and distortion at each of several weight widths, measured on `images` like `rd_report`
+    (its rules for `images`, `lmbda`, `batch` and `units`) under torch.no_grad(), BEFORE calibration: weights only (activation
+    quantisation is off in every state), round to nearest.  The states, all over the same images:
+      'fp'                    qnn.set_quant_state(False, False): the 'fp' state of `rd_report`
+      one per (unit, width)   qnn.set_quant_state(False, False); unit.set_quant_state(True, False), with every weighted QuantModule of
+                              the unit temporarily at width b: in `units()` order, the widths in the order given
+    Grids: a weight quantiser with the plain asymmetric 'max' scale takes delta and zero point of all widths from ONE
+    `ops.uaq_width_scan` of its weight (the bits of `uaq_init_minmax` at 2^b levels: what its own first forward at that width would
+    set); any other scale_method takes them from its own `init_quantization_scale` after `bitwidth_refactor(b)`, and the scan scores them
+    in given mode, so the weight columns always come from the kernel.
+    -> OrderedDict:
+      'fp'       the row of `rd_report`'s 'fp'
+      'units'    name -> width -> row: the keys of an `rd_report` unit row (bits, bits_total, sse, bpp, mse, psnr_db, loss, d_bits, d_bpp,
+                 d_mse, d_psnr_db, d_loss), and size_bits = b x the unit's weight elements, weight_err = the sum over the unit's modules
+                 and rows of sum (w - wq)^2 in float64, weight_sqnr_db = 10 log10(sum energy / sum err) in float64 (inf at zero error)
+      'weights'  name -> weight elements of the unit (its weighted QuantModules; biases are not counted)
+      'widths' (list), 'n', 'pixels', 'lmbda', 'batch'
+    State: the fields n_bits, n_levels, delta, zero_point and inited of every weight quantiser of the chosen units and every module's
+    use_weight_quant | use_act_quant pair are recorded first and put back in a `finally` (the same objects, so the same bits);
+    `drop_weight_pack()` runs at every switch and at the end; a quantiser that had not been initialised is left uninitialised.
+    Data parallel: as `rd_report` (images sharded by rank, float64 sums all-reduced, every rank returns the same table); every rank
+    scans the weights itself, which gives the same bits.
+    Cost: len(units) * len(widths) + 1 passes over `images`.
+    Raises ValueError before any GPU work for what `rd_report` refuses, for widths that are not a non-empty sequence of at most 8
+    distinct whole numbers in 2 .. MAX_BITS, and for a chosen unit that holds a trained module (the table is taken before calibration)."""
+    from hipops import ops
+    from .quantizer import MAX_BITS, _scale_shape
+    what = "bit_report"
+    chosen = _rd_report_args(qnn, images, lmbda, False, batch, units, what=what)
+    widths = ops.width_list(what, widths, MAX_BITS)
+    mods = OrderedDict((name, weighted_modules(u)) for name, u in chosen)
+    for name, ms in mods.items():
+        if any(is_trained(m) for m in ms):
+            raise ValueError(f"{what}: unit {name!r} holds a trained module: the table is taken before calibration")
+    run = _StateRunner(qnn, images, lmbda, batch, what)
+    held = [(m, {f: getattr(m.weight_quantizer, f) for f in _QUANTIZER_FIELDS}) for ms in mods.values() for m in ms]
+    states, weight_cols = [], OrderedDict()
+    try:
+        with quant_state(qnn):
+            grids = {}
+            for name, ms in mods.items():
+                grids[name] = [_width_grids(m, widths) for m in ms]
+                err = torch.stack([g[2].sum(1) for g in grids[name]]).sum(0).cpu()            # float64 [K]
+                energy = float(torch.stack([g[3].sum() for g in grids[name]]).sum())
+                weight_cols[name] = (err, energy)
+            qnn.set_quant_state(False, False)
+            states.append(run.measure())
+            for name, u in chosen:
+                for k, b in enumerate(widths):
+                    qnn.set_quant_state(False, False)
+                    u.set_quant_state(True, False)
+                    for m, (d, z, _, _) in zip(mods[name], grids[name]):
+                        q = m.weight_quantizer
+                        shape = _scale_shape(m.weight, q.tconv) if q.channel_wise else ()
+                        q.bitwidth_refactor(b)
+                        q.delta, q.zero_point, q.inited = d[k].reshape(shape), z[k].reshape(shape), True
+                        m.drop_weight_pack()
+                    states.append(run.measure())
+    finally:
+        for m, fields in held:
+            for f, v in fields.items():
+                setattr(m.weight_quantizer, f, v)
+            m.drop_weight_pack()
+    run.reduce(states)
+    fp = run.row(states[0])
+    rep = OrderedDict()
+    rep["fp"], rep["units"], rep["weights"] = fp, OrderedDict(), OrderedDict()
+    it = iter(states[1:])
+    for name, _ in chosen:
+        count = sum(int(m.weight.numel()) for m in mods[name])
+        err, energy = weight_cols[name]
+        rep["weights"][name] = count
+        rep["units"][name] = OrderedDict()
+        for k, b in enumerate(widths):
+            r = run.against(run.row(next(it)), fp)
+            e = float(err[k])
+            r["size_bits"], r["weight_err"] = b * count, e
+            r["weight_sqnr_db"] = float("inf") if e == 0 else 10.0 * math.log10(energy / e)
+            rep["units"][name][b] = r
+    rep["widths"], rep["n"], rep["pixels"], rep["lmbda"], rep["batch"] = list(widths), run.n, run.pixels, float(lmbda), batch
+    return rep
+
+
+def _hull(options):
+    """options: [(width, size, cost)] of one unit -> its hull points in ascending size: the lower convex hull from the smallest size up to
+    the least-cost point (among equal costs the smallest).  Going down the list from the end, the cost per bit saved rises from step to
+    step; points on a chord are kept."""
+    pts = sorted(options, key=lambda p: p[1])
+    best = min(range(len(pts)), key=lambda i: (pts[i][2], pts[i][1]))
+    hull = []
+    for p in pts[:best + 1]:
+        # q = hull[-1] lies above the chord hull[-2] -> p when stepping p -> q costs more per bit than q -> hull[-2]
+        while len(hull) >= 2 and (hull[-1][2] - p[2]) / (p[1] - hull[-1][1]) > (hull[-2][2] - hull[-1][2]) / (hull[-1][1] - hull[-2][1]):
+            hull.pop()
+        hull.append(p)
+    return hull
+
+
+def allocate_bits(report, budget_bits=None, avg_bits=None, fixed=None) -> dict:
+    """Choose one weight width per unit from a `bit_report` table under a size budget.  Pure host code.
+    `budget_bits`: a whole number of weight bits, or `avg_bits`: a real number of bits per weight, the budget then being
+    floor(avg_bits * sum of report['weights']); exactly one of the two.  `fixed`: name -> width, a unit that has that one option.
+    The rule.  Each unit's options are the points (size_bits, d_loss) of its row.  Kept is the lower convex hull of the options from the
+    smallest size up to the unit's least-cost point (among equal costs the smallest); larger widths that cost more are dropped.  Every
+    unit starts at its least-cost hull point.  While the total size exceeds the budget, the hull step with the smallest slope is taken,
+    slope = cost added / size saved in float64, ties to the earlier unit in `units()` order; the first total <= budget stops it.
+    ValueError, naming the smallest reachable size, when even that exceeds the budget.
+    -> {'bits': OrderedDict name -> width, 'size_bits', 'avg_bits' (size_bits / sum of weights), 'cost' (sum of the chosen d_loss, added
+    in unit order), 'budget_bits', 'steps': [(unit, from width, to width, slope)] in the order taken}.
+    Guaranteed: no assignment of total size <= the returned size_bits has a lower total cost.  (Hull steps taken in slope order visit
+    the minimisers of cost + s * size for the rising step slope s >= 0 -- the Lagrangian property; an assignment A' with size' <= size
+    has cost' >= cost + s (size - size') >= cost.  Before the first step s = 0: every unit sits at its least cost.)
+    Not guaranteed: that no assignment BETWEEN the returned size and the budget costs less (the rule does not search the gap), and
+    anything about the calibrated model: the table is round-to-nearest and its costs are not additive (`rd_report`'s 'additivity'); on
+    random-init models the costs are noise of either sign."""
+    what = "allocate_bits"
+    try:
+        table, weights = report["units"], report["weights"]
+        names = list(table)
+        opts = OrderedDict((n, [(b, table[n][b]["size_bits"], float(table[n][b]["d_loss"])) for b in table[n]]) for n in names)
+    except (KeyError, TypeError, IndexError) as e:
+        raise ValueError(f"{what}: report must be a `bit_report` table ('units': name -> width -> row with size_bits and d_loss; "
+                         f"'weights'): {e!r}")
+    if not names or any(not o for o in opts.values()):
+        raise ValueError(f"{what}: the table holds no unit, or a unit without a width")
+    if list(weights) != names or any(isinstance(w, bool) or not isinstance(w, int) or w < 1 for w in weights.values()):
+        raise ValueError(f"{what}: report['weights'] must give a positive element count for every unit of the table, in its order")
+    for n, o in opts.items():
+        for b, size, cost in o:
+            if isinstance(size, bool) or not isinstance(size, int) or size < 1 or not math.isfinite(cost):
+                raise ValueError(f"{what}: unit {n!r} at width {b}: size_bits {size!r} must be a positive whole number and d_loss {cost!r} finite")
+        if len({size for _, size, _ in o}) != len(o):
+            raise ValueError(f"{what}: unit {n!r} has two widths of the same size")
+    total_w = sum(weights.values())
+    if (budget_bits is None) == (avg_bits is None):
+        raise ValueError(f"{what}: exactly one of budget_bits and avg_bits must be given")
+    if budget_bits is not None:
+        if isinstance(budget_bits, bool) or not isinstance(budget_bits, int) or budget_bits < 1:
+            raise ValueError(f"{what}: budget_bits must be a whole number >= 1, got {budget_bits!r}")
+        budget = int(budget_bits)
+    else:
+        if isinstance(avg_bits, bool) or not isinstance(avg_bits, (int, float)) or not math.isfinite(avg_bits) or avg_bits <= 0:
+            raise ValueError(f"{what}: avg_bits must be a positive finite number, got {avg_bits!r}")
+        budget = math.floor(avg_bits * total_w)
+    fixed = {} if fixed is None else fixed
+    if not isinstance(fixed, dict):
+        raise ValueError(f"{what}: fixed must be None or a dict name -> width, got {fixed!r}")
+    for n, b in fixed.items():
+        if n not in opts:
+            raise ValueError(f"{what}: fixed names the unknown unit {n!r}; the table has {names}")
+        if isinstance(b, bool) or b not in table[n]:
+            raise ValueError(f"{what}: fixed gives unit {n!r} the width {b!r}; the table has {list(table[n])}")
+    hulls = [_hull([p for p in opts[n] if n not in fixed or p[0] == fixed[n]]) for n in names]
+    least = sum(h[0][1] for h in hulls)
+    if least > budget:
+        raise ValueError(f"{what}: the smallest reachable size is {least} bits; the budget is {budget}")
+    at = [len(h) - 1 for h in hulls]
+    size = sum(h[i][1] for h, i in zip(hulls, at))
+    steps = []
+    while size > budget:
+        pick, slope = None, None
+        for u, (h, i) in enumerate(zip(hulls, at)):
+            if i == 0:
+                continue
+            s = (h[i - 1][2] - h[i][2]) / (h[i][1] - h[i - 1][1])
+            if pick is None or s < slope:
+                pick, slope = u, s
+        h, i = hulls[pick], at[pick]
+        steps.append((names[pick], h[i][0], h[i - 1][0], slope))
+        size -= h[i][1] - h[i - 1][1]
+        at[pick] = i - 1
+    cost = 0.0
+    for h, i in zip(hulls, at):
+        cost += h[i][2]
+    return {"bits": OrderedDict((n, h[i][0]) for n, h, i in zip(names, hulls, at)), "size_bits": size, "avg_bits": size / total_w,
+            "cost": cost, "budget_bits": budget, "steps": steps}
 
 
 def dequantize(entry) -> torch.Tensor:

@@ -127,6 +127,67 @@ class QuantModel(nn.Module):
         from .export import rd_report
         return rd_report(self, images, lmbda=lmbda, act_quant=act_quant, batch=batch, units=units)
 
+    def bit_report(self, images, widths=(4, 6, 8), lmbda=0.01, batch=8, units=None):
+        """What every unit costs in rate and distortion at each of several weight widths when it alone is quantised (round to nearest,
+        weights only), with each width's size and weight error: the table `export.allocate_bits` chooses from (`export.bit_report`).
+        len(units) * len(widths) + 1 passes over `images`; taken before calibration."""
+        from .export import bit_report
+        return bit_report(self, images, widths=widths, lmbda=lmbda, batch=batch, units=units)
+
+    def set_weight_bits(self, bits):
+        """Give the weights of the units their widths before calibration: `bits` is one whole number in 2 .. MAX_BITS for every unit, or
+        a mapping unit name -> width (what `export.allocate_bits(...)['bits']` is; units it does not name keep theirs).  Names and widths
+        are validated and a unit that holds a trained module is refused (ValueError) before anything is written; then every weighted
+        QuantModule of each named unit gets `bitwidth_refactor(b)`, `inited = False` (its scale is initialised at the new width on its
+        next use) and `drop_weight_pack()`.  Activation quantisers are not touched."""
+        from collections.abc import Mapping
+        from numbers import Integral
+        from .export import is_trained, weighted_modules
+        from .quantizer import MAX_BITS
+        what = "set_weight_bits"
+        known = self.units()
+
+        def whole(b):
+            return not isinstance(b, bool) and isinstance(b, Integral) and 2 <= b <= MAX_BITS
+        if isinstance(bits, Mapping):
+            unknown = [n for n in bits if n not in known]
+            if unknown:
+                raise ValueError(f"{what}: unknown unit name(s) {unknown}; QuantModel.units() has {list(known)}")
+            plan = [(n, bits[n]) for n in known if n in bits]
+        elif whole(bits):
+            plan = [(n, bits) for n in known]
+        else:
+            raise ValueError(f"{what}: bits must be a whole number in 2 .. {MAX_BITS} or a mapping unit name -> width, got {bits!r}")
+        for n, b in plan:
+            if not whole(b):
+                raise ValueError(f"{what}: the width of unit {n!r} must be a whole number in 2 .. {MAX_BITS}, got {b!r}")
+            if any(is_trained(m) for m in weighted_modules(known[n])):
+                raise ValueError(f"{what}: unit {n!r} holds a trained module: its rounding belongs to the width it was calibrated at")
+        for n, b in plan:
+            for m in weighted_modules(known[n]):
+                m.weight_quantizer.bitwidth_refactor(int(b))
+                m.weight_quantizer.inited = False
+                m.drop_weight_pack()
+
+    def weight_bits(self):
+        """OrderedDict unit name -> {'bits': OrderedDict module name (inside the unit; '' for a layer unit) -> n_bits, 'weights': the
+        unit's weight elements, 'size_bits': sum of n_bits x elements}, and 'total' -> {'weights', 'size_bits', 'avg_bits'}."""
+        from collections import OrderedDict
+        out = OrderedDict()
+        tw = ts = 0
+        for name, u in self.units().items():
+            row = {"bits": OrderedDict(), "weights": 0, "size_bits": 0}
+            for mn, m in u.named_modules():
+                if isinstance(m, QuantModule) and m.org_weight is not None:
+                    b, cnt = int(m.weight_quantizer.n_bits), int(m.weight.numel())
+                    row["bits"][mn] = b
+                    row["weights"] += cnt
+                    row["size_bits"] += b * cnt
+            out[name] = row
+            tw, ts = tw + row["weights"], ts + row["size_bits"]
+        out["total"] = {"weights": tw, "size_bits": ts, "avg_bits": ts / tw if tw else 0.0}
+        return out
+
     def forward(self, input):
         return self.model(input)
 
