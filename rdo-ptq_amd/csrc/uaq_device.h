@@ -1,15 +1,29 @@
 // Device functions of the uniform affine quantiser that more than one file evaluates (adaround.hip: rdo_uaq_fakequant and
-// rdo_uaq_init_minmax; bit_alloc.hip: rdo_uaq_width_scan): ONE statement of each expression, so that the files cannot drift apart by a
-// rounding.  Both files are built with -ffp-contract=off.
+// rdo_uaq_init_minmax; bit_alloc.hip: rdo_uaq_width_scan; weight_pack.hip: rdo_weight_pack and rdo_weight_unpack): ONE statement of each
+// expression, so that the files cannot drift apart by a rounding.  All of them are built with -ffp-contract=off.
 #pragma once
 #include <hip/hip_runtime.h>
 
 namespace rdo {
 
+// the level (an integer-valued float in [0, Lm1]) of round-to-nearest on the grid (dl, z) of Lm1 + 1 levels
+__device__ __forceinline__ float uaq_level_nearest(float wv, float dl, float z, float Lm1) {
+    const float xint = rintf(wv / dl) + z;
+    return fminf(fmaxf(xint, 0.f), Lm1);
+}
+
+// the level of the hard AdaRound rounding: down, plus one where the rounding logit av is >= 0 (the hard branch of ada_fwd_kernel)
+__device__ __forceinline__ float uaq_level_hard(float wv, float av, float dl, float z, float Lm1) {
+    const float xint = floorf(wv / dl) + (av >= 0.f ? 1.f : 0.f) + z;
+    return fminf(fmaxf(xint, 0.f), Lm1);
+}
+
+// the value of a level: the tail expression of both fake-quantisation kernels
+__device__ __forceinline__ float uaq_dequant(float level, float dl, float z) { return (level - z) * dl; }
+
 // round-to-nearest fake quantisation of one value on the grid (dl, z) of Lm1 + 1 levels (quantizer.py:372-376 of the reference)
 __device__ __forceinline__ float uaq_nearest(float wv, float dl, float z, float Lm1) {
-    const float xint = rintf(wv / dl) + z;
-    return (fminf(fmaxf(xint, 0.f), Lm1) - z) * dl;
+    return uaq_dequant(uaq_level_nearest(wv, dl, z, Lm1), dl, z);
 }
 
 // the 'max' grid of a row whose min and max (clamped through 0) are mn, mx ('max' init, quantizer.py:281-298: python-double arithmetic

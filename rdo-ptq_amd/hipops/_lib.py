@@ -198,6 +198,14 @@ EXPORTS_BITS = tuple(_SIGS_BITS)
 WIDTH_SCAN_MAX_K = 8      # RDO_WIDTH_SCAN_MAX_K, _MIN_BITS, _MAX_BITS, _LDS_ROW and _CHUNK of include/rdo_ptq_bits.h
 WIDTH_SCAN_MIN_BITS, WIDTH_SCAN_MAX_BITS = 2, 16
 WIDTH_SCAN_LDS_ROW, WIDTH_SCAN_CHUNK = 8192, 4096
+# include/rdo_ptq_pack.h: n-bit weight levels packed at their own width (what a packed checkpoint stores)
+_SIGS_PACK = {
+    "rdo_weight_pack": (C.c_int, [P, P, P, P, C.c_int32, C.c_int64, C.c_int32, P, P]),
+    "rdo_weight_unpack": (C.c_int, [P, P, P, C.c_int32, C.c_int64, C.c_int32, P, P, P]),
+    "rdo_pack_row_words": (C.c_int64, [C.c_int64, C.c_int32]),
+}
+EXPORTS_PACK = tuple(_SIGS_PACK)
+PACK_MIN_BITS, PACK_MAX_BITS = 2, 16      # RDO_PACK_MIN_BITS and RDO_PACK_MAX_BITS of include/rdo_ptq_pack.h
 
 _lib = None
 
@@ -214,7 +222,8 @@ def lib():
         # "no ROCm-capable device is detected"
         import torch  # noqa: F401
         h = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(_SIGS.items()) + list(_SIGS_GDN.items()) + list(_SIGS_BIAS.items()) + list(_SIGS_BITS.items()):
+        for name, (res, args) in (list(_SIGS.items()) + list(_SIGS_GDN.items()) + list(_SIGS_BIAS.items()) + list(_SIGS_BITS.items())
+                                  + list(_SIGS_PACK.items())):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         _lib = h

@@ -629,6 +629,113 @@ def uaq_width_scan(w_rows, widths, delta=None, zp=None):
     return out_d, out_z, err, energy
 
 
+def pack_row_words(inner, bits):
+    """W = ceil(inner * bits / 32): the 32-bit words one row of `inner` codes of `bits` bits occupies (rdo_pack_row_words on the host)"""
+    return -(-int(inner) * int(bits) // 32)
+
+
+def _pack_bits(what, bits):
+    if isinstance(bits, bool) or not isinstance(bits, numbers.Integral) or not L.PACK_MIN_BITS <= bits <= L.PACK_MAX_BITS:
+        raise ValueError(f"{what}: bits must be a whole number in {L.PACK_MIN_BITS} .. {L.PACK_MAX_BITS}, got {bits!r}")
+    return int(bits)
+
+
+def _pack_operand(what, name, t, dtype, shape, device=None, like=None):
+    """a contiguous tensor of `dtype` and `shape` (on `device`, when given), else ValueError; `like`: how the message words the dtype"""
+    if (not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous()
+            or (device is not None and t.device != device)):
+        where = "" if device is None else f" on {device}"
+        raise ValueError(f"{what}: {name} must be a contiguous {like} {list(shape)}{where}, got "
+                         f"{(t.dtype, tuple(t.shape), t.device) if torch.is_tensor(t) else type(t).__name__}")
+
+
+def _pack_geometry(what, rows, inner, bits):
+    W = pack_row_words(inner, bits)
+    if rows > 0x7fffffff or W > 0x7fffffff or rows * W > 2 ** 40:
+        raise ValueError(f"{what}: [{rows}, {inner}] at {bits} bits is beyond 2^31 - 1 rows, 2^31 - 1 words a row or 2^40 words")
+    return W
+
+
+def weight_pack(w_rows, delta, zp, bits, alpha_rows=None, out=None):
+    """Quantise a weight-row matrix to integer levels and pack them at their own width (rdo_weight_pack; include/rdo_ptq_pack.h states
+    the bit layout): w_rows contiguous fp32 [rows, inner] (what `UniformAffineQuantizer._rows` gives, flattened to rank 2), delta and zp
+    fp32 [rows] on its device, bits a whole number in 2 .. 16.  alpha_rows None: round to nearest, the level inside `uaq_fakequant`;
+    given (fp32 [rows, inner]): down, plus one where alpha >= 0, the level inside `adaround_fwd(..., soft=False)`.
+    -> int32 [rows, W] holding raw bits, W = ceil(inner * bits / 32); every word is written, the padding bits are zero.  `out`: a
+    contiguous int32 [rows, W] to write into.  Everything is checked on the host before a pointer is taken."""
+    what = "weight_pack"
+    if not torch.is_tensor(w_rows) or w_rows.dtype != torch.float32:
+        raise ValueError(f"{what}: w_rows must be an fp32 tensor, got {w_rows.dtype if torch.is_tensor(w_rows) else type(w_rows).__name__}")
+    if w_rows.dim() != 2:
+        raise ValueError(f"{what}: w_rows must be of rank 2 [rows, inner], got rank {w_rows.dim()}")
+    if w_rows.numel() == 0:
+        raise ValueError(f"{what}: w_rows is empty: {tuple(w_rows.shape)}")
+    if not w_rows.is_contiguous():
+        raise ValueError(f"{what}: w_rows must be contiguous")
+    bits = _pack_bits(what, bits)
+    rows, inner, dev = int(w_rows.shape[0]), int(w_rows.shape[1]), w_rows.device
+    _pack_operand(what, "delta", delta, torch.float32, (rows,), dev, "fp32")
+    _pack_operand(what, "zp", zp, torch.float32, (rows,), dev, "fp32")
+    if alpha_rows is not None:
+        _pack_operand(what, "alpha_rows", alpha_rows, torch.float32, (rows, inner), dev, "fp32")
+    W = _pack_geometry(what, rows, inner, bits)
+    if out is not None:
+        _pack_operand(what, "out", out, torch.int32, (rows, W), dev, "int32")
+    if not w_rows.is_cuda:
+        raise ValueError(f"{what}: w_rows is on {dev}; there is no CPU path")
+    out = torch.empty(rows, W, device=dev, dtype=torch.int32) if out is None else out
+    L.check(L.lib().rdo_weight_pack(_ptr(w_rows), _ptr(alpha_rows), _ptr(delta), _ptr(zp), rows, inner, bits, _ptr(out), _stream()),
+            "rdo_weight_pack")
+    return out
+
+
+def weight_unpack(packed, delta, zp, inner, bits, levels=True, dequant=True, levels_out=None, wq_out=None):
+    """Unpack what `weight_pack` made (rdo_weight_unpack): packed contiguous int32 [rows, W] with W = ceil(inner * bits / 32), delta and zp
+    fp32 [rows] on its device (both may be None when `dequant` is False).  -> (levels, wq): int32 [rows, inner] when `levels`, else None;
+    fp32 [rows, inner] = (level - zp) * delta, the tail expression of the fake-quantisation kernels, when `dequant`, else None.  At
+    least one of the two must be asked for.  `levels_out`, `wq_out`: contiguous tensors to write into.  Everything is checked on the
+    host before a pointer is taken."""
+    what = "weight_unpack"
+    if not torch.is_tensor(packed) or packed.dtype != torch.int32:
+        raise ValueError(f"{what}: packed must be an int32 tensor, got {packed.dtype if torch.is_tensor(packed) else type(packed).__name__}")
+    if packed.dim() != 2:
+        raise ValueError(f"{what}: packed must be of rank 2 [rows, W], got rank {packed.dim()}")
+    if packed.numel() == 0:
+        raise ValueError(f"{what}: packed is empty: {tuple(packed.shape)}")
+    if not packed.is_contiguous():
+        raise ValueError(f"{what}: packed must be contiguous")
+    bits = _pack_bits(what, bits)
+    if isinstance(inner, bool) or not isinstance(inner, numbers.Integral) or inner < 1:
+        raise ValueError(f"{what}: inner must be a whole number >= 1, got {inner!r}")
+    if not isinstance(levels, bool) or not isinstance(dequant, bool) or not (levels or dequant):
+        raise ValueError(f"{what}: levels and dequant must be True or False, and one of them True; got {levels!r}, {dequant!r}")
+    rows, inner, dev = int(packed.shape[0]), int(inner), packed.device
+    W = _pack_geometry(what, rows, inner, bits)
+    if packed.shape[1] != W:
+        raise ValueError(f"{what}: packed is {tuple(packed.shape)}; {inner} codes of {bits} bits make W = {W} words a row")
+    if dequant or delta is not None or zp is not None:
+        _pack_operand(what, "delta", delta, torch.float32, (rows,), dev, "fp32")
+        _pack_operand(what, "zp", zp, torch.float32, (rows,), dev, "fp32")
+    if levels_out is not None:
+        if not levels:
+            raise ValueError(f"{what}: levels_out is given but levels is False")
+        _pack_operand(what, "levels_out", levels_out, torch.int32, (rows, inner), dev, "int32")
+    if wq_out is not None:
+        if not dequant:
+            raise ValueError(f"{what}: wq_out is given but dequant is False")
+        _pack_operand(what, "wq_out", wq_out, torch.float32, (rows, inner), dev, "fp32")
+    if not packed.is_cuda:
+        raise ValueError(f"{what}: packed is on {dev}; there is no CPU path")
+    lv = wq = None
+    if levels:
+        lv = torch.empty(rows, inner, device=dev, dtype=torch.int32) if levels_out is None else levels_out
+    if dequant:
+        wq = torch.empty(rows, inner, device=dev, dtype=torch.float32) if wq_out is None else wq_out
+    L.check(L.lib().rdo_weight_unpack(_ptr(packed), _ptr(delta) if dequant else None, _ptr(zp) if dequant else None, rows, inner, bits,
+                                      _ptr(lv), _ptr(wq), _stream()), "rdo_weight_unpack")
+    return lv, wq
+
+
 def actquant_static_bwd(x, g, rng, drange, dx=None, n_bits=8, ws=None):
     """Backward of `actquant_static` with a straight-through round: returns dx (= g inside the range, 0 outside; `dx` may be g) and
     accumulates the per-channel range gradient into drange [2C] = dlo | dhi.  x, g: [..., C] channels-last, contiguous."""

@@ -188,6 +188,18 @@ class QuantModel(nn.Module):
         out["total"] = {"weights": tw, "size_bits": ts, "avg_bits": ts / tw if tw else 0.0}
         return out
 
+    def save_packed(self, path):
+        """Write the packed checkpoint of this model: every weight's integer levels packed at their own width, the grids, the biases
+        and the frozen activation ranges -- no fp32 weight (`packed.save_packed`).  -> the sizes written."""
+        from .packed import save_packed
+        return save_packed(self, path)
+
+    def load_packed(self, path):
+        """Install a packed checkpoint into this model, which must be of the file's architecture and not calibrated; it then computes bit
+        for bit what the saved model computed (`packed.load_packed`).  A refusal leaves the model as it was."""
+        from .packed import load_packed
+        return load_packed(self, path)
+
     def forward(self, input):
         return self.model(input)
 
