@@ -2,14 +2,17 @@
 
 Conventions: every tensor is a contiguous fp32 CUDA tensor; activations are NHWC `[B,H,W,C]`, conv weights OHWI
 `[Cout,KH,KW,Cin]` (the memory image of torch's channels_last OIHW weight).  Calls are enqueued on torch's current stream.
-When a plan is being recorded (hipops.plan.Plan.record()), the same calls are captured instead of launched."""
+When a plan is being recorded (hipops.plan.Plan.record()), the same calls are captured instead of launched.
+A wrapper that checks its arguments does so with the functions of `_args` (one tensor check, one whole-number check), and every check
+runs before a pointer is taken (`_ptr`, `_ptr64`) or a library call made.  Workspaces a wrapper keeps between calls come from
+`_workspace`; the convolutions' split-K scratch has its own rule (`_scratch`)."""
 import ctypes as C
 import math
-import numbers
 import threading
 
 import torch
 
+from . import _args as A
 from . import _lib as L
 
 
@@ -30,16 +33,21 @@ class H2:
         return self.t.device
 
 
-def _ptr(t):
+def _ptr(t, dtypes=(torch.float32, torch.int32, torch.int16), names="fp32/int32"):
     if t is None:
         return None
     if isinstance(t, H2):
         t = t.t
     if not t.is_cuda:
         raise RuntimeError(f"librdoptq_hip has no CPU path: tensor is on {t.device}")
-    if t.dtype not in (torch.float32, torch.int32, torch.int16) or not t.is_contiguous():
-        raise RuntimeError(f"librdoptq_hip needs contiguous fp32/int32 tensors, got {t.dtype} contiguous={t.is_contiguous()}")
+    if t.dtype not in dtypes or not t.is_contiguous():
+        raise RuntimeError(f"librdoptq_hip needs contiguous {names} tensors, got {t.dtype} contiguous={t.is_contiguous()}")
     return C.c_void_p(t.data_ptr())
+
+
+def _ptr64(t):
+    """`_ptr` for the float64 operands: tap sums, bias shifts, scan errors and scores"""
+    return _ptr(t, (torch.float64,), "float64")
 
 
 def _pscale(planes):
@@ -70,6 +78,27 @@ def _scratch(device, n_floats):
     if not pool or pool[-1].numel() < n_floats:
         pool.append(torch.empty(max(n_floats, 1 << 22), device=device, dtype=torch.float32))
     return pool[-1]
+
+
+_WORKSPACE = {}     # (op, device, *key) -> the workspace a wrapper keeps between its calls
+
+
+def _workspace(op, device, need, dtype=torch.float32, *key):
+    """Workspace of wrapper `op` on `device` (one without an index is the current one) for `key`: at least `need` elements of `dtype`,
+    made or replaced by a larger one when there is none that large.  Launches are stream-ordered, so one buffer per key suffices.  Not
+    for a wrapper that a plan records: a replaced buffer is let go (`_scratch` keeps its ones)."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    ws = _WORKSPACE.get((op, device) + key)
+    if ws is None or ws.numel() < need:
+        ws = _WORKSPACE[(op, device) + key] = torch.empty(need, device=device, dtype=dtype)
+    return ws
+
+
+def _workspaces(op):
+    """the live workspaces of wrapper `op` (for the tests that poison them between two launches)"""
+    return [ws for k, ws in _WORKSPACE.items() if k[0] == op]
 
 
 def uses_bf16x6(x_shape, w_shape, stride, pad):
@@ -376,25 +405,20 @@ def actquant_score(x, cand, err, clip=None, energy=None, n_bits=8, ws=None):
     """The measured squared error of K grids on x [..., C]: cand [K, 2C] = rows lo_k | hi_k; err [C, K] += sum (x - Q_k(x))^2 with Q_k the
     expression of `actquant_static` on row k; clip [C, K, 2] (int32) += the counts of x < lo_k | x > hi_k; energy [C] += sum x^2.  `clip`
     and `energy` may be None (err is the same bits).  Everything is checked on the host before the call."""
-    def bad(t, shape, dtype):
-        return not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous()
-    if not torch.is_tensor(x) or x.dim() < 1 or x.dtype != torch.float32 or not x.is_contiguous() or x.numel() == 0:
-        raise ValueError("actquant_score: x must be a non-empty contiguous fp32 tensor [..., C]")
+    what = "actquant_score"
+    A.tensor(what, "x", x, contiguous=True)
+    if x.dim() < 1:
+        raise ValueError(f"{what}: x must be [..., C], got a scalar")
     Cc = x.shape[-1]
-    if not torch.is_tensor(cand) or cand.dim() != 2 or not 1 <= cand.shape[0] <= ACT_SCORE_MAX:
-        raise ValueError(f"actquant_score: cand must be [K, 2C] with K in 1..{ACT_SCORE_MAX}, got "
+    if not torch.is_tensor(cand) or cand.dim() != 2 or not 1 <= cand.shape[0] <= ACT_SCORE_MAX:      # (K is read off cand: its own check)
+        raise ValueError(f"{what}: cand must be [K, 2C] with K in 1..{ACT_SCORE_MAX}, got "
                          f"{tuple(cand.shape) if torch.is_tensor(cand) else type(cand).__name__}")
     K = int(cand.shape[0])
-    if bad(cand, (K, 2 * Cc), torch.float32):
-        raise ValueError(f"actquant_score: cand must be a contiguous fp32 [{K}, {2 * Cc}], got {cand.dtype} {tuple(cand.shape)}")
-    if bad(err, (Cc, K), torch.float32):
-        raise ValueError(f"actquant_score: err must be a contiguous fp32 [{Cc}, {K}]")
-    if clip is not None and bad(clip, (Cc, K, 2), torch.int32):
-        raise ValueError(f"actquant_score: clip must be a contiguous int32 [{Cc}, {K}, 2] or None")
-    if energy is not None and bad(energy, (Cc,), torch.float32):
-        raise ValueError(f"actquant_score: energy must be a contiguous fp32 [{Cc}] or None")
-    if isinstance(n_bits, bool) or not isinstance(n_bits, int) or not 2 <= n_bits <= 16:
-        raise ValueError(f"actquant_score: n_bits {n_bits!r} outside [2, 16]")
+    A.tensor(what, "cand", cand, shape=(K, 2 * Cc), contiguous=True, oneshot=True)
+    A.tensor(what, "err", err, shape=(Cc, K), contiguous=True, oneshot=True)
+    A.tensor(what, "clip", clip, torch.int32, "int32", shape=(Cc, K, 2), contiguous=True, optional=True, oneshot=True)
+    A.tensor(what, "energy", energy, shape=(Cc,), contiguous=True, optional=True, oneshot=True)
+    n_bits = A.whole(what, "n_bits", n_bits, 2, 16)
     need = int(L.lib().rdo_actquant_score_workspace(Cc, K))
     if ws is None or ws.numel() < need:
         ws = torch.empty(need, device=x.device, dtype=torch.float32)
@@ -403,43 +427,33 @@ def actquant_score(x, cand, err, clip=None, energy=None, n_bits=8, ws=None):
     return err
 
 
-_PAIR_WS = {}       # (device, C) -> workspace of pair_moments (launches are stream-ordered, so one buffer per key suffices)
-
-
 def pair_moments(a, b, out=None):
     """Per-channel moments of two tensors of the same channels-last storage [..., C]: with d = a - b formed in fp32, -> float32 [3, C] =
     sum d | sum d^2 | sum a^2 over the pixels, in one read of both (a fixed summation order: the same input gives the same bits).  `out`:
     a contiguous fp32 [3, C] on the operands' device that is ADDED TO; None makes a zero one.  Everything is checked on the host before
     a pointer is taken."""
+    what = "pair_moments"
     for name, t in (("a", a), ("b", b)):
-        if not torch.is_tensor(t) or t.dtype != torch.float32:
-            raise ValueError(f"pair_moments: {name} must be an fp32 tensor, got {t.dtype if torch.is_tensor(t) else type(t).__name__}")
+        A.tensor(what, name, t, nonempty=False)
     if a.shape != b.shape:
-        raise ValueError(f"pair_moments: a is {tuple(a.shape)}, b is {tuple(b.shape)}: the shapes differ")
+        raise ValueError(f"{what}: a is {tuple(a.shape)}, b is {tuple(b.shape)}: the shapes differ")
     if a.dim() < 1 or a.numel() == 0:
-        raise ValueError(f"pair_moments: the operands are empty or scalars: {tuple(a.shape)}")
-    if not a.is_contiguous() or not b.is_contiguous():
-        raise ValueError("pair_moments: a and b must be contiguous")
-    if a.device != b.device:
-        raise ValueError(f"pair_moments: a is on {a.device}, b on {b.device}")
+        raise ValueError(f"{what}: the operands are empty or scalars: {tuple(a.shape)}")
+    for name, t in (("a", a), ("b", b)):
+        A.tensor(what, name, t, contiguous=True)
+    A.tensor(what, "a", a, device=b.device, other="b")
     Cc = int(a.shape[-1])
-    if out is not None and (not torch.is_tensor(out) or tuple(out.shape) != (3, Cc) or out.dtype != torch.float32 or out.device != a.device
-                            or not out.is_contiguous()):
-        raise ValueError(f"pair_moments: out must be a contiguous fp32 [3, {Cc}] on {a.device}, got "
-                         f"{(out.dtype, tuple(out.shape), out.device) if torch.is_tensor(out) else type(out).__name__}")
+    A.tensor(what, "out", out, shape=(3, Cc), contiguous=True, device=a.device, optional=True, oneshot=True)
     if not a.is_cuda:
-        raise ValueError(f"pair_moments: the operands are on {a.device}; there is no CPU path")
+        raise ValueError(f"{what}: the operands are on {a.device}; there is no CPU path")
     if out is None:
         out = torch.zeros(3, Cc, device=a.device, dtype=torch.float32)
-    ws = _PAIR_WS.get((a.device, Cc))
-    if ws is None:
-        ws = _PAIR_WS[(a.device, Cc)] = torch.empty(int(L.lib().rdo_pair_moments_workspace(Cc)), device=a.device, dtype=torch.float32)
+    ws = _workspace(what, a.device, int(L.lib().rdo_pair_moments_workspace(Cc)), torch.float32, Cc)
     L.check(L.lib().rdo_pair_moments(_ptr(a), _ptr(b), a.numel() // Cc, Cc, _ptr(out), _ptr(ws), _stream()), "rdo_pair_moments")
     return out
 
 
 TAP_MAX_SEGMENTS = 48    # kTapMaxSegs of csrc/bias_correct.hip: index runs per axis the kernel arguments hold
-_TAP_WS = {}        # (device, C, k) -> workspace of tap_sums (launches are stream-ordered, so one buffer per key suffices)
 
 
 def tap_out_size(n, k, stride, pad, transposed=False, output_padding=0):
@@ -447,13 +461,6 @@ def tap_out_size(n, k, stride, pad, transposed=False, output_padding=0):
     if transposed:
         return (n - 1) * stride - 2 * pad + k + output_padding
     return (n + 2 * pad - k) // stride + 1
-
-
-def _whole(what, name, v, lo):
-    """an integer (Python's or numpy's; not a bool) >= lo, as an int"""
-    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < lo:
-        raise ValueError(f"{what}: {name} must be a whole number >= {lo}, got {v!r}")
-    return int(v)
 
 
 def tap_sums(x, k, stride, pad, out_hw, transposed=False, out=None):
@@ -464,20 +471,16 @@ def tap_sums(x, k, stride, pad, out_hw, transposed=False, out=None):
     ADDED TO; None makes a zero one.  One read of x in a fixed summation order: the same input gives the same bits.  Everything is
     checked on the host before a pointer is taken."""
     what = "tap_sums"
-    if not torch.is_tensor(x) or x.dtype != torch.float32:
-        raise ValueError(f"{what}: x must be an fp32 tensor, got {x.dtype if torch.is_tensor(x) else type(x).__name__}")
-    k = _whole(what, "k", k, 1)
+    A.tensor(what, "x", x, nonempty=False)
+    k = A.whole(what, "k", k, 1)
     if k > L.TAP_MAX_K:
         raise ValueError(f"{what}: k = {k}, at most {L.TAP_MAX_K} is supported")
-    stride, pad = _whole(what, "stride", stride, 1), _whole(what, "pad", pad, 0)
+    stride, pad = A.whole(what, "stride", stride, 1), A.whole(what, "pad", pad, 0)
     if not isinstance(transposed, bool):
         raise ValueError(f"{what}: transposed must be True or False, got {transposed!r}")
     if x.dim() != 4 and not (k == 1 and x.dim() >= 2):
         raise ValueError(f"{what}: x must be channels-last of rank 4 [N, H, W, C] (any rank >= 2 for k = 1), got rank {x.dim()}")
-    if x.numel() == 0:
-        raise ValueError(f"{what}: x is empty: {tuple(x.shape)}")
-    if not x.is_contiguous():
-        raise ValueError(f"{what}: x must be contiguous")
+    A.tensor(what, "x", x, contiguous=True)
     Cc = int(x.shape[-1])
     if x.dim() == 4:
         N, H, W = (int(v) for v in x.shape[:3])
@@ -489,10 +492,11 @@ def tap_sums(x, k, stride, pad, out_hw, transposed=False, out=None):
         if x.dim() != 4 and out_hw is not None:
             raise ValueError(f"{what}: out_hw must be None for a token tensor of rank {x.dim()}")
         out_hw = (H, W)
-    if (not isinstance(out_hw, (tuple, list)) or len(out_hw) != 2
-            or any(isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < 1 for v in out_hw)):
-        raise ValueError(f"{what}: out_hw must be a pair of positive whole numbers (Ho, Wo), got {out_hw!r}")
-    for name, n_in, n_out in (("Ho", H, int(out_hw[0])), ("Wo", W, int(out_hw[1]))):
+    pair = "a pair of positive whole numbers (Ho, Wo)"
+    if not isinstance(out_hw, (tuple, list)) or len(out_hw) != 2:
+        raise ValueError(f"{what}: out_hw must be {pair}, got {out_hw!r}")
+    Ho, Wo = (A.whole(what, "out_hw", v, 1, want=pair) for v in out_hw)
+    for name, n_in, n_out in (("Ho", H, Ho), ("Wo", W, Wo)):
         if transposed:
             lo = (n_in - 1) * stride - 2 * pad + k
             if not lo <= n_out < lo + stride:
@@ -507,19 +511,14 @@ def tap_sums(x, k, stride, pad, out_hw, transposed=False, out=None):
     if transposed and 2 * (-(-pad // stride)) > TAP_MAX_SEGMENTS:
         # (a conv has at most 2 (k - 1) border indices, and no axis more than 4 k + 4 distinct tap masks: only this one can happen)
         raise ValueError(f"{what}: geometry: pad {pad} at stride {stride} leaves more than {TAP_MAX_SEGMENTS} border indices on an axis")
-    if out is not None and (not torch.is_tensor(out) or tuple(out.shape) != (k * k, Cc) or out.dtype != torch.float32
-                            or out.device != x.device or not out.is_contiguous()):
-        raise ValueError(f"{what}: out must be a contiguous fp32 [{k * k}, {Cc}] on {x.device}, got "
-                         f"{(out.dtype, tuple(out.shape), out.device) if torch.is_tensor(out) else type(out).__name__}")
+    A.tensor(what, "out", out, shape=(k * k, Cc), contiguous=True, device=x.device, optional=True, oneshot=True)
     if not x.is_cuda:
         raise ValueError(f"{what}: x is on {x.device}; there is no CPU path")
     if out is None:
         out = torch.zeros(k * k, Cc, device=x.device, dtype=torch.float32)
-    ws = _TAP_WS.get((x.device, Cc, k))
-    if ws is None:
-        ws = _TAP_WS[(x.device, Cc, k)] = torch.empty(int(L.lib().rdo_tap_sums_workspace(Cc, k)), device=x.device, dtype=torch.float32)
-    L.check(L.lib().rdo_tap_sums(_ptr(x), N, H, W, Cc, k, stride, pad, int(out_hw[0]), int(out_hw[1]), int(transposed), _ptr(out),
-                                 _ptr(ws), _stream()), "rdo_tap_sums")
+    ws = _workspace(what, x.device, int(L.lib().rdo_tap_sums_workspace(Cc, k)), torch.float32, Cc, k)
+    L.check(L.lib().rdo_tap_sums(_ptr(x), N, H, W, Cc, k, stride, pad, Ho, Wo, int(transposed), _ptr(out), _ptr(ws), _stream()),
+            "rdo_tap_sums")
     return out
 
 
@@ -530,16 +529,9 @@ def bias_shift(w_ref, w_q, s_ref, s_q, n, org_bias, shift=None, bias_out=None):
     difference in float64, and bias_out fp32 [O] = float32(org_bias + shift)).  Everything is checked on the host before a pointer is
     taken."""
     what = "bias_shift"
-    for name, t, dt in (("w_ref", w_ref, torch.float32), ("w_q", w_q, torch.float32), ("org_bias", org_bias, torch.float32),
-                        ("s_ref", s_ref, torch.float64), ("s_q", s_q, torch.float64)):
-        if not torch.is_tensor(t) or t.dtype != dt:
-            raise ValueError(f"{what}: {name} must be a {str(dt).split('.')[-1]} tensor, got {t.dtype if torch.is_tensor(t) else type(t).__name__}")
-        if t.numel() == 0:
-            raise ValueError(f"{what}: {name} is empty")
-        if not t.is_contiguous():
-            raise ValueError(f"{what}: {name} must be contiguous")
-        if t.device != w_ref.device:
-            raise ValueError(f"{what}: {name} is on {t.device}, w_ref on {w_ref.device}")
+    f32, f64 = (torch.float32, "float32"), (torch.float64, "float64")
+    for name, t, dt in (("w_ref", w_ref, f32), ("w_q", w_q, f32), ("org_bias", org_bias, f32), ("s_ref", s_ref, f64), ("s_q", s_q, f64)):
+        A.tensor(what, name, t, *dt, contiguous=True, device=None if t is w_ref else w_ref.device, other="w_ref")
     if w_ref.dim() < 2 or w_q.shape != w_ref.shape:
         raise ValueError(f"{what}: w_ref {tuple(w_ref.shape)} and w_q {tuple(w_q.shape)} must be the same rows [O, ...] of rank >= 2")
     O = int(w_ref.shape[0])
@@ -547,25 +539,17 @@ def bias_shift(w_ref, w_q, s_ref, s_q, n, org_bias, shift=None, bias_out=None):
     for name, t in (("s_ref", s_ref), ("s_q", s_q)):
         if t.numel() != K:
             raise ValueError(f"{what}: {name} holds {t.numel()} elements, the weight rows {K}")
-    if tuple(org_bias.shape) != (O,):
-        raise ValueError(f"{what}: org_bias has shape {tuple(org_bias.shape)}, expected ({O},)")
-    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
-        raise ValueError(f"{what}: n must be a positive whole number of output pixels, got {n!r}")
-    for name, t, dt in (("shift", shift, torch.float64), ("bias_out", bias_out, torch.float32)):
-        if t is not None and (not torch.is_tensor(t) or tuple(t.shape) != (O,) or t.dtype != dt or t.device != w_ref.device
-                              or not t.is_contiguous()):
-            raise ValueError(f"{what}: {name} must be a contiguous {str(dt).split('.')[-1]} [{O}] on {w_ref.device}")
+    A.tensor(what, "org_bias", org_bias, *f32, shape=(O,))
+    n = A.whole(what, "n", n, 1, want="a positive whole number of output pixels")
+    for name, t, dt in (("shift", shift, f64), ("bias_out", bias_out, f32)):
+        A.tensor(what, name, t, *dt, shape=(O,), contiguous=True, device=w_ref.device, optional=True, oneshot=True)
     if not w_ref.is_cuda:
         raise ValueError(f"{what}: the operands are on {w_ref.device}; there is no CPU path")
     shift = torch.empty(O, device=w_ref.device, dtype=torch.float64) if shift is None else shift
     bias_out = torch.empty(O, device=w_ref.device, dtype=torch.float32) if bias_out is None else bias_out
-    dptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731  (float64 operands: _ptr admits fp32 / int only)
-    L.check(L.lib().rdo_bias_shift(_ptr(w_ref), _ptr(w_q), dptr(s_ref), dptr(s_q), 1.0 / n, _ptr(org_bias), O, K, dptr(shift),
+    L.check(L.lib().rdo_bias_shift(_ptr(w_ref), _ptr(w_q), _ptr64(s_ref), _ptr64(s_q), 1.0 / n, _ptr(org_bias), O, K, _ptr64(shift),
                                    _ptr(bias_out), _stream()), "rdo_bias_shift")
     return shift, bias_out
-
-
-_SCAN_WS = {}       # device -> workspace of uaq_width_scan (launches are stream-ordered, so one growing buffer per device suffices)
 
 
 def width_list(what, widths, max_bits=L.WIDTH_SCAN_MAX_BITS):
@@ -575,10 +559,7 @@ def width_list(what, widths, max_bits=L.WIDTH_SCAN_MAX_BITS):
     widths = list(widths)
     if not 1 <= len(widths) <= L.WIDTH_SCAN_MAX_K:
         raise ValueError(f"{what}: widths must hold 1 .. {L.WIDTH_SCAN_MAX_K} entries, got {len(widths)}")
-    for b in widths:
-        if isinstance(b, bool) or not isinstance(b, numbers.Integral) or not L.WIDTH_SCAN_MIN_BITS <= b <= max_bits:
-            raise ValueError(f"{what}: every width must be a whole number in {L.WIDTH_SCAN_MIN_BITS} .. {max_bits}, got {b!r}")
-    widths = [int(b) for b in widths]
+    widths = [A.whole(what, "every width", b, L.WIDTH_SCAN_MIN_BITS, max_bits) for b in widths]
     if len(set(widths)) != len(widths):
         raise ValueError(f"{what}: widths must be distinct, got {widths}")
     return widths
@@ -592,14 +573,7 @@ def uaq_width_scan(w_rows, widths, delta=None, zp=None):
     bit for bit; with both given (fp32 [K, rows] on w_rows' device) they are copied through and scored.  Float64 sums in a fixed order:
     the same input gives the same bits.  Everything is checked on the host before a pointer is taken."""
     what = "uaq_width_scan"
-    if not torch.is_tensor(w_rows) or w_rows.dtype != torch.float32:
-        raise ValueError(f"{what}: w_rows must be an fp32 tensor, got {w_rows.dtype if torch.is_tensor(w_rows) else type(w_rows).__name__}")
-    if w_rows.dim() != 2:
-        raise ValueError(f"{what}: w_rows must be of rank 2 [rows, inner], got rank {w_rows.dim()}")
-    if w_rows.numel() == 0:
-        raise ValueError(f"{what}: w_rows is empty: {tuple(w_rows.shape)}")
-    if not w_rows.is_contiguous():
-        raise ValueError(f"{what}: w_rows must be contiguous")
+    A.tensor(what, "w_rows", w_rows, rank=2, layout="of rank 2 [rows, inner]", contiguous=True)
     widths = width_list(what, widths)
     rows, inner, K = int(w_rows.shape[0]), int(w_rows.shape[1]), len(widths)
     if rows > 0x7fffffff:
@@ -607,46 +581,25 @@ def uaq_width_scan(w_rows, widths, delta=None, zp=None):
     if (delta is None) != (zp is None):
         raise ValueError(f"{what}: delta and zp must be given together or not at all")
     for name, t in (("delta", delta), ("zp", zp)):
-        if t is not None and (not torch.is_tensor(t) or tuple(t.shape) != (K, rows) or t.dtype != torch.float32 or t.device != w_rows.device
-                              or not t.is_contiguous()):
-            raise ValueError(f"{what}: {name} must be a contiguous fp32 [{K}, {rows}] on {w_rows.device}, got "
-                             f"{(t.dtype, tuple(t.shape), t.device) if torch.is_tensor(t) else type(t).__name__}")
+        A.tensor(what, name, t, shape=(K, rows), contiguous=True, device=w_rows.device, optional=True, oneshot=True)
     if inner > L.WIDTH_SCAN_LDS_ROW and rows * -(-inner // L.WIDTH_SCAN_CHUNK) > 0x7fffffff:
         raise ValueError(f"{what}: [{rows}, {inner}] splits into more shares than 32-bit workgroup indices hold")
     if not w_rows.is_cuda:
         raise ValueError(f"{what}: w_rows is on {w_rows.device}; there is no CPU path")
-    need = int(L.lib().rdo_uaq_width_scan_workspace(rows, inner, K))
-    ws = _SCAN_WS.get(w_rows.device)
-    if ws is None or ws.numel() * 8 < need:
-        ws = _SCAN_WS[w_rows.device] = torch.empty(-(-need // 8), device=w_rows.device, dtype=torch.float64)
+    need = int(L.lib().rdo_uaq_width_scan_workspace(rows, inner, K))              # in bytes
+    ws = _workspace(what, w_rows.device, -(-need // 8), torch.float64)
     out_d = torch.empty(K, rows, device=w_rows.device, dtype=torch.float32)
     out_z = torch.empty_like(out_d)
     err = torch.empty(K, rows, device=w_rows.device, dtype=torch.float64)
     energy = torch.empty(rows, device=w_rows.device, dtype=torch.float64)
-    dptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731  (float64 operands: _ptr admits fp32 / int only)
     L.check(L.lib().rdo_uaq_width_scan(_ptr(w_rows), rows, inner, (C.c_int32 * K)(*widths), K, _ptr(delta), _ptr(zp), _ptr(out_d), _ptr(out_z),
-                                       dptr(err), dptr(energy), dptr(ws), _stream()), "rdo_uaq_width_scan")
+                                       _ptr64(err), _ptr64(energy), _ptr64(ws), _stream()), "rdo_uaq_width_scan")
     return out_d, out_z, err, energy
 
 
 def pack_row_words(inner, bits):
     """W = ceil(inner * bits / 32): the 32-bit words one row of `inner` codes of `bits` bits occupies (rdo_pack_row_words on the host)"""
     return -(-int(inner) * int(bits) // 32)
-
-
-def _pack_bits(what, bits):
-    if isinstance(bits, bool) or not isinstance(bits, numbers.Integral) or not L.PACK_MIN_BITS <= bits <= L.PACK_MAX_BITS:
-        raise ValueError(f"{what}: bits must be a whole number in {L.PACK_MIN_BITS} .. {L.PACK_MAX_BITS}, got {bits!r}")
-    return int(bits)
-
-
-def _pack_operand(what, name, t, dtype, shape, device=None, like=None):
-    """a contiguous tensor of `dtype` and `shape` (on `device`, when given), else ValueError; `like`: how the message words the dtype"""
-    if (not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous()
-            or (device is not None and t.device != device)):
-        where = "" if device is None else f" on {device}"
-        raise ValueError(f"{what}: {name} must be a contiguous {like} {list(shape)}{where}, got "
-                         f"{(t.dtype, tuple(t.shape), t.device) if torch.is_tensor(t) else type(t).__name__}")
 
 
 def _pack_geometry(what, rows, inner, bits):
@@ -664,23 +617,15 @@ def weight_pack(w_rows, delta, zp, bits, alpha_rows=None, out=None):
     -> int32 [rows, W] holding raw bits, W = ceil(inner * bits / 32); every word is written, the padding bits are zero.  `out`: a
     contiguous int32 [rows, W] to write into.  Everything is checked on the host before a pointer is taken."""
     what = "weight_pack"
-    if not torch.is_tensor(w_rows) or w_rows.dtype != torch.float32:
-        raise ValueError(f"{what}: w_rows must be an fp32 tensor, got {w_rows.dtype if torch.is_tensor(w_rows) else type(w_rows).__name__}")
-    if w_rows.dim() != 2:
-        raise ValueError(f"{what}: w_rows must be of rank 2 [rows, inner], got rank {w_rows.dim()}")
-    if w_rows.numel() == 0:
-        raise ValueError(f"{what}: w_rows is empty: {tuple(w_rows.shape)}")
-    if not w_rows.is_contiguous():
-        raise ValueError(f"{what}: w_rows must be contiguous")
-    bits = _pack_bits(what, bits)
+    A.tensor(what, "w_rows", w_rows, rank=2, layout="of rank 2 [rows, inner]", contiguous=True)
+    bits = A.whole(what, "bits", bits, L.PACK_MIN_BITS, L.PACK_MAX_BITS)
     rows, inner, dev = int(w_rows.shape[0]), int(w_rows.shape[1]), w_rows.device
-    _pack_operand(what, "delta", delta, torch.float32, (rows,), dev, "fp32")
-    _pack_operand(what, "zp", zp, torch.float32, (rows,), dev, "fp32")
-    if alpha_rows is not None:
-        _pack_operand(what, "alpha_rows", alpha_rows, torch.float32, (rows, inner), dev, "fp32")
+    fits = dict(contiguous=True, device=dev, oneshot=True)
+    A.tensor(what, "delta", delta, shape=(rows,), **fits)
+    A.tensor(what, "zp", zp, shape=(rows,), **fits)
+    A.tensor(what, "alpha_rows", alpha_rows, shape=(rows, inner), optional=True, **fits)
     W = _pack_geometry(what, rows, inner, bits)
-    if out is not None:
-        _pack_operand(what, "out", out, torch.int32, (rows, W), dev, "int32")
+    A.tensor(what, "out", out, torch.int32, "int32", shape=(rows, W), optional=True, **fits)
     if not w_rows.is_cuda:
         raise ValueError(f"{what}: w_rows is on {dev}; there is no CPU path")
     out = torch.empty(rows, W, device=dev, dtype=torch.int32) if out is None else out
@@ -696,34 +641,25 @@ def weight_unpack(packed, delta, zp, inner, bits, levels=True, dequant=True, lev
     least one of the two must be asked for.  `levels_out`, `wq_out`: contiguous tensors to write into.  Everything is checked on the
     host before a pointer is taken."""
     what = "weight_unpack"
-    if not torch.is_tensor(packed) or packed.dtype != torch.int32:
-        raise ValueError(f"{what}: packed must be an int32 tensor, got {packed.dtype if torch.is_tensor(packed) else type(packed).__name__}")
-    if packed.dim() != 2:
-        raise ValueError(f"{what}: packed must be of rank 2 [rows, W], got rank {packed.dim()}")
-    if packed.numel() == 0:
-        raise ValueError(f"{what}: packed is empty: {tuple(packed.shape)}")
-    if not packed.is_contiguous():
-        raise ValueError(f"{what}: packed must be contiguous")
-    bits = _pack_bits(what, bits)
-    if isinstance(inner, bool) or not isinstance(inner, numbers.Integral) or inner < 1:
-        raise ValueError(f"{what}: inner must be a whole number >= 1, got {inner!r}")
-    if not isinstance(levels, bool) or not isinstance(dequant, bool) or not (levels or dequant):
+    A.tensor(what, "packed", packed, torch.int32, "int32", rank=2, layout="of rank 2 [rows, W]", contiguous=True)
+    bits = A.whole(what, "bits", bits, L.PACK_MIN_BITS, L.PACK_MAX_BITS)
+    inner = A.whole(what, "inner", inner, 1)
+    if not (isinstance(levels, bool) and isinstance(dequant, bool) and (levels or dequant)):
         raise ValueError(f"{what}: levels and dequant must be True or False, and one of them True; got {levels!r}, {dequant!r}")
-    rows, inner, dev = int(packed.shape[0]), int(inner), packed.device
+    rows, dev = int(packed.shape[0]), packed.device
+    fits = dict(contiguous=True, device=dev, oneshot=True)
     W = _pack_geometry(what, rows, inner, bits)
     if packed.shape[1] != W:
         raise ValueError(f"{what}: packed is {tuple(packed.shape)}; {inner} codes of {bits} bits make W = {W} words a row")
     if dequant or delta is not None or zp is not None:
-        _pack_operand(what, "delta", delta, torch.float32, (rows,), dev, "fp32")
-        _pack_operand(what, "zp", zp, torch.float32, (rows,), dev, "fp32")
-    if levels_out is not None:
-        if not levels:
-            raise ValueError(f"{what}: levels_out is given but levels is False")
-        _pack_operand(what, "levels_out", levels_out, torch.int32, (rows, inner), dev, "int32")
-    if wq_out is not None:
-        if not dequant:
-            raise ValueError(f"{what}: wq_out is given but dequant is False")
-        _pack_operand(what, "wq_out", wq_out, torch.float32, (rows, inner), dev, "fp32")
+        A.tensor(what, "delta", delta, shape=(rows,), **fits)
+        A.tensor(what, "zp", zp, shape=(rows,), **fits)
+    if levels_out is not None and not levels:
+        raise ValueError(f"{what}: levels_out is given but levels is False")
+    A.tensor(what, "levels_out", levels_out, torch.int32, "int32", shape=(rows, inner), optional=True, **fits)
+    if wq_out is not None and not dequant:
+        raise ValueError(f"{what}: wq_out is given but dequant is False")
+    A.tensor(what, "wq_out", wq_out, shape=(rows, inner), optional=True, **fits)
     if not packed.is_cuda:
         raise ValueError(f"{what}: packed is on {dev}; there is no CPU path")
     lv = wq = None
@@ -774,19 +710,24 @@ def actquant_hist(x, rng, hist):
     """hist [C, 1024] (int32) += the per-channel counts of x [..., C] on the observed range rng = lo[C] | hi[C] (the bin rule of
     include/rdo_ptq_hip.h).  The caller keeps a channel's total below 2^31."""
     Cc, npix = _act_range_check(x, rng, "actquant_hist")
-    if tuple(hist.shape) != (Cc, ACT_HIST_BINS) or hist.dtype != torch.int32 or not hist.is_contiguous():
-        raise ValueError(f"actquant_hist: hist must be a contiguous int32 [{Cc}, {ACT_HIST_BINS}], got {hist.dtype} {tuple(hist.shape)}")
+    A.tensor("actquant_hist", "hist", hist, torch.int32, "int32", shape=(Cc, ACT_HIST_BINS), contiguous=True, oneshot=True)
     L.check(L.lib().rdo_actquant_hist(_ptr(x), npix, Cc, _ptr(rng), _ptr(hist), _stream()), "rdo_actquant_hist")
     return hist
+
+
+def _hist_operands(what, hist, rng):
+    """-> C of a contiguous int32 histogram [C, 1024] whose range holds 2C floats"""
+    Cc = hist.shape[0]
+    A.tensor(what, "hist", hist, torch.int32, "int32", shape=(Cc, ACT_HIST_BINS), contiguous=True, oneshot=True)
+    if rng.numel() != 2 * Cc:
+        raise ValueError(f"{what}: the range holds {rng.numel()} floats, the histogram has {Cc} channels: not [2C]")
+    return Cc
 
 
 def act_percentile_select(hist, rng, tail):
     """-> a new range [2C]: every channel's observed range rng with whole bins dropped from each end while the dropped count stays within
     floor(tail * n) (tail = 1 - p / 100; 0 returns rng bit for bit)."""
-    Cc = hist.shape[0]
-    if tuple(hist.shape) != (Cc, ACT_HIST_BINS) or hist.dtype != torch.int32 or not hist.is_contiguous() or rng.numel() != 2 * Cc:
-        raise ValueError(f"act_percentile_select: hist {hist.dtype} {tuple(hist.shape)} / range [{rng.numel()}] are not int32 "
-                         f"[C, {ACT_HIST_BINS}] / [2C]")
+    Cc = _hist_operands("act_percentile_select", hist, rng)
     out = torch.empty_like(rng)
     L.check(L.lib().rdo_act_percentile_select(_ptr(hist), Cc, _ptr(rng), float(tail), _ptr(out), _stream()), "rdo_act_percentile_select")
     return out
@@ -796,18 +737,12 @@ def act_hist_mse_select(hist, rng, n_bits, score=False):
     """-> a new range [2C]: every channel's observed range rng with the whole bins dropped from each end that minimise the modelled
     squared quantisation error on a grid of n_bits (exhaustive search over all clip pairs: the rule of include/rdo_ptq_hip.h).
     `score`: -> (range, float64 [C, 2] = S of the choice | S(0, 0); 0 | 0 for a channel that kept its range)."""
-    Cc = hist.shape[0]
-    if tuple(hist.shape) != (Cc, ACT_HIST_BINS) or hist.dtype != torch.int32 or not hist.is_contiguous() or rng.numel() != 2 * Cc:
-        raise ValueError(f"act_hist_mse_select: hist {hist.dtype} {tuple(hist.shape)} / range [{rng.numel()}] are not int32 "
-                         f"[C, {ACT_HIST_BINS}] / [2C]")
-    if isinstance(n_bits, bool) or not isinstance(n_bits, int) or not 2 <= n_bits <= 16:
-        raise ValueError(f"act_hist_mse_select: n_bits {n_bits!r} outside [2, 16]")
+    Cc = _hist_operands("act_hist_mse_select", hist, rng)
+    n_bits = A.whole("act_hist_mse_select", "n_bits", n_bits, 2, 16)
     out = torch.empty_like(rng)
-    sc = torch.empty(Cc, 2, device=rng.device, dtype=torch.float64) if score else None
-    # (the scores are the library's only float64 tensor: made here, on rng's device, after _ptr has checked the others)
     hp, rp, op = _ptr(hist), _ptr(rng), _ptr(out)
-    L.check(L.lib().rdo_act_hist_mse_select(hp, Cc, rp, n_bits, op, C.c_void_p(sc.data_ptr()) if score else None, _stream()),
-            "rdo_act_hist_mse_select")
+    sc = torch.empty(Cc, 2, device=rng.device, dtype=torch.float64) if score else None     # (made on rng's device once _ptr has accepted the others)
+    L.check(L.lib().rdo_act_hist_mse_select(hp, Cc, rp, n_bits, op, _ptr64(sc), _stream()), "rdo_act_hist_mse_select")
     return (out, sc) if score else out
 
 
@@ -1060,28 +995,10 @@ def conv_transpose2d(x, w_iohw_rows, bias, stride, pad, output_padding, epilogue
     return conv2d_fwd_pack(xu, pack.get("zi", lambda: WeightPack(pack.w.flip(1, 2), pack.bias)), 1, 0, epilogue=epilogue)
 
 
-def _row_tensor(what, name, t, ref=None, numel=None, shape=None, optional=False):
-    """Argument check of the LayerNorm / GELU / attention wrappers, made before any pointer is taken: `t` is a non-empty fp32 tensor (on
-    `ref`'s device), of `numel` elements or of `shape` when given.  The kernels index every operand by the first one's geometry, so
-    anything else is an out-of-bounds device access."""
-    if t is None and optional:
-        return
-    if not torch.is_tensor(t) or t.dtype != torch.float32:
-        raise ValueError(f"{what}: {name} must be an fp32 tensor, got {t.dtype if torch.is_tensor(t) else type(t).__name__}")
-    if t.numel() == 0:
-        raise ValueError(f"{what}: {name} is empty")
-    if ref is not None and t.device != ref.device:
-        raise ValueError(f"{what}: {name} is on {t.device}, the other operands on {ref.device}")
-    if numel is not None and t.numel() != numel:
-        raise ValueError(f"{what}: {name} holds {t.numel()} elements, expected {numel}")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{what}: {name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
-
-
 def _ln_operands(what, x, weight, bias=None, same=(), slabs=None, max_c=None, vec=False):
     """-> (rows, C, nslabs) of a LayerNorm call on x [..., C]: weight / bias [C] (or None), every tensor of `same` of x's shape (or None),
-    `slabs` [n >= 1, C]"""
-    _row_tensor(what, "x", x)
+    `slabs` [n >= 1, C]; all of them non-empty fp32 tensors on x's device"""
+    A.tensor(what, "x", x)
     if x.dim() < 1:
         raise ValueError(f"{what}: x must be [..., C], got a scalar")
     Cc = x.shape[-1]
@@ -1089,13 +1006,13 @@ def _ln_operands(what, x, weight, bias=None, same=(), slabs=None, max_c=None, ve
         raise ValueError(f"{what}: C = {Cc} channels, at most {max_c} are supported")
     if vec and Cc % 4:
         raise ValueError(f"{what}: C = {Cc} must be a multiple of 4")
-    _row_tensor(what, "weight", weight, x, shape=(Cc,), optional=True)
-    _row_tensor(what, "bias", bias, x, shape=(Cc,), optional=True)
+    A.tensor(what, "weight", weight, device=x.device, shape=(Cc,), optional=True)
+    A.tensor(what, "bias", bias, device=x.device, shape=(Cc,), optional=True)
     for name, t in same:
-        _row_tensor(what, name, t, x, shape=x.shape, optional=True)
+        A.tensor(what, name, t, device=x.device, shape=x.shape, optional=True)
     ns = 0
     if slabs is not None:
-        _row_tensor(what, "dgamma_slabs", slabs, x)
+        A.tensor(what, "dgamma_slabs", slabs, device=x.device)
         if slabs.dim() != 2 or slabs.shape[1] != Cc:
             raise ValueError(f"{what}: dgamma_slabs must be [n >= 1, {Cc}], got {tuple(slabs.shape)}")
         ns = slabs.shape[0]
@@ -1160,7 +1077,7 @@ def add_layer_norm(a, b, weight, bias, eps=1e-5, sum_out=None, out=None):
 def layer_norm_bwd_add(x, weight, dy, add1=None, add2=None, eps=1e-5, dx=None, dgamma_slabs=None):
     """dx = (add1) (+ add2) + LayerNorm-backward(dy); dgamma partial sums as in `layer_norm_bwd`."""
     what = "layer_norm_bwd_add"
-    _row_tensor(what, "dy", dy)
+    A.tensor(what, "dy", dy)
     rows, Cc, ns = _ln_operands(what, x, weight, same=(("dy", dy), ("add1", add1), ("add2", add2), ("dx", dx)), slabs=dgamma_slabs,
                                 max_c=512, vec=True)
     if add2 is not None and add1 is None:
@@ -1176,10 +1093,10 @@ def layer_norm_bwd_add(x, weight, dy, add1=None, add2=None, eps=1e-5, dx=None, d
 
 def add3(a, b, c, out=None):
     """(a + b) + c"""
-    _row_tensor("add3", "a", a)
+    A.tensor("add3", "a", a)
     for name, t in (("b", b), ("c", c)):
-        _row_tensor("add3", name, t, a, numel=a.numel())
-    _row_tensor("add3", "out", out, a, numel=a.numel(), optional=True)
+        A.tensor("add3", name, t, device=a.device, numel=a.numel())
+    A.tensor("add3", "out", out, device=a.device, numel=a.numel(), optional=True)
     if a.numel() % 4:
         raise ValueError(f"add3: {a.numel()} elements, the count must be a multiple of 4")
     out = torch.empty_like(a) if out is None else out
@@ -1190,7 +1107,7 @@ def add3(a, b, c, out=None):
 def layer_norm_bwd(x, weight, dy, eps=1e-5, dx=None, dgamma_slabs=None):
     """dx (returned) and, when `dgamma_slabs` [nslabs, C] is given, the partial sums of dy * xhat."""
     what = "layer_norm_bwd"
-    _row_tensor(what, "dy", dy)
+    A.tensor(what, "dy", dy)
     rows, Cc, ns = _ln_operands(what, x, weight, same=(("dy", dy), ("dx", dx)), slabs=dgamma_slabs, max_c=512)
     if dx is None and dgamma_slabs is None:
         raise ValueError(f"{what}: nothing to compute (neither dx nor dgamma_slabs)")
@@ -1227,13 +1144,13 @@ def window_attention(d, qkv, bias, out=None, probs=None, compute_out=True):
     """Fused (S)W-MSA core on [B, H, W, 3C] -> [B, H, W, C]; `probs` [windows, N, N, heads] is filled when given."""
     what = "window_attention"
     pixels, N, windows = _attn_geometry(what, d)
-    _row_tensor(what, "qkv", qkv, numel=pixels * 3 * d.C)
-    _row_tensor(what, "bias", bias, qkv, numel=d.heads * N * N)
-    _row_tensor(what, "probs", probs, qkv, numel=windows * N * N * d.heads, optional=True)
+    A.tensor(what, "qkv", qkv, numel=pixels * 3 * d.C)
+    A.tensor(what, "bias", bias, device=qkv.device, numel=d.heads * N * N)
+    A.tensor(what, "probs", probs, device=qkv.device, numel=windows * N * N * d.heads, optional=True)
     if not compute_out and probs is None:
         raise ValueError(f"{what}: compute_out=False without probs leaves nothing to compute")
     if compute_out:
-        _row_tensor(what, "out", out, qkv, numel=pixels * d.C, optional=True)
+        A.tensor(what, "out", out, device=qkv.device, numel=pixels * d.C, optional=True)
         if out is None:
             out = torch.empty((d.B, d.H, d.W, d.C), device=qkv.device, dtype=torch.float32)
     L.check(L.lib().rdo_window_attention_fwd(C.byref(d), _ptr(qkv), _ptr(bias), _ptr(out) if compute_out else None, _ptr(probs),
@@ -1244,9 +1161,9 @@ def window_attention(d, qkv, bias, out=None, probs=None, compute_out=True):
 def window_attention_pv(d, qkv, probs, out=None):
     what = "window_attention_pv"
     pixels, N, windows = _attn_geometry(what, d)
-    _row_tensor(what, "qkv", qkv, numel=pixels * 3 * d.C)
-    _row_tensor(what, "probs", probs, qkv, numel=windows * N * N * d.heads)
-    _row_tensor(what, "out", out, qkv, numel=pixels * d.C, optional=True)
+    A.tensor(what, "qkv", qkv, numel=pixels * 3 * d.C)
+    A.tensor(what, "probs", probs, device=qkv.device, numel=windows * N * N * d.heads)
+    A.tensor(what, "out", out, device=qkv.device, numel=pixels * d.C, optional=True)
     out = torch.empty((d.B, d.H, d.W, d.C), device=qkv.device, dtype=torch.float32) if out is None else out
     L.check(L.lib().rdo_window_attention_pv(C.byref(d), _ptr(qkv), _ptr(probs), _ptr(out), _stream()), "rdo_window_attention_pv")
     return out
@@ -1255,10 +1172,10 @@ def window_attention_pv(d, qkv, probs, out=None):
 def window_attention_bwd(d, qkv, bias, dout, dqkv=None):
     what = "window_attention_bwd"
     pixels, N, windows = _attn_geometry(what, d)
-    _row_tensor(what, "qkv", qkv, numel=pixels * 3 * d.C)
-    _row_tensor(what, "bias", bias, qkv, numel=d.heads * N * N)
-    _row_tensor(what, "dout", dout, qkv, numel=pixels * d.C)
-    _row_tensor(what, "dqkv", dqkv, qkv, numel=qkv.numel(), optional=True)
+    A.tensor(what, "qkv", qkv, numel=pixels * 3 * d.C)
+    A.tensor(what, "bias", bias, device=qkv.device, numel=d.heads * N * N)
+    A.tensor(what, "dout", dout, device=qkv.device, numel=pixels * d.C)
+    A.tensor(what, "dqkv", dqkv, device=qkv.device, numel=qkv.numel(), optional=True)
     dqkv = torch.empty_like(qkv) if dqkv is None else dqkv
     L.check(L.lib().rdo_window_attention_bwd(C.byref(d), _ptr(qkv), _ptr(bias), _ptr(dout), _ptr(dqkv), _stream()),
             "rdo_window_attention_bwd")
@@ -1266,25 +1183,25 @@ def window_attention_bwd(d, qkv, bias, dout, dqkv=None):
 
 
 def gelu(x, out=None):
-    _row_tensor("gelu", "x", x)
-    _row_tensor("gelu", "out", out, x, numel=x.numel(), optional=True)
+    A.tensor("gelu", "x", x)
+    A.tensor("gelu", "out", out, device=x.device, numel=x.numel(), optional=True)
     out = torch.empty_like(x) if out is None else out
     L.check(L.lib().rdo_gelu_fwd(_ptr(x), x.numel(), _ptr(out), _stream()), "rdo_gelu_fwd")
     return out
 
 
 def gelu_bwd(dy, x, dx=None):
-    _row_tensor("gelu_bwd", "x", x)
-    _row_tensor("gelu_bwd", "dy", dy, x, numel=x.numel())
-    _row_tensor("gelu_bwd", "dx", dx, x, numel=x.numel(), optional=True)
+    A.tensor("gelu_bwd", "x", x)
+    A.tensor("gelu_bwd", "dy", dy, device=x.device, numel=x.numel())
+    A.tensor("gelu_bwd", "dx", dx, device=x.device, numel=x.numel(), optional=True)
     dx = torch.empty_like(x) if dx is None else dx
     L.check(L.lib().rdo_gelu_bwd(_ptr(dy), _ptr(x), x.numel(), _ptr(dx), _stream()), "rdo_gelu_bwd")
     return dx
 
 
 def round_(x, out=None):
-    _row_tensor("round_", "x", x)
-    _row_tensor("round_", "out", out, x, numel=x.numel(), optional=True)
+    A.tensor("round_", "x", x)
+    A.tensor("round_", "out", out, device=x.device, numel=x.numel(), optional=True)
     out = torch.empty_like(x) if out is None else out
     L.check(L.lib().rdo_round(_ptr(x), x.numel(), _ptr(out), _stream()), "rdo_round")
     return out
@@ -1341,16 +1258,11 @@ def _fp32_operands(what, optional=(), **named):
     that is not a non-empty fp32 tensor of that count on the same device (the operands named in `optional` may be None).  -> the count"""
     first = None
     for name, t in named.items():
-        if t is None and name in optional:
-            continue
-        if not torch.is_tensor(t) or t.dtype != torch.float32:
-            raise ValueError(f"{what}: {name} must be an fp32 tensor, got {t.dtype if torch.is_tensor(t) else type(t).__name__}")
         if first is None:
-            first = (name, t)
-            if t.numel() == 0:
-                raise ValueError(f"{what}: {name} is empty")
-        elif t.numel() != first[1].numel() or t.device != first[1].device:
-            raise ValueError(f"{what}: {name} holds {t.numel()} elements on {t.device}, {first[0]} {first[1].numel()} on {first[1].device}")
+            A.tensor(what, name, t, optional=name in optional)
+            first = None if t is None else (name, t)
+        else:
+            A.tensor(what, name, t, device=first[1].device, other=first[0], numel=first[1].numel(), optional=name in optional)
     return first[1].numel()
 
 
@@ -1360,21 +1272,16 @@ def _eb_operands(what, z, params, medians=False):
     if z.dim() < 1:
         raise ValueError(f"{what}: z must be channels-last [..., C], got a scalar")
     Cc = z.shape[-1]
-    for name, t, shape in (("params", params, (Cc, 58)),) + ((("medians", medians, (Cc,)),) if medians is not False else ()):
-        if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != shape or t.device != z.device:
-            raise ValueError(f"{what}: {name} must be fp32 {list(shape)} on {z.device} for a tensor of {Cc} channels, got "
-                             f"{(t.dtype, tuple(t.shape), t.device) if torch.is_tensor(t) else type(t).__name__}")
+    A.tensor(what, "params", params, shape=(Cc, 58), device=z.device, oneshot=True)
+    if medians is not False:
+        A.tensor(what, "medians", medians, shape=(Cc,), device=z.device, oneshot=True)
     return Cc
 
 
 def _sum_out(what, ref, out):
     """the accumulator of a rate / distortion sum: one fp32 element on the operands' device (made zero when None)"""
-    if out is None:
-        return torch.zeros(1, device=ref.device, dtype=torch.float32)
-    if not torch.is_tensor(out) or out.dtype != torch.float32 or out.numel() != 1 or out.device != ref.device:
-        raise ValueError(f"{what}: out must be one fp32 element on {ref.device}, got "
-                         f"{(out.dtype, tuple(out.shape), out.device) if torch.is_tensor(out) else type(out).__name__}")
-    return out
+    A.tensor(what, "out", out, numel=1, device=ref.device, optional=True, oneshot=True)
+    return torch.zeros(1, device=ref.device, dtype=torch.float32) if out is None else out
 
 
 def factorized_likelihood(z_cl, params, medians):
@@ -1425,16 +1332,9 @@ def sq_diff_sum(a, b, scale=1.0, clamp01=False, out=None):
     return out
 
 
-_ORDERED_WS = {}    # device -> workspace of the ordered sums (launches are stream-ordered, so one buffer per device suffices)
-
-
 def _ordered_ws(device):
-    device = torch.device(device)
-    device = torch.device("cuda", torch.cuda.current_device()) if device.index is None else device
-    ws = _ORDERED_WS.get(device)
-    if ws is None:
-        ws = _ORDERED_WS[device] = torch.empty(int(L.lib().rdo_ordered_sum_workspace()), device=device, dtype=torch.float32)
-    return ws
+    """the workspace the two ordered sums share"""
+    return _workspace("ordered_sum", device, int(L.lib().rdo_ordered_sum_workspace()))
 
 
 def neg_log2_sum_ordered(lik, scale=1.0, out=None):
@@ -1455,26 +1355,15 @@ def sq_diff_sum_ordered(a, b, scale=1.0, clamp01=False, out=None):
     return out
 
 
-_CHANNEL_WS = {}    # (device, floats) -> workspace of neg_log2_channel_sums (launches are stream-ordered, so one buffer per key suffices)
-
-
 def neg_log2_channel_sums(lik, out=None):
     """Per-channel rate of a 4-D fp32 likelihood tensor [B, C, H, W] on the GPU: -> float32 [C], out[c] = sum over b, h, w of -log2 lik,
     in one read and a fixed summation order (the same input gives the same bits; a NaN stays in its channel).  NCHW-contiguous and
     channels-last-contiguous storage are read as they are (outer, inner = B, H W or B H W, 1); anything else is made contiguous first.
     `out`: a contiguous fp32 [C] on lik's device that is OVERWRITTEN.  Everything is checked on the host before a pointer is taken."""
     what = "neg_log2_channel_sums"
-    if not torch.is_tensor(lik) or lik.dtype != torch.float32:
-        raise ValueError(f"{what}: lik must be an fp32 tensor, got {lik.dtype if torch.is_tensor(lik) else type(lik).__name__}")
-    if lik.dim() != 4:
-        raise ValueError(f"{what}: lik must be 4-D [B, C, H, W], got {tuple(lik.shape)}")
-    if lik.numel() == 0:
-        raise ValueError(f"{what}: lik is empty: {tuple(lik.shape)}")
+    A.tensor(what, "lik", lik, rank=4, layout="4-D [B, C, H, W]")
     B, Cc, H, W = (int(v) for v in lik.shape)
-    if out is not None and (not torch.is_tensor(out) or tuple(out.shape) != (Cc,) or out.dtype != torch.float32 or out.device != lik.device
-                            or not out.is_contiguous()):
-        raise ValueError(f"{what}: out must be a contiguous fp32 [{Cc}] on {lik.device}, got "
-                         f"{(out.dtype, tuple(out.shape), out.device) if torch.is_tensor(out) else type(out).__name__}")
+    A.tensor(what, "out", out, shape=(Cc,), contiguous=True, device=lik.device, optional=True, oneshot=True)
     if not lik.is_cuda:
         raise ValueError(f"{what}: lik is on {lik.device}; there is no CPU path")
     if lik.is_contiguous():
@@ -1488,9 +1377,7 @@ def neg_log2_channel_sums(lik, out=None):
     n_ws = int(L.lib().rdo_neg_log2_channel_sums_workspace(outer, Cc, inner))
     if n_ws <= 0:
         raise ValueError(f"{what}: {tuple(lik.shape)} is beyond the kernel's index arithmetic (C <= 65535, B H W < 2^31)")
-    ws = _CHANNEL_WS.get((lik.device, n_ws))
-    if ws is None:
-        ws = _CHANNEL_WS[(lik.device, n_ws)] = torch.empty(n_ws, device=lik.device, dtype=torch.float32)
+    ws = _workspace(what, lik.device, n_ws, torch.float32, n_ws)
     L.check(L.lib().rdo_neg_log2_channel_sums(_ptr(lik), outer, Cc, inner, _ptr(out), _ptr(ws), _stream()), "rdo_neg_log2_channel_sums")
     return out
 

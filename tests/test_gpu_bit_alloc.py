@@ -101,8 +101,8 @@ def test_scan_matches_the_kernels_it_stands_in_for(rows, inner, widths):
         live = en_c > 0
         assert bool((err_c[order[0]][live] > err_c[order[-1]][live]).all())
     # the same bits again, also behind a poisoned workspace
-    assert ops._SCAN_WS
-    for ws in ops._SCAN_WS.values():
+    assert ops._workspaces("uaq_width_scan")
+    for ws in ops._workspaces("uaq_width_scan"):
         ws.fill_(float("nan"))
     again = ops.uaq_width_scan(wg, widths)
     torch.cuda.synchronize()

@@ -226,7 +226,8 @@ def test_sums_random_cases_within_the_derived_bounds(n):
         # the ordered form: the same bits on every launch, whatever the workspace held
         bits = []
         for _ in range(3):
-            ops._ordered_ws(torch.device("cuda")).fill_(float("nan"))
+            for ws in ops._workspaces("ordered_sum"):
+                ws.fill_(float("nan"))
             bits.append(float(run(_forms()["ordered"], _out(1.5))))
         assert bits[0] == bits[1] == bits[2] and math.isfinite(bits[0]), (what, n, bits)
 

@@ -37,7 +37,7 @@ def _both(lik):
 
 
 def _poison_workspaces(ops):
-    for ws in ops._CHANNEL_WS.values():
+    for ws in ops._workspaces("neg_log2_channel_sums"):
         ws.fill_(float("nan"))
 
 
@@ -56,7 +56,7 @@ def test_kernel_stays_within_the_derived_bound(outer, C, inner):
             _poison_workspaces(ops)
             runs.append(ops.neg_log2_channel_sums(x).clone())
         torch.cuda.synchronize()
-        assert ops._CHANNEL_WS
+        assert ops._workspaces("neg_log2_channel_sums")
         r = runs[0]
         assert r.shape == (C,) and r.dtype == torch.float32 and r.is_cuda
         assert torch.equal(runs[1], r) and torch.equal(runs[2], r) and bool(torch.isfinite(r).all())
