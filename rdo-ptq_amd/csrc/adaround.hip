@@ -11,6 +11,7 @@
 // This file is built with -ffp-contract=off so products and sums round separately, as the reference's op chain does.
 #include "rdo_common.h"
 #include "gather_body.h"
+#include "../../include/rdo_ptq_subpel.h"
 #include "uaq_device.h"
 
 namespace {
@@ -62,6 +63,8 @@ struct AdaArgs {
     unsigned short* lin_fwd;     // optional: planes of wq * lin_pscale in rdo_linear_h2's fragment order ([plane][inner/32][rows/16][lane][8])
     unsigned short* lin_bwd;     // optional: the same of the transpose (rows and inner swapped)
     float lin_pscale;
+    int row_groups;              // 4: rows in 4 groups (rdo_adaround_step_batch_gather_px; tile form only) -- the slabs are read and the forward
+                                 // planes written at row (r & 3) rows / 4 + (r >> 2) of logical row r; 0: everything in logical order
 };
 #ifdef RDO_DIAG
 // ablation mask of a diagnostic build (tools/ada_step_ablate.py; set by rdo_diag_ada_ablate, read by the kernels at run time so that
@@ -355,6 +358,8 @@ __device__ __forceinline__ void ada_step_tile_body(const AdaArgs& a, int bid) {
     float rl_local = 0.f;
     vec_t o4 = {0.f, 0.f, 0.f, 0.f};
     const long e0 = ((long)row * taps + tap) * Cin + ci;
+    const int rowg = a.row_groups ? rdo::group_row(row, nrows) : row;      // where the slabs and the forward planes keep this row
+    const long eg = ((long)rowg * taps + tap) * Cin + ci;
     if (live) {
         const vec_t wv4 = *reinterpret_cast<const vec_t*>(a.w + e0);
         vec_t al4 = *reinterpret_cast<const vec_t*>(a.alpha + e0);
@@ -362,7 +367,7 @@ __device__ __forceinline__ void ada_step_tile_body(const AdaArgs& a, int bid) {
         if (a.mode == 2) {
             g4 = *reinterpret_cast<const vec_t*>(a.dalpha_in + e0);
         } else if (!ADA_ABL(1)) {
-            const float* sp = a.slabs + e0;                     // same summation order as the flat form
+            const float* sp = a.slabs + eg;                     // same summation order as the flat form
             int s = 0;
             for (; s + 16 <= a.nsplit; s += 16) {
                 vec_t t[16];
@@ -455,7 +460,7 @@ __device__ __forceinline__ void ada_step_tile_body(const AdaArgs& a, int bid) {
                 *reinterpret_cast<u32x2*>(a.lin_fwd + (long)nrows * Cin + f) = pl;
             }
             if (a.wq_planes) {
-                const long f0 = (Cin & 15) ? e0 : (((((long)(ci >> 4) * taps + tap) * nrows + row) << 4) + (ci & 15));   // rdo::frag_index
+                const long f0 = (Cin & 15) ? eg : (((((long)(ci >> 4) * taps + tap) * nrows + rowg) << 4) + (ci & 15));   // rdo::frag_index
                 if (a.wq_pscale > 0.f) {
                     unsigned hh, ll;
                     u32x2 ph, pl;
@@ -821,7 +826,7 @@ int rdo_adaround_step(const rdo_ada_desc* d, const float* w, const float* delta,
 
 static int step_batch_impl(const rdo_ada_step_item* items, int32_t n, int32_t mode, float grad_scale, float round_weight,
                            const rdo_sched_row* sched, const int32_t* iter_ptr, float* round_loss_out, int32_t* advance_iter,
-                           int32_t* iter_shadow, const rdo_gather_desc* next, void* stream) {
+                           int32_t* iter_shadow, const rdo_gather_desc* next, void* stream, const int32_t* row_groups = nullptr) {
     RDO_REQUIRE(items && n >= 1 && n <= kMaxBatch, "rdo_adaround_step_batch: bad argument (1 <= n <= %d)", kMaxBatch);
     RDO_REQUIRE(mode >= 0 && mode <= 2, "rdo_adaround_step_batch: mode %d (0 fused step, 1 gradient only, 2 apply)", mode);
     RDO_REQUIRE(mode == 1 || (sched && iter_ptr), "rdo_adaround_step_batch: schedule / iteration counter missing");
@@ -855,6 +860,12 @@ static int step_batch_impl(const rdo_ada_step_item* items, int32_t n, int32_t mo
             a.lin_fwd = static_cast<unsigned short*>(it.lin_fwd_planes);
             a.lin_bwd = static_cast<unsigned short*>(it.lin_bwd_planes);
             a.lin_pscale = it.lin_plane_scale;
+        }
+        if (row_groups && row_groups[i]) {
+            RDO_REQUIRE(row_groups[i] == 4 && tile_ok(it.d, mode) && (a.wq_pscale > 0.f || !a.wq_planes),
+                        "rdo_adaround_step_batch_gather_px: item %d: rows in 4 groups need a conv layout with rows %% 4 == 0 and Cin %% 4 == 0, mode 0 "
+                        "or 2, and fp16 forward planes (row_groups %d)", i, row_groups[i]);
+            a.row_groups = 4;
         }
         a.ovf = rdo::h2_overflow_flag();          // behind the item's last argument check: the look-up may allocate the word
         b.tile[i] = tile_ok(it.d, mode) ? 1 : 0;
@@ -914,6 +925,12 @@ int rdo_adaround_step_batch_gather(const rdo_ada_step_item* items, int32_t n, in
                                    const rdo_gather_desc* next, void* stream) {
     RDO_REQUIRE(next != nullptr, "rdo_adaround_step_batch_gather: null gather descriptor");
     return step_batch_impl(items, n, mode, grad_scale, round_weight, sched, iter_ptr, round_loss_out, nullptr, iter_shadow, next, stream);
+}
+
+int rdo_adaround_step_batch_gather_px(const rdo_ada_step_item* items, int32_t n, int32_t mode, float grad_scale, float round_weight,
+                                      const rdo_sched_row* sched, const int32_t* iter_ptr, float* round_loss_out, int32_t* iter_shadow,
+                                      const rdo_gather_desc* next, const int32_t* row_groups, void* stream) {
+    return step_batch_impl(items, n, mode, grad_scale, round_weight, sched, iter_ptr, round_loss_out, nullptr, iter_shadow, next, stream, row_groups);
 }
 
 int rdo_adaround_grad(const rdo_ada_desc* d, const float* w, const float* alpha, const float* delta, const float* zp,

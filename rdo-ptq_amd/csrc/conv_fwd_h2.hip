@@ -17,6 +17,7 @@
 // finishes the 16 channels of one slice of one pixel (consecutive lanes on consecutive pixels = the H2 record order): bias / aux /
 // residual, fp32 out / pre, and the two fp16 planes of the result (scaled by the output tensor's own s), two 16-byte stores per plane.
 #include "conv_h2_common.h"
+#include "../../include/rdo_ptq_subpel.h"
 
 namespace {
 
@@ -581,6 +582,8 @@ __global__ __launch_bounds__(512, 2) void conv_fwd_h2h_kernel(H2Args a) {
 }
 
 // split-K second pass: sum the partial accumulators, then the same per-slice finish (planes included); lanes along pixels
+// RM: with the store remap of rdo_conv2d_fwd_h2_px (an instantiation of its own: the plain one keeps its code)
+template <bool RM>
 __global__ __launch_bounds__(256) void h2_splitk_epilogue_kernel(H2Args a) {
     const int spr = a.Cout / 16;                             // slices per row
     const long total = (long)a.M * spr;
@@ -600,7 +603,7 @@ __global__ __launch_bounds__(256) void h2_splitk_epilogue_kernel(H2Args a) {
                 for (int k = 0; k < 4; ++k) v[4 * c + k] += t4[k];
             }
         }
-        finish16(a, m, n, v, bad);
+        finish16<RM>(a, m, n, v, bad);
     }
     rdo::h2_report(bad, a.ovf);
 }
@@ -635,6 +638,15 @@ __global__ __launch_bounds__(256) void split_h2_conv_kernel(const float* w, long
     int bad = 0;
     for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < numel; e += (long)gridDim.x * blockDim.x)
         rdo::h2_split_store(w[e], scale, planes, numel, rdo::frag_index(e, Cout, KH, KW, Cin), bad);
+    rdo::h2_report(bad, ovf);
+}
+// ... with the rows in 4 groups (rdo_split_h2_conv_px): the planes of logical row r go where row (r & 3) Cout / 4 + (r >> 2) goes
+__global__ __launch_bounds__(256) void split_h2_conv_groups_kernel(const float* w, long numel, int Cout, int KH, int KW, int Cin, float scale,
+                                                                   u16* planes, int* ovf) {
+    int bad = 0;
+    const long inner = (long)KH * KW * Cin;
+    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < numel; e += (long)gridDim.x * blockDim.x)
+        rdo::h2_split_store(w[e], scale, planes, numel, rdo::frag_index(rdo::group_row_elem(e, Cout, inner), Cout, KH, KW, Cin), bad);
     rdo::h2_report(bad, ovf);
 }
 
@@ -708,19 +720,34 @@ extern "C" int rdo_split_h2(const float* x, int64_t npix, int32_t C, float scale
         stream, "split_h2", 0.0, 8.0 * n);
 }
 
-extern "C" int rdo_split_h2_conv(const float* w, int32_t Cout, int32_t KH, int32_t KW, int32_t Cin, float scale, void* planes, void* stream) {
+static int split_h2_conv_impl(const float* w, int32_t Cout, int32_t KH, int32_t KW, int32_t Cin, float scale, void* planes, int32_t row_groups,
+                              void* stream) {
     RDO_REQUIRE(w && planes && Cout > 0 && KH > 0 && KW > 0 && Cin > 0, "rdo_split_h2_conv: bad argument");
     RDO_REQUIRE(pow2_scale(scale), "rdo_split_h2_conv: scale %g is not a power of two", (double)scale);
+    RDO_REQUIRE(row_groups == 0 || (row_groups == 4 && Cout % 4 == 0), "rdo_split_h2_conv_px: row_groups %d (0, or 4 with Cout %% 4 == 0)", row_groups);
     const long numel = (long)Cout * KH * KW * Cin;
     u16* p = reinterpret_cast<u16*>(planes);
     int* ovf = rdo::h2_overflow_flag();
     return rdo::dispatch(
         [=](hipStream_t s) {
             long g = rdo::ceil_div(numel, 256);
-            hipLaunchKernelGGL(split_h2_conv_kernel, dim3((unsigned)(g > 2048 ? 2048 : g)), dim3(256), 0, s, w, numel, Cout, KH, KW, Cin, scale, p, ovf);
+            if (row_groups)
+                hipLaunchKernelGGL(split_h2_conv_groups_kernel, dim3((unsigned)(g > 2048 ? 2048 : g)), dim3(256), 0, s, w, numel, Cout, KH, KW, Cin, scale,
+                                   p, ovf);
+            else
+                hipLaunchKernelGGL(split_h2_conv_kernel, dim3((unsigned)(g > 2048 ? 2048 : g)), dim3(256), 0, s, w, numel, Cout, KH, KW, Cin, scale, p, ovf);
             return rdo::check_launch("split_h2_conv");
         },
         stream, "split_h2_conv", 0.0, 8.0 * (double)numel);
+}
+
+extern "C" int rdo_split_h2_conv(const float* w, int32_t Cout, int32_t KH, int32_t KW, int32_t Cin, float scale, void* planes, void* stream) {
+    return split_h2_conv_impl(w, Cout, KH, KW, Cin, scale, planes, 0, stream);
+}
+
+extern "C" int rdo_split_h2_conv_px(const float* w, int32_t Cout, int32_t KH, int32_t KW, int32_t Cin, float scale, void* planes, int32_t row_groups,
+                                    void* stream) {
+    return split_h2_conv_impl(w, Cout, KH, KW, Cin, scale, planes, row_groups, stream);
 }
 
 extern "C" int rdo_conv2d_fwd_h2_supported(const rdo_conv_desc* d) {
@@ -755,8 +782,10 @@ static int h2_halo_shape(const rdo_conv_desc* d) {
 
 static int conv2d_fwd_h2_impl(const rdo_conv_desc* d, const void* x_planes, float x_scale, const void* wplanes, float w_scale, const float* bias,
                               const float* aux, const void* aux_planes, const float* residual, float* out, float* pre, void* out_planes,
-                              float out_scale, float* workspace, int64_t workspace_floats, void* stream, const H2Args* tail) {
+                              float out_scale, float* workspace, int64_t workspace_floats, void* stream, const H2Args* tail, int store_mode = 0) {
     RDO_REQUIRE(d && x_planes && wplanes && (out || out_planes || pre), "rdo_conv2d_fwd_h2: null argument");
+    RDO_REQUIRE(store_mode == 0 || (rdo_conv2d_fwd_h2_px_supported(d, store_mode) && !pre && !tail),
+                "rdo_conv2d_fwd_h2_px: store mode %d is not supported for this shape, or comes with `pre` (rdo_conv2d_fwd_h2_px_supported)", store_mode);
     RDO_REQUIRE(rdo_conv2d_fwd_h2_supported(d), "rdo_conv2d_fwd_h2: shape not on the split-precision plane path (rdo_conv2d_fwd_h2_supported)");
     RDO_REQUIRE(pow2_scale(x_scale) && pow2_scale(w_scale) && (!out_planes || pow2_scale(out_scale)),
                 "rdo_conv2d_fwd_h2: the scales (%g, %g, %g) must be powers of two", (double)x_scale, (double)w_scale, (double)out_scale);
@@ -783,6 +812,7 @@ static int conv2d_fwd_h2_impl(const rdo_conv_desc* d, const void* x_planes, floa
     a.M = d->B * d->Ho * d->Wo;
     a.oplane = (long)a.M * a.Cout;
     a.epilogue = d->epilogue; a.add_residual = d->add_residual;
+    rdo::h2_set_store_mode(a, store_mode);
     a.xcd_mode = rdo::tuning(rdo::T_XCD);
     a.stagger = rdo::tuning(rdo::T_H2_STAGGER);
 #ifdef RDO_DIAG
@@ -820,7 +850,8 @@ static int conv2d_fwd_h2_impl(const rdo_conv_desc* d, const void* x_planes, floa
                     [k, kshape](hipStream_t s) {
                         if (int rc = rdo::h2k_launch(k, kshape, s)) return rc;
                         long g = rdo::ceil_div((long)k.M * k.Cout / 16, 256);
-                        hipLaunchKernelGGL(h2_splitk_epilogue_kernel, dim3((unsigned)(g > 2048 ? 2048 : g)), dim3(256), 0, s, k);
+                        if (k.st_mode) hipLaunchKernelGGL(h2_splitk_epilogue_kernel<true>, dim3((unsigned)(g > 2048 ? 2048 : g)), dim3(256), 0, s, k);
+                        else hipLaunchKernelGGL(h2_splitk_epilogue_kernel<false>, dim3((unsigned)(g > 2048 ? 2048 : g)), dim3(256), 0, s, k);
                         return rdo::check_launch("h2_splitk_epilogue");
                     },
                     stream, "conv_fwd_h2_halo64k", flops, bytes);
@@ -844,6 +875,8 @@ static int conv2d_fwd_h2_impl(const rdo_conv_desc* d, const void* x_planes, floa
             return rdo::dispatch([k, shape](hipStream_t s) { return rdo::h2k_launch(k, shape, s); }, stream,
                                  shape == 1 ? "conv_fwd_h2_halo" : "conv_fwd_h2_halo64", flops, bytes);
     }
+    // (only the two K32 launches above know the store remap)
+    RDO_REQUIRE(!a.st_mode, "rdo_conv2d_fwd_h2_px: the launch this shape takes has no store remap (workspace too small for its K split?)");
     if (halo == 1 && ks == 1)
         return rdo::dispatch(
             [a](hipStream_t s) {
@@ -896,7 +929,7 @@ static int conv2d_fwd_h2_impl(const rdo_conv_desc* d, const void* x_planes, floa
             if (int rc = rdo::check_launch("conv_fwd_h2")) return rc;
             if (a.ksplit > 1) {
                 long g = rdo::ceil_div((long)a.M * a.Cout / 16, 256);
-                hipLaunchKernelGGL(h2_splitk_epilogue_kernel, dim3((unsigned)(g > 2048 ? 2048 : g)), dim3(256), 0, s, a);
+                hipLaunchKernelGGL(h2_splitk_epilogue_kernel<false>, dim3((unsigned)(g > 2048 ? 2048 : g)), dim3(256), 0, s, a);
                 return rdo::check_launch("h2_splitk_epilogue");
             }
             return RDO_OK;
@@ -909,6 +942,54 @@ extern "C" int rdo_conv2d_fwd_h2(const rdo_conv_desc* d, const void* x_planes, f
                                  void* out_planes, float out_scale, float* workspace, int64_t workspace_floats, void* stream) {
     return conv2d_fwd_h2_impl(d, x_planes, x_scale, wplanes, w_scale, bias, aux, aux_planes, residual, out, pre, out_planes, out_scale, workspace,
                               workspace_floats, stream, nullptr);
+}
+
+// Which of the two K32 launches that know the store remap rdo_conv2d_fwd_h2 gives this shape (the conditions of conv2d_fwd_h2_impl, in its
+// order): 1 the halo kernel's direct epilogue, 2 its K-split form + second pass, 0 neither.  *ntile: output channels per workgroup.
+static int h2_px_path(const rdo_conv_desc* d, int* ntile) {
+    H2Args k{};
+    k.B = d->B; k.H = d->H; k.W = d->W; k.Cin = d->Cin; k.Ho = d->Ho; k.Wo = d->Wo; k.Cout = d->Cout;
+    k.KH = d->KH; k.KW = d->KW; k.stride = d->stride; k.pad = d->pad;
+    k.xplane = (long)d->B * d->H * d->W * d->Cin;
+    const int halo = h2_halo_shape(d);
+    int shape = 2;
+    if (!halo) {
+        const int ks2 = h2k_ksplit(d, &shape);
+        k.ksplit = ks2;
+        k.partial = reinterpret_cast<float*>(&k);            // (non-null: h2k_supported pairs it with the split count)
+        if (ks2 < 2 || !rdo::h2k_supported(k, shape)) return 0;
+        *ntile = 16;                                         // the second pass finishes one 16-channel record at a time
+        return 2;
+    }
+    if (!rdo::tuning(rdo::T_H2_K32)) return 0;
+    k.ksplit = 1;
+    shape = halo;
+    const long patches = (long)d->B * d->H * d->W / 256;
+    if (halo == 2 && rdo::tuning(rdo::T_H2_N48) && d->Cout % 48 == 0 && patches * (d->Cout / 64) < 256 && patches * (d->Cout / 48) <= 256 &&
+        rdo::h2k_supported(k, 3))
+        shape = 3;
+    if (!rdo::h2k_supported(k, shape)) return 0;
+    *ntile = shape == 1 ? 192 : (shape == 3 ? 48 : 64);
+    return 1;
+}
+
+extern "C" int rdo_conv2d_fwd_h2_px_supported(const rdo_conv_desc* d, int32_t store_mode) {
+    if (!d || !rdo_conv2d_fwd_h2_supported(d)) return 0;
+    if (store_mode == 0) return 1;
+    if (store_mode != 1 && store_mode != 2) return 0;
+    if ((double)d->B * d->Ho * d->Wo * d->Cout * 2.0 >= 2147483648.0) return 0;
+    int ntile = 0;
+    if (!h2_px_path(d, &ntile)) return 0;
+    if (store_mode == 1) return d->Cout % 4 == 0 && (d->Cout / 4) % 16 == 0 && (d->Cout / 4) % ntile == 0;
+    return d->Ho % 2 == 0 && d->Wo % 2 == 0;
+}
+
+extern "C" int rdo_conv2d_fwd_h2_px(const rdo_conv_desc* d, const void* x_planes, float x_scale, const void* wplanes, float w_scale,
+                                    const float* bias, const float* aux, const void* aux_planes, const float* residual, float* out, float* pre,
+                                    void* out_planes, float out_scale, float* workspace, int64_t workspace_floats, int32_t store_mode,
+                                    void* stream) {
+    return conv2d_fwd_h2_impl(d, x_planes, x_scale, wplanes, w_scale, bias, aux, aux_planes, residual, out, pre, out_planes, out_scale, workspace,
+                              workspace_floats, stream, nullptr, store_mode);
 }
 
 extern "C" int rdo_conv2d_fwd_h2_tail_supported(const rdo_conv_desc* d) {

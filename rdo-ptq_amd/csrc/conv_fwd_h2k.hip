@@ -62,7 +62,10 @@ __device__ __forceinline__ float tail4_math(const H2Args& a, f32x4& v, const f32
 // WM x WN waves (8), wave tile TP pixel tiles x TC channel tiles of 16 x 16: WM * TP = 16 (256 patch pixels), BN = WN * TC * 16
 // ABL (diagnostic builds only, `make DIAG=1`; the shipped library instantiates ABL = 0): compile-time ablation mask -- 1 no halo DMA,
 // 2 no weight DMA, 4 no MFMA, 8 no fragment reads, 16 no epilogue.  Results are wrong when non-zero.
-template <int WM, int WN, int TP, int TC, int ABL = 0, int ORD = 0>
+// SM: the direct epilogue forms its STORE offsets through the store remap of H2Args (rdo_conv2d_fwd_h2_px: the r = 2 pixel shuffle /
+// unshuffle of the result as an address change of whole quads and quarter records); an instantiation of its own, so that the plain
+// kernels keep the code they had.  BN divides st_C, so a workgroup's channels lie inside one group.
+template <int WM, int WN, int TP, int TC, int ABL = 0, int ORD = 0, bool SM = false>
 __global__ __launch_bounds__(512, 2) void conv_fwd_h2k_kernel(H2Args a) {
     static_assert(WM * WN == 8 && WM * TP == 16, "eight waves, 256 patch pixels");
     constexpr int BN = WN * TC * 16;
@@ -365,6 +368,7 @@ __global__ __launch_bounds__(512, 2) void conv_fwd_h2k_kernel(H2Args a) {
     float tail_loss = 0.f;
     int bad = 0;
     typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+    const int sgrp = SM ? n0 / a.st_C : 0;                   // the workgroup's channel group (wave-uniform)
 #pragma unroll
     for (int i = 0; i < TC; ++i) {
         const int n = n0 + wn0 + 16 * i + 4 * kg;
@@ -408,10 +412,12 @@ __global__ __launch_bounds__(512, 2) void conv_fwd_h2k_kernel(H2Args a) {
                 for (int e = 0; e < 4; ++e) v[e] = q0[j][e] * (a.epilogue == RDO_EPI_IGDN ? __fsqrt_rn(v[e]) : __frsqrt_rn(v[e]));
             }
             if (a.add_residual) v += q1[j];
-            if (a.out) *reinterpret_cast<f32x4*>(a.out + o) = v;
+            StoreAt st{m, n};
+            if constexpr (SM) st = store_at(a, pb, h0 + wrow * TP + j, w0 + l16, n, sgrp);
+            if (a.out) *reinterpret_cast<f32x4*>(a.out + (SM ? (long)st.m * a.st_Co + st.n : o)) = v;
             if (need_planes) {
                 if (f_y) tail_loss += tail4_math(a, v, q1[j], rp0[j], rp1[j]);
-                u16* dst = a.outp + ((long)(n >> 4) * a.M + m) * 16 + (n & 15);
+                u16* dst = a.outp + ((long)(st.n >> 4) * (SM ? a.st_Mo : a.M) + st.m) * 16 + (st.n & 15);
                 u32x2 hi, lo;
                 unsigned h, l;
                 rdo::h2_split_pk(v[0], v[1], a.out_scale, h, l, bad); hi[0] = h; lo[0] = l;
@@ -434,20 +440,20 @@ __global__ __launch_bounds__(512, 2) void conv_fwd_h2k_kernel(H2Args a) {
     rdo::h2_report(bad, a.ovf);
 }
 
-template <int WM, int WN, int TP, int TC, int ABL = 0, int ORD = 0>
+template <int WM, int WN, int TP, int TC, int ABL = 0, int ORD = 0, bool SM = false>
 int launch(const H2Args& a, const char* what, hipStream_t s) {
     constexpr int BN = WN * TC * 16;
     constexpr size_t lds = (size_t)2 * 42 * 1024 + 1024 + (size_t)3 * 2 * BN * 64;
     static_assert(lds <= 160 * 1024, "LDS of the K32 halo kernel");
     static rdo::PerDevice attr;
     if (!attr.done()) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fwd_h2k_kernel<WM, WN, TP, TC, ABL, ORD>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fwd_h2k_kernel<WM, WN, TP, TC, ABL, ORD, SM>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)lds) != hipSuccess)
             return rdo::set_error(RDO_EHIP, "hipFuncSetAttribute(%s) failed", what);
         attr.mark();
     }
     dim3 grid((unsigned)(a.M / 256), (unsigned)(a.Cout / BN), (unsigned)a.ksplit);
-    hipLaunchKernelGGL((conv_fwd_h2k_kernel<WM, WN, TP, TC, ABL, ORD>), grid, dim3(512), lds, s, a);
+    hipLaunchKernelGGL((conv_fwd_h2k_kernel<WM, WN, TP, TC, ABL, ORD, SM>), grid, dim3(512), lds, s, a);
     return rdo::check_launch(what);
 }
 
@@ -462,6 +468,11 @@ bool h2k_supported(const H2Args& a, int shape) {
 }
 
 int h2k_launch(const H2Args& a, int shape, hipStream_t s) {
+    if (a.st_mode && !a.partial) {                           // remapped stores (the K-split form writes plain partial sums: its second pass remaps)
+        if (shape == 1) return launch<4, 2, 4, 6, 0, 0, true>(a, "conv_fwd_h2k 256x192 px", s);
+        if (shape == 3) return launch<8, 1, 2, 3, 0, 0, true>(a, "conv_fwd_h2k 256x48 px", s);
+        return launch<8, 1, 2, 4, 0, 0, true>(a, "conv_fwd_h2k 256x64 px", s);
+    }
     if (shape == 1) {
 #ifdef RDO_DIAG
         switch (a.ablate) {                                  // tuning key "x6p_ablate" (diagnostic builds)

@@ -49,7 +49,23 @@ struct H2Args {
     // with the tests folded away at compile time the scheduler's own order was 13-20 % slower on the 4 x 128^2 conv (137-145 us
     // against 121 us, same box).
     int ablate;
+    // store remap of rdo_conv2d_fwd_h2_px (st_mode 1: pixel shuffle r = 2 of a conv whose weight rows are in group order, 2: its inverse;
+    // 0: none, and nothing below is read).  Output element (image b, row y, column x, channel n) is STORED at pixel
+    //   b st_sb + (y >> st_sh) st_sy + (x >> st_sh) st_sx + (g >> 1) st_gy + (g & 1)                       g = n / st_C
+    // and channel n - g st_C + (2 (y & st_msk) + (x & st_msk)) Cout of a tensor [st_Mo][st_Co] (`store_at`): integer arithmetic on the
+    // store addresses only -- every load of the epilogue keeps the plain index.  (Appended: the fields above keep their kernarg offsets.)
+    int st_mode, st_sb, st_sh, st_sy, st_sx, st_gy, st_msk, st_C, st_Mo, st_Co;
 };
+// the remap's strides for the conv output grid [B][Ho][Wo][Cout] (host side)
+inline void h2_set_store_mode(H2Args& a, int mode) {
+    a.st_mode = mode;
+    a.st_sb = a.Ho * a.Wo; a.st_sh = 0; a.st_sy = a.Wo; a.st_sx = 1; a.st_gy = 0; a.st_msk = 0; a.st_C = 0x7fffffff; a.st_Mo = a.M; a.st_Co = a.Cout;
+    if (mode == 1) {
+        a.st_sb = 4 * a.Ho * a.Wo; a.st_sy = 4 * a.Wo; a.st_sx = 2; a.st_gy = 2 * a.Wo; a.st_C = a.Cout / 4; a.st_Mo = 4 * a.M; a.st_Co = a.Cout / 4;
+    } else if (mode == 2) {
+        a.st_sb = a.Ho * a.Wo / 4; a.st_sh = 1; a.st_sy = a.Wo / 2; a.st_msk = 1; a.st_Mo = a.M / 4; a.st_Co = 4 * a.Cout;
+    }
+}
 }  // namespace rdo
 
 namespace {
@@ -119,9 +135,22 @@ __device__ __forceinline__ f32x4 aux_quad(const H2Args& a, int m, int n, long o)
     return f32x4{0.f, 0.f, 0.f, 0.f};
 }
 
-// the two H2 records of (slice n / 16, pixel m) from 16 finished channel values: 32 bytes per plane
-__device__ __forceinline__ void store_slice(const H2Args& a, int m, int n, const float (&v)[16], int& bad) {
-    u16* dst = a.outp + ((long)(n >> 4) * a.M + m) * 16;
+// where the store remap (H2Args::st_mode) puts channel n (of group g = n / st_C) of output pixel (b, y, x): pixel and channel of [st_Mo][st_Co]
+struct StoreAt { int m, n; };
+__device__ __forceinline__ StoreAt store_at(const H2Args& a, int b, int y, int x, int n, int g) {
+    StoreAt s;
+    s.m = b * a.st_sb + (y >> a.st_sh) * a.st_sy + (x >> a.st_sh) * a.st_sx + (g >> 1) * a.st_gy + (g & 1);
+    s.n = n - g * a.st_C + (((y & a.st_msk) << 1) + (x & a.st_msk)) * a.Cout;
+    return s;
+}
+__device__ __forceinline__ StoreAt store_at(const H2Args& a, int m, int n) {      // from the pixel's plain index
+    const int x = m % a.Wo, r = m / a.Wo, y = r % a.Ho;
+    return store_at(a, r / a.Ho, y, x, n, n / a.st_C);
+}
+
+// the two H2 records of (slice n / 16, pixel m) from 16 finished channel values: 32 bytes per plane (M: pixels of the tensor written)
+__device__ __forceinline__ void store_slice(const H2Args& a, int m, int n, const float (&v)[16], int& bad, int M) {
+    u16* dst = a.outp + ((long)(n >> 4) * M + m) * 16;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         u32x4 p0, p1;
@@ -130,8 +159,11 @@ __device__ __forceinline__ void store_slice(const H2Args& a, int m, int n, const
         *reinterpret_cast<u32x4*>(dst + a.oplane + 8 * h) = p1;
     }
 }
+__device__ __forceinline__ void store_slice(const H2Args& a, int m, int n, const float (&v)[16], int& bad) { store_slice(a, m, n, v, bad, a.M); }
 
-// finish the 16 channels [n, n+16) (one slice, n % 16 == 0) of output pixel m from their raw sums `v` (bias not yet added)
+// finish the 16 channels [n, n+16) (one slice, n % 16 == 0) of output pixel m from their raw sums `v` (bias not yet added).
+// RM: the results go where the store remap says (the loads keep the plain index; the host refuses `pre` together with a remap)
+template <bool RM = false>
 __device__ __forceinline__ void finish16(const H2Args& a, int m, int n, float (&v)[16], int& bad) {
     const long o = (long)m * a.Cout + n;
     if (a.bias) {
@@ -162,11 +194,14 @@ __device__ __forceinline__ void finish16(const H2Args& a, int m, int n, float (&
             for (int k = 0; k < 4; ++k) v[4 * c + k] += r4[k];
         }
     }
+    StoreAt st{m, n};
+    if constexpr (RM) st = store_at(a, m, n);
+    const long so = RM ? (long)st.m * a.st_Co + st.n : o;
     if (a.out) {
 #pragma unroll
-        for (int c = 0; c < 4; ++c) *reinterpret_cast<f32x4*>(a.out + o + 4 * c) = f32x4{v[4 * c], v[4 * c + 1], v[4 * c + 2], v[4 * c + 3]};
+        for (int c = 0; c < 4; ++c) *reinterpret_cast<f32x4*>(a.out + so + 4 * c) = f32x4{v[4 * c], v[4 * c + 1], v[4 * c + 2], v[4 * c + 3]};
     }
-    if (a.outp) store_slice(a, m, n, v, bad);
+    if (a.outp) store_slice(a, st.m, st.n, v, bad, RM ? a.st_Mo : a.M);
 }
 
 // Unit tail on the 16 finished channels [n, n+16) of pixel m (v = conv + bias, the pre-activation): v becomes dL/dpre, the return value

@@ -25,6 +25,7 @@
 #include "gather_body.h"
 #include "gdn_device.h"
 #include "../../include/rdo_ptq_gdn.h"
+#include "../../include/rdo_ptq_subpel.h"
 
 namespace {
 
@@ -61,13 +62,15 @@ struct GdnArgs {
     float* dx;                     // nullable
     H2Out dxp;                     // p nullable
     float* loss_out;
+    H2Out gp;                      // rdo_gdn_fwd_bwd_px: dL/dout as planes of [B][H/2][W/2][4 * 192] in unshuffle order (p nullable)
+    int W, HW, Mq;                 // ... of tokens that are the pixels of [B][H][W]; Mq = M / 4 pixels of the half-size grid
 };
 
 __device__ __forceinline__ const f32x4& ldq(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ void stq(float* p, const f32x4& v) { *reinterpret_cast<f32x4*>(p) = v; }
 
-// INV: IGDN; RES: a residual is added to the output
-template <bool INV, bool RES>
+// INV: IGDN; RES: a residual is added to the output; PX: dL/dout leaves as planes in unshuffle order (gp) -- an instantiation of its own
+template <bool INV, bool RES, bool PX = false>
 __global__ __launch_bounds__(512, 2) void gdn_fwd_bwd_kernel(GdnArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* scl = reinterpret_cast<float*>(smem + 2 * PLANE);          // [BM]: 1 / scale of the token's c^2
@@ -195,6 +198,17 @@ __global__ __launch_bounds__(512, 2) void gdn_fwd_bwd_kernel(GdnArgs a) {
                 yv[i] = ldq(yrow + 16 * i);
                 if (RES) rv[i] = ldq(a.res + g0 + lane_e + 16 * i);
             }
+            // PX: token (b, y, x) -> pixel (b, y >> 1, x >> 1) of the half-size grid, its 192 channels behind those of the group's
+            // (2 (y & 1) + (x & 1)) predecessors: the lane's quad of block 3 cg + i is a quarter of record 12 group + 3 cg + i
+            // (32-bit element offsets: M * 192 < 2^31; the overflow mark is handed over per token tile, so that it does not live
+            //  across the GEMMs)
+            unsigned ge = 0;
+            int bad_g = 0;
+            if constexpr (PX) {
+                const int rem = (int)m - b * a.HW, y = rem / a.W, x = rem - y * a.W;
+                const int m2 = b * (a.HW >> 2) + (y >> 1) * (a.W >> 1) + (x >> 1), grp = ((y & 1) << 1) + (x & 1);
+                ge = (unsigned)(((12 * grp + 3 * cg) * a.Mq + m2) * 16 + 4 * kg);
+            }
             float tmax = 0.f;
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
@@ -204,6 +218,14 @@ __global__ __launch_bounds__(512, 2) void gdn_fwd_bwd_kernel(GdnArgs a) {
                 lsum += loss_gdn_quad(xv[i], n, yv[i], RES ? &rv[i] : nullptr, INV ? 1 : 0, gs, o, g, tv);
                 if (a.out) stq(a.out + g0 + lane_e + 16 * i, o);
                 if (a.gout) stq(a.gout + g0 + lane_e + 16 * i, g);
+                if constexpr (PX) {
+                    unsigned h0, l0, h1, l1;
+                    rdo::h2_split_pk(g[0], g[1], a.gp.s, h0, l0, bad_g);
+                    rdo::h2_split_pk(g[2], g[3], a.gp.s, h1, l1, bad_g);
+                    u16* gd = a.gp.p + (ge + (unsigned)(i * 16 * a.Mq));
+                    *reinterpret_cast<u32x2*>(gd) = u32x2{h0, h1};
+                    *reinterpret_cast<u32x2*>(gd + a.M * CH) = u32x2{l0, l1};
+                }
                 stq(a.t + g0 + lane_e + 16 * i, tv);
                 // IGDN: the chain takes sqrt(norm) in two launches, and they round differently: in the tail the call merges with the
                 // sqrt inside the reciprocal square root and inherits its relaxed accuracy, in rdo_gdn_bwd_dx_h2 it stands alone and
@@ -217,6 +239,7 @@ __global__ __launch_bounds__(512, 2) void gdn_fwd_bwd_kernel(GdnArgs a) {
             tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
             tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
             if (kg == 0) wmax[cg * BM + tok] = tmax;
+            if constexpr (PX) rdo::h2_report(bad_g, a.gp.ovf);
         }
         __syncthreads();                                              // every wave has left GEMM 1: the panel is free; the partial maxima are in
         // ---- t as planes, with the per-token scale over all 192 channels
@@ -275,10 +298,11 @@ extern "C" int rdo_gdn_fwd_bwd_supported(int64_t M, int32_t C) {
     return C == CH && M > 0 && M % BM == 0 && rdo_linear_h2_supported(M, C, C);
 }
 
-extern "C" int rdo_gdn_fwd_bwd(const float* c, const void* fwd_planes, const void* bwd_planes, float wscale, const float* beta,
-                               const float* residual, const float* tgt_cache, const int32_t* idx_table, const int32_t* iter_ptr, int32_t B,
-                               int64_t per_image, int32_t C, float coef, int32_t inverse, float* out, float* grad_out, float* t, float* dx,
-                               void* dx_planes, float dx_scale, float* loss_out, void* stream) {
+static int gdn_fwd_bwd_impl(const float* c, const void* fwd_planes, const void* bwd_planes, float wscale, const float* beta,
+                            const float* residual, const float* tgt_cache, const int32_t* idx_table, const int32_t* iter_ptr, int32_t B,
+                            int64_t per_image, int32_t C, float coef, int32_t inverse, float* out, float* grad_out, float* t, float* dx,
+                            void* dx_planes, float dx_scale, float* loss_out, void* stream, void* dup_planes, float dup_scale, int32_t W,
+                            void* dup_flag) {
     RDO_REQUIRE(c && fwd_planes && bwd_planes && beta && tgt_cache && idx_table && iter_ptr && t, "rdo_gdn_fwd_bwd: null pointer");
     RDO_REQUIRE(B > 0 && C > 0 && per_image > 0 && per_image % C == 0, "rdo_gdn_fwd_bwd: bad shape");
     const int64_t M = (int64_t)B * (per_image / C);
@@ -298,14 +322,23 @@ extern "C" int rdo_gdn_fwd_bwd(const float* c, const void* fwd_planes, const voi
     a.out = out; a.gout = grad_out; a.t = t; a.dx = dx;
     a.dxp = H2Out{reinterpret_cast<u16*>(dx_planes), dx_scale, rdo::h2_overflow_flag()};
     a.loss_out = loss_out;
+    a.gp = H2Out{reinterpret_cast<u16*>(dup_planes), dup_scale, dup_flag ? reinterpret_cast<int*>(dup_flag) : rdo::h2_overflow_flag()};
+    a.W = W; a.HW = (int)(per_image / C); a.Mq = (int)(M / 4);
     const double n = (double)M * C;
     // passes it really makes: c, target (+ residual) in; t (+ out, g, dx, dx planes) out; both weights
-    const double bytes = n * (12.0 + 4.0 * ((residual != nullptr) + (out != nullptr) + (grad_out != nullptr) + (dx != nullptr)) + (dx_planes ? 4.0 : 0.0)) +
+    const double bytes = n * (12.0 + 4.0 * ((residual != nullptr) + (out != nullptr) + (grad_out != nullptr) + (dx != nullptr)) + (dx_planes ? 4.0 : 0.0) + (dup_planes ? 4.0 : 0.0)) +
                          2.0 * 4.0 * C * C;
     return rdo::dispatch(
         [a](hipStream_t s) {
             const int wgs = cu_count();                               // one resident workgroup per CU walks the tiles
             const dim3 grid((unsigned)(a.ntiles < wgs ? a.ntiles : wgs));
+            if (a.gp.p) {
+                if (a.inverse && a.res) hipLaunchKernelGGL((gdn_fwd_bwd_kernel<true, true, true>), grid, dim3(512), LDS_BYTES, s, a);
+                else if (a.inverse) hipLaunchKernelGGL((gdn_fwd_bwd_kernel<true, false, true>), grid, dim3(512), LDS_BYTES, s, a);
+                else if (a.res) hipLaunchKernelGGL((gdn_fwd_bwd_kernel<false, true, true>), grid, dim3(512), LDS_BYTES, s, a);
+                else hipLaunchKernelGGL((gdn_fwd_bwd_kernel<false, false, true>), grid, dim3(512), LDS_BYTES, s, a);
+                return rdo::check_launch("gdn_fwd_bwd_px");
+            }
             if (a.inverse && a.res) hipLaunchKernelGGL((gdn_fwd_bwd_kernel<true, true>), grid, dim3(512), LDS_BYTES, s, a);
             else if (a.inverse) hipLaunchKernelGGL((gdn_fwd_bwd_kernel<true, false>), grid, dim3(512), LDS_BYTES, s, a);
             else if (a.res) hipLaunchKernelGGL((gdn_fwd_bwd_kernel<false, true>), grid, dim3(512), LDS_BYTES, s, a);
@@ -313,4 +346,28 @@ extern "C" int rdo_gdn_fwd_bwd(const float* c, const void* fwd_planes, const voi
             return rdo::check_launch("gdn_fwd_bwd");
         },
         stream, "linear_h2_gdn", 2.0 * 2.0 * (double)M * C * C, bytes);
+}
+
+extern "C" int rdo_gdn_fwd_bwd(const float* c, const void* fwd_planes, const void* bwd_planes, float wscale, const float* beta,
+                               const float* residual, const float* tgt_cache, const int32_t* idx_table, const int32_t* iter_ptr, int32_t B,
+                               int64_t per_image, int32_t C, float coef, int32_t inverse, float* out, float* grad_out, float* t, float* dx,
+                               void* dx_planes, float dx_scale, float* loss_out, void* stream) {
+    return gdn_fwd_bwd_impl(c, fwd_planes, bwd_planes, wscale, beta, residual, tgt_cache, idx_table, iter_ptr, B, per_image, C, coef, inverse, out,
+                            grad_out, t, dx, dx_planes, dx_scale, loss_out, stream, nullptr, 1.f, 0, nullptr);
+}
+
+extern "C" int rdo_gdn_fwd_bwd_px_supported(int64_t M, int32_t C, int32_t H, int32_t W) {
+    return rdo_gdn_fwd_bwd_supported(M, C) && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && M % ((int64_t)H * W) == 0 && M * C < (1LL << 31);
+}
+
+extern "C" int rdo_gdn_fwd_bwd_px(const float* c, const void* fwd_planes, const void* bwd_planes, float wscale, const float* beta,
+                                  const float* residual, const float* tgt_cache, const int32_t* idx_table, const int32_t* iter_ptr, int32_t B,
+                                  int32_t H, int32_t W, int32_t C, float coef, int32_t inverse, float* out, void* dup_planes, float dup_scale,
+                                  void* dup_overflow_flag, float* t, float* dx, void* dx_planes, float dx_scale, float* loss_out, void* stream) {
+    RDO_REQUIRE(dup_planes && (reinterpret_cast<uintptr_t>(dup_planes) & 15) == 0, "rdo_gdn_fwd_bwd_px: dup_planes null or not 16-byte aligned");
+    RDO_REQUIRE(pow2(dup_scale), "rdo_gdn_fwd_bwd_px: dup_scale %g is not a power of two", (double)dup_scale);
+    RDO_REQUIRE(B > 0 && rdo_gdn_fwd_bwd_px_supported((int64_t)B * H * W, C, H, W),
+                "rdo_gdn_fwd_bwd_px: %d x %d x %d tokens x %d channels is not supported (rdo_gdn_fwd_bwd_px_supported)", B, H, W, C);
+    return gdn_fwd_bwd_impl(c, fwd_planes, bwd_planes, wscale, beta, residual, tgt_cache, idx_table, iter_ptr, B, (int64_t)H * W * C, C, coef, inverse,
+                            out, nullptr, t, dx, dx_planes, dx_scale, loss_out, stream, dup_planes, dup_scale, W, dup_overflow_flag);
 }

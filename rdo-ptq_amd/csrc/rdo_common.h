@@ -85,6 +85,13 @@ __host__ __device__ inline long frag_index(long e, int Cout, int KH, int KW, int
     const long co = t / KH;
     return (((((long)(ci >> 4) * KH + kh) * KW + kw) * Cout + co) << 4) + (ci & 15);
 }
+// "rows in 4 groups" (include/rdo_ptq_subpel.h): the kernels see a sub-pixel conv's logical row r = 4 c + g at row g * rows / 4 + c
+__host__ __device__ inline int group_row(int r, int rows) { return (r & 3) * (rows >> 2) + (r >> 2); }
+// ... and element e of the weight [rows][inner] at that row
+__host__ __device__ inline long group_row_elem(long e, int rows, long inner) {
+    const long r = e / inner;
+    return (long)group_row((int)r, rows) * inner + (e - r * inner);
+}
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // workgroups of 256 threads for a grid-stride loop over n items: capped at kGridCap (MI355X: 256 CUs x 8), the loop covers the rest

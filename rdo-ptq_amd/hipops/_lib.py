@@ -180,6 +180,19 @@ _SIGS_GDN = {
     "rdo_gdn_fwd_bwd": (C.c_int, [P, P, P, C.c_float, P, P, P, P, P, C.c_int32, C.c_int64, C.c_int32, C.c_float, C.c_int32, P, P, P, P, P, C.c_float, P, P]),
 }
 EXPORTS_GDN = tuple(_SIGS_GDN)
+# include/rdo_ptq_subpel.h: the r = 2 pixel shuffle of a sub-pixel conv (and its inverse) in the stores of the kernels that write the tensor
+_SIGS_SUBPEL = {
+    "rdo_conv2d_fwd_h2_px_supported": (C.c_int, [C.POINTER(ConvDesc), C.c_int32]),
+    "rdo_conv2d_fwd_h2_px": (C.c_int, [C.POINTER(ConvDesc), P, C.c_float, P, C.c_float, P, P, P, P, P, P, P, C.c_float, P, C.c_int64, C.c_int32, P]),
+    "rdo_split_h2_conv_px": (C.c_int, [P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, P, C.c_int32, P]),
+    "rdo_gdn_fwd_bwd_px_supported": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    "rdo_gdn_fwd_bwd_px": (C.c_int, [P, P, P, C.c_float, P, P, P, P, P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, P, P, C.c_float,
+                                     P, P, P, P, C.c_float, P, P]),
+    "rdo_adaround_step_batch_gather_px": (C.c_int, [C.POINTER(AdaStepItem), C.c_int32, C.c_int32, C.c_float, C.c_float, P, P, P, P,
+                                                    C.POINTER(GatherDesc), C.POINTER(C.c_int32), P]),
+}
+EXPORTS_SUBPEL = tuple(_SIGS_SUBPEL)
+STORE_PLAIN, STORE_SHUFFLE, STORE_UNSHUFFLE = 0, 1, 2      # store modes of rdo_conv2d_fwd_h2_px
 # include/rdo_ptq_bias.h: bias correction after calibration (tap sums of a layer input, the float64 bias shift)
 _SIGS_BIAS = {
     "rdo_tap_sums": (C.c_int, [P] + [C.c_int32] * 10 + [P, P, P]),
@@ -223,7 +236,7 @@ def lib():
         import torch  # noqa: F401
         h = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(_SIGS.items()) + list(_SIGS_GDN.items()) + list(_SIGS_BIAS.items()) + list(_SIGS_BITS.items())
-                                  + list(_SIGS_PACK.items())):
+                                  + list(_SIGS_PACK.items()) + list(_SIGS_SUBPEL.items())):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         _lib = h

@@ -279,12 +279,15 @@ def iter_bind_publish(word):
     return bool(L.lib().rdo_iter_bind_publish(_ptr(word)))
 
 
-def adaround_step_batch(items, grad_scale, round_weight, sched, iter_ptr, round_log, advance_iter=None, mode=0, iter_shadow=None, gather=None):
+def adaround_step_batch(items, grad_scale, round_weight, sched, iter_ptr, round_log, advance_iter=None, mode=0, iter_shadow=None, gather=None,
+                        row_groups=None):
     """items: list of dicts(d, w, delta, zp, slabs, alpha, m, v, wq, wd, wq_planes, wd_planes[, dalpha, lin_fwd, lin_bwd]) -- one launch for every
     weight tensor of a unit (<= 8, numel % 4 == 0): mode 0 the fused AdaRound step, 1 the data gradient into `dalpha`, 2 the update
     from an (all-reduced) `dalpha`; `advance_iter`: the device iteration counter to increment afterwards.
     `gather`: dict(cache_q, cache_fp, idx_table, B, batch_offset, prob, seed, out, out_planes) -- the launch also assembles the NEXT
-    iteration's mini-batch (rdo_adaround_step_batch_gather)."""
+    iteration's mini-batch (rdo_adaround_step_batch_gather).
+    `row_groups` (None: the plain entries): one 0 or 4 per item -- 4: the item's slabs are read and its forward planes written with the rows in 4 groups
+    (rdo_adaround_step_batch_gather_px, include/rdo_ptq_subpel.h; with or without a gather, not with advance_iter)."""
     _bind_out(None)            # weight planes raise the enclosing block's word
     arr = (L.AdaStepItem * len(items))()
     dp = lambda t: None if t is None else _ptr(t).value
@@ -300,6 +303,15 @@ def adaround_step_batch(items, grad_scale, round_weight, sched, iter_ptr, round_
         lf, lb = it.get("lin_fwd"), it.get("lin_bwd")      # H2 planes in rdo_linear_h2's fragment order, written by the step itself
         a.lin_fwd_planes, a.lin_bwd_planes = dp(lf), dp(lb)
         a.lin_plane_scale = float((lf if lf is not None else lb).scale) if (lf is not None or lb is not None) else 0.0
+    px = row_groups is not None
+    if px and (advance_iter is not None or len(row_groups) != len(items)):
+        raise ValueError("adaround_step_batch: row_groups needs one entry per item and moves the counter by hand-over (iter_shadow), not advance_iter")
+    if px and gather is None:
+        rg = (C.c_int32 * len(items))(*[int(v) for v in row_groups])
+        L.check(L.lib().rdo_adaround_step_batch_gather_px(arr, len(items), int(mode), grad_scale, round_weight, _ptr(sched), _ptr(iter_ptr),
+                                                          _ptr(round_log), _ptr(iter_shadow), None, rg, _stream()),
+                "rdo_adaround_step_batch_gather_px")
+        return
     if gather is not None:
         if advance_iter is not None:
             raise ValueError("adaround_step_batch: the gather form moves the counter by hand-over (iter_shadow), not advance_iter")
@@ -310,6 +322,12 @@ def adaround_step_batch(items, grad_scale, round_weight, sched, iter_ptr, round_
         g.per_image, g.C, g.prob, g.seed = cq[0].numel(), int(cq.shape[-1]), float(gather["prob"]), int(gather["seed"])
         g.out, g.out_planes, g.out_scale = dp(gather.get("out")), dp(pl), (float(pl.scale) if pl is not None else 0.0)
         g.overflow_flag = dp(getattr(pl, "flag", None))      # the gathered planes raise their own overflow word
+        if px:
+            rg = (C.c_int32 * len(items))(*[int(v) for v in row_groups])
+            L.check(L.lib().rdo_adaround_step_batch_gather_px(arr, len(items), int(mode), grad_scale, round_weight, _ptr(sched), _ptr(iter_ptr),
+                                                              _ptr(round_log), _ptr(iter_shadow), C.byref(g), rg, _stream()),
+                    "rdo_adaround_step_batch_gather_px")
+            return
         L.check(L.lib().rdo_adaround_step_batch_gather(arr, len(items), int(mode), grad_scale, round_weight, _ptr(sched), _ptr(iter_ptr),
                                                        _ptr(round_log), _ptr(iter_shadow), C.byref(g), _stream()), "rdo_adaround_step_batch_gather")
         return
@@ -1525,9 +1543,10 @@ def split_h2(x, planes=None, scale=None):
     return planes
 
 
-def split_h2_conv(w, planes=None, scale=None):
+def split_h2_conv(w, planes=None, scale=None, row_groups=0):
     """Conv weight in kernel layout [Cout,KH,KW,Cin] (or [C,C] = 1x1) -> H2 weight planes int16 [2, Cout,KH,KW,Cin] in the fragment
-    order the split-precision kernels read ([Cin/16][KH][KW][Cout][16])."""
+    order the split-precision kernels read ([Cin/16][KH][KW][Cout][16]).  row_groups = 4: with the rows in 4 groups (logical row r at
+    row (r & 3) Cout / 4 + (r >> 2): rdo_split_h2_conv_px, include/rdo_ptq_subpel.h)."""
     if w.dim() == 2:
         w = w.reshape(w.shape[0], 1, 1, w.shape[1])
     if w.dim() != 4:
@@ -1536,7 +1555,10 @@ def split_h2_conv(w, planes=None, scale=None):
         planes = H2(torch.empty((2,) + tuple(w.shape), device=w.device, dtype=torch.int16), pow2_scale(w.abs().max()) if scale is None else scale)
     co, kh, kw, ci = w.shape
     _bind_out(planes)
-    L.check(L.lib().rdo_split_h2_conv(_ptr(w), co, kh, kw, ci, planes.scale, _ptr(planes), _stream()), "rdo_split_h2_conv")
+    if row_groups:
+        L.check(L.lib().rdo_split_h2_conv_px(_ptr(w), co, kh, kw, ci, planes.scale, _ptr(planes), int(row_groups), _stream()), "rdo_split_h2_conv_px")
+    else:
+        L.check(L.lib().rdo_split_h2_conv(_ptr(w), co, kh, kw, ci, planes.scale, _ptr(planes), _stream()), "rdo_split_h2_conv")
     return planes
 
 
@@ -1561,6 +1583,33 @@ def conv2d_fwd_h2(xp, x_shape, w_shape, wplanes, bias=None, stride=1, pad=0, epi
                                       _ptr(residual), _ptr(out), _ptr(pre), _ptr(out_planes), _oscale(out_planes), _ptr(ws),
                                       ws.numel() if ws is not None else 0, _stream()), "rdo_conv2d_fwd_h2")
     return out
+
+
+def conv_h2_px_supported(x_shape, w_shape, stride, pad, store_mode):
+    """rdo_conv2d_fwd_h2_px takes this shape with this store mode (L.STORE_SHUFFLE / L.STORE_UNSHUFFLE)"""
+    d = conv_desc(x_shape, w_shape, stride, pad)
+    return bool(L.lib().rdo_conv2d_fwd_h2_px_supported(C.byref(d), int(store_mode)))
+
+
+def conv2d_fwd_h2_px(xp, x_shape, w_shape, wplanes, store_mode, bias=None, stride=1, pad=0, epilogue=L.EPI_NONE, aux=None, residual=None, out=None,
+                     out_planes=None, aux_planes=None):
+    """conv2d_fwd_h2 whose stores carry the r = 2 pixel shuffle (store_mode 1: `wplanes` and `bias` with the rows in 4 groups, out /
+    out_planes [B,2Ho,2Wo,Cout/4]) or its inverse (2: out / out_planes [B,Ho/2,Wo/2,4 Cout], channels in group order)."""
+    d = conv_desc(x_shape, w_shape, stride, pad, epilogue, False, residual is not None)
+    need = int(L.lib().rdo_conv2d_fwd_h2_workspace(C.byref(d)))
+    ws = _scratch(xp.device, need) if need else None
+    _bind_out(out_planes)
+    L.check(L.lib().rdo_conv2d_fwd_h2_px(C.byref(d), _ptr(xp), xp.scale, _ptr(wplanes), wplanes.scale, _ptr(bias), _ptr(aux), _ptr(aux_planes),
+                                         _ptr(residual), _ptr(out), None, _ptr(out_planes), _oscale(out_planes), _ptr(ws),
+                                         ws.numel() if ws is not None else 0, int(store_mode), _stream()), "rdo_conv2d_fwd_h2_px")
+    return out
+
+
+def group_rows(rows):
+    """index tensor p with p[g * C + c] = 4 c + g (C = rows / 4): t[p] is t with its rows in 4 groups (include/rdo_ptq_subpel.h)"""
+    if rows % 4:
+        raise ValueError("group_rows: the row count must be a multiple of 4")
+    return torch.arange(rows).view(rows // 4, 4).t().reshape(-1)
 
 
 def conv_h2_tail_supported(x_shape, w_shape, stride, pad):
@@ -1628,6 +1677,27 @@ def gdn_fwd_bwd(c, fwd_planes, bwd_planes, beta, residual, tgt_cache, idx_table,
                                     _ptr(tgt_cache), _ptr(idx_table), _ptr(iter_ptr), B, per_image, c.shape[-1], coef, int(inverse), _ptr(out),
                                     _ptr(grad_out), _ptr(t), _ptr(dx), _ptr(dx_planes), _oscale(dx_planes), _ptr(loss_log), _stream()),
             "rdo_gdn_fwd_bwd")
+
+
+def gdn_fwd_bwd_px_supported(shape):
+    """rdo_gdn_fwd_bwd_px takes the block over an NHWC tensor of `shape`"""
+    B, H, W, Cc = shape
+    return bool(L.lib().rdo_gdn_fwd_bwd_px_supported(int(B) * int(H) * int(W), int(Cc), int(H), int(W)))
+
+
+def gdn_fwd_bwd_px(c, fwd_planes, bwd_planes, beta, residual, tgt_cache, idx_table, iter_ptr, coef, inverse, loss_log, t, dup_planes, out=None,
+                   dx=None, dx_planes=None):
+    """gdn_fwd_bwd whose dL/dout leaves as `dup_planes`: the planes of pixel_unshuffle2(dL/dout) [B,H/2,W/2,4C] with the channels in group
+    order (the dY operand of the weight gradient of a sub-pixel conv whose rows are in 4 groups).  `dup_planes` raise their own overflow
+    words where they have some."""
+    if fwd_planes.scale != bwd_planes.scale:
+        raise ValueError("gdn_fwd_bwd_px: the planes of gamma' and of its transpose must share one scale")
+    B, H, W, Cc = c.shape
+    _bind_out(dx_planes)
+    L.check(L.lib().rdo_gdn_fwd_bwd_px(_ptr(c), _ptr(fwd_planes), _ptr(bwd_planes), float(fwd_planes.scale), _ptr(beta), _ptr(residual),
+                                       _ptr(tgt_cache), _ptr(idx_table), _ptr(iter_ptr), B, H, W, Cc, coef, int(inverse), _ptr(out),
+                                       _ptr(dup_planes), dup_planes.scale, _ptr(getattr(dup_planes, "flag", None)), _ptr(t), _ptr(dx),
+                                       _ptr(dx_planes), _oscale(dx_planes), _ptr(loss_log), _stream()), "rdo_gdn_fwd_bwd_px")
 
 
 def pixel_shuffle_h2(x, out=None, out_planes=None):

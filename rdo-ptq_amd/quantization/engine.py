@@ -128,10 +128,11 @@ def _split_lin(w, planes):
     ops.split_h2_linear(w, planes=planes)
 
 
-def _split_conv(w, planes):
-    """by the format the buffer was allocated in: ops.H2 for the plane-input kernels, bf16 three-way for the fp32-input ones"""
+def _split_conv(w, planes, row_groups=0):
+    """by the format the buffer was allocated in: ops.H2 for the plane-input kernels (row_groups: `_Weights.row_groups`), bf16 three-way
+    for the fp32-input ones"""
     if isinstance(planes, ops.H2):
-        ops.split_h2_conv(w, planes=planes)
+        ops.split_h2_conv(w, planes=planes, row_groups=row_groups)
     else:
         ops.split_bf16x3(w, planes)
 
@@ -156,6 +157,10 @@ class _Weights:
         self.qm = qm
         self.tconv = None                     # (stride, padding, output_padding) of a ConvTranspose2d
         self.tc_phase = self.wp = self.bias_p = self.wbp = self.wd = None
+        # 4: a sub-pixel conv whose pixel shuffle sits in its kernel's stores (`UnitEngine._fb_gdn_block`, include/rdo_ptq_subpel.h) -- its
+        # forward planes `wq_planes` and its gradient slabs have the rows in 4 groups, `bias_g` is the bias in that order; everything
+        # else of the op (w, alpha, the Adam moments, wq, wd) keeps the logical row order.  Set while a plan is recorded.
+        self.row_groups, self.bias_g = 0, None
         self.drop_planes()
 
     def drop_planes(self):
@@ -207,7 +212,10 @@ class _Weights:
                 continue
             src, split = self.PLANE_BUFFERS[n]
             w = getattr(self, src)
-            split(w() if callable(w) else w, planes)
+            if n == "wq_planes" and self.row_groups:
+                split(w() if callable(w) else w, planes, self.row_groups)
+            else:
+                split(w() if callable(w) else w, planes)
 
     def lin_planes(self, fwd: bool):
         """Planes of this Linear's weight (fwd) / of its transpose (input gradient) for rdo_linear_h2: allocated on first use -- while
@@ -352,6 +360,9 @@ class UnitEngine(DpLoop, RdTask):
         # the GDN / IGDN block of an RBWS / RBU unit -- norm pool, loss tail, gamma'^T GEMM and dx -- in one launch (ops.gdn_fwd_bwd) where
         # both GEMMs would run on rdo_linear_h2; 0: the four launches
         self.gdn_fused = os.environ.get("RDO_GDN_FUSED", "1") != "0"
+        # the four pixel (un)shuffles of an RBU unit in the stores of the kernels that write their inputs (the two sub-pixel convs, the
+        # one-launch GDN block, the dgrad of the 3 x 3 conv: `_fb_gdn_block`); 0: a launch each
+        self.subpel_fused = os.environ.get("RDO_SUBPEL_FUSED", "1") != "0"
         self._next_gather = None
         self._rd_init(rd, include_act_func)    # opt-in R + lambda*D task loss (loss_mode='rd', engine_rd.RdTask): separate kernels, fp32
         if rd is not None:
@@ -505,11 +516,10 @@ class UnitEngine(DpLoop, RdTask):
             C4 = sp.rows
             r = int(self.mods["upscale"])
             C = C4 // (r * r)
-            t["sp"] = self._buf(B, H, W, C4)           # lrelu(subpel conv) before the shuffle
+            # (sp = lrelu(subpel conv) before the shuffle, up, dout and dh1 only feed a pixel (un)shuffle launch: `_tmp`)
             t["h1"] = self._buf(B, H * r, W * r, C)
-            t["up"] = self._buf(B, H, W, C4)
             t["ups"] = self._buf(B, H * r, W * r, C)
-            for n_ in ("c", "out", "dout", "t", "dc", "dh1"):
+            for n_ in ("c", "out", "t", "dc"):
                 t[n_] = self._buf(B, H * r, W * r, C)
             t["dsp"] = self._buf(B, H, W, C4)
             t["dup"] = self._buf(B, H, W, C4)
@@ -519,11 +529,13 @@ class UnitEngine(DpLoop, RdTask):
             op.slabs = None     # allocated at record time when the activation shapes are known
 
     GDN_TMP = ("norm", "acc")
+    SUBPEL_TMP = ("sp", "up", "dout", "dh1")
 
     def _tmp(self, name, like):
         """`norm` / `acc` of an RBWS / RBU unit: they only carry values from one launch of the GDN block to the next, so they are made
         on first use -- by the probe iterations and by a plan that runs the block as separate launches -- and not at all by a plan
-        that runs it as one (`_fb_gdn_block`)"""
+        that runs it as one (`_fb_gdn_block`).  The same for the inputs of an RBU unit's four pixel (un)shuffle launches (SUBPEL_TMP)
+        and a plan that has those in its kernels' stores."""
         if name not in self.t:
             self.t[name] = self._buf(*like.shape)
         return self.t[name]
@@ -937,18 +949,34 @@ class UnitEngine(DpLoop, RdTask):
         # activations: the launches are independent and either order computes the same values; each form keeps the order its plans
         # have always had, so that the op list of a unit stays comparable from one version of this file to the next
         side_first = self.h2_plan is not None
+        # norm pool, tail, gamma'^T GEMM and dx in ONE launch where both GEMMs would run on rdo_linear_h2 (same bits; norm and acc do not
+        # exist).  dL/dout is written only where something reads it: the weight gradient of the side branch
+        one = (self.fused and self.gdn_fused and self._gdn_lin_ok(g, c) and tt.planes is None
+               and ops.gdn_fwd_bwd_supported(math.prod(c.shape[:-1]), c.shape[-1]))
+        px = rbu and self._subpel_plan(one, x, h1, dc, first, side, cv)
         self._gather(x)
-        if rbu:
-            self._conv(first, x, t["sp"], epilogue=L.EPI_LRELU)    # LeakyReLU commutes with the pixel shuffle
+        if px:
+            # sub-pixel convs with their rows in 4 groups: the pixel shuffle is an address change in the epilogue's stores, sp and up never
+            # exist (LeakyReLU commutes with the shuffle)
+            for op in (first, side):
+                op.enable_planes(True, False, h2=True)
+                ops.conv2d_fwd_h2_px(x.planes, x.shape, op.w4, op.wq_planes, L.STORE_SHUFFLE, op.bias_g, op.stride, op.pad,
+                                     epilogue=L.EPI_LRELU if op is first else L.EPI_NONE, out=h1.f32 if op is first else t["ups"],
+                                     out_planes=h1.planes if op is first else None)
+            self._conv(cv, h1, c)
+            res = t["ups"]
+        elif rbu:
+            sp, up = self._tmp("sp", t["dsp"]), self._tmp("up", t["dsp"])
+            self._conv(first, x, sp, epilogue=L.EPI_LRELU)         # LeakyReLU commutes with the pixel shuffle
             if side_first:
-                self._conv(side, x, t["up"])
-            self._shuffle(t["sp"], r, h1)
+                self._conv(side, x, up)
+            self._shuffle(sp, r, h1)
             if side_first:
-                self._shuffle(t["up"], r, t["ups"])
+                self._shuffle(up, r, t["ups"])
             self._conv(cv, h1, c)
             if not side_first:
-                self._conv(side, x, t["up"])
-                self._shuffle(t["up"], r, t["ups"])
+                self._conv(side, x, up)
+                self._shuffle(up, r, t["ups"])
             res = t["ups"]
         else:
             self._conv(first, x, h1, epilogue=L.EPI_LRELU)         # (fp32 input: the planes of h1 by a split of their own)
@@ -958,46 +986,83 @@ class UnitEngine(DpLoop, RdTask):
             if side is not None and not side_first:
                 self._conv(side, x.f32, t["sk"])
             res = x if side is None else t["sk"]
-        # norm pool, tail, gamma'^T GEMM and dx in ONE launch where both GEMMs would run on rdo_linear_h2 (same bits; norm and acc do not
-        # exist).  dL/dout is written only where something reads it: the weight gradient of the side branch
-        one = (self.fused and self.gdn_fused and self._gdn_lin_ok(g, c) and tt.planes is None
-               and ops.gdn_fwd_bwd_supported(math.prod(c.shape[:-1]), c.shape[-1]))
-        if one:
+        dout = self._tmp("dout", c) if (rbu and not px) else t.get("dout")
+        if px:                                                        # dL/dout leaves the launch as the planes of its unshuffle
+            self._task_is_rec = True
+            dup = self._act("dup")
+            ops.gdn_fwd_bwd_px(c, g.lin_planes(True), g.lin_planes(False), g.beta, _f32(res), self.co, self.idx, self.it, 2.0, True, self.loss_log,
+                               tt.f32, dup.planes, dx=dc.f32, dx_planes=dc.planes)
+        elif one:
             self._task_is_rec = True
             ops.gdn_fwd_bwd(c, g.lin_planes(True), g.lin_planes(False), g.beta, _f32(res), self.co, self.idx, self.it, 2.0, rbu, self.loss_log,
-                            tt.f32, grad_out=t["dout"] if (rbu or side is not None) else None, dx=dc.f32, dx_planes=dc.planes)
+                            tt.f32, grad_out=dout if (rbu or side is not None) else None, dx=dc.f32, dx_planes=dc.planes)
         elif self.fused:
             self._gdn_pool(g, c, self._tmp("norm", c))
-            self._tail_gdn(c, t["norm"], res, rbu, t["dout"], tt)
+            self._tail_gdn(c, t["norm"], res, rbu, dout, tt)
         else:
             self._conv(g, c, t["out"], epilogue=L.EPI_IGDN if rbu else L.EPI_GDN, aux=c, residual=res, pre=self._tmp("norm", c), square=True)
-            self._loss(t["out"], t["dout"])
-        if rbu:
+            self._loss(t["out"], dout)
+        if px:
+            self._wgrad(side, x, dup)                                 # (slab rows in the order of dup's channels: in 4 groups)
+        elif rbu:
             dup = self._act("dup")
-            self._unshuffle(t["dout"], r, dup)
+            self._unshuffle(dout, r, dup)
             self._wgrad(side, x, dup)
         elif side is not None:
-            self._wgrad(side, x.f32, t["dout"])
+            self._wgrad(side, x.f32, dout)
         if not self.fused:                                            # the fused tail has already written t
-            ops.gdn_bwd_t(t["dout"], c, t["norm"], rbu, tt.f32)
+            ops.gdn_bwd_t(dout, c, t["norm"], rbu, tt.f32)
         if not one:
             self._gdn_acc(g, tt, self._tmp("acc", c))                 # t . gamma'
             if dc.planes is not None or c.numel() % 4 == 0:
-                ops.gdn_bwd_dx_h2(t["dout"], c, t["norm"], t["acc"], rbu, dx=dc.f32, dx_planes=dc.planes)   # 16-byte accesses
+                ops.gdn_bwd_dx_h2(dout, c, t["norm"], t["acc"], rbu, dx=dc.f32, dx_planes=dc.planes)   # 16-byte accesses
             else:
-                ops.gdn_bwd_dx(t["dout"], c, t["norm"], t["acc"], rbu, dc.f32)
+                ops.gdn_bwd_dx(dout, c, t["norm"], t["acc"], rbu, dc.f32)
         self._wgrad(g, c, tt.f32, square=True)                        # dgamma'[k][i] = sum_m t_k x_i^2
         self._wgrad(cv, h1, dc)
-        dh1 = self._act("dh1")
-        self._dgrad(cv, dc, dh1, epilogue=L.EPI_LRELU_BWD, aux=h1)
+        if px:                                                        # the dgrad's epilogue stores the unshuffle; fp32 dh1 never exists
+            dsp = self._act("dsp")
+            cv.enable_planes(False, True, h2=True)
+            ops.conv2d_fwd_h2_px(dc.planes, dc.shape, tuple(cv.wd4().shape), cv.wd_planes, L.STORE_UNSHUFFLE, None, 1, cv.K - 1 - cv.pad,
+                                 epilogue=L.EPI_LRELU_BWD, aux=h1.f32, aux_planes=_planes_only(h1), out_planes=dsp.planes)
+            self._wgrad(first, x, dsp)
+            return
         if rbu:
+            if "dh1" not in t:
+                self._tmp("dh1", c)
+            dh1 = self._act("dh1")
+            self._dgrad(cv, dc, dh1, epilogue=L.EPI_LRELU_BWD, aux=h1)
             dsp = self._act("dsp")
             self._unshuffle(dh1, r, dsp)
             self._split_point()
             self._wgrad(first, x, dsp)
         else:
+            dh1 = self._act("dh1")
+            self._dgrad(cv, dc, dh1, epilogue=L.EPI_LRELU_BWD, aux=h1)
             self._split_point()
             self._wgrad(first, x, dh1)
+
+    def _subpel_plan(self, one, x, h1, dc, first, side, cv):
+        """Does this RBU unit take the plan that has its four pixel (un)shuffles in the stores of the kernels around them -- as a whole, or
+        not at all?  It does on the H2 plan with the unit input on planes and the GDN block as one launch, where the four kernels take
+        the shapes (conv_h2_px_supported, gdn_fwd_bwd_px_supported) and the unit's step is the batched launch that knows rows in 4
+        groups.  Not while probing, not on fp32 activations, not under data parallelism (the gradient-only launch reads the slabs in
+        logical order).  Marks the two sub-pixel convs (`_Weights.row_groups`) either way: a plan is recorded from a clean slate."""
+        for op in self.ops.values():
+            op.row_groups, op.bias_g = 0, None
+        if not (self.subpel_fused and not self._probing and self.h2_plan == "rbu" and self.r == 2 and one and not self.split and self._handover
+                and x.planes is not None and h1.planes is not None and dc.planes is not None
+                and self.forms.get("dup") == PLANES and self.forms.get("dsp") == PLANES):
+            return False
+        xs, wd4 = tuple(x.shape), tuple(cv.wd4().shape)
+        if not (all(ops.conv_h2_px_supported(xs, op.w4, op.stride, op.pad, L.STORE_SHUFFLE) for op in (first, side))
+                and ops.conv_h2_px_supported(tuple(dc.shape), wd4, 1, cv.K - 1 - cv.pad, L.STORE_UNSHUFFLE)
+                and ops.gdn_fwd_bwd_px_supported(tuple(dc.shape))):
+            return False
+        for op in (first, side):
+            op.row_groups = 4
+            op.bias_g = None if op.bias is None else op.bias[ops.group_rows(op.rows).to(op.bias.device)].contiguous()
+        return True
 
     def _probe_amax(self, names):
         """One eager iteration of the unit on fp32 activations and the plain fp32 kernels (no planes, no AdaRound step) at the CURRENT
@@ -1040,6 +1105,9 @@ class UnitEngine(DpLoop, RdTask):
         self._clear_probe()
         for n_ in self.GDN_TMP:                               # (the probe ran the GDN block as separate launches; the plan may not: `_tmp`)
             if self.kind in ("rbws", "rbu"):
+                self.t.pop(n_, None)
+        if self.kind == "rbu":
+            for n_ in self.SUBPEL_TMP:                        # (... and the pixel (un)shuffles)
                 self.t.pop(n_, None)
         if self.world > 1:
             # every rank probes its own shard: agree on the magnitudes (MAX) so that all ranks record the same scales, take the same
@@ -1182,7 +1250,9 @@ class UnitEngine(DpLoop, RdTask):
                 it, kw = self.it, dict(iter_shadow=self.it_shadow if i == 0 else None)
             else:
                 it, kw = self.it, dict(advance_iter=self.it if last else None)
-            ops.adaround_step_batch(self._items(opl[i:i + self.STEP_BATCH]), scale, self.weight, self.sched, it, self.round_log, mode=mode, **kw)
+            ops.adaround_step_batch(self._items(opl[i:i + self.STEP_BATCH]), scale, self.weight, self.sched, it, self.round_log, mode=mode,
+                                    row_groups=[op.row_groups for op in opl[i:i + self.STEP_BATCH]] if any(op.row_groups for op in opl) else None,
+                                    **kw)
 
     @property
     def _handover(self):
