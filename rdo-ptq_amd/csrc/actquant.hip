@@ -1,10 +1,10 @@
 // K6 -- per-channel activation quantisers on NHWC fp32 tensors (channel = fastest dim): the dynamic quantiser (min | max of the tensor
 // itself), the static one (a frozen lo | hi pair), the range search, the range scoring, the static backward, the Adam step of learned
-// ranges, the per-channel histogram with its percentile and its histogram-MSE selection, and the pair moments of two tensors (the
-// per-unit output error report).
+// ranges, the per-channel histogram with its percentile and its histogram-MSE selection, the pair moments of two tensors (the
+// per-unit output error report), and the width scan (one grid scored at K widths: include/rdo_ptq_actbits.h).
 // Built with -ffp-contract=off (products and sums round separately, like the reference's op chains).
 //
-// Five of them reduce over the pixels per channel, and all five do it the same way, without atomics: up to kAqBlocks workgroups each
+// Six of them reduce over the pixels per channel, and all six do it the same way, without atomics: up to kAqBlocks workgroups each
 // leave one row of partial values for their share of the pixels (aq_partial below), a small second kernel folds the rows (aq_fold_kernel).
 // (The first version let 1024 workgroups atomicMin / atomicMax into the same 2 C words: 0.4 M contended atomics per call were most of its
 // time.)  The order of the fp32 additions is fixed HERE, once, and frozen ranges depend on it: a thread's running sum over its pixels in
@@ -14,6 +14,7 @@
 #include <initializer_list>
 #include <type_traits>
 
+#include "../../include/rdo_ptq_actbits.h"
 #include "rdo_common.h"
 
 namespace {
@@ -271,6 +272,77 @@ struct AqScore {
 template <int W, int K>
 __global__ __launch_bounds__(256) void aqc_partial_kernel(const float* x, long npix, int C, const float* cand, float bit_range, float* part) {
     aq_partial<W, 1>(AqScore<W, K>{x, cand, bit_range}, npix, C, part);
+}
+
+// ---- width scan: the measured squared error of ONE grid lo | hi per channel at K widths, err[c][k] = sum over pixels of (x - Q_k(x))^2
+// with Q_k the static quantiser's own expression at 2^b_k - 1 steps (aq_quant on max(hi - lo, 1e-6), lower clamp 0), next to it the
+// channel's energy sum x^2: the scoring kernel with the grid fixed and the step count varied, the counts dropped.  One read of x, W x
+// (K + 1) running sums (and as many closed ones) in registers, so one pixel in flight like the score; part = [workgroup][C][err[K] |
+// energy].  The step counts travel as a kernel argument (a host array by contract).
+constexpr int kAqwMax = RDO_ACT_WIDTH_SCAN_MAX_K;
+struct AqwSteps { float v[kAqwMax]; };
+template <int W, int K>
+struct AqWidthScan {
+    typedef float in_t __attribute__((ext_vector_type(W)));
+    static constexpr int N = K + 1;
+    static constexpr bool kChain = true, kChannelMajor = true;
+    const float* x;
+    const float* range;
+    AqwSteps steps;
+    float lo[W], rng[W];
+    __device__ static float zero(int) { return 0.f; }
+    __device__ static float combine(float a, float v, int) { return a + v; }
+    __device__ void begin(int q, int C) {
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+            lo[k] = range[q * W + k];
+            rng[k] = fmaxf(range[C + q * W + k] - lo[k], 1e-6f);
+        }
+    }
+    __device__ in_t load(long off) const { return *reinterpret_cast<const in_t*>(x + off); }
+    __device__ void pixel(const in_t& v, long, float (&acc)[W][N]) const {
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                const float d = v[k] - aq_quant(v[k], lo[k], rng[k], steps.v[j], 0.f);
+                acc[k][j] += d * d;
+            }
+            acc[k][K] += v[k] * v[k];
+        }
+    }
+};
+template <int W, int K>
+__global__ __launch_bounds__(256) void aqw_partial_kernel(const float* x, long npix, int C, const float* range, AqwSteps steps, float* part) {
+    aq_partial<W, 1>(AqWidthScan<W, K>{x, range, steps}, npix, C, part);
+}
+
+// fold of the scan's partial rows [workgroup][C][K + 1]: the lanes and the order of aq_fold_kernel<true> (lane j adds the rows j, j + 16,
+// .. serially from zero, then the xor tree 8, 4, 2, 1).  err and energy = the sum (WRITTEN); energy may be null.
+__global__ __launch_bounds__(256) void aqw_fold_kernel(const float* part, int nblk, int C, int K, float* err, float* energy) {
+    const int N = K + 1, n = C * N;
+    const int i = blockIdx.x * 16 + (threadIdx.x >> 4), j = threadIdx.x & 15;
+    const bool live = i < n;
+    const int c = i / N, e = i - c * N;
+    float r = 0.f;
+    if (live) {
+        const float* src = part + i;
+        int b = j;
+        for (; b + 48 < nblk; b += 64) {
+            float v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) v[u] = src[(long)(b + 16 * u) * n];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) r = r + v[u];
+        }
+        for (; b < nblk; b += 16) r = r + src[(long)b * n];
+    }
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) r = r + __shfl_xor(r, o, 16);
+    if (live && j == 0) {
+        if (e < K) err[c * K + e] = r;
+        else if (energy) energy[c] = r;
+    }
 }
 
 // ---- pair moments: per channel the three sums over the pixels of d = a - b (fp32), d * d and a * a, in one read of both tensors (the
@@ -806,6 +878,49 @@ int rdo_actquant_score(const float* x, int64_t npix, int32_t C, int32_t n_bits, 
 
 int64_t rdo_actquant_score_workspace(int32_t C, int32_t K) {
     return C > 0 && K >= 1 && K <= kAqcMax ? (int64_t)C * (3 * K + 1) * kAqBlocks : 0;
+}
+
+int rdo_actquant_width_scan(const float* x, int64_t npix, int32_t C, const float* range, const int32_t* widths, int32_t K, float* err,
+                            float* energy, float* ws, void* stream) {
+    RDO_REQUIRE(x && range && widths && err && ws && npix > 0 && C > 0, "rdo_actquant_width_scan: bad argument");
+    RDO_REQUIRE(K >= 1 && K <= kAqwMax, "rdo_actquant_width_scan: K %d outside [1, %d]", K, kAqwMax);
+    RDO_REQUIRE(npix <= 0x7fffffffLL, "rdo_actquant_width_scan: %lld pixels are beyond 32-bit pixel counts", (long long)npix);
+    RDO_REQUIRE((int64_t)C * (kAqwMax + 1) <= 0x7fffffffLL, "rdo_actquant_width_scan: %d channels are too many for 32-bit entry indices", C);
+    AqwSteps steps{};
+    for (int k = 0; k < K; ++k) {
+        if (const int e = aq_bit_range(widths[k], "rdo_actquant_width_scan", &steps.v[k])) return e;
+        for (int j = 0; j < k; ++j)
+            RDO_REQUIRE(widths[j] != widths[k], "rdo_actquant_width_scan: the width %d is given twice", widths[k]);
+    }
+    const bool vec = aq_vec(C, {x});
+    return rdo::dispatch(
+        [=](hipStream_t s) {
+            aq_with_width(vec, [&](auto w) {
+                constexpr int W = decltype(w)::value;
+                const int nblk = aq_blocks(npix, C, W);
+                auto launch = [&](auto k) {
+                    hipLaunchKernelGGL((aqw_partial_kernel<W, decltype(k)::value>), dim3(nblk), dim3(256), 0, s, x, (long)npix, C, range, steps,
+                                       ws);
+                };
+                switch (K) {
+                    case 1: launch(std::integral_constant<int, 1>{}); break;
+                    case 2: launch(std::integral_constant<int, 2>{}); break;
+                    case 3: launch(std::integral_constant<int, 3>{}); break;
+                    case 4: launch(std::integral_constant<int, 4>{}); break;
+                    case 5: launch(std::integral_constant<int, 5>{}); break;
+                    case 6: launch(std::integral_constant<int, 6>{}); break;
+                    case 7: launch(std::integral_constant<int, 7>{}); break;
+                    default: launch(std::integral_constant<int, 8>{}); break;
+                }
+                hipLaunchKernelGGL(aqw_fold_kernel, aq_fold_grid(C * (K + 1)), dim3(256), 0, s, ws, nblk, C, K, err, energy);
+            });
+            return rdo::check_launch("actquant_width_scan");
+        },
+        stream, "actquant_width_scan", 0.0, 4.0 * npix * C);
+}
+
+int64_t rdo_actquant_width_scan_workspace(int32_t C, int32_t K) {
+    return C > 0 && (int64_t)C * (kAqwMax + 1) <= 0x7fffffffLL && K >= 1 && K <= kAqwMax ? (int64_t)C * (K + 1) * kAqBlocks : 0;
 }
 
 int rdo_pair_moments(const float* a, const float* b, int64_t npix, int32_t C, float* out, float* ws, void* stream) {

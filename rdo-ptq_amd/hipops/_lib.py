@@ -220,6 +220,15 @@ _SIGS_PACK = {
 EXPORTS_PACK = tuple(_SIGS_PACK)
 PACK_MIN_BITS, PACK_MAX_BITS = 2, 16      # RDO_PACK_MIN_BITS and RDO_PACK_MAX_BITS of include/rdo_ptq_pack.h
 
+# include/rdo_ptq_actbits.h: activation widths per unit (the squared error of one activation grid at K widths in one read of the tensor)
+_SIGS_ACTBITS = {
+    "rdo_actquant_width_scan": (C.c_int, [P, C.c_int64, C.c_int32, P, C.POINTER(C.c_int32), C.c_int32, P, P, P, P]),
+    "rdo_actquant_width_scan_workspace": (C.c_int64, [C.c_int32, C.c_int32]),
+}
+EXPORTS_ACTBITS = tuple(_SIGS_ACTBITS)
+ACT_WIDTH_SCAN_MAX_K = 8  # RDO_ACT_WIDTH_SCAN_MAX_K, _MIN_BITS and _MAX_BITS of include/rdo_ptq_actbits.h
+ACT_WIDTH_SCAN_MIN_BITS, ACT_WIDTH_SCAN_MAX_BITS = 2, 16
+
 _lib = None
 
 
@@ -236,7 +245,7 @@ def lib():
         import torch  # noqa: F401
         h = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(_SIGS.items()) + list(_SIGS_GDN.items()) + list(_SIGS_BIAS.items()) + list(_SIGS_BITS.items())
-                                  + list(_SIGS_PACK.items()) + list(_SIGS_SUBPEL.items())):
+                                  + list(_SIGS_PACK.items()) + list(_SIGS_SUBPEL.items()) + list(_SIGS_ACTBITS.items())):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         _lib = h

@@ -356,6 +356,11 @@ def set_tuning(key, value):
     return prev
 
 
+def actquant_workspace(channels):
+    """floats `actquant_perchannel` needs in `ws`; the call leaves the tensor's min[C] | max[C] in the first 2 C of them"""
+    return int(L.lib().rdo_actquant_workspace(int(channels)))
+
+
 def actquant_perchannel(x, out=None, ws=None, n_bits=8):
     """x: [..., C] channels-last; per-channel dynamic quant-dequant (8 bit = the reference's hard-wired width)."""
     Cc = x.shape[-1]
@@ -613,6 +618,36 @@ def uaq_width_scan(w_rows, widths, delta=None, zp=None):
     L.check(L.lib().rdo_uaq_width_scan(_ptr(w_rows), rows, inner, (C.c_int32 * K)(*widths), K, _ptr(delta), _ptr(zp), _ptr(out_d), _ptr(out_z),
                                        _ptr64(err), _ptr64(energy), _ptr64(ws), _stream()), "rdo_uaq_width_scan")
     return out_d, out_z, err, energy
+
+
+def actquant_width_scan(x, rng, widths):
+    """What ONE per-channel grid costs an activation at several widths, in one read of the tensor (rdo_actquant_width_scan,
+    include/rdo_ptq_actbits.h): x contiguous fp32 [..., C] channels-last, rng fp32 [2C] = lo | hi on x's device, widths: 1 .. 8 distinct
+    whole numbers in 2 .. 16.  -> (err fp32 [C, K] = sum (x - Q_k(x))^2 with Q_k the expression of `actquant_static` on rng at n_bits =
+    widths[k]; energy fp32 [C] = sum x^2), both WRITTEN by the call (a caller that adds batches does so itself, in float64).  With rng =
+    the tensor's own per-channel min | max, Q_k is `actquant_perchannel` at that width too.  fp32 sums in a fixed order: the same input
+    gives the same bits.  Everything is checked on the host before a pointer is taken."""
+    what = "actquant_width_scan"
+    A.tensor(what, "x", x, contiguous=True)
+    if x.dim() < 1:
+        raise ValueError(f"{what}: x must be [..., C], got a scalar")
+    Cc = int(x.shape[-1])
+    npix = x.numel() // Cc
+    A.tensor(what, "rng", rng, shape=(2 * Cc,), contiguous=True, device=x.device, oneshot=True)
+    widths = width_list(what, widths, L.ACT_WIDTH_SCAN_MAX_BITS)
+    K = len(widths)
+    if npix > 0x7fffffff:
+        raise ValueError(f"{what}: {npix} pixels are beyond 32-bit pixel counts")
+    if Cc * (L.ACT_WIDTH_SCAN_MAX_K + 1) > 0x7fffffff:
+        raise ValueError(f"{what}: {Cc} channels are too many for 32-bit entry indices")
+    if not x.is_cuda:
+        raise ValueError(f"{what}: x is on {x.device}; there is no CPU path")
+    ws = _workspace(what, x.device, int(L.lib().rdo_actquant_width_scan_workspace(Cc, K)), torch.float32, Cc, K)
+    err = torch.empty(Cc, K, device=x.device, dtype=torch.float32)
+    energy = torch.empty(Cc, device=x.device, dtype=torch.float32)
+    L.check(L.lib().rdo_actquant_width_scan(_ptr(x), npix, Cc, _ptr(rng), (C.c_int32 * K)(*widths), K, _ptr(err), _ptr(energy), _ptr(ws),
+                                            _stream()), "rdo_actquant_width_scan")
+    return err, energy
 
 
 def pack_row_words(inner, bits):

@@ -535,5 +535,240 @@ def allocate_bits(report, budget_bits=None, avg_bits=None, fixed=None) -> dict:
             "cost": cost, "budget_bits": budget, "steps": steps}
 
 
+def act_modules(unit):
+    """(name inside the unit, module) of every QuantModule / BaseQuantBlock of a unit, the unit itself included ('' is its name): the
+    holders of the unit's activation quantisers, in module order"""
+    return [(mn, m) for mn, m in unit.named_modules() if isinstance(m, (QuantModule, BaseQuantBlock))]
+
+
+def act_applied(m):
+    """does a forward with act_quant=True apply this module's activation quantiser?"""
+    return bool(m.trained) and not getattr(m, "disable_act_quant", False)
+
+
+def _distinct(quantisers):
+    """de-duplicated by identity, in order"""
+    seen, out = set(), []
+    for q in quantisers:
+        if id(q) not in seen:
+            seen.add(id(q))
+            out.append(q)
+    return out
+
+
+def _sqnr_db(energy, err):
+    return torch.where(err == 0, torch.full_like(err, float("inf")), 10.0 * torch.log10(energy / err))
+
+
+def _reduce_scans(scans):
+    """all-reduce (SUM) the closed scan sums in place, in the fixed order of the list: scans = [[(site name, {err, energy, n})]] of every
+    state; the counts travel as float64 (whole numbers far below 2^53).  Nothing to do for one rank."""
+    from . import dp
+    if dp.world()[1] <= 1:
+        return
+    rows = [st for state in scans for _, st in state]
+    if not rows:
+        return
+    dev = rows[0]["err"].device
+    flat = torch.cat([t for st in rows for t in (st["err"].reshape(-1), st["energy"], torch.tensor([st["n"]], dtype=torch.float64, device=dev))])
+    dp.reduce_act_stats(sums=[flat])
+    off = 0
+    for st in rows:
+        for f in ("err", "energy"):
+            k = st[f].numel()
+            st[f].copy_(flat[off:off + k].reshape(st[f].shape))
+            off += k
+        st["n"] = int(flat[off])
+        off += 1
+
+
+def _close_scans(named):
+    """close the scan of every (name, quantiser) -> [(site name, sums)] in order; site names follow `QuantModel.act_ranges`"""
+    out = []
+    for name, q in named:
+        sums = q.act_scan_close()
+        for site in sorted(sums):
+            out.append((name if site == 0 else f"{name}#{site}", sums[site]))
+    return out
+
+
+def act_width_report(qnn, images, widths=(4, 6, 8), batch=8) -> "OrderedDict":
+    """The one-pass screening table of activation widths: what the grid of every applied activation quantiser costs the values it sees, at
+    each of `widths`, measured on `images` (the rules of `rd_report` for `images` and `batch`) under torch.no_grad().  The model runs ONCE
+    over the images in qnn.set_quant_state(True, True) -- `rd_report`'s 'all' state with act_quant=True: `trained`, `disable_act_quant`
+    and the widths as they stand -- with a width scan open on every applied quantiser (`UniformAffineQuantizer.act_scan`,
+    `ops.actquant_width_scan`: one read of each tensor for all K widths, where K passes of the scoring kernel would read it K times).
+    What flows downstream is the model's own quantised activation at its own width; the scanned grid is the site's frozen range (static)
+    or the tensor's own min | max (dynamic).
+    -> OrderedDict:
+      'sites'   site name (those of `QuantModel.act_ranges`: 'name', 'name#1') -> {unit (None outside `units()`), mode, n_bits (current),
+                channels, n (values seen per channel), err float64 [K, C] = sum (x - Q_k(x))^2, energy float64 [C] = sum x^2, sqnr_db
+                float64 [K, C] = 10 log10(energy / err) (inf at zero error), total {err float64 [K], energy, sqnr_db float64 [K]}: the same
+                over the summed channels}, on the CPU
+      'widths' (list), 'n' (images), 'batch' (the batch used: 1 when an applied quantiser is on a dynamic grid)
+    Frozen ranges are used as they stand at every width: a 'hist_mse' / 'auto' range was chosen for the width it was calibrated at.
+    State: the quant-state flags are recorded first and restored in a `finally`, where the scans are closed too; nothing else is written.
+    Data parallel: as `rd_report`, the scan sums joining a float64 all-reduce in a fixed order.
+    Raises ValueError before any GPU work for what `rd_report` refuses of images and batch and `ops.width_list` of widths."""
+    from hipops import ops
+    from .quantizer import MAX_BITS
+    what = "act_width_report"
+    _rd_report_args(qnn, images, 0.01, True, batch, None, what=what)
+    widths = ops.width_list(what, widths, MAX_BITS)
+    unit_of = {id(m): name for name, u in qnn.units().items() for _, m in act_modules(u)}
+    named, meta, seen = [], {}, set()
+    for name, m in qnn.named_modules():
+        if isinstance(m, (QuantModule, BaseQuantBlock)) and act_applied(m) and id(m.act_quantizer) not in seen:
+            seen.add(id(m.act_quantizer))
+            named.append((f"{name}.act_quantizer", m.act_quantizer))
+            meta[f"{name}.act_quantizer"] = (unit_of.get(id(m)), m.act_quantizer)
+    bs = 1 if _dynamic_grids(qnn) else batch
+    run = _StateRunner(qnn, images, 0.01, bs, what)
+    try:
+        with quant_state(qnn):
+            qnn.set_quant_state(True, True)
+            for _, q in named:
+                q.act_scan(widths)
+            with torch.no_grad():
+                for i in range(0, run.mine.shape[0], bs):
+                    qnn(run.mine[i:i + bs].to(run.device).contiguous())
+    finally:
+        scans = _close_scans(named)
+    _reduce_scans([scans])
+    rep = OrderedDict()
+    rep["sites"] = OrderedDict()
+    for site, st in scans:
+        unit, q = meta[site.split("#")[0]]
+        err, energy = st["err"].cpu(), st["energy"].cpu()
+        rep["sites"][site] = {"unit": unit, "mode": getattr(q, "act_mode", "dynamic"), "n_bits": int(getattr(q, "dynamic_bits", 8)),
+                              "channels": int(energy.numel()), "n": int(st["n"]), "err": err, "energy": energy,
+                              "sqnr_db": _sqnr_db(energy.unsqueeze(0), err),
+                              "total": {"err": err.sum(1), "energy": float(energy.sum()), "sqnr_db": _sqnr_db(energy.sum(), err.sum(1))}}
+    rep["widths"], rep["n"], rep["batch"] = list(widths), run.n, bs
+    return rep
+
+
+_MISSING = object()
+
+
+def act_bit_report(qnn, images, widths=(4, 6, 8), lmbda=0.01, weight_quant=False, batch=8, units=None) -> "OrderedDict":
+    """What each reconstruction unit costs in rate and distortion at each of several ACTIVATION widths, measured on `images` like
+    `rd_report` (its rules for `images`, `lmbda`, `batch` and `units`) under torch.no_grad(), on a calibrated model: the sibling of
+    `bit_report`.  The states, all over the same images:
+      'fp'                    qnn.set_quant_state(False, False): the 'fp' state of `rd_report`
+      one per (unit, width)   qnn.set_quant_state(False, False); set_quant_state(weight_quant, True) on the unit and on every
+                              QuantModule / BaseQuantBlock in it (what `QuantModel.set_quant_state` does on the whole model: the
+                              block wrappers nested in a Swin unit, its window attentions, switch with it, so both of their sites
+                              are measured), with every activation quantiser of the unit (the `act_quantizer` of each of these
+                              modules, de-duplicated by identity) temporarily at dynamic_bits = b and the applied ones scanning at
+                              [b]: in `units()` order, the widths in the order given
+    -> OrderedDict:
+      'fp'        the row of `rd_report`'s 'fp'
+      'units'     name -> width -> row: the keys of an `rd_report` unit row (bits, bits_total, sse, bpp, mse, psnr_db, loss, d_bits, d_bpp,
+                  d_mse, d_psnr_db, d_loss), and size_bits = b x the unit's elements, act_err = the sum over the unit's sites and
+                  channels of sum (x - Q_b(x))^2 in float64, act_sqnr_db = 10 log10(sum energy / sum err) in float64 (inf at zero error)
+      'elements'  name -> the activation values the unit quantises per image, counted from the calls (a whole number)
+      'skipped'   name -> why a unit has no row: none of its quantisers is applied (nothing trained, or all disabled).  Only with
+                  units=None; such a unit is refused when it is named
+      'widths' (list), 'n', 'pixels', 'lmbda', 'weight_quant', 'batch' (the batch used)
+    Frozen ranges are used as they stand at every width: a 'hist_mse' / 'auto' range was chosen for the width it was calibrated at, and is
+    not selected again (re-selection per width is out of scope).  A dynamic grid follows its tensor at every width.
+    Batch: 1 whatever `batch` says when an applied quantiser of a chosen unit is on a dynamic grid (the batch-1 rule of `rd_report`).
+    State: dynamic_bits and act_stats of every activation quantiser of the chosen units and every module's use_weight_quant |
+    use_act_quant pair are recorded first and put back in a `finally`, where open scans are closed; ranges, alpha, delta and zero points
+    are not written.
+    Data parallel: as `rd_report`, the scan sums joining the float64 all-reduce in a fixed order (state by state, site by site).
+    Cost: len(units) * len(widths) + 1 passes over `images`.
+    Raises ValueError before any GPU work for what `rd_report` refuses, for weight_quant not a bool, for widths that are not a non-empty
+    sequence of at most 8 distinct whole numbers in 2 .. MAX_BITS, and for a named unit in which no quantiser is applied."""
+    from hipops import ops
+    from .quantizer import MAX_BITS
+    what = "act_bit_report"
+    chosen = _rd_report_args(qnn, images, lmbda, True, batch, units, what=what)
+    if not isinstance(weight_quant, bool):
+        raise ValueError(f"{what}: weight_quant must be True or False, got {weight_quant!r}")
+    widths = ops.width_list(what, widths, MAX_BITS)
+    every, applied, skipped = OrderedDict(), OrderedDict(), OrderedDict()
+    for name, u in chosen:
+        ms = act_modules(u)
+        on, seen = [], set()
+        for mn, m in ms:
+            if act_applied(m) and id(m.act_quantizer) not in seen:
+                seen.add(id(m.act_quantizer))
+                on.append((f"{mn}.act_quantizer" if mn else "act_quantizer", m.act_quantizer))
+        if not on:
+            why = "no activation quantiser of the unit is applied (nothing trained, or all disabled)"
+            if units is not None:
+                raise ValueError(f"{what}: unit {name!r}: {why}")
+            skipped[name] = why
+            continue
+        every[name], applied[name] = _distinct(m.act_quantizer for _, m in ms), on
+    chosen = [(name, u) for name, u in chosen if name in every]
+    dynamic = any(getattr(q, "act_mode", "dynamic") != "static" for qs in applied.values() for _, q in qs)
+    bs = 1 if dynamic else batch
+    run = _StateRunner(qnn, images, lmbda, bs, what)
+    held = [(q, q.__dict__.get("dynamic_bits", _MISSING), q.__dict__.get("act_stats", _MISSING))
+            for q in _distinct(q for qs in every.values() for q in qs)]
+    states, scans = [], []
+    try:
+        with quant_state(qnn):
+            qnn.set_quant_state(False, False)
+            states.append(run.measure())
+            for name, u in chosen:
+                for b in widths:
+                    qnn.set_quant_state(False, False)
+                    for _, m in act_modules(u):
+                        m.set_quant_state(weight_quant, True)
+                    for q in every[name]:
+                        q.dynamic_bits = b
+                    for _, q in applied[name]:
+                        q.act_scan([b])
+                    states.append(run.measure())
+                    scans.append(_close_scans(applied[name]))
+    finally:
+        for q, bits, stats in held:
+            q.act_scan_close()
+            for f, v in (("dynamic_bits", bits), ("act_stats", stats)):
+                if v is _MISSING:
+                    q.__dict__.pop(f, None)
+                else:
+                    setattr(q, f, v)
+    run.reduce(states)
+    _reduce_scans(scans)
+    fp = run.row(states[0])
+    rep = OrderedDict()
+    rep["fp"], rep["units"], rep["elements"], rep["skipped"] = fp, OrderedDict(), OrderedDict(), skipped
+    it, sc = iter(states[1:]), iter(scans)
+    for name, _ in chosen:
+        rep["units"][name] = OrderedDict()
+        for b in widths:
+            r = run.against(run.row(next(it)), fp)
+            sites = next(sc)
+            values = sum(int(st["n"]) * int(st["energy"].numel()) for _, st in sites)
+            if values % run.n or rep["elements"].setdefault(name, values // run.n) != values // run.n:
+                raise RuntimeError(f"{what}: unit {name!r} quantised {values} values over {run.n} images at width {b}: not the same whole "
+                                   "number per image")
+            e = float(sum(float(st["err"].sum()) for _, st in sites))
+            energy = float(sum(float(st["energy"].sum()) for _, st in sites))
+            r["size_bits"], r["act_err"] = b * rep["elements"][name], e
+            r["act_sqnr_db"] = float("inf") if e == 0 else 10.0 * math.log10(energy / e)
+            rep["units"][name][b] = r
+    rep["widths"], rep["n"], rep["pixels"], rep["lmbda"] = list(widths), run.n, run.pixels, float(lmbda)
+    rep["weight_quant"], rep["batch"] = weight_quant, bs
+    return rep
+
+
+def allocate_act_bits(report, budget_bits=None, avg_bits=None, fixed=None) -> dict:
+    """Choose one activation width per unit from an `act_bit_report` table under a size budget: `allocate_bits` on the table with the
+    units' elements (activation values per image) in the place of the weight counts -- its rule, its guarantees and its result, with
+    sizes in activation bits per image and `avg_bits` in bits per quantised activation value.  What it returns under 'bits' is what
+    `QuantModel.set_act_bits` takes."""
+    try:
+        table = {"units": report["units"], "weights": report["elements"]}
+    except (KeyError, TypeError, IndexError) as e:
+        raise ValueError(f"allocate_act_bits: report must be an `act_bit_report` table ('units', 'elements'): {e!r}")
+    return allocate_bits(table, budget_bits=budget_bits, avg_bits=avg_bits, fixed=fixed)
+
+
 def dequantize(entry) -> torch.Tensor:
     return (entry["levels"].to(torch.float32) - entry["zero_point"]) * entry["delta"]

@@ -188,6 +188,65 @@ class QuantModel(nn.Module):
         out["total"] = {"weights": tw, "size_bits": ts, "avg_bits": ts / tw if tw else 0.0}
         return out
 
+    def act_width_report(self, images, widths=(4, 6, 8), batch=8):
+        """The one-pass screening table of activation widths: per site, the error of its grid at each of several widths, from one pass
+        of the quantised model over `images` (`export.act_width_report`)."""
+        from .export import act_width_report
+        return act_width_report(self, images, widths=widths, batch=batch)
+
+    def act_bit_report(self, images, widths=(4, 6, 8), lmbda=0.01, weight_quant=False, batch=8, units=None):
+        """What every unit costs in rate and distortion at each of several activation widths when its activation quantisers alone are
+        on, with each width's size and activation error: the table `export.allocate_act_bits` chooses from (`export.act_bit_report`).
+        len(units) * len(widths) + 1 passes over `images`; taken on a calibrated model."""
+        from .export import act_bit_report
+        return act_bit_report(self, images, widths=widths, lmbda=lmbda, weight_quant=weight_quant, batch=batch, units=units)
+
+    def set_act_bits(self, bits):
+        """Give the activation grids of the units their widths: `bits` is one whole number in 2 .. MAX_BITS for every unit, or a mapping
+        unit name -> width (what `export.allocate_act_bits(...)['bits']` is; units it does not name keep theirs).  Names and widths are
+        validated before anything is written; then every activation quantiser of each named unit (the `act_quantizer` of each
+        QuantModule / BaseQuantBlock in it) gets `dynamic_bits = b`, and its `act_stats` (measured at the old width) are dropped.
+        Frozen ranges stay as they are.  Allowed before and after calibration: an activation width carries no rounding state.  Weight
+        quantisers are not touched."""
+        from collections.abc import Mapping
+        from numbers import Integral
+        from .export import act_modules
+        from .quantizer import MAX_BITS
+        what = "set_act_bits"
+        known = self.units()
+
+        def whole(b):
+            return not isinstance(b, bool) and isinstance(b, Integral) and 2 <= b <= MAX_BITS
+        if isinstance(bits, Mapping):
+            unknown = [n for n in bits if n not in known]
+            if unknown:
+                raise ValueError(f"{what}: unknown unit name(s) {unknown}; QuantModel.units() has {list(known)}")
+            plan = [(n, bits[n]) for n in known if n in bits]
+        elif whole(bits):
+            plan = [(n, bits) for n in known]
+        else:
+            raise ValueError(f"{what}: bits must be a whole number in 2 .. {MAX_BITS} or a mapping unit name -> width, got {bits!r}")
+        for n, b in plan:
+            if not whole(b):
+                raise ValueError(f"{what}: the width of unit {n!r} must be a whole number in 2 .. {MAX_BITS}, got {b!r}")
+        for n, b in plan:
+            for _, m in act_modules(known[n]):
+                m.act_quantizer.dynamic_bits = int(b)
+                m.act_quantizer.act_stats = {}
+
+    def act_bits(self):
+        """OrderedDict unit name -> {'bits': OrderedDict module name (inside the unit; '' for the unit itself) -> dynamic_bits of its
+        activation quantiser, 'applied': the module names whose quantiser a forward with act_quant=True applies (trained, not
+        disabled)}."""
+        from collections import OrderedDict
+        from .export import act_applied, act_modules
+        out = OrderedDict()
+        for name, u in self.units().items():
+            ms = act_modules(u)
+            out[name] = {"bits": OrderedDict((mn, int(getattr(m.act_quantizer, "dynamic_bits", 8))) for mn, m in ms),
+                         "applied": [mn for mn, m in ms if act_applied(m)]}
+        return out
+
     def save_packed(self, path):
         """Write the packed checkpoint of this model: every weight's integer levels packed at their own width, the grids, the biases
         and the frozen activation ranges -- no fp32 weight (`packed.save_packed`).  -> the sizes written."""

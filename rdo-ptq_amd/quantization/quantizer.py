@@ -180,6 +180,10 @@ class UniformAffineQuantizer(nn.Module):
         self.act_score_n = {}
         self.act_score_kind = "auto"
         self.act_stats = {}
+        # the width scan (`act_scan`): the widths being scanned (None: no scan is open) and site -> {err float64 [K, C], energy float64
+        # [C], n: values seen per channel (on the host)}.  Absent on models pickled before they existed: read with getattr
+        self.act_scan_widths = None
+        self.act_scan_sums = {}
 
     def _apply(self, fn, *args, **kwargs):
         super()._apply(fn, *args, **kwargs)
@@ -368,6 +372,51 @@ class UniformAffineQuantizer(nn.Module):
     def act_frozen(self):
         return getattr(self, "act_mode", "dynamic") == "static" and getattr(self, "act_phase", "idle") == "frozen"
 
+    def act_scan(self, widths):
+        """Open a width scan: every application with act=True then adds, per site, what the grid it quantises on costs the values it
+        sees at each of `widths` (`ops.actquant_width_scan`: the squared error of the static expression on that grid at every width, and
+        the energy) into float64 device sums.  The grid is the site's frozen range in static mode and the call's own per-channel min | max
+        in dynamic mode (what `ops.actquant_perchannel` quantises on).  What the quantiser returns is not changed.  RuntimeError on a
+        static quantiser that is not frozen and while another phase (observe, search, hist, score, learn) is active."""
+        widths = ops.width_list("act_scan", widths, MAX_BITS)
+        phase = getattr(self, "act_phase", "idle")
+        if getattr(self, "act_mode", "dynamic") == "static":
+            if phase != "frozen":
+                raise RuntimeError(f"act_scan: the static quantiser is not frozen (phase {phase!r}): calibrate it first")
+        elif phase not in ("idle", "frozen"):
+            raise RuntimeError(f"act_scan: the phase {phase!r} is active")
+        self.act_scan_widths, self.act_scan_sums = widths, {}
+
+    def act_scan_close(self):
+        """Close the scan -> site -> {'err': float64 [K, C], 'energy': float64 [C], 'n': values seen per channel}, on the device; the sums
+        are cleared.  A site that was not applied has no entry."""
+        sums = getattr(self, "act_scan_sums", None) or {}
+        self.act_scan_widths, self.act_scan_sums = None, {}
+        return sums
+
+    def _act_scan_one(self, xr, rng, site):
+        """one call's scan into the site's float64 sums"""
+        err, energy = ops.actquant_width_scan(xr, rng, self.act_scan_widths)
+        st = self.act_scan_sums.get(site)
+        if st is None:
+            st = self.act_scan_sums[site] = {"err": torch.zeros(err.shape[1], err.shape[0], dtype=torch.float64, device=err.device),
+                                             "energy": torch.zeros(energy.shape[0], dtype=torch.float64, device=err.device), "n": 0}
+        if st["energy"].numel() != energy.numel():
+            raise ValueError(f"act_scan (site {site}): scanned {st['energy'].numel()} channels before, got {energy.numel()}")
+        st["err"] += err.t().double()
+        st["energy"] += energy.double()
+        st["n"] += xr.numel() // xr.shape[-1]
+
+    def _act_dynamic_scan(self, x, site, channels_last):
+        """the dynamic quantiser with a scan open: the same kernels on the same operands as `ActQuantizer` (the same bits out), with the
+        min | max they leave in the workspace as the scanned grid"""
+        xr, back = _act_rows(x, channels_last)
+        Cc = xr.shape[-1]
+        ws = torch.empty(ops.actquant_workspace(Cc), device=xr.device, dtype=torch.float32)
+        out = ops.actquant_perchannel(xr, ws=ws, n_bits=getattr(self, "dynamic_bits", 8))
+        self._act_scan_one(xr, ws[:2 * Cc], site)
+        return back(out)
+
     def _act_static(self, x, site, channels_last):
         xr, back = _act_rows(x, channels_last)
         bits, Cc, phase = getattr(self, "dynamic_bits", 8), xr.shape[-1], self.act_phase
@@ -387,6 +436,8 @@ class UniformAffineQuantizer(nn.Module):
             self._act_count(xr, rng, site)
         if phase == "score":
             self._act_score_one(xr, site, bits)
+        if getattr(self, "act_scan_widths", None):
+            self._act_scan_one(xr, rng.detach(), site)
         if torch.is_grad_enabled() and (phase == "learn" or (phase == "frozen" and getattr(self, "act_ste", False) and x.requires_grad)):
             from hipops.autograd import ActQuantStaticFn
             return ActQuantStaticFn.apply(x, rng, bits, channels_last)
@@ -460,6 +511,8 @@ class UniformAffineQuantizer(nn.Module):
         if act:
             if getattr(self, "act_mode", "dynamic") == "static":
                 return self._act_static(x, site, channels_last)
+            if getattr(self, "act_scan_widths", None):
+                return self._act_dynamic_scan(x, site, channels_last)
             if channels_last:
                 return ops.actquant_perchannel(x.detach().contiguous(), n_bits=getattr(self, "dynamic_bits", 8))
             return ActQuantizer(x, getattr(self, "dynamic_bits", 8))
