@@ -143,7 +143,7 @@ def load_packed(qnn, path) -> dict:
     and the weight pack is dropped.  Blocks get their `trained`, activation quantisers their `act_mode` and `dynamic_bits`, and frozen
     static ones their ranges (phase "frozen").  -> the header's totals."""
     from hipops import ops
-    from .export import is_trained
+    from .widths import is_trained
     what = "load_packed"
     try:
         header, arrays = packed_io.read_packed(path)

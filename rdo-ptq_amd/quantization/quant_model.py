@@ -7,6 +7,7 @@ from lic import EntropyBottleneck
 from .fold_bn import search_fold_and_remove_bn
 from .quant_block import BaseQuantBlock, specials
 from .quant_layer import GDN_TYPES, QuantModule, StraightThrough
+from .widths import act_applied, act_modules, is_trained, weighted_modules, width_plan
 
 _WRAPPABLE = (nn.Conv2d, nn.ConvTranspose2d, nn.Linear, nn.LayerNorm, nn.PixelShuffle) + GDN_TYPES
 _FUSABLE_ACT = (nn.LeakyReLU, nn.GELU, nn.ReLU, nn.ReLU6)
@@ -78,19 +79,19 @@ class QuantModel(nn.Module):
     def act_report(self):
         """OrderedDict name -> the measured statistics of every frozen static range that was recorded (args.act_report):
         `export.activation_report`, under the site names of `act_ranges`."""
-        from .export import activation_report
+        from .reports import activation_report
         return activation_report(self)
 
     def unit_report(self):
         """OrderedDict unit name -> the measured output error of every calibrated unit that recorded it (args.unit_report): per output
         channel, learned rounding against round-to-nearest (`export.unit_report`)."""
-        from .export import unit_report
+        from .reports import unit_report
         return unit_report(self)
 
     def bias_report(self):
         """OrderedDict unit name -> what the bias correction of every unit that ran it did (args.bias_correct): the corrected layers'
         shifts and the unit's output error before and after (`export.bias_report`)."""
-        from .export import bias_report
+        from .reports import bias_report
         return bias_report(self)
 
     def clear_bias_correction(self):
@@ -124,14 +125,14 @@ class QuantModel(nn.Module):
     def rd_report(self, images, lmbda=0.01, act_quant=False, batch=8, units=None):
         """What every unit costs in rate and distortion when it alone is quantised, next to the full-precision and the fully
         quantised model, measured on `images` (`export.rd_report`)."""
-        from .export import rd_report
+        from .reports import rd_report
         return rd_report(self, images, lmbda=lmbda, act_quant=act_quant, batch=batch, units=units)
 
     def bit_report(self, images, widths=(4, 6, 8), lmbda=0.01, batch=8, units=None):
         """What every unit costs in rate and distortion at each of several weight widths when it alone is quantised (round to nearest,
         weights only), with each width's size and weight error: the table `export.allocate_bits` chooses from (`export.bit_report`).
         len(units) * len(widths) + 1 passes over `images`; taken before calibration."""
-        from .export import bit_report
+        from .reports import bit_report
         return bit_report(self, images, widths=widths, lmbda=lmbda, batch=batch, units=units)
 
     def set_weight_bits(self, bits):
@@ -140,27 +141,9 @@ class QuantModel(nn.Module):
         are validated and a unit that holds a trained module is refused (ValueError) before anything is written; then every weighted
         QuantModule of each named unit gets `bitwidth_refactor(b)`, `inited = False` (its scale is initialised at the new width on its
         next use) and `drop_weight_pack()`.  Activation quantisers are not touched."""
-        from collections.abc import Mapping
-        from numbers import Integral
-        from .export import is_trained, weighted_modules
-        from .quantizer import MAX_BITS
-        what = "set_weight_bits"
-        known = self.units()
-
-        def whole(b):
-            return not isinstance(b, bool) and isinstance(b, Integral) and 2 <= b <= MAX_BITS
-        if isinstance(bits, Mapping):
-            unknown = [n for n in bits if n not in known]
-            if unknown:
-                raise ValueError(f"{what}: unknown unit name(s) {unknown}; QuantModel.units() has {list(known)}")
-            plan = [(n, bits[n]) for n in known if n in bits]
-        elif whole(bits):
-            plan = [(n, bits) for n in known]
-        else:
-            raise ValueError(f"{what}: bits must be a whole number in 2 .. {MAX_BITS} or a mapping unit name -> width, got {bits!r}")
-        for n, b in plan:
-            if not whole(b):
-                raise ValueError(f"{what}: the width of unit {n!r} must be a whole number in 2 .. {MAX_BITS}, got {b!r}")
+        what, known = "set_weight_bits", self.units()
+        plan = width_plan(what, known, bits)
+        for n, _ in plan:
             if any(is_trained(m) for m in weighted_modules(known[n])):
                 raise ValueError(f"{what}: unit {n!r} holds a trained module: its rounding belongs to the width it was calibrated at")
         for n, b in plan:
@@ -191,14 +174,14 @@ class QuantModel(nn.Module):
     def act_width_report(self, images, widths=(4, 6, 8), batch=8):
         """The one-pass screening table of activation widths: per site, the error of its grid at each of several widths, from one pass
         of the quantised model over `images` (`export.act_width_report`)."""
-        from .export import act_width_report
+        from .reports import act_width_report
         return act_width_report(self, images, widths=widths, batch=batch)
 
     def act_bit_report(self, images, widths=(4, 6, 8), lmbda=0.01, weight_quant=False, batch=8, units=None):
         """What every unit costs in rate and distortion at each of several activation widths when its activation quantisers alone are
         on, with each width's size and activation error: the table `export.allocate_act_bits` chooses from (`export.act_bit_report`).
         len(units) * len(widths) + 1 passes over `images`; taken on a calibrated model."""
-        from .export import act_bit_report
+        from .reports import act_bit_report
         return act_bit_report(self, images, widths=widths, lmbda=lmbda, weight_quant=weight_quant, batch=batch, units=units)
 
     def set_act_bits(self, bits):
@@ -208,28 +191,8 @@ class QuantModel(nn.Module):
         QuantModule / BaseQuantBlock in it) gets `dynamic_bits = b`, and its `act_stats` (measured at the old width) are dropped.
         Frozen ranges stay as they are.  Allowed before and after calibration: an activation width carries no rounding state.  Weight
         quantisers are not touched."""
-        from collections.abc import Mapping
-        from numbers import Integral
-        from .export import act_modules
-        from .quantizer import MAX_BITS
-        what = "set_act_bits"
         known = self.units()
-
-        def whole(b):
-            return not isinstance(b, bool) and isinstance(b, Integral) and 2 <= b <= MAX_BITS
-        if isinstance(bits, Mapping):
-            unknown = [n for n in bits if n not in known]
-            if unknown:
-                raise ValueError(f"{what}: unknown unit name(s) {unknown}; QuantModel.units() has {list(known)}")
-            plan = [(n, bits[n]) for n in known if n in bits]
-        elif whole(bits):
-            plan = [(n, bits) for n in known]
-        else:
-            raise ValueError(f"{what}: bits must be a whole number in 2 .. {MAX_BITS} or a mapping unit name -> width, got {bits!r}")
-        for n, b in plan:
-            if not whole(b):
-                raise ValueError(f"{what}: the width of unit {n!r} must be a whole number in 2 .. {MAX_BITS}, got {b!r}")
-        for n, b in plan:
+        for n, b in width_plan("set_act_bits", known, bits):
             for _, m in act_modules(known[n]):
                 m.act_quantizer.dynamic_bits = int(b)
                 m.act_quantizer.act_stats = {}
@@ -239,7 +202,6 @@ class QuantModel(nn.Module):
         activation quantiser, 'applied': the module names whose quantiser a forward with act_quant=True applies (trained, not
         disabled)}."""
         from collections import OrderedDict
-        from .export import act_applied, act_modules
         out = OrderedDict()
         for name, u in self.units().items():
             ms = act_modules(u)

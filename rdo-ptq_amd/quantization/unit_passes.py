@@ -14,7 +14,7 @@ from hipops import ops
 from .quant_block import BaseQuantBlock, QuantRSTB
 from .quant_layer import QuantModule, _nhwc, _sq
 from .quantizer import AdaRoundQuantizer, to_rows
-from .utils import quant_state
+from .utils import distinct, quant_state
 
 BIAS_CORRECT_MODES = ("weight", "output")
 _MOMENTS = ("shift", "err", "energy")          # the rows of `ops.pair_moments`
@@ -83,8 +83,7 @@ def _rank_sums(sums, counts, device, dtype=torch.int64):
 def _act_quantizers(mods, frozen=False):
     """the distinct activation quantisers of the QuantModules and block wrappers `mods` (`quant_state.mods`: module order); `frozen`:
     those with frozen ranges only"""
-    quants = {id(m.act_quantizer): m.act_quantizer for m in mods}
-    return [q for q in quants.values() if not frozen or q.act_frozen()]
+    return [q for q in distinct(m.act_quantizer for m in mods) if not frozen or q.act_frozen()]
 
 
 def _sites(quants, name):

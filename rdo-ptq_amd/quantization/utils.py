@@ -2,8 +2,11 @@
 
 `save_inp_oup_data` runs the (partially quantised) model up to a target unit with a forward hook that captures the unit's
 input/output and aborts the pass (utils.py:92-139, 175-258).  Differences from the reference, none of which change values:
-tensors never bounce through host memory, and the per-sample `print` is dropped."""
+tensors never bounce through host memory, and the per-sample `print` is dropped.
+
+Not in the reference: `quant_state` and `held_attrs`, the two context managers that put back what a pass or a report switched."""
 import time
+from contextlib import contextmanager
 from typing import Union
 
 import torch
@@ -52,6 +55,36 @@ class quant_state:
     def __exit__(self, *exc):
         for m, (w, a) in zip(self.mods, self.held):
             m.use_weight_quant, m.use_act_quant = w, a
+
+
+_MISSING = object()
+
+
+@contextmanager
+def held_attrs(objs, fields):
+    """Context manager over the instance attributes `fields` of every object of `objs` (the quantiser fields a report switches: widths,
+    grids, `act_stats`): records what `vars(obj)` holds under each name and puts it back on the way out, whatever was raised and whatever
+    the block set, replaced or deleted in between -- the same object, not a copy; an attribute that was absent is deleted again.  The
+    one place of this package that restores quantiser attributes."""
+    held = [(o, f, vars(o).get(f, _MISSING)) for o in objs for f in fields]
+    try:
+        yield
+    finally:
+        for o, f, v in held:
+            if v is _MISSING:
+                vars(o).pop(f, None)
+            else:
+                setattr(o, f, v)
+
+
+def distinct(items, of=lambda item: item):
+    """the items whose `of(item)` has not been seen before (by identity), in the order first seen"""
+    seen, out = set(), []
+    for item in items:
+        if id(of(item)) not in seen:
+            seen.add(id(of(item)))
+            out.append(item)
+    return out
 
 
 class LinearTempDecay:

@@ -305,11 +305,49 @@ def test_quant_state_puts_back_what_it_found_whatever_the_block_did():
     assert flags() == before
 
 
+def test_held_attrs_puts_back_what_it_found_whatever_the_block_did():
+    """`utils.held_attrs` on two plain objects: a present attribute gets its identical object back, an absent one is absent again --
+    after a normal exit and after an exception, and when the block itself replaced, set or deleted the attribute"""
+    from quantization.utils import held_attrs
+
+    class Thing:
+        pass
+    a, b = Thing(), Thing()
+    grid, stats = [1.0, 2.0], {"n": 3}
+    a.delta, a.act_stats = grid, stats                                   # b has neither; `other` is not held
+    a.other = b.other = "kept"
+    fields = ("delta", "act_stats")
+
+    def check():
+        assert a.delta is grid and a.act_stats is stats and vars(a) == {"delta": grid, "act_stats": stats, "other": a.other}
+        assert vars(b) == {"other": b.other}
+    with held_attrs([a, b], fields):                                     # nothing touched
+        pass
+    check()
+    with held_attrs([a, b], fields):                                     # replaced by an equal copy; set where absent
+        a.delta, a.act_stats = list(grid), dict(stats)
+        b.delta, b.act_stats = [0.5], {}
+        a.other = b.other = "written"                                    # (a field that is not held stays as the block left it)
+    check()
+    assert a.other == "written"
+    with held_attrs([a, b], fields):                                     # deleted, and set then deleted
+        del a.delta, a.act_stats
+        b.delta = [0.5]
+        del b.delta
+    check()
+    with pytest.raises(KeyError, match="inside"):
+        with held_attrs([a, b], fields):
+            a.delta, b.act_stats = None, {}
+            del a.act_stats
+            raise KeyError("inside")
+    check()
+
+
 def test_product_still_never_imports_the_oracle():
     for base, _, files in os.walk(os.path.join(ROOT, "rdo-ptq_amd")):
         for f in files:
             if f.endswith(".py"):
                 txt = open(os.path.join(base, f)).read()
                 assert not re.search(r"^\s*(from|import)\s+oracle", txt, re.M), f"{f} imports the oracle"
-    for f in ("hipops/ops.py", "quantization/export.py", "quantization/quant_model.py"):
+    for f in ("hipops/ops.py", "quantization/export.py", "quantization/reports.py", "quantization/widths.py", "quantization/quant_model.py"):
         assert "oracle" not in open(os.path.join(ROOT, "rdo-ptq_amd", f)).read()
