@@ -228,6 +228,12 @@ _SIGS_ACTBITS = {
 EXPORTS_ACTBITS = tuple(_SIGS_ACTBITS)
 ACT_WIDTH_SCAN_MAX_K = 8  # RDO_ACT_WIDTH_SCAN_MAX_K, _MIN_BITS and _MAX_BITS of include/rdo_ptq_actbits.h
 ACT_WIDTH_SCAN_MIN_BITS, ACT_WIDTH_SCAN_MAX_BITS = 2, 16
+# include/rdo_ptq_attnq.h: the backward of the two products of the activation-quantised window attention (probabilities as given data)
+_SIGS_ATTNQ = {
+    "rdo_window_attention_pv_bwd": (C.c_int, [C.POINTER(AttnDesc), P, P, P, P, P, P]),
+    "rdo_window_attention_probs_bwd": (C.c_int, [C.POINTER(AttnDesc), P, P, P, P, P]),
+}
+EXPORTS_ATTNQ = tuple(_SIGS_ATTNQ)
 
 _lib = None
 
@@ -245,7 +251,8 @@ def lib():
         import torch  # noqa: F401
         h = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(_SIGS.items()) + list(_SIGS_GDN.items()) + list(_SIGS_BIAS.items()) + list(_SIGS_BITS.items())
-                                  + list(_SIGS_PACK.items()) + list(_SIGS_SUBPEL.items()) + list(_SIGS_ACTBITS.items())):
+                                  + list(_SIGS_PACK.items()) + list(_SIGS_SUBPEL.items()) + list(_SIGS_ACTBITS.items())
+                                  + list(_SIGS_ATTNQ.items())):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         _lib = h

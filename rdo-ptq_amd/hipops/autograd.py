@@ -224,6 +224,46 @@ class WindowAttentionFn(torch.autograd.Function):
         return ops.window_attention_bwd(ctx.desc, qc, bias, g.contiguous()).reshape(qc.shape), None, None
 
 
+class WindowAttentionProbsFn(torch.autograd.Function):
+    """The probabilities [windows, N, N, heads] of the window attention core, the first piece of the activation-quantised attention
+    (quant_block.QuantWindowAttention): rdo_window_attention_fwd without the P V product / rdo_window_attention_probs_bwd, which
+    differentiates the float32 probabilities the forward wrote (they stay alive until the backward; nothing is recomputed)."""
+
+    @staticmethod
+    def forward(ctx, qkv, desc, bias):
+        qc = qkv.contiguous()
+        N = desc.window * desc.window
+        probs = torch.empty((desc.B * (desc.H // desc.window) * (desc.W // desc.window), N, N, desc.heads), device=qc.device,
+                            dtype=torch.float32)
+        ops.window_attention(desc, qc, bias, probs=probs, compute_out=False)
+        ctx.desc = desc
+        ctx.save_for_backward(qc, probs)
+        return probs
+
+    @staticmethod
+    def backward(ctx, g):
+        qc, probs = ctx.saved_tensors
+        return ops.window_attention_probs_bwd(ctx.desc, qc, probs, g.contiguous()).reshape(qc.shape), None, None
+
+
+class WindowAttentionPVFn(torch.autograd.Function):
+    """out [B, H, W, C] = probs_q @ v from given (quantised) probabilities, the second piece: rdo_window_attention_pv /
+    rdo_window_attention_pv_bwd -> gradients for qkv (its v third; zeros in the others) and for probs_q."""
+
+    @staticmethod
+    def forward(ctx, qkv, probs_q, desc):
+        qc, pc = qkv.contiguous(), probs_q.contiguous()
+        ctx.desc = desc
+        ctx.save_for_backward(qc, pc)
+        return ops.window_attention_pv(desc, qc, pc)
+
+    @staticmethod
+    def backward(ctx, g):
+        qc, pc = ctx.saved_tensors
+        dprobs, dqkv = ops.window_attention_pv_bwd(ctx.desc, qc, pc, g.contiguous())
+        return dqkv.reshape(qc.shape), dprobs.reshape(pc.shape), None
+
+
 class GeluFn(torch.autograd.Function):
     """nn.GELU() (exact erf form): rdo_gelu_fwd / rdo_gelu_bwd."""
 

@@ -1235,6 +1235,38 @@ def window_attention_bwd(d, qkv, bias, dout, dqkv=None):
     return dqkv
 
 
+def window_attention_pv_bwd(d, qkv, probs_q, dout, dprobs=None, dqkv=None):
+    """Backward of `window_attention_pv` from the probabilities it was given -> (dprobs [windows, N, N, heads], dqkv [B, H, W, 3C] with
+    dV in its last third and zeros in the other two); every element of both is written."""
+    what = "window_attention_pv_bwd"
+    pixels, N, windows = _attn_geometry(what, d)
+    A.tensor(what, "qkv", qkv, numel=pixels * 3 * d.C)
+    A.tensor(what, "probs_q", probs_q, device=qkv.device, numel=windows * N * N * d.heads)
+    A.tensor(what, "dout", dout, device=qkv.device, numel=pixels * d.C)
+    A.tensor(what, "dprobs", dprobs, device=qkv.device, numel=probs_q.numel(), optional=True)
+    A.tensor(what, "dqkv", dqkv, device=qkv.device, numel=qkv.numel(), optional=True)
+    dprobs = torch.empty((windows, N, N, d.heads), device=qkv.device, dtype=torch.float32) if dprobs is None else dprobs
+    dqkv = torch.empty_like(qkv) if dqkv is None else dqkv
+    L.check(L.lib().rdo_window_attention_pv_bwd(C.byref(d), _ptr(qkv), _ptr(probs_q), _ptr(dout), _ptr(dprobs), _ptr(dqkv), _stream()),
+            "rdo_window_attention_pv_bwd")
+    return dprobs, dqkv
+
+
+def window_attention_probs_bwd(d, qkv, probs, dprobs, dqkv=None):
+    """Backward of the probabilities `window_attention(..., compute_out=False)` wrote, from those float32 values and their gradient ->
+    dqkv [B, H, W, 3C] with dQ | dK in its first two thirds and zeros in the last; every element is written."""
+    what = "window_attention_probs_bwd"
+    pixels, N, windows = _attn_geometry(what, d)
+    A.tensor(what, "qkv", qkv, numel=pixels * 3 * d.C)
+    A.tensor(what, "probs", probs, device=qkv.device, numel=windows * N * N * d.heads)
+    A.tensor(what, "dprobs", dprobs, device=qkv.device, numel=probs.numel())
+    A.tensor(what, "dqkv", dqkv, device=qkv.device, numel=qkv.numel(), optional=True)
+    dqkv = torch.empty_like(qkv) if dqkv is None else dqkv
+    L.check(L.lib().rdo_window_attention_probs_bwd(C.byref(d), _ptr(qkv), _ptr(probs), _ptr(dprobs), _ptr(dqkv), _stream()),
+            "rdo_window_attention_probs_bwd")
+    return dqkv
+
+
 def gelu(x, out=None):
     A.tensor("gelu", "x", x)
     A.tensor("gelu", "out", out, device=x.device, numel=x.numel(), optional=True)

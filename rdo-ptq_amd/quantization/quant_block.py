@@ -199,10 +199,22 @@ class QuantWindowAttention(BaseQuantBlock):
         bias = self.position_bias()
         if self.use_act_quant and self.trained:
             if _tracked(qkv):
-                # the activation-quantised attention below runs raw kernels (no grad_fn): under torch's tape (loss_mode='rd' behind a unit,
-                # a second calibration pass) the gradient through the attention path would be cut silently
-                raise NotImplementedError("QuantWindowAttention: a trained, activation-quantised attention cannot sit on torch's tape "
-                                          "(its quantised probabilities carry no gradient); run the R + lambda*D task loss with act_quant=False")
+                # under torch's tape (loss_mode='rd' behind a unit, a second calibration pass, `learn_act_ranges`) the raw launches below
+                # (no grad_fn) would cut the gradient through the attention path silently.  With STATIC ranges that themselves go on the
+                # tape (the "learn" phase, or frozen with `act_ste`: `ActQuantStaticFn`, straight-through round) the same two quantiser
+                # calls sit between the tape forms of the two products; both keep a [windows, N, N, heads] tensor until the backward
+                q = self.act_quantizer
+                phase = getattr(q, "act_phase", "idle")
+                if getattr(q, "act_mode", "dynamic") != "static" or not (phase == "learn" or (phase == "frozen" and getattr(q, "act_ste", False))):
+                    raise NotImplementedError("QuantWindowAttention: a trained, activation-quantised attention sits on torch's tape only "
+                                              "with static ranges that go on it themselves (act_mode='static', learning or frozen with "
+                                              "act_ste): a dynamic grid or a detached frozen one carries no gradient; run the "
+                                              "R + lambda*D task loss with act_quant=False or with static ranges")
+                from hipops.autograd import WindowAttentionProbsFn, WindowAttentionPVFn
+                probs = WindowAttentionProbsFn.apply(qkv.view(B, H, W, 3 * C), d, bias)
+                probs = q(probs, True, site=0, channels_last=True)
+                o = q(WindowAttentionPVFn.apply(qkv.view(B, H, W, 3 * C), probs, d).view(B, H * W, C), True, site=1)
+                return self.proj(o)
             n = window * window
             probs = torch.empty((B * (H // window) * (W // window), n, n, self.num_heads), device=qkv.device, dtype=torch.float32)
             ops.window_attention(d, qkv, bias, probs=probs, compute_out=False)

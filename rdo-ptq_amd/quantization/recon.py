@@ -15,8 +15,8 @@ from .engine import UnitEngine
 from .quant_block import BaseQuantBlock
 from .swin_engine import TapeEngine
 from .quant_layer import QuantModule, _nhwc
-from .unit_passes import (BIAS_CORRECT_MODES, _check_learn, _check_percentile, _is_rstb, calibrate_act_ranges, correct_unit_bias,
-                          learn_act_ranges, report_act_ranges, report_unit)
+from .unit_passes import (BIAS_CORRECT_MODES, SWIN_LEARN_REFUSAL, _check_learn, _check_percentile, _is_rstb, calibrate_act_ranges,
+                          correct_unit_bias, learn_act_ranges, report_act_ranges, report_unit)
 from .unit_passes import _TapCollector, _bias_rows, _nearest_alpha, _reduce_scores, _tap_call, _tap_layer  # noqa: F401  (importable from here as before)
 from .utils import LinearTempDecay, save_inp_oup_data, set_mode
 
@@ -149,7 +149,8 @@ def _act_args(args):
     args.act_range: how a static range is fixed, 'max' (default: min / max over the calibration set), 'l2' (each channel then shrinks
     to the best of ten candidates by squared error) or 'learned' (the 'l2' ranges are then trained on the unit's reconstruction error:
     `learn_act_ranges`, with args.act_iters steps, default 500, of size args.act_lr, default 1e-3, relative to a channel's observed
-    width) or 'percentile' (a second pass takes a 1024-bin histogram of every channel on its observed range; each end then gives up whole
+    width; a Swin (RSTB) unit only with args.act_learn_swin=True, default False, a bool) or 'percentile' (a second pass takes a
+    1024-bin histogram of every channel on its observed range; each end then gives up whole
     bins while they hold no more than a share 1 - args.act_percentile / 100, default 99.99, of the channel's values) or 'hist_mse' (the
     same histogram pass; each channel then takes the clip pair, out of all 524 800, that minimises the modelled squared error on its
     grid width: `ops.act_hist_mse_select`) or 'auto' (one pass takes the 'l2' error sums and the histograms, the ranges that 'max', 'l2',
@@ -166,7 +167,7 @@ def _act_args(args):
 
 def _pass_options(args):
     """Every option `_act_args` describes, read and validated once, a bad one reported in this order -> a namespace of act_mode,
-    act_range, act_iters, act_lr, act_percentile, act_report, unit_report and bias_correct."""
+    act_range, act_iters, act_lr, act_learn_swin, act_percentile, act_report, unit_report and bias_correct."""
     mode, how = _arg(args, "act_mode", "dynamic"), _arg(args, "act_range", "max")
     if mode not in ("dynamic", "static"):
         raise ValueError(f"unknown act_mode {mode!r} ('dynamic' or 'static')")
@@ -174,8 +175,8 @@ def _pass_options(args):
         raise ValueError(f"unknown act_range {how!r} ('max', 'l2', 'learned', 'percentile', 'hist_mse' or 'auto')")
     iters, lr = _act_learn_args(args)
     return types.SimpleNamespace(act_mode=mode, act_range=how, act_iters=iters, act_lr=lr, act_percentile=_act_percentile_args(args),
-                                 act_report=_act_report_args(args), unit_report=_unit_report_args(args),
-                                 bias_correct=_bias_correct_args(args))
+                                 act_report=_act_report_args(args), act_learn_swin=_bool_arg(args, "act_learn_swin"),
+                                 unit_report=_unit_report_args(args), bias_correct=_bias_correct_args(args))
 
 
 def _bool_arg(args, name):
@@ -249,9 +250,8 @@ def _reconstruct(model, unit, unit_name, cali_data, batch_size=32, iters=20000, 
         raise ValueError("--task_loss < 1 has no finite gradient at zero error")
     rd_metric = _rd_metric(args, cali_data)
     opt = _pass_options(args)
-    if act_quant and opt.act_mode == "static" and opt.act_range == "learned" and _is_rstb(unit):
-        raise NotImplementedError("act_range='learned': a Swin (RSTB) unit's activation-quantised window attention cannot sit on torch's "
-                                  "tape (quant_block.QuantWindowAttention); calibrate it with act_range='max' or 'l2'")
+    if act_quant and opt.act_mode == "static" and opt.act_range == "learned" and _is_rstb(unit) and not opt.act_learn_swin:
+        raise NotImplementedError(f"act_range='learned': {SWIN_LEARN_REFUSAL}")
     rank, world_size = dp.world()
     if world_size > 1:                      # data parallel: this rank calibrates on its shard with its share of the batch
         if batch_size % world_size != 0:
@@ -377,7 +377,7 @@ def _reconstruct(model, unit, unit_name, cali_data, batch_size=32, iters=20000, 
         t4 = _mark()
         if opt.act_range == "learned":
             calibrate_act_ranges(unit, inp_q, "l2", batch=cache_bs, keep_obs=True)         # the starting ranges
-            learn_act_ranges(unit, inp_q, out_fp, opt.act_iters, opt.act_lr, batch_size, seed=unit_seed(unit_name))
+            learn_act_ranges(unit, inp_q, out_fp, opt.act_iters, opt.act_lr, batch_size, seed=unit_seed(unit_name), swin=opt.act_learn_swin)
         else:
             calibrate_act_ranges(unit, inp_q, opt.act_range, batch=cache_bs, percentile=opt.act_percentile)
         if opt.act_report:

@@ -379,7 +379,12 @@ def correct_unit_bias(unit, unit_name, inp_q, inp_fp, out_fp, mode="weight", bat
     return unit.bias_stats
 
 
-def learn_act_ranges(unit, inp_q, out_fp, iters=500, lr=1e-3, batch=32, seed=0, idx_table=None):
+SWIN_LEARN_REFUSAL = ("a Swin (RSTB) unit learns its ranges only on request (learn_act_ranges(..., swin=True) / args.act_learn_swin=True: "
+                      "every window attention of the unit then keeps two [windows, N, N, heads] tensors until the backward); "
+                      "use act_range='max' or 'l2' for it otherwise")
+
+
+def learn_act_ranges(unit, inp_q, out_fp, iters=500, lr=1e-3, batch=32, seed=0, idx_table=None, swin=False):
     """Train the frozen static activation ranges of a calibrated unit on its reconstruction error (the activation-grid step of BRECQ /
     QDrop, after the rounding has been learned).  The unit runs in the W8A8 state with its hard-rounded weights under torch's tape (the
     modules' tape forwards; every frozen quantiser as `ActQuantStaticFn`, straight-through round) on mini-batches inp_q[idx] of `batch`
@@ -388,11 +393,15 @@ def learn_act_ranges(unit, inp_q, out_fp, iters=500, lr=1e-3, batch=32, seed=0, 
     (`ops.act_range_step`: step size relative to the observed width, the range stays inside the observed max range).  Under data
     parallelism the range gradients of all sites, concatenated in the fixed site order of `calibrate_act_ranges`, are summed over the
     ranks and divided by the world size before the step, so every rank holds the same grids.  The quantisers end frozen; every quant
-    state flag is left as it was found."""
+    state flag is left as it was found.  A Swin (RSTB) unit is refused unless `swin` is True (a bool): its activation-quantised window
+    attentions then run as `WindowAttentionProbsFn` -> quantiser -> `WindowAttentionPVFn` -> quantiser, the unit called as
+    unit(x, (H, W))."""
     from hipops.autograd import SqDiffSumFn
-    if _is_rstb(unit):
-        raise NotImplementedError("learn_act_ranges: a Swin (RSTB) unit's activation-quantised window attention cannot sit on torch's tape "
-                                  "(quant_block.QuantWindowAttention); use act_range='max' or 'l2' for it")
+    if not isinstance(swin, bool):
+        raise ValueError(f"learn_act_ranges: swin must be True or False, got {swin!r}")
+    rstb = _is_rstb(unit)
+    if rstb and not swin:
+        raise NotImplementedError(f"learn_act_ranges: {SWIN_LEARN_REFUSAL}")
     iters, lr = _check_learn(iters, lr)
     n = inp_q.shape[0]
     B = max(1, min(int(batch), n))
@@ -416,7 +425,7 @@ def learn_act_ranges(unit, inp_q, out_fp, iters=500, lr=1e-3, batch=32, seed=0, 
                 x = inp_q.index_select(0, idx).detach().requires_grad_(True)
                 tgt = out_fp.index_select(0, idx)
                 with torch.enable_grad():
-                    out = unit(x)
+                    out = unit(x, (x.shape[2], x.shape[3])) if rstb else unit(x)
                     loss = SqDiffSumFn.apply(out, tgt, float(out.shape[1]) / out.numel())      # = lp_loss(out, tgt, p=2)
                     grads = torch.autograd.grad(loss, [q.act_range[k] for q, k in sites], allow_unused=True)
                 if world_size > 1:
