@@ -234,6 +234,16 @@ _SIGS_ATTNQ = {
     "rdo_window_attention_probs_bwd": (C.c_int, [C.POINTER(AttnDesc), P, P, P, P, P]),
 }
 EXPORTS_ATTNQ = tuple(_SIGS_ATTNQ)
+# include/rdo_ptq_mx.h: OCP microscaling block formats for weights (32-element blocks, one E8M0 scale each, FP4 / FP6 / FP8 elements)
+_SIGS_MX = {
+    "rdo_mx_fakequant": (C.c_int, [P, C.c_int32, C.c_int64, C.c_int32, P, P, P, P, P, P, P]),
+    "rdo_mx_fakequant_workspace": (C.c_int64, [C.c_int32, C.c_int64]),
+    "rdo_mx_dequant": (C.c_int, [P, P, C.c_int32, C.c_int64, C.c_int32, P, P]),
+    "rdo_mx_format_bits": (C.c_int32, [C.c_int32]),
+}
+EXPORTS_MX = tuple(_SIGS_MX)
+MX_BLOCK = 32             # RDO_MX_BLOCK of include/rdo_ptq_mx.h
+MX_FORMATS = {"mxfp4": (0, 4), "mxfp6_e2m3": (1, 6), "mxfp6_e3m2": (2, 6), "mxfp8_e4m3": (3, 8), "mxfp8_e5m2": (4, 8)}      # name -> (id, element bits)
 
 _lib = None
 
@@ -252,7 +262,7 @@ def lib():
         h = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(_SIGS.items()) + list(_SIGS_GDN.items()) + list(_SIGS_BIAS.items()) + list(_SIGS_BITS.items())
                                   + list(_SIGS_PACK.items()) + list(_SIGS_SUBPEL.items()) + list(_SIGS_ACTBITS.items())
-                                  + list(_SIGS_ATTNQ.items())):
+                                  + list(_SIGS_ATTNQ.items()) + list(_SIGS_MX.items())):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         _lib = h

@@ -650,6 +650,87 @@ def actquant_width_scan(x, rng, widths):
     return err, energy
 
 
+MX_OUTPUTS = ("wq", "scales", "codes", "err", "energy")      # what `mx_fakequant` can be asked for, in the order of the C entry
+
+
+def mx_format(what, fmt):
+    """(id, element bits) of the MX format named `fmt`; ValueError listing the table for anything else"""
+    if not isinstance(fmt, str) or fmt not in L.MX_FORMATS:
+        raise ValueError(f"{what}: unknown MX format {fmt!r}; the formats are {list(L.MX_FORMATS)}")
+    return L.MX_FORMATS[fmt]
+
+
+def _mx_geometry(what, rows, inner):
+    nb = -(-inner // L.MX_BLOCK)
+    if rows > 0x7fffffff or rows * nb > 2 ** 40:
+        raise ValueError(f"{what}: [{rows}, {inner}] is beyond 2^31 - 1 rows or 2^40 blocks")
+    return nb
+
+
+def mx_fakequant(w_rows, fmt, want=("wq",), wq_out=None):
+    """Quantise a weight-row matrix to an MX block format (rdo_mx_fakequant; include/rdo_ptq_mx.h states the formats): w_rows contiguous
+    fp32 [rows, inner] (what `to_rows` gives, flattened to rank 2), fmt a name of `MX_FORMATS`, want a non-empty sequence of distinct
+    names out of `MX_OUTPUTS`.  -> dict of the requested outputs: 'wq' fp32 [rows, inner], 'scales' uint8 [rows, ceil(inner / 32)] (E8M0
+    codes, 255 for a block that holds a NaN or an infinity), 'codes' uint8 [rows, inner], 'err' float64 [rows] = sum (w - wq)^2 with
+    the difference formed in fp32, 'energy' float64 [rows] = sum w^2.  Float64 sums in a fixed order: the same input gives the same bits.
+    `wq_out`: a contiguous fp32 [rows, inner] to write 'wq' into; it may be w_rows itself.  Everything is checked on the host before a
+    pointer is taken."""
+    what = "mx_fakequant"
+    A.tensor(what, "w_rows", w_rows, rank=2, layout="of rank 2 [rows, inner]", contiguous=True)
+    fid, _ = mx_format(what, fmt)
+    if isinstance(want, (str, bytes)) or not hasattr(want, "__iter__"):
+        raise ValueError(f"{what}: want must be a sequence of names out of {list(MX_OUTPUTS)}, got {want!r}")
+    want = list(want)
+    if not want or any(n not in MX_OUTPUTS for n in want) or len(set(want)) != len(want):
+        raise ValueError(f"{what}: want must hold at least one and only distinct names out of {list(MX_OUTPUTS)}, got {want!r}")
+    rows, inner, dev = int(w_rows.shape[0]), int(w_rows.shape[1]), w_rows.device
+    nb = _mx_geometry(what, rows, inner)
+    if wq_out is not None and "wq" not in want:
+        raise ValueError(f"{what}: wq_out is given but 'wq' is not wanted")
+    A.tensor(what, "wq_out", wq_out, shape=(rows, inner), contiguous=True, device=dev, optional=True, oneshot=True)
+    if not w_rows.is_cuda:
+        raise ValueError(f"{what}: w_rows is on {dev}; there is no CPU path")
+    out = {}
+    if "wq" in want:
+        out["wq"] = torch.empty(rows, inner, device=dev, dtype=torch.float32) if wq_out is None else wq_out
+    if "scales" in want:
+        out["scales"] = torch.empty(rows, nb, device=dev, dtype=torch.uint8)
+    if "codes" in want:
+        out["codes"] = torch.empty(rows, inner, device=dev, dtype=torch.uint8)
+    for n in ("err", "energy"):
+        if n in want:
+            out[n] = torch.empty(rows, device=dev, dtype=torch.float64)
+    ws = None
+    if "err" in want or "energy" in want:
+        ws = _workspace(what, dev, -(-int(L.lib().rdo_mx_fakequant_workspace(rows, inner)) // 8), torch.float64)
+    u8 = ((torch.uint8,), "uint8")
+    L.check(L.lib().rdo_mx_fakequant(_ptr(w_rows), rows, inner, fid, _ptr(out.get("wq")), _ptr(out.get("scales"), *u8),
+                                     _ptr(out.get("codes"), *u8), _ptr64(out.get("err")), _ptr64(out.get("energy")), _ptr64(ws), _stream()),
+            "rdo_mx_fakequant")
+    return {n: out[n] for n in want}
+
+
+def mx_dequant(codes, scales, inner, fmt):
+    """fp32 [rows, inner] from what `mx_fakequant` gave as 'codes' (contiguous uint8 [rows, inner]) and 'scales' (contiguous uint8 [rows,
+    ceil(inner / 32)] on its device): bit for bit the 'wq' of that call (rdo_mx_dequant).  A scale code of 255 gives NaN.  Everything is
+    checked on the host before a pointer is taken."""
+    what = "mx_dequant"
+    A.tensor(what, "codes", codes, torch.uint8, "uint8", rank=2, layout="of rank 2 [rows, inner]", contiguous=True)
+    fid, _ = mx_format(what, fmt)
+    inner = A.whole(what, "inner", inner, 1)
+    rows, dev = int(codes.shape[0]), codes.device
+    if codes.shape[1] != inner:
+        raise ValueError(f"{what}: codes is {tuple(codes.shape)}; inner is {inner}")
+    nb = _mx_geometry(what, rows, inner)
+    A.tensor(what, "scales", scales, torch.uint8, "uint8", shape=(rows, nb), contiguous=True, device=dev, oneshot=True)
+    if not codes.is_cuda:
+        raise ValueError(f"{what}: codes is on {dev}; there is no CPU path")
+    w = torch.empty(rows, inner, device=dev, dtype=torch.float32)
+    u8 = ((torch.uint8,), "uint8")
+    L.check(L.lib().rdo_mx_dequant(_ptr(codes, *u8), _ptr(scales, *u8), rows, inner, fid, _ptr(w), _stream()), "rdo_mx_dequant")
+    return w
+
+
 def pack_row_words(inner, bits):
     """W = ceil(inner * bits / 32): the 32-bit words one row of `inner` codes of `bits` bits occupies (rdo_pack_row_words on the host)"""
     return -(-int(inner) * int(bits) // 32)

@@ -15,7 +15,10 @@ from .quantizer import AdaRoundQuantizer
 
 def integer_state(qnn) -> "OrderedDict[str, dict]":
     """name -> {levels (uint8, or int32 above 8 bits; logical weight shape), delta, zero_point, n_bits, bias, kind}.  `bias` is the one
-    the quantised forward uses (`m.bias`): `org_bias` unless a bias correction moved it (`unit_passes.correct_unit_bias`)."""
+    the quantised forward uses (`m.bias`): `org_bias` unless a bias correction moved it (`unit_passes.correct_unit_bias`).  ValueError
+    for a model that holds an `MXQuantizer` (`QuantModel.set_weight_format`): an MX grid has no levels, delta and zero point."""
+    from .mx import refuse_mx
+    refuse_mx("integer_state", qnn.named_modules(), ValueError, "an MX grid has no integer levels, delta and zero point to export")
     out = OrderedDict()
     for name, m in qnn.named_modules():
         if not isinstance(m, QuantModule) or m.org_weight is None:
@@ -50,5 +53,5 @@ def dequantize(entry) -> torch.Tensor:
     return (entry["levels"].to(torch.float32) - entry["zero_point"]) * entry["delta"]
 
 
-from .reports import act_bit_report, act_width_report, activation_report, bias_report, bit_report, rd_report, unit_report  # noqa: E402,F401
+from .reports import act_bit_report, act_width_report, activation_report, bias_report, bit_report, format_report, rd_report, unit_report  # noqa: E402,F401
 from .widths import act_applied, act_modules, allocate_act_bits, allocate_bits, is_trained, weighted_modules  # noqa: E402,F401

@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import packed_io
+from .mx import refuse_mx
 from .quant_block import BaseQuantBlock
 from .quant_layer import QuantModule
 from .quantizer import MAX_BITS, AdaRoundQuantizer, UniformAffineQuantizer, from_rows
@@ -45,6 +46,7 @@ def save_packed(qnn, path) -> dict:
     from hipops import ops
     what = "save_packed"
     mods = _weighted(qnn)
+    refuse_mx(what, mods, ValueError, "a packed MX container is not built; nothing was written")
     for name, m in mods:
         q = m.weight_quantizer
         if not getattr(q, "inited", True) or q.delta is None or q.zero_point is None:

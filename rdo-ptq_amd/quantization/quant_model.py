@@ -7,7 +7,7 @@ from lic import EntropyBottleneck
 from .fold_bn import search_fold_and_remove_bn
 from .quant_block import BaseQuantBlock, specials
 from .quant_layer import GDN_TYPES, QuantModule, StraightThrough
-from .widths import act_applied, act_modules, is_trained, weighted_modules, width_plan
+from .widths import act_applied, act_modules, format_plan, is_trained, weighted_modules, width_plan
 
 _WRAPPABLE = (nn.Conv2d, nn.ConvTranspose2d, nn.Linear, nn.LayerNorm, nn.PixelShuffle) + GDN_TYPES
 _FUSABLE_ACT = (nn.LeakyReLU, nn.GELU, nn.ReLU, nn.ReLU6)
@@ -150,6 +150,40 @@ class QuantModel(nn.Module):
             for m in weighted_modules(known[n]):
                 m.weight_quantizer.bitwidth_refactor(int(b))
                 m.weight_quantizer.inited = False
+                m.drop_weight_pack()
+
+    def format_report(self, images, formats=("mxfp4", "mxfp6_e2m3", "mxfp8_e4m3"), lmbda=0.01, batch=8, units=None):
+        """What every unit costs in rate and distortion in each of several MX block formats when it alone is quantised (round to nearest,
+        weights only), with each format's size and weight error: `bit_report` with formats in place of widths (`export.format_report`).
+        len(units) * len(formats) + 1 passes over `images`; taken before calibration."""
+        from .reports import format_report
+        return format_report(self, images, formats=formats, lmbda=lmbda, batch=batch, units=units)
+
+    def set_weight_format(self, formats):
+        """Leave the weights of the units in an MX block format for evaluation: `formats` is one name for every unit, or a mapping unit
+        name -> name (units it does not name keep theirs); a name is one of `hipops._lib.MX_FORMATS` or 'int'.  A format swaps the
+        `weight_quantizer` of every weighted QuantModule of the unit for an `mx.MXQuantizer` and keeps the replaced quantiser on the
+        module (`int_weight_quantizer`); 'int' puts that object back (a unit that holds no MX quantiser is left alone).  Names are
+        validated and a unit that holds a trained module is refused (ValueError) before anything is written; every swap calls
+        `drop_weight_pack()`.  Activation quantisers are not touched."""
+        from .mx import MX_FORMATS, MXQuantizer, is_mx
+        what, known = "set_weight_format", self.units()
+        plan = format_plan(what, known, formats, MX_FORMATS + ("int",))
+        for n, _ in plan:
+            if any(is_trained(m) for m in weighted_modules(known[n])):
+                raise ValueError(f"{what}: unit {n!r} holds a trained module: its rounding belongs to the grid it was calibrated on")
+        for n, fmt in plan:
+            for m in weighted_modules(known[n]):
+                q = m.weight_quantizer
+                if fmt == "int":
+                    if not is_mx(q):
+                        continue
+                    m.weight_quantizer = m.int_weight_quantizer
+                    del m.int_weight_quantizer
+                else:
+                    if not is_mx(q):
+                        m.int_weight_quantizer = q
+                    m.weight_quantizer = MXQuantizer(fmt, tconv=m.if_tconv)
                 m.drop_weight_pack()
 
     def weight_bits(self):

@@ -221,7 +221,12 @@ def reconstruct(model, unit, unit_name, cali_data, *a, **kw):
     """`_reconstruct` with the cross-unit state tidied up: the full-precision cache memo of the schedule
     (quantization/utils.py::_FpMemo) is dropped when a unit raises, so a schedule that dies half-way pins no device memory; and the
     quantisers that `_reconstruct` put on torch's tape for the unit (`act_ste`: loss_mode='rd' behind frozen activation quantisers) are
-    taken off it again, whatever happened."""
+    taken off it again, whatever happened.  A unit that holds an `MXQuantizer` is refused (NotImplementedError) before any cache is
+    built."""
+    from .mx import refuse_mx
+    inside = unit.named_modules() if isinstance(unit, torch.nn.Module) else ()
+    refuse_mx("reconstruct", [(f"{unit_name}.{n}" if n else unit_name, m) for n, m in inside], NotImplementedError,
+              "learned rounding on MX grids is not built (QuantModel.set_weight_format('int') puts the integer grid back)")
     ste = []
     try:
         return _reconstruct(model, unit, unit_name, cali_data, *a, _ste=ste, **kw)

@@ -1,8 +1,8 @@
 """Reports on a QuantModel.  Three read what the calibration left on the model: `activation_report` (the frozen activation ranges),
 `unit_report` (each unit's output error, learned rounding against round-to-nearest) and `bias_report` (what the bias correction did).
-Four measure on images: `rd_report` (rate and distortion cost of each unit), `bit_report` / `act_bit_report` (the same at several weight /
-activation widths: the tables `widths.allocate_bits` / `allocate_act_bits` choose from) and `act_width_report` (one-pass screening of
-activation widths).  The measuring ones are lists of states handed to one sweep driver, `_Sweep`, which owns the argument checks, the
+Five measure on images: `rd_report` (rate and distortion cost of each unit), `bit_report` / `act_bit_report` (the same at several weight /
+activation widths: the tables `widths.allocate_bits` / `allocate_act_bits` choose from), `format_report` (the same in several MX block
+formats) and `act_width_report` (one-pass screening of activation widths).  The measuring ones are lists of states handed to one sweep driver, `_Sweep`, which owns the argument checks, the
 rank sharding, the passes, the restore, the rank reduction and the rows."""
 import math
 from collections import OrderedDict
@@ -445,6 +445,93 @@ def bit_report(qnn, images, widths=(4, 6, 8), lmbda=0.01, batch=8, units=None) -
                                      lambda name, k: (float(weight_cols[name][0][k]), weight_cols[name][1]), "weight")
     rep["weights"] = counts
     rep["widths"], rep["n"], rep["pixels"], rep["lmbda"], rep["batch"] = list(widths), sweep.n, sweep.pixels, float(lmbda), batch
+    return rep
+
+
+def _format_list(what, formats):
+    """`formats` as a list of names: a non-empty sequence of distinct names of `hipops._lib.MX_FORMATS`, else ValueError"""
+    from hipops import ops
+    if isinstance(formats, (str, bytes)) or not hasattr(formats, "__len__") or not hasattr(formats, "__iter__"):
+        raise ValueError(f"{what}: formats must be a sequence of MX format names, got {formats!r}")
+    formats = list(formats)
+    if not formats:
+        raise ValueError(f"{what}: formats must hold at least one name")
+    for f in formats:
+        ops.mx_format(what, f)
+    if len(set(formats)) != len(formats):
+        raise ValueError(f"{what}: formats must be distinct, got {formats}")
+    return formats
+
+
+def format_report(qnn, images, formats=("mxfp4", "mxfp6_e2m3", "mxfp8_e4m3"), lmbda=0.01, batch=8, units=None) -> "OrderedDict":
+    """What each reconstruction unit costs in rate and distortion in each of several MX block formats (include/rdo_ptq_mx.h), measured on
+    `images` like `rd_report` (its rules for `images`, `lmbda`, `batch` and `units`) under torch.no_grad(), BEFORE calibration: weights
+    only (activation quantisation is off in every state), round to nearest.  `bit_report` with formats in place of widths.  The states,
+    all over the same images:
+      'fp'                     qnn.set_quant_state(False, False): the 'fp' state of `rd_report`
+      one per (unit, format)   qnn.set_quant_state(False, False); unit.set_quant_state(True, False), with every weighted QuantModule of
+                               the unit temporarily holding an `mx.MXQuantizer` of the format: in `units()` order, the formats in the
+                               order given
+    -> OrderedDict:
+      'fp'       the row of `rd_report`'s 'fp'
+      'units'    name -> format -> row: the keys of an `rd_report` unit row (bits, bits_total, sse, bpp, mse, psnr_db, loss, d_bits, d_bpp,
+                 d_mse, d_psnr_db, d_loss), and size_bits = the sum over the unit's modules of element bits x elements + 8 x blocks,
+                 weight_err = the sum over the unit's modules and rows of the kernel's sum (w - wq)^2 in float64, weight_sqnr_db = 10
+                 log10(sum energy / sum err) in float64 (inf at zero error), bits_per_weight = size_bits / the unit's weight elements
+      'weights'  name -> weight elements of the unit (its weighted QuantModules; biases are not counted)
+      'formats' (list), 'n', 'pixels', 'lmbda', 'batch'
+    State: the `weight_quantizer` of every weighted module of the chosen units and every module's use_weight_quant | use_act_quant
+    pair are recorded first and put back in a `finally` (the same objects, so the same bits); `drop_weight_pack()` runs at every switch
+    and at the end.
+    Data parallel: as `rd_report`; every rank scores the weights itself, which gives the same bits.
+    Cost: len(units) * len(formats) + 1 passes over `images`.
+    Raises ValueError before any GPU work for what `rd_report` refuses, for formats that are not a non-empty sequence of distinct names
+    of `MX_FORMATS`, and for a chosen unit that holds a trained module (the table is taken before calibration)."""
+    from .mx import MXQuantizer
+    what = "format_report"
+    sweep = _Sweep(what, qnn, images, batch, (lmbda, False, units))
+    formats = _format_list(what, formats)
+    mods = OrderedDict((name, weighted_modules(u)) for name, u in sweep.chosen)
+    for name, ms in mods.items():
+        if any(is_trained(m) for m in ms):
+            raise ValueError(f"{what}: unit {name!r} holds a trained module: the table is taken before calibration")
+    sweep.shard(batch)
+    every = [m for ms in mods.values() for m in ms]
+    made = {(name, f): [MXQuantizer(f, tconv=m.if_tconv) for m in ms] for name, ms in mods.items() for f in formats}
+    weight_cols = {}
+
+    def scan():
+        """the weights of every chosen unit in every format, once, in front of the 'fp' pass: the first GPU work"""
+        for (name, f), qs in made.items():
+            costs = [q.weight_cost(m.weight) for q, m in zip(qs, mods[name])]
+            weight_cols[name, f] = (float(torch.stack([e.sum() for e, _ in costs]).sum()), float(torch.stack([en.sum() for _, en in costs]).sum()))
+
+    def at(name, u, f):
+        def enter():
+            u.set_quant_state(True, False)
+            for m, q in zip(mods[name], made[name, f]):
+                m.weight_quantizer = q
+                m.drop_weight_pack()
+        return enter
+    states = [("fp", scan)] + [((name, f), at(name, u, f)) for name, u in sweep.chosen for f in formats]
+    try:
+        rows, _ = sweep.run(states, held=every, fields=("weight_quantizer",))
+    finally:
+        for m in every:                                                                     # (the quantisers are back: no pack of a format stays)
+            m.drop_weight_pack()
+    counts = OrderedDict((name, sum(int(m.weight.numel()) for m in ms)) for name, ms in mods.items())
+    rep = OrderedDict()
+    rep["fp"], rep["units"] = rows["fp"], OrderedDict()
+    for name, ms in mods.items():
+        rep["units"][name] = OrderedDict()
+        for f in formats:
+            r, (err, energy) = rows[name, f], weight_cols[name, f]
+            r["size_bits"] = sum(q.size_bits(m.weight) for q, m in zip(made[name, f], ms))
+            r["weight_err"], r["weight_sqnr_db"] = err, _sqnr_db_float(energy, err)
+            r["bits_per_weight"] = r["size_bits"] / counts[name]
+            rep["units"][name][f] = r
+    rep["weights"] = counts
+    rep["formats"], rep["n"], rep["pixels"], rep["lmbda"], rep["batch"] = list(formats), sweep.n, sweep.pixels, float(lmbda), batch
     return rep
 
 

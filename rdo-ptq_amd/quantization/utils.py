@@ -64,15 +64,19 @@ _MISSING = object()
 def held_attrs(objs, fields):
     """Context manager over the instance attributes `fields` of every object of `objs` (the quantiser fields a report switches: widths,
     grids, `act_stats`): records what `vars(obj)` holds under each name and puts it back on the way out, whatever was raised and whatever
-    the block set, replaced or deleted in between -- the same object, not a copy; an attribute that was absent is deleted again.  The
-    one place of this package that restores quantiser attributes."""
-    held = [(o, f, vars(o).get(f, _MISSING)) for o in objs for f in fields]
+    the block set, replaced or deleted in between -- the same object, not a copy; an attribute that was absent is deleted again.  A
+    submodule of an nn.Module (a module's `weight_quantizer`, which `format_report` swaps) is held like any other attribute.  The one
+    place of this package that restores quantiser attributes."""
+    def found(o, f):
+        return vars(o).get(f, vars(o).get("_modules", {}).get(f, _MISSING))
+    held = [(o, f, found(o, f)) for o in objs for f in fields]
     try:
         yield
     finally:
         for o, f, v in held:
             if v is _MISSING:
                 vars(o).pop(f, None)
+                vars(o).get("_modules", {}).pop(f, None)
             else:
                 setattr(o, f, v)
 

@@ -53,6 +53,27 @@ def width_plan(what, known, bits):
     return plan
 
 
+def format_plan(what, known, formats, names):
+    """The `formats` argument of `QuantModel.set_weight_format` (named `what` in the messages) -> [(unit name, format name)] in the order
+    of `known` (`QuantModel.units()`): one name out of `names` for every unit, or a mapping unit name -> name for the units it names.
+    ValueError for anything else, an unknown unit or an unknown format (listing `names`); nothing is written here."""
+    def named(f):
+        return isinstance(f, str) and f in names
+    if isinstance(formats, Mapping):
+        unknown = [n for n in formats if n not in known]
+        if unknown:
+            raise ValueError(f"{what}: unknown unit name(s) {unknown}; QuantModel.units() has {list(known)}")
+        plan = [(n, formats[n]) for n in known if n in formats]
+    elif named(formats):
+        plan = [(n, formats) for n in known]
+    else:
+        raise ValueError(f"{what}: formats must be one of {list(names)} or a mapping unit name -> format, got {formats!r}")
+    for n, f in plan:
+        if not named(f):
+            raise ValueError(f"{what}: the format of unit {n!r} must be one of {list(names)}, got {f!r}")
+    return plan
+
+
 def _hull(options):
     """options: [(width, size, cost)] of one unit -> its hull points in ascending size: the lower convex hull from the smallest size up to
     the least-cost point (among equal costs the smallest).  Going down the list from the end, the cost per bit saved rises from step to
