@@ -244,6 +244,14 @@ _SIGS_MX = {
 EXPORTS_MX = tuple(_SIGS_MX)
 MX_BLOCK = 32             # RDO_MX_BLOCK of include/rdo_ptq_mx.h
 MX_FORMATS = {"mxfp4": (0, 4), "mxfp6_e2m3": (1, 6), "mxfp6_e3m2": (2, 6), "mxfp8_e4m3": (3, 8), "mxfp8_e5m2": (4, 8)}      # name -> (id, element bits)
+# include/rdo_ptq_mxround.h: learned rounding on the MX grids (neighbours of a weight on its blocks' grids, init, forward, the fused step)
+_SIGS_MXROUND = {
+    "rdo_mx_neighbours": (C.c_int, [P, C.c_int32, C.c_int64, C.c_int32, P, P, P, P]),
+    "rdo_mx_round_init_alpha": (C.c_int, [P, P, P, C.c_int64, P, P]),
+    "rdo_mx_round_fwd": (C.c_int, [C.POINTER(AdaDesc), P, P, P, C.c_int32, P, P, P, P, C.c_int32, P]),
+    "rdo_mx_round_step": (C.c_int, [C.POINTER(AdaDesc), P, P, P, C.c_int32, C.c_float, C.c_float, P, P, P, P, P, P, P, P, P]),
+}
+EXPORTS_MXROUND = tuple(_SIGS_MXROUND)
 
 _lib = None
 
@@ -262,7 +270,7 @@ def lib():
         h = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(_SIGS.items()) + list(_SIGS_GDN.items()) + list(_SIGS_BIAS.items()) + list(_SIGS_BITS.items())
                                   + list(_SIGS_PACK.items()) + list(_SIGS_SUBPEL.items()) + list(_SIGS_ACTBITS.items())
-                                  + list(_SIGS_ATTNQ.items()) + list(_SIGS_MX.items())):
+                                  + list(_SIGS_ATTNQ.items()) + list(_SIGS_MX.items()) + list(_SIGS_MXROUND.items())):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         _lib = h

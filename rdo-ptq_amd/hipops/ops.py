@@ -731,6 +731,105 @@ def mx_dequant(codes, scales, inner, fmt):
     return w
 
 
+# ---- learned rounding on the MX grids (include/rdo_ptq_mxround.h) -----------------------------------------------------------------------
+_U8 = ((torch.uint8,), "uint8")
+
+
+def _mx_cuda(what, t, name):
+    if not t.is_cuda:
+        raise ValueError(f"{what}: {name} is on {t.device}; there is no CPU path")
+
+
+def mx_neighbours(w_rows, fmt, want_scales=False):
+    """The neighbours of every element of a weight-row matrix on the grid of its block (rdo_mx_neighbours; include/rdo_ptq_mxround.h states
+    the definitions): w_rows contiguous fp32 [rows, inner] -> (lo, gap) fp32 [rows, inner], lo the largest grid value <= w and gap the
+    distance to the next one; gap == 0 marks a pinned element (lo = +-max X) or a block that is not finite (lo = NaN).  want_scales:
+    -> (lo, gap, scales), scales uint8 [rows, ceil(inner / 32)], the bytes `mx_fakequant` gives.  Checked on the host before a pointer
+    is taken."""
+    what = "mx_neighbours"
+    A.tensor(what, "w_rows", w_rows, rank=2, layout="of rank 2 [rows, inner]", contiguous=True)
+    fid, _ = mx_format(what, fmt)
+    rows, inner, dev = int(w_rows.shape[0]), int(w_rows.shape[1]), w_rows.device
+    nb = _mx_geometry(what, rows, inner)
+    _mx_cuda(what, w_rows, "w_rows")
+    lo, gap = torch.empty_like(w_rows), torch.empty_like(w_rows)
+    scales = torch.empty(rows, nb, device=dev, dtype=torch.uint8) if want_scales else None
+    L.check(L.lib().rdo_mx_neighbours(_ptr(w_rows), rows, inner, fid, _ptr(lo), _ptr(gap), _ptr(scales, *_U8), _stream()), "rdo_mx_neighbours")
+    return (lo, gap, scales) if want_scales else (lo, gap)
+
+
+def _mx_same(what, first, **named):
+    """every named tensor: contiguous fp32 with the element count and device of `first` = (name, tensor), itself checked first"""
+    A.tensor(what, first[0], first[1], contiguous=True)
+    for name, t in named.items():
+        A.tensor(what, name, t, numel=first[1].numel(), contiguous=True, device=first[1].device, other=first[0])
+    _mx_cuda(what, first[1], first[0])
+    return first[1].numel()
+
+
+def mx_round_init_alpha(w, lo, gap, alpha=None):
+    """alpha0 = -log(1.2 / (rest + 0.1) - 1) with rest = (w - lo) / gap in fp32; 0 for a pinned element (rdo_mx_round_init_alpha).
+    w, lo, gap (and alpha, made when None): contiguous fp32 of one element count on one device."""
+    what = "mx_round_init_alpha"
+    alpha = torch.empty_like(w) if (alpha is None and torch.is_tensor(w)) else alpha
+    n = _mx_same(what, ("w", w), lo=lo, gap=gap, alpha=alpha)
+    L.check(L.lib().rdo_mx_round_init_alpha(_ptr(w), _ptr(lo), _ptr(gap), n, _ptr(alpha), _stream()), "rdo_mx_round_init_alpha")
+    return alpha
+
+
+def _mx_desc(what, d, lo):
+    if not isinstance(d, L.AdaDesc) or d.numel != lo.numel() or d.rows < 1 or d.numel % d.rows:
+        raise ValueError(f"{what}: d must be an `ada_desc` of the {lo.numel()} elements of lo, got "
+                         f"{(d.numel, d.rows) if isinstance(d, L.AdaDesc) else type(d).__name__}")
+
+
+def mx_round_fwd(d, lo, gap, alpha, soft, fmt, wq=None, wd=None, codes=None, scales=None):
+    """Soft (soft=True) or hard weight lo + gap * h on an MX grid into the kernel layouts of `adaround_fwd` (rdo_mx_round_fwd): `wq` in
+    the layout of lo (made when None), `wd` (optional) the dgrad layout of the descriptor `d` (`ada_desc`; a gamma's transpose), the GDN
+    re-parametrisation of `d` applied.  codes=True (hard only; needs `scales`, uint8 [rows, ceil(inner / 32)] of `mx_neighbours` /
+    `mx_fakequant`): -> (wq, codes), codes uint8 [rows, inner] with `mx_dequant(codes, scales)` the hard weight before the reparam bit for
+    bit.  Everything is checked on the host before a pointer is taken."""
+    what = "mx_round_fwd"
+    fid, _ = mx_format(what, fmt)
+    wq = torch.empty_like(lo) if (wq is None and torch.is_tensor(lo)) else wq
+    _mx_same(what, ("lo", lo), gap=gap, alpha=alpha, wq=wq)
+    A.tensor(what, "wd", wd, numel=lo.numel(), contiguous=True, device=lo.device, optional=True, oneshot=True)
+    _mx_desc(what, d, lo)
+    rows, inner = int(d.rows), int(d.numel // d.rows)
+    cd = None
+    if codes:
+        if soft:
+            raise ValueError(f"{what}: codes describe the hard weight: soft must be False")
+        A.tensor(what, "scales", scales, torch.uint8, "uint8", shape=(rows, _mx_geometry(what, rows, inner)), contiguous=True, device=lo.device,
+                 oneshot=True)
+        cd = torch.empty(rows, inner, device=lo.device, dtype=torch.uint8)
+    L.check(L.lib().rdo_mx_round_fwd(C.byref(d), _ptr(lo), _ptr(gap), _ptr(alpha), int(bool(soft)), _ptr(wq), _ptr(wd), _ptr(cd, *_U8),
+                                     _ptr(scales if codes else None, *_U8), fid, _stream()), "rdo_mx_round_fwd")
+    return (wq, cd) if codes else wq
+
+
+def mx_round_step(d, lo, gap, slabs, grad_scale, round_weight, sched, iter_ptr, alpha, m, v, wq, wd, round_log):
+    """One fused AdaRound step on an MX grid (rdo_mx_round_step): `adaround_step` with (lo, gap) in place of (w, delta, zp) and no plane
+    outputs.  slabs fp32 [nsplit, ...] of nsplit * numel elements; sched fp32 [iters, 4] (`make_sched`); iter_ptr one int32; round_log
+    fp32 [iters, LOG_SLOTS] or None.  Pinned elements (gap == 0) keep alpha, m and v.  Checked on the host before a pointer is taken."""
+    what = "mx_round_step"
+    n = _mx_same(what, ("lo", lo), gap=gap, alpha=alpha, m=m, v=v, wq=wq)
+    dev = lo.device
+    A.tensor(what, "wd", wd, numel=n, contiguous=True, device=dev, optional=True, oneshot=True)
+    _mx_desc(what, d, lo)
+    A.tensor(what, "slabs", slabs, contiguous=True, device=dev, other="lo")
+    if slabs.dim() < 1 or slabs.shape[0] < 1 or slabs.numel() != slabs.shape[0] * n:
+        raise ValueError(f"{what}: slabs must be [nsplit, ...] with {n} elements a slab, got {tuple(slabs.shape)}")
+    A.tensor(what, "sched", sched, rank=2, layout="of rank 2 [iters, 4]", contiguous=True, device=dev, other="lo")
+    if sched.shape[1] != 4:
+        raise ValueError(f"{what}: sched must be [iters, 4], got {tuple(sched.shape)}")
+    A.tensor(what, "iter_ptr", iter_ptr, torch.int32, "int32", numel=1, device=dev, other="lo")
+    A.tensor(what, "round_log", round_log, shape=(sched.shape[0], L.LOG_SLOTS), contiguous=True, device=dev, optional=True, oneshot=True)
+    L.check(L.lib().rdo_mx_round_step(C.byref(d), _ptr(lo), _ptr(gap), _ptr(slabs), int(slabs.shape[0]), float(grad_scale), float(round_weight),
+                                      _ptr(sched), _ptr(iter_ptr), _ptr(alpha), _ptr(m), _ptr(v), _ptr(wq), _ptr(wd), _ptr(round_log), _stream()),
+            "rdo_mx_round_step")
+
+
 def pack_row_words(inner, bits):
     """W = ceil(inner * bits / 32): the 32-bit words one row of `inner` codes of `bits` bits occupies (rdo_pack_row_words on the host)"""
     return -(-int(inner) * int(bits) // 32)

@@ -142,6 +142,7 @@ class _Weights:
     the frozen `swin_engine._FpOp` share, so that `UnitEngine._conv` / `._dgrad` take either.  A subclass provides `wq` and, where
     it has an input gradient, `wd` (the weights the kernels read now, as `wq4()` / `wd4()`) and `plane_scale()`."""
     is_gdn = False
+    is_mx = False                              # `_MxOp`: the AdaRound state lives on an MX grid (lo / gap in place of delta / zp)
     name = None                                # (a trainable op has one: its key in `UnitEngine.ops`)
     # plane buffer -> (the weight it is split from: an attribute or a method, how), in the order `split_planes` issues its launches; the
     # buffers are made on first use while a plan is being recorded
@@ -307,8 +308,8 @@ class _Op(_Weights):
         self.wq = torch.empty_like(self.w)
         # wd: dgrad layout for convs, transpose for gamma (always needed: GDN backward uses gamma'^T)
         self.wd = torch.empty_like(self.w) if (need_dgrad or self.is_gdn) else None
-        ops.adaround_init_alpha(self.desc, self.w, self.delta, self.alpha)
-        ops.adaround_fwd(self.desc, self.w, self.alpha, self.delta, self.zp, True, self.wq, self.wd)
+        self.init_alpha()
+        self.set_weight(True)
         self.slabs = self.slabs_p = None
         self.dalpha = None                     # data parallel: this op's view of the unit's gradient bucket (`UnitEngine._build_ops`)
         # phase form of a transposed conv: the AdaRound state stays in the kernel layout of the transposed conv; the phase weight is
@@ -319,6 +320,19 @@ class _Op(_Weights):
     def plane_scale(self):
         return self.wscale
 
+    def init_alpha(self):
+        """alpha of round to nearest: where a unit starts and restarts"""
+        ops.adaround_init_alpha(self.desc, self.w, self.delta, self.alpha)
+
+    def set_weight(self, soft):
+        """soft- or hard-rounded weight of the current alpha into wq / wd"""
+        ops.adaround_fwd(self.desc, self.w, self.alpha, self.delta, self.zp, bool(soft), self.wq, self.wd)
+
+    def step(self, eng, scale):
+        """this op's own launch of the fused AdaRound step (the per-op path of `UnitEngine._step_ops`)"""
+        ops.adaround_step(self.desc, self.w, self.delta, self.zp, self.slabs, scale, eng.weight, eng.sched, eng.it, self.alpha, self.m, self.v,
+                          self.wq, self.wd, eng.round_log, self.wq_planes, self.wd_planes)
+
     def refresh_planes(self):
         """soft weights -> every plane buffer the recorded kernels read (the exact bf16 three-way splits of the split-bf16 MFMA path,
         the fp16 planes of the plane-input kernels): eagerly after the recording, then inside the plan behind every step"""
@@ -326,6 +340,80 @@ class _Op(_Weights):
 
     def numel(self):
         return self.w.numel()
+
+
+class _MxOp(_Op):
+    """A trainable QuantModule whose weight quantiser is an `mx.MXAdaRoundQuantizer`: the AdaRound state on the grid of an MX block
+    format (include/rdo_ptq_mxround.h).  `lo` and `gap` (fp32, the layout of `w`) take the place of `delta` and `zp`; alpha, m, v, wq and
+    wd are as in `_Op`.  The blocks run along the rows of `to_rows(weight, tconv)`, so the neighbours are computed on those rows and, for
+    a transposed conv, flipped with the same `.flip(1, 2)` as every other tensor of the op (a block spans taps whenever Cin % 32 != 0)."""
+    is_mx = True
+
+    def __init__(self, name, qm: QuantModule, need_dgrad: bool):
+        _Weights.__init__(self, qm)
+        self.name, self.need_dgrad = name, need_dgrad
+        self.is_gdn, self.is_ln = qm.kind == "gdn", False
+        if qm.kind not in ("conv", "gdn", "tconv", "linear"):
+            raise NotImplementedError(f"calibration engine: learned rounding on MX grids is not built for QuantModule kind '{qm.kind}'")
+        q = qm.weight_quantizer
+        self.fmt = q.fmt
+        if self.is_gdn:
+            self.w = to_rows(qm.org_weight.detach())
+            self.rows = self.w.shape[0]
+            self.stride, self.pad, self.K = 1, 0, 1
+            self.w4 = (self.rows, 1, 1, self.rows)
+            self.bias = None
+        else:
+            self._layout(qm.bias)
+        self.channel_wise = True
+        self.delta = self.zp = None
+        self.n_levels = q.n_levels
+        rows = to_rows(qm.org_weight.detach(), self.tconv is not None)            # unflipped: where the blocks are
+        lo, gap = ops.mx_neighbours(rows.reshape(rows.shape[0], -1), self.fmt)
+        lo, gap = lo.reshape(rows.shape), gap.reshape(rows.shape)
+        if self.tconv is not None:
+            lo, gap = lo.flip(1, 2), gap.flip(1, 2)
+        self.lo, self.gap = lo.reshape(self.w.shape).contiguous(), gap.reshape(self.w.shape).contiguous()
+        if self.is_gdn:
+            self.inverse = bool(qm.fwd_kwargs["inverse"])
+            self.beta, reparam = qm.gdn_constants()
+            self.beta = self.beta.to(self.w.device).contiguous()
+            self.desc = ops.ada_desc(self.w, self.n_levels, reparam=reparam)
+        else:
+            self.desc = ops.ada_desc(self.w, self.n_levels)
+        # bound of |soft weight| over the whole run: both neighbours of every element (through the GDN re-parametrisation)
+        wb = float(torch.maximum(self.lo.abs(), (self.lo + self.gap).abs()).max())
+        if not math.isfinite(wb):
+            raise ValueError(f"calibration engine: the weight of op '{name}' is not finite")
+        if self.is_gdn:
+            wb = max(wb, float(self.desc.reparam_bound)) ** 2
+        self.wscale = ops.pow2_scale(wb)
+        self.alpha = torch.empty_like(self.w)
+        self.m = torch.zeros_like(self.w)
+        self.v = torch.zeros_like(self.w)
+        self.wq = torch.empty_like(self.w)
+        self.wd = torch.empty_like(self.w) if (need_dgrad or self.is_gdn) else None
+        self.init_alpha()
+        self.set_weight(True)
+        self.slabs = self.slabs_p = None
+        self.dalpha = None
+        if self.tconv is not None and os.environ.get("RDO_TCONV_PHASE", "1") != "0":
+            self._init_phase()
+
+    def init_alpha(self):
+        ops.mx_round_init_alpha(self.w, self.lo, self.gap, self.alpha)
+
+    def set_weight(self, soft):
+        ops.mx_round_fwd(self.desc, self.lo, self.gap, self.alpha, bool(soft), self.fmt, wq=self.wq, wd=self.wd)
+
+    def step(self, eng, scale):
+        ops.mx_round_step(self.desc, self.lo, self.gap, self.slabs, scale, eng.weight, eng.sched, eng.it, self.alpha, self.m, self.v,
+                          self.wq, self.wd, eng.round_log)
+
+
+def _make_op(name, qm, need_dgrad):
+    from .mx import is_mx_learned
+    return (_MxOp if is_mx_learned(qm.weight_quantizer) else _Op)(name, qm, need_dgrad)
 
 
 class UnitEngine(DpLoop, RdTask):
@@ -427,26 +515,34 @@ class UnitEngine(DpLoop, RdTask):
         m, k = self.mods, self.kind
         o = OrderedDict()
         if k == "layer":
-            o["layer"] = _Op("layer", m["layer"], False)
+            o["layer"] = _make_op("layer", m["layer"], False)
         elif k == "rb":
-            o["conv1"] = _Op("conv1", m["conv1"], False)
-            o["conv2"] = _Op("conv2", m["conv2"], True)
+            o["conv1"] = _make_op("conv1", m["conv1"], False)
+            o["conv2"] = _make_op("conv2", m["conv2"], True)
             if m.get("skip") is not None:
-                o["skip"] = _Op("skip", m["skip"], False)
+                o["skip"] = _make_op("skip", m["skip"], False)
         elif k == "rbws":
-            o["conv1"] = _Op("conv1", m["conv1"], False)
-            o["conv2"] = _Op("conv2", m["conv2"], True)
-            o["gdn"] = _Op("gdn", m["gdn"], False)
+            o["conv1"] = _make_op("conv1", m["conv1"], False)
+            o["conv2"] = _make_op("conv2", m["conv2"], True)
+            o["gdn"] = _make_op("gdn", m["gdn"], False)
             if m.get("skip") is not None:
-                o["skip"] = _Op("skip", m["skip"], False)
+                o["skip"] = _make_op("skip", m["skip"], False)
         elif k == "rbu":
-            o["subpel_conv"] = _Op("subpel_conv", m["subpel_conv"], False)
-            o["conv"] = _Op("conv", m["conv"], True)
-            o["igdn"] = _Op("igdn", m["igdn"], False)
-            o["upsample"] = _Op("upsample", m["upsample"], False)
+            o["subpel_conv"] = _make_op("subpel_conv", m["subpel_conv"], False)
+            o["conv"] = _make_op("conv", m["conv"], True)
+            o["igdn"] = _make_op("igdn", m["igdn"], False)
+            o["upsample"] = _make_op("upsample", m["upsample"], False)
         for op in o.values():
             if op.need_dgrad and (op.stride != 1 or 2 * op.pad != op.K - 1):
                 raise NotImplementedError("calibration engine: dgrad is built for stride-1 'same' convolutions only")
+        mx = [n for n, op in o.items() if op.is_mx]
+        if mx and len(mx) != len(o):
+            raise NotImplementedError(f"calibration engine: ops {mx} are on MX grids and {[n for n in o if n not in mx]} on integer grids: "
+                                      "a unit is calibrated on one kind of grid")
+        if mx and (self.split or self.rd is not None):
+            # the MX step is the per-op fused launch only (rdo_mx_round_step): no gradient-only / apply pair, no batched form
+            raise NotImplementedError("calibration engine: learned rounding on MX grids is not built for " +
+                                      ("data-parallel calibration (world_size > 1)" if self.split else "loss_mode='rd'"))
         self.ops = o
         # Data parallel: one flat bucket of d(rec+task)/d(alpha) per unit.  The op whose weight gradient is the LAST kernel of the
         # backward pass (the block's first conv) sits at the end of the bucket: everything in front of it is complete before that
@@ -1079,7 +1175,7 @@ class UnitEngine(DpLoop, RdTask):
     def _set_weights(self, soft):
         """soft-rounded (the state the loop runs in) or hard-rounded weights in every op's wq / wd (set-up only)"""
         for op in self.ops.values():
-            ops.adaround_fwd(op.desc, op.w, op.alpha, op.delta, op.zp, bool(soft), op.wq, op.wd)
+            op.set_weight(soft)
             if op.tc_phase is not None:
                 op.expand_phase()
 
@@ -1180,7 +1276,7 @@ class UnitEngine(DpLoop, RdTask):
             lg.warning("calibration unit left the fp16 range of its H2 planes%s: restarting it on fp32 activations",
                        " again" if self.h2_restarts > 1 else " with non-finite values")
         for op in self.ops.values():
-            ops.adaround_init_alpha(op.desc, op.w, op.delta, op.alpha)
+            op.init_alpha()
             op.m.zero_(); op.v.zero_()
             op.drop_planes()
         self._set_weights(soft=True)
@@ -1235,7 +1331,7 @@ class UnitEngine(DpLoop, RdTask):
     def _batchable(self, opl):
         """The tensors can go through rdo_adaround_step_batch: in ONE launch up to STEP_BATCH of them, else in ceil(n / STEP_BATCH) launches
         (an RSTB with six blocks has 37 trainable tensors: 37 single-tensor steps, 24 transposes and 48 plane splits per iteration before)."""
-        return self.batch_step and len(opl) >= 1 and all(op.numel() % 4 == 0 for op in opl)
+        return self.batch_step and len(opl) >= 1 and all(op.numel() % 4 == 0 and not op.is_mx for op in opl)
 
     def _step_batches(self, opl, scale, mode):
         """The batched step (mode 0) / update (mode 2) of `opl`.  The iteration counter moves by hand-over (the FIRST launch leaves
@@ -1309,7 +1405,8 @@ class UnitEngine(DpLoop, RdTask):
 
     def _step_ops(self, apply=False):
         """AdaRound step of every op of the unit + iteration counter: one batched launch (+ one for the dgrad layouts) when the
-        tensors allow it, else one launch per op.  The bf16 planes of the new weights are written by the same launches.
+        tensors allow it, else one launch per op.  The bf16 planes of the new weights are written by the same launches -- except for
+        ops on an MX grid (`_MxOp`: never batchable), whose step writes no planes: the split kernels follow it.
         apply (data parallel, plan B): the step from the all-reduced gradient bucket instead of from the weight-gradient slabs."""
         opl = list(self.ops.values())
         scale = self.bucket.scale if apply else 1.0
@@ -1318,11 +1415,16 @@ class UnitEngine(DpLoop, RdTask):
             self._after_step(lin_done=True)
             return
         for op in opl:
-            (ops.adaround_apply if apply else ops.adaround_step)(
-                op.desc, op.w, op.delta, op.zp, op.dalpha if apply else op.slabs, scale, self.weight, self.sched, self.it,
-                op.alpha, op.m, op.v, op.wq, op.wd, self.round_log, op.wq_planes, op.wd_planes)
+            if apply:
+                ops.adaround_apply(op.desc, op.w, op.delta, op.zp, op.dalpha, scale, self.weight, self.sched, self.it,
+                                   op.alpha, op.m, op.v, op.wq, op.wd, self.round_log, op.wq_planes, op.wd_planes)
+            else:
+                op.step(self, scale)
         ops.iter_advance(self.it)
         self._after_step()
+        for op in opl:
+            if op.is_mx:                       # rdo_mx_round_step writes no planes: the split kernels refresh them
+                op.split_planes(("wq_planes", "wd_planes"))
 
     def _next_plan(self):
         """close the plan being recorded and go on recording into a new one"""
@@ -1451,11 +1553,20 @@ class UnitEngine(DpLoop, RdTask):
 
     def finish(self):
         """Hand the trained rounding back to the modules: AdaRoundQuantizer with hard targets, `trained` flags
-        (layer_opt.py:313-316 / block_opt.py:316-321)."""
+        (layer_opt.py:313-316 / block_opt.py:316-321).  An op on an MX grid writes alpha into the module's own `MXAdaRoundQuantizer`:
+        no AdaRoundQuantizer is made for it."""
         self._check_overflow()
         for name, op in self.ops.items():
             qm = op.qm
             rows = op.alpha.flip(1, 2).contiguous() if op.tconv is not None else op.alpha
+            if op.is_mx:
+                # the module's MXAdaRoundQuantizer takes the rounding itself (alpha in `to_rows` layout: un-flipped for a transposed conv)
+                q = qm.weight_quantizer
+                q.alpha = rows.detach().clone().reshape(to_rows(qm.org_weight.data, op.tconv is not None).shape)
+                q.soft_targets = False
+                qm.act_quantizer.is_training = False
+                qm.drop_weight_pack()
+                continue
             if qm.kind == "linear":
                 rows = op.alpha.reshape(op.alpha.shape[0], -1)
             if not op.channel_wise and not op.is_ln:

@@ -47,12 +47,16 @@ class DpLoop:
     def _dp_capture(self):
         """One data-parallel iteration -- the recorded kernels of the plans AND the collectives -- as one graph, closed by the heartbeat:
         a device counter incremented and copied to pinned host memory by the graph's last two nodes.  torch's NCCL watchdog does not see
-        collectives replayed from a graph; the heartbeat is what tells the host that replays still complete (`_hb_wait`)."""
+        collectives replayed from a graph; the heartbeat is what tells the host that replays still complete (`_hb_wait`).
+        The capture is thread-local, like the plans' own (csrc/runtime.hip): a process group brings threads of its own -- torch's
+        watchdog polls the events of the eager iteration's collectives every 100 ms or so -- and under torch's default ("global") an
+        event query by ANY thread while this one captures invalidates the capture and fails in the thread that made it; there it is
+        nobody's exception to catch, and the process aborts."""
         if self._hb_dev is None:
             self._hb_dev = torch.zeros(1, dtype=torch.int64, device=self.dev)
             self._hb_host = torch.zeros(1, dtype=torch.int64).pin_memory()
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
+        with torch.cuda.graph(g, capture_error_mode="thread_local"):
             self._dp_iteration(False)
             self._hb_dev.add_(1)
             self._hb_host.copy_(self._hb_dev, non_blocking=True)

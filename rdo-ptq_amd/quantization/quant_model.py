@@ -159,15 +159,22 @@ class QuantModel(nn.Module):
         from .reports import format_report
         return format_report(self, images, formats=formats, lmbda=lmbda, batch=batch, units=units)
 
-    def set_weight_format(self, formats):
-        """Leave the weights of the units in an MX block format for evaluation: `formats` is one name for every unit, or a mapping unit
+    def set_weight_format(self, formats, rounding="nearest"):
+        """Leave the weights of the units in an MX block format: `formats` is one name for every unit, or a mapping unit
         name -> name (units it does not name keep theirs); a name is one of `hipops._lib.MX_FORMATS` or 'int'.  A format swaps the
         `weight_quantizer` of every weighted QuantModule of the unit for an `mx.MXQuantizer` and keeps the replaced quantiser on the
         module (`int_weight_quantizer`); 'int' puts that object back (a unit that holds no MX quantiser is left alone).  Names are
         validated and a unit that holds a trained module is refused (ValueError) before anything is written; every swap calls
-        `drop_weight_pack()`.  Activation quantisers are not touched."""
-        from .mx import MX_FORMATS, MXQuantizer, is_mx
+        `drop_weight_pack()`.  Activation quantisers are not touched.
+
+        rounding: 'nearest' (default: round to nearest, for evaluation) or 'learned' -- the unit gets `mx.MXAdaRoundQuantizer`s, which
+        round to nearest until `block_reconstruction` / `layer_reconstruction` has learned the rounding of the unit on its MX grid.
+        Anything else is a ValueError before anything is written.  Both classes swap back and re-swap alike."""
+        from .mx import MX_FORMATS, MX_ROUNDINGS, MXAdaRoundQuantizer, MXQuantizer, is_mx_any as is_mx
         what, known = "set_weight_format", self.units()
+        if not isinstance(rounding, str) or rounding not in MX_ROUNDINGS:
+            raise ValueError(f"{what}: rounding must be one of {list(MX_ROUNDINGS)}, got {rounding!r}")
+        make = MXAdaRoundQuantizer if rounding == "learned" else MXQuantizer
         plan = format_plan(what, known, formats, MX_FORMATS + ("int",))
         for n, _ in plan:
             if any(is_trained(m) for m in weighted_modules(known[n])):
@@ -183,7 +190,7 @@ class QuantModel(nn.Module):
                 else:
                     if not is_mx(q):
                         m.int_weight_quantizer = q
-                    m.weight_quantizer = MXQuantizer(fmt, tconv=m.if_tconv)
+                    m.weight_quantizer = make(fmt, tconv=m.if_tconv)
                 m.drop_weight_pack()
 
     def weight_bits(self):

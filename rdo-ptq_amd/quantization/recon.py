@@ -217,16 +217,45 @@ def _act_percentile_args(args):
     return _check_percentile(_arg(args, "act_percentile", 99.99))
 
 
+def _check_mx_learned(unit, named, args):
+    """A unit whose weighted modules hold `mx.MXAdaRoundQuantizer`s runs on the per-op MX step of the engine: all of them must hold one,
+    and what that first version does not serve is refused (NotImplementedError naming the option) before any cache is built."""
+    from .mx import is_mx_learned
+    weighted = [(n, m) for n, m in named if isinstance(m, QuantModule) and m.org_weight is not None]
+    learned = [n for n, m in weighted if is_mx_learned(m.weight_quantizer)]
+    if not learned:
+        return
+    what = "reconstruct: learned rounding on MX grids"
+    other = [n for n, m in weighted if not is_mx_learned(m.weight_quantizer)]
+    if other:
+        raise NotImplementedError(f"{what}: module {other[0]!r} holds an integer-grid quantiser next to the MXAdaRoundQuantizer of module "
+                                  f"{learned[0]!r}: a unit is calibrated on one kind of grid (set_weight_format names whole units)")
+    if _is_rstb(unit):
+        raise NotImplementedError(f"{what} is not built for RSTB / Swin units (unit of module {learned[0]!r})")
+    if dp.world()[1] > 1:
+        raise NotImplementedError(f"{what} is not built for data-parallel calibration (world_size > 1)")
+    if _arg(args, "loss_mode", "lp") == "rd":
+        raise NotImplementedError(f"{what} is not built for loss_mode='rd'")
+    if _arg(args, "bias_correct", None) not in (None, False):
+        raise NotImplementedError(f"{what}: args.bias_correct is not built for it (the correction reads an integer grid)")
+    if _arg(args, "unit_report", False):
+        raise NotImplementedError(f"{what}: args.unit_report is not built for it (the report re-rounds an integer grid to nearest)")
+
+
 def reconstruct(model, unit, unit_name, cali_data, *a, **kw):
     """`_reconstruct` with the cross-unit state tidied up: the full-precision cache memo of the schedule
     (quantization/utils.py::_FpMemo) is dropped when a unit raises, so a schedule that dies half-way pins no device memory; and the
     quantisers that `_reconstruct` put on torch's tape for the unit (`act_ste`: loss_mode='rd' behind frozen activation quantisers) are
     taken off it again, whatever happened.  A unit that holds an `MXQuantizer` is refused (NotImplementedError) before any cache is
-    built."""
+    built; one whose weighted modules all hold an `MXAdaRoundQuantizer` is calibrated on its MX grid (`_check_mx_learned` has what that
+    path refuses)."""
     from .mx import refuse_mx
     inside = unit.named_modules() if isinstance(unit, torch.nn.Module) else ()
-    refuse_mx("reconstruct", [(f"{unit_name}.{n}" if n else unit_name, m) for n, m in inside], NotImplementedError,
-              "learned rounding on MX grids is not built (QuantModel.set_weight_format('int') puts the integer grid back)")
+    named = [(f"{unit_name}.{n}" if n else unit_name, m) for n, m in inside]
+    refuse_mx("reconstruct", named, NotImplementedError,
+              "learned rounding on MX grids is not built (QuantModel.set_weight_format('int') puts the integer grid back; "
+              "set_weight_format(..., rounding='learned') installs the quantiser that this loop calibrates)", learned=False)
+    _check_mx_learned(unit, named, kw.get("args", a[13] if len(a) > 13 else None))
     ste = []
     try:
         return _reconstruct(model, unit, unit_name, cali_data, *a, _ste=ste, **kw)
