@@ -8,33 +8,25 @@
 //   layer_opt.py:159-165  round_loss = weight * sum(1 - (2|h - .5|)^b)
 //   layer_opt.py:254,307  torch.optim.Adam(lr=1e-3, betas=(.9,.999), eps=1e-8), one step per iteration
 //   quant_layer.py:142-146 (GDN gamma): gamma' = max(w~, bound)^2 - pedestal, LowerBound gradient rule (CompressAI)
-// This file is built with -ffp-contract=off so products and sums round separately, as the reference's op chain does.
+// The element step itself is stated in ada_device.h, which mx_round.hip shares; this file supplies the integer grid (IntGrid) and the
+// layouts of its two forms.  Built with -ffp-contract=off so products and sums round separately, as the reference's op chain does.
 #include "rdo_common.h"
 #include "gather_body.h"
 #include "../../include/rdo_ptq_subpel.h"
 #include "uaq_device.h"
 
+#ifdef RDO_DIAG
 namespace {
+// ablation mask of a diagnostic build (tools/ada_step_ablate.py; set by rdo_diag_ada_ablate, read by the kernels at run time so that
+// captured graphs follow it): 1 slab reads off, 2 plane writes off, 4 rounding term off, 8 Adam state off, 16 dgrad-layout work off,
+// 32 fp32 wq write off
+__device__ int g_ada_abl = 0;
+}  // namespace
+#define ADA_ABL(bit) ((g_ada_abl & (bit)) != 0)
+#endif
+#include "ada_device.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr float kGamma = -0.1f, kZeta = 1.1f;
-constexpr float kBeta2 = 0.999f, kAdamEps = 1e-8f;
-// 1 - beta as torch.optim.Adam forms it (in double, then one rounding): 1.f - 0.999f is 1.3e-5 below 0.001, and until
-// tests/test_gpu_adaround_step.py read adam_v against float64 every second moment carried that factor.  beta1 = 0.9 enters as 1 - beta1 only.
-constexpr float kOmBeta1 = (float)(1.0 - 0.9), kOmBeta2 = (float)(1.0 - 0.999);
-
-__device__ __forceinline__ float sigmoidf_(float a) { return 1.0f / (1.0f + __expf(-a)); }
-
-// u^p for u in [0, 1], p in [1, 19] (the rounding regulariser's (2|h - 1/2|)^(b-1)) on the transcendental unit: exp2(p * log2 u).
-// HIP's __powf is the correctly rounded library pow -- ~190 instructions, more than the rest of an element's step together and
-// ~150 us of every calibration step of the Cheng2020 schedule (tools/ada_step_ablate.py, profiles/r06a_ada_step_ablate.md).  v_log_f32 /
-// v_exp_f32 are good to 1 ulp of their results: the power's relative error is <= 4e-8 * |p log2 u|, i.e. <= 3 ulp wherever the
-// result is above 1e-3 and an absolute error below 1e-9 everywhere else (the term is a regulariser's value and slope next to a data
-// gradient that carries the fp32 summation-order noise of 65 536-pixel reductions).
-__device__ __forceinline__ float pow_u(float u, float p) {
-    return (u > 0.f) ? __builtin_amdgcn_exp2f(__builtin_amdgcn_logf(u) * p) : 0.f;
-}
+namespace {
 
 struct AdaArgs {
     rdo_ada_desc d;
@@ -66,15 +58,6 @@ struct AdaArgs {
     int row_groups;              // 4: rows in 4 groups (rdo_adaround_step_batch_gather_px; tile form only) -- the slabs are read and the forward
                                  // planes written at row (r & 3) rows / 4 + (r >> 2) of logical row r; 0: everything in logical order
 };
-#ifdef RDO_DIAG
-// ablation mask of a diagnostic build (tools/ada_step_ablate.py; set by rdo_diag_ada_ablate, read by the kernels at run time so that
-// captured graphs follow it): 1 slab reads off, 2 plane writes off, 4 rounding term off, 8 Adam state off, 16 dgrad-layout work off,
-// 32 fp32 wq write off
-__device__ int g_ada_abl = 0;
-#define ADA_ABL(bit) ((g_ada_abl & (bit)) != 0)
-#else
-#define ADA_ABL(bit) false
-#endif
 
 // element (n, k) of W [rows][inner] in the fragment order of rdo_linear_h2 (linear_h2.hip, rdo_split_h2_linear): half index inside a plane
 __device__ __forceinline__ long lin_frag_index(int n, int k, int nblk) {
@@ -89,37 +72,23 @@ __device__ __forceinline__ void lin_split(float v, float scale, unsigned short& 
     if (!(fabsf(x) <= 65504.f)) bad = 1;
 }
 
-// exact three-way bf16 split (hardware RNE conversions), as rdo_split_bf16x3
-__device__ __forceinline__ void split3_store(float v, unsigned short* planes, long n, long i) {
-    const __bf16 h = (__bf16)v;
-    const float r1 = v - (float)h;
-    const __bf16 m = (__bf16)r1;
-    const __bf16 l = (__bf16)(r1 - (float)m);
-    planes[i] = __builtin_bit_cast(unsigned short, h);
-    planes[n + i] = __builtin_bit_cast(unsigned short, m);
-    planes[2 * n + i] = __builtin_bit_cast(unsigned short, l);
-}
-
-__device__ __forceinline__ long wd_index(const rdo_ada_desc& d, long e) {
-    // e = ((co*KH + kh)*KW + kw)*Cin + ci  ->  ((ci*KH + KH-1-kh)*KW + KW-1-kw)*Cout + co
-    const int Cin = d.Cin, KW = d.KW, KH = d.KH;
-    long t = e / Cin;
-    const int ci = (int)(e - t * Cin);
-    const int kw = (int)(t % KW); t /= KW;
-    const int kh = (int)(t % KH);
-    const long co = t / KH;
-    return (((long)ci * KH + (KH - 1 - kh)) * KW + (KW - 1 - kw)) * d.rows + co;
-}
-
-// emit kernel-layout weight(s) from the quantised value
-__device__ __forceinline__ void emit(const rdo_ada_desc& d, long e, float q, float* wq, float* wd) {
-    float o = q;
-    if (d.reparam) {
-        const float lb = fmaxf(q, d.reparam_bound);
-        o = lb * lb - d.reparam_pedestal;
+// The integer grid of one weight in a row of step delta and zero point zp (ada_element's Grid): xf = floor(w / delta), Lm1 = L - 1
+struct IntGrid {
+    float xf, z, dl, Lm1;
+    __device__ __forceinline__ float q(float h) const { return (fminf(fmaxf(xf + h + z, 0.f), Lm1) - z) * dl; }   // (x_floor + h) + zp
+    __device__ __forceinline__ float dq_dh(float g, float h) const {
+        const float xint = xf + h + z;
+        const float pass_q = (xint >= 0.f && xint <= Lm1) ? 1.f : 0.f;
+        return (g * dl) * pass_q;
     }
-    wq[e] = o;
-    if (wd && d.Cin > 0) wd[wd_index(d, e)] = o;
+};
+
+// One element's step, for both forms: element k of the thread's vectors (ada_element), a weight of a row of step dl and zero point z
+template <typename V>
+__device__ __forceinline__ void ada_int_element(const AdaArgs& a, const rdo_ada_desc& d, int mode, float Lm1, const rdo_sched_row& sc,
+                                                float dl, float z, int k, const V& w, const V& g, V& al, V& m, V& v, V& o, float& rl_local) {
+    const IntGrid grid{floorf(w[k] / dl), z, dl, Lm1};
+    ada_element(grid, d, mode, k, g, al, m, v, o, a.grad_scale, a.round_weight, sc.b, sc.round_on, sc.step_size, sc.bc2_sqrt, rl_local);
 }
 
 // One thread per 4 consecutive weight elements (16-byte accesses on every stream: w, alpha, m, v, nsplit slabs, wq).
@@ -130,16 +99,16 @@ __device__ __forceinline__ void ada_step_body(const AdaArgs& a, const long bid, 
     const rdo_ada_desc d = a.d;
     const long inner = d.numel / d.rows;
     const float Lm1 = (float)(d.n_levels - 1);
-    float b = 0.f, round_on = 0.f, step_size = 0.f, bc2 = 1.f;
+    rdo_sched_row sc = {0.f, 0.f, 0.f, 1.f};
     int it = 0;
     if (a.mode != 1) {
         it = *a.iter_ptr;
-        const rdo_sched_row s = a.sched[it];
-        b = s.b; round_on = s.round_on; step_size = s.step_size; bc2 = s.bc2_sqrt;
+        sc = a.sched[it];
     }
     float rl_local = 0.f;
     const long nq = d.numel / W;
     for (long qi = bid * blockDim.x + threadIdx.x; qi < nq; qi += nblk * blockDim.x) {
+        // ---- load the streams
         const long e0 = qi * W;
         const vec_t wv4 = *reinterpret_cast<const vec_t*>(a.w + e0);
         vec_t al4 = *reinterpret_cast<const vec_t*>(a.alpha + e0);
@@ -147,31 +116,7 @@ __device__ __forceinline__ void ada_step_body(const AdaArgs& a, const long bid, 
         if (a.mode == 2) {
             g4 = *reinterpret_cast<const vec_t*>(a.dalpha_in + e0);
         } else if (!ADA_ABL(1)) {
-            // eight slab loads in flight per thread: with ~5 waves per CU at these sizes a serial chain of nsplit dependent
-            // loads (one L2 / fabric round trip each) was the whole kernel time
-            const float* sp = a.slabs + e0;
-            int s = 0;
-            for (; s + 16 <= a.nsplit; s += 16) {            // long chains (the 28-slab 3x3 convs, the 256-slab 1x1): sixteen in flight
-                vec_t t[16];
-#pragma unroll
-                for (int u = 0; u < 16; ++u) t[u] = *reinterpret_cast<const vec_t*>(sp + (long)(s + u) * d.numel);
-                g4 += (((t[0] + t[1]) + (t[2] + t[3])) + ((t[4] + t[5]) + (t[6] + t[7]))) +
-                      (((t[8] + t[9]) + (t[10] + t[11])) + ((t[12] + t[13]) + (t[14] + t[15])));
-            }
-            for (; s + 8 <= a.nsplit; s += 8) {
-                vec_t t[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) t[u] = *reinterpret_cast<const vec_t*>(sp + (long)(s + u) * d.numel);
-                g4 += ((t[0] + t[1]) + (t[2] + t[3])) + ((t[4] + t[5]) + (t[6] + t[7]));
-            }
-            if (s + 4 <= a.nsplit) {
-                vec_t t[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) t[u] = *reinterpret_cast<const vec_t*>(sp + (long)(s + u) * d.numel);
-                g4 += (t[0] + t[1]) + (t[2] + t[3]);
-                s += 4;
-            }
-            for (; s < a.nsplit; ++s) g4 += *reinterpret_cast<const vec_t*>(sp + (long)s * d.numel);
+            g4 = slab_sum(g4, a.slabs + e0, a.nsplit, d.numel);
         }
         vec_t m4 = wv4 * 0.f, v4 = m4, o4 = m4;
         if (a.mode != 1 && !ADA_ABL(8)) {
@@ -191,60 +136,11 @@ __device__ __forceinline__ void ada_step_body(const AdaArgs& a, const long bid, 
 #pragma unroll
             for (int k = 0; k < W; ++k) rows[k] = (int)((e0 + k) / inner);
         }
+        // ---- the element step
 #pragma unroll
-        for (int k = 0; k < W; ++k) {
-            const int row = rows[k];
-            const float dl = a.delta[row], z = a.zp[row], wv = wv4[k];
-            float al = al4[k];
-            const float xf = floorf(wv / dl);
-            const float sg = sigmoidf_(al);
-            const float hraw = sg * (kZeta - kGamma) + kGamma;
-            const float h = fminf(fmaxf(hraw, 0.f), 1.f);
-            const float xint = xf + h + z;       // (x_floor + h) + zp
-            const float pass_h = (hraw >= 0.f && hraw <= 1.f) ? 1.f : 0.f;
-            const float dh_da = pass_h * ((kZeta - kGamma) * (sg * (1.f - sg)));
-            float g_alpha = g4[k];  // mode 2: already the data gradient w.r.t. alpha
-            if (a.mode != 2) {
-                float g = g4[k];
-                if (d.reparam) {
-                    const float q = (fminf(fmaxf(xint, 0.f), Lm1) - z) * dl;
-                    const float lb = fmaxf(q, d.reparam_bound);
-                    const float go = g * (2.f * lb);                      // d(lb^2)/dlb
-                    g = (q >= d.reparam_bound || go < 0.f) ? go : 0.f;    // LowerBound backward
-                }
-                const float pass_q = (xint >= 0.f && xint <= Lm1) ? 1.f : 0.f;
-                g_alpha = (g * dl) * pass_q * dh_da;
-            }
-            if (a.mode == 1) {
-                o4[k] = g_alpha;
-                continue;
-            }
-            // rounding regulariser (value of the current alpha, gradient through h)
-            float g_total = g_alpha * a.grad_scale;
-            if (round_on != 0.f && !ADA_ABL(4)) {
-                const float u = fabsf(h - 0.5f) * 2.f;
-                const float ub1 = pow_u(u, b - 1.f);                       // u^(b-1); u^b = u * u^(b-1)
-                rl_local += a.round_weight * (1.f - u * ub1);
-                const float sgn = (h > 0.5f) ? 1.f : ((h < 0.5f) ? -1.f : 0.f);
-                g_total += (-a.round_weight * (b * ub1) * 2.f * sgn) * dh_da;
-            }
-            // Adam (torch.optim.Adam defaults; alpha has no weight decay)
-            float mm = m4[k], vv = v4[k];
-            mm = fmaf(g_total - mm, kOmBeta1, mm);                       // lerp as one fma: a single rounding behind the difference
-            vv = fmaf(vv, kBeta2, kOmBeta2 * g_total * g_total);
-            const float denom = sqrtf(vv) / bc2 + kAdamEps;
-            al = al - step_size * (mm / denom);
-            m4[k] = mm; v4[k] = vv; al4[k] = al;
-            // next iteration's soft weight
-            const float sg2 = sigmoidf_(al);
-            const float h2 = fminf(fmaxf(sg2 * (kZeta - kGamma) + kGamma, 0.f), 1.f);
-            float o = (fminf(fmaxf(xf + h2 + z, 0.f), Lm1) - z) * dl;
-            if (d.reparam) {
-                const float lb = fmaxf(o, d.reparam_bound);
-                o = lb * lb - d.reparam_pedestal;
-            }
-            o4[k] = o;
-        }
+        for (int k = 0; k < W; ++k)
+            ada_int_element(a, d, a.mode, Lm1, sc, a.delta[rows[k]], a.zp[rows[k]], k, wv4, g4, al4, m4, v4, o4, rl_local);
+        // ---- store: dalpha (mode 1), or the state, the next soft weight and its planes
         if (a.mode == 1) {
             *reinterpret_cast<vec_t*>(a.dalpha_out + e0) = o4;
         } else {
@@ -278,14 +174,7 @@ __device__ __forceinline__ void ada_step_body(const AdaArgs& a, const long bid, 
             if (a.wq_planes && a.wq_pscale > 0.f) {            // fp16 two-way split of wq * scale, fragment order
                 int bad = 0;
                 if constexpr (W == 4) {
-                    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-                    u32x2 ph, pl;
-                    unsigned h, l;
-                    rdo::h2_split_pk(o4[0], o4[1], a.wq_pscale, h, l, bad); ph[0] = h; pl[0] = l;
-                    rdo::h2_split_pk(o4[2], o4[3], a.wq_pscale, h, l, bad); ph[1] = h; pl[1] = l;
-                    const long f0 = d.Cin > 0 ? rdo::frag_index(e0, d.rows, d.KH, d.KW, d.Cin) : e0;
-                    *reinterpret_cast<u32x2*>(a.wq_planes + f0) = ph;
-                    *reinterpret_cast<u32x2*>(a.wq_planes + d.numel + f0) = pl;
+                    h2_store4(o4, a.wq_pscale, a.wq_planes, d.numel, d.Cin > 0 ? rdo::frag_index(e0, d.rows, d.KH, d.KW, d.Cin) : e0, bad);
                 } else {
 #pragma unroll
                     for (int k = 0; k < W; ++k)
@@ -294,24 +183,9 @@ __device__ __forceinline__ void ada_step_body(const AdaArgs& a, const long bid, 
                 }
                 rdo::h2_report(bad, a.ovf);
             } else if (a.wq_planes) {
-                if constexpr (W == 4) {                        // one 8-byte store per plane
-                    typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
-                    u16x4 ph, pm, pl;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const __bf16 h = (__bf16)o4[k];
-                        const float r1 = o4[k] - (float)h;
-                        const __bf16 m = (__bf16)r1;
-                        const __bf16 l = (__bf16)(r1 - (float)m);
-                        ph[k] = __builtin_bit_cast(unsigned short, h);
-                        pm[k] = __builtin_bit_cast(unsigned short, m);
-                        pl[k] = __builtin_bit_cast(unsigned short, l);
-                    }
+                if constexpr (W == 4) {
                     // fragment order (rdo::frag_index): four consecutive channels stay consecutive (Cin % 16 == 0, e0 % 4 == 0)
-                    const long f0 = d.Cin > 0 ? rdo::frag_index(e0, d.rows, d.KH, d.KW, d.Cin) : e0;
-                    *reinterpret_cast<u16x4*>(a.wq_planes + f0) = ph;
-                    *reinterpret_cast<u16x4*>(a.wq_planes + d.numel + f0) = pm;
-                    *reinterpret_cast<u16x4*>(a.wq_planes + 2 * d.numel + f0) = pl;
+                    split3_store4(o4, a.wq_planes, d.numel, d.Cin > 0 ? rdo::frag_index(e0, d.rows, d.KH, d.KW, d.Cin) : e0);
                 } else {
 #pragma unroll
                     for (int k = 0; k < W; ++k)
@@ -320,12 +194,7 @@ __device__ __forceinline__ void ada_step_body(const AdaArgs& a, const long bid, 
             }
         }
     }
-    if (a.mode != 1 && a.round_loss_out && round_on != 0.f) {
-        const float t = rdo::block_sum(rl_local);           // the condition holds kernel arguments only: uniform over the workgroup
-        if (threadIdx.x == 0) {
-            if (t != 0.f) atomicAdd(a.round_loss_out + (long)it * RDO_LOG_SLOTS + (bid & (RDO_LOG_SLOTS - 1)), t);
-        }
-    }
+    if (a.mode != 1) publish_round_loss(a.round_loss_out, sc.round_on, it, bid, rl_local);
 }
 
 
@@ -338,9 +207,7 @@ __device__ __forceinline__ void ada_step_body(const AdaArgs& a, const long bid, 
 // (wd_transpose_batch_kernel) that re-read wq: 13 launches and ~0.1-0.2 ms of every calibration step of the Cheng2020 schedule
 // (profiles/r06a_ada_step_ablate.md).  Needs Cin % 4 == 0 and rows % 4 == 0; everything else stays on the flat form above.
 __device__ __forceinline__ void ada_step_tile_body(const AdaArgs& a, int bid) {
-    typedef float vec_t __attribute__((ext_vector_type(4)));
-    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-    typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
+    typedef f32x4 vec_t;
     const rdo_ada_desc d = a.d;
     const int Cin = d.Cin, taps = d.KH * d.KW, nrows = d.rows;
     const int ctiles = (Cin + 31) >> 5;
@@ -354,42 +221,21 @@ __device__ __forceinline__ void ada_step_tile_body(const AdaArgs& a, int bid) {
     const float Lm1 = (float)(d.n_levels - 1);
     const int it = *a.iter_ptr;
     const rdo_sched_row sc = a.sched[it];
-    const float b = sc.b, round_on = sc.round_on, step_size = sc.step_size, bc2 = sc.bc2_sqrt;
+    const int mode = a.mode == 2 ? 2 : 0;                     // (mode 1 never takes this form: tile_ok)
     float rl_local = 0.f;
     vec_t o4 = {0.f, 0.f, 0.f, 0.f};
     const long e0 = ((long)row * taps + tap) * Cin + ci;
     const int rowg = a.row_groups ? rdo::group_row(row, nrows) : row;      // where the slabs and the forward planes keep this row
     const long eg = ((long)rowg * taps + tap) * Cin + ci;
     if (live) {
+        // ---- load the streams
         const vec_t wv4 = *reinterpret_cast<const vec_t*>(a.w + e0);
         vec_t al4 = *reinterpret_cast<const vec_t*>(a.alpha + e0);
         vec_t g4 = {0.f, 0.f, 0.f, 0.f};
-        if (a.mode == 2) {
+        if (mode == 2) {
             g4 = *reinterpret_cast<const vec_t*>(a.dalpha_in + e0);
         } else if (!ADA_ABL(1)) {
-            const float* sp = a.slabs + eg;                     // same summation order as the flat form
-            int s = 0;
-            for (; s + 16 <= a.nsplit; s += 16) {
-                vec_t t[16];
-#pragma unroll
-                for (int u = 0; u < 16; ++u) t[u] = *reinterpret_cast<const vec_t*>(sp + (long)(s + u) * d.numel);
-                g4 += (((t[0] + t[1]) + (t[2] + t[3])) + ((t[4] + t[5]) + (t[6] + t[7]))) +
-                      (((t[8] + t[9]) + (t[10] + t[11])) + ((t[12] + t[13]) + (t[14] + t[15])));
-            }
-            for (; s + 8 <= a.nsplit; s += 8) {
-                vec_t t[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) t[u] = *reinterpret_cast<const vec_t*>(sp + (long)(s + u) * d.numel);
-                g4 += ((t[0] + t[1]) + (t[2] + t[3])) + ((t[4] + t[5]) + (t[6] + t[7]));
-            }
-            if (s + 4 <= a.nsplit) {
-                vec_t t[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) t[u] = *reinterpret_cast<const vec_t*>(sp + (long)(s + u) * d.numel);
-                g4 += (t[0] + t[1]) + (t[2] + t[3]);
-                s += 4;
-            }
-            for (; s < a.nsplit; ++s) g4 += *reinterpret_cast<const vec_t*>(sp + (long)s * d.numel);
+            g4 = slab_sum(g4, a.slabs + eg, a.nsplit, d.numel);     // same summation order as the flat form
         }
         vec_t m4 = {0.f, 0.f, 0.f, 0.f}, v4 = m4;
         if (!ADA_ABL(8)) {
@@ -397,51 +243,10 @@ __device__ __forceinline__ void ada_step_tile_body(const AdaArgs& a, int bid) {
             v4 = *reinterpret_cast<const vec_t*>(a.v + e0);
         }
         const float dl = a.delta[row], z = a.zp[row];
+        // ---- the element step
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float al = al4[k];
-            const float xf = floorf(wv4[k] / dl);
-            const float sg = sigmoidf_(al);
-            const float hraw = sg * (kZeta - kGamma) + kGamma;
-            const float h = fminf(fmaxf(hraw, 0.f), 1.f);
-            const float xint = xf + h + z;
-            const float pass_h = (hraw >= 0.f && hraw <= 1.f) ? 1.f : 0.f;
-            const float dh_da = pass_h * ((kZeta - kGamma) * (sg * (1.f - sg)));
-            float g_alpha = g4[k];
-            if (a.mode != 2) {
-                float g = g4[k];
-                if (d.reparam) {
-                    const float qv = (fminf(fmaxf(xint, 0.f), Lm1) - z) * dl;
-                    const float lb = fmaxf(qv, d.reparam_bound);
-                    const float go = g * (2.f * lb);
-                    g = (qv >= d.reparam_bound || go < 0.f) ? go : 0.f;
-                }
-                const float pass_q = (xint >= 0.f && xint <= Lm1) ? 1.f : 0.f;
-                g_alpha = (g * dl) * pass_q * dh_da;
-            }
-            float g_total = g_alpha * a.grad_scale;
-            if (round_on != 0.f && !ADA_ABL(4)) {
-                const float u = fabsf(h - 0.5f) * 2.f;
-                const float ub1 = pow_u(u, b - 1.f);
-                rl_local += a.round_weight * (1.f - u * ub1);
-                const float sgn = (h > 0.5f) ? 1.f : ((h < 0.5f) ? -1.f : 0.f);
-                g_total += (-a.round_weight * (b * ub1) * 2.f * sgn) * dh_da;
-            }
-            float mm = m4[k], vv = v4[k];
-            mm = fmaf(g_total - mm, kOmBeta1, mm);                       // lerp as one fma: a single rounding behind the difference
-            vv = fmaf(vv, kBeta2, kOmBeta2 * g_total * g_total);
-            const float denom = sqrtf(vv) / bc2 + kAdamEps;
-            al = al - step_size * (mm / denom);
-            m4[k] = mm; v4[k] = vv; al4[k] = al;
-            const float sg2 = sigmoidf_(al);
-            const float h2 = fminf(fmaxf(sg2 * (kZeta - kGamma) + kGamma, 0.f), 1.f);
-            float o = (fminf(fmaxf(xf + h2 + z, 0.f), Lm1) - z) * dl;
-            if (d.reparam) {
-                const float lb = fmaxf(o, d.reparam_bound);
-                o = lb * lb - d.reparam_pedestal;
-            }
-            o4[k] = o;
-        }
+        for (int k = 0; k < 4; ++k) ada_int_element(a, d, mode, Lm1, sc, dl, z, k, wv4, g4, al4, m4, v4, o4, rl_local);
+        // ---- store the state, the next soft weight and its forward planes
         if (!ADA_ABL(8)) {
             *reinterpret_cast<vec_t*>(a.m + e0) = m4;
             *reinterpret_cast<vec_t*>(a.v + e0) = v4;
@@ -450,47 +255,19 @@ __device__ __forceinline__ void ada_step_tile_body(const AdaArgs& a, int bid) {
         if (!ADA_ABL(32)) *reinterpret_cast<vec_t*>(a.wq + e0) = o4;
         if (!ADA_ABL(2)) {
             int bad = 0;
-            if (a.lin_fwd) {                                    // rdo_linear_h2 planes of W [rows][Cin]: four consecutive k = 8 bytes
-                unsigned hh, ll;
-                u32x2 ph, pl;
-                rdo::h2_split_pk(o4[0], o4[1], a.lin_pscale, hh, ll, bad); ph[0] = hh; pl[0] = ll;
-                rdo::h2_split_pk(o4[2], o4[3], a.lin_pscale, hh, ll, bad); ph[1] = hh; pl[1] = ll;
-                const long f = lin_frag_index(row, ci, nrows >> 4);
-                *reinterpret_cast<u32x2*>(a.lin_fwd + f) = ph;
-                *reinterpret_cast<u32x2*>(a.lin_fwd + (long)nrows * Cin + f) = pl;
-            }
+            // rdo_linear_h2 planes of W [rows][Cin]: four consecutive k = 8 bytes
+            if (a.lin_fwd) h2_store4(o4, a.lin_pscale, a.lin_fwd, (long)nrows * Cin, lin_frag_index(row, ci, nrows >> 4), bad);
             if (a.wq_planes) {
                 const long f0 = (Cin & 15) ? eg : (((((long)(ci >> 4) * taps + tap) * nrows + rowg) << 4) + (ci & 15));   // rdo::frag_index
-                if (a.wq_pscale > 0.f) {
-                    unsigned hh, ll;
-                    u32x2 ph, pl;
-                    rdo::h2_split_pk(o4[0], o4[1], a.wq_pscale, hh, ll, bad); ph[0] = hh; pl[0] = ll;
-                    rdo::h2_split_pk(o4[2], o4[3], a.wq_pscale, hh, ll, bad); ph[1] = hh; pl[1] = ll;
-                    *reinterpret_cast<u32x2*>(a.wq_planes + f0) = ph;
-                    *reinterpret_cast<u32x2*>(a.wq_planes + d.numel + f0) = pl;
-                } else {
-                    u16x4 ph, pm, pl;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const __bf16 hb = (__bf16)o4[k];
-                        const float r1 = o4[k] - (float)hb;
-                        const __bf16 mb = (__bf16)r1;
-                        const __bf16 lb = (__bf16)(r1 - (float)mb);
-                        ph[k] = __builtin_bit_cast(unsigned short, hb);
-                        pm[k] = __builtin_bit_cast(unsigned short, mb);
-                        pl[k] = __builtin_bit_cast(unsigned short, lb);
-                    }
-                    *reinterpret_cast<u16x4*>(a.wq_planes + f0) = ph;
-                    *reinterpret_cast<u16x4*>(a.wq_planes + d.numel + f0) = pm;
-                    *reinterpret_cast<u16x4*>(a.wq_planes + 2 * d.numel + f0) = pl;
-                }
+                if (a.wq_pscale > 0.f) h2_store4(o4, a.wq_pscale, a.wq_planes, d.numel, f0, bad);
+                else split3_store4(o4, a.wq_planes, d.numel, f0);
             }
             rdo::h2_report(bad, a.ovf);
         }
     }
     // ---- dgrad layout: transpose the tile's new soft weights through LDS (wave-uniform condition: the barrier is reached by all or none)
-    __shared__ float tile[32][33];
     if ((a.wd || a.lin_bwd) && !ADA_ABL(16)) {
+        float(&tile)[32][33] = lds_tile32();
 #pragma unroll
         for (int k = 0; k < 4; ++k) tile[r][4 * q + k] = o4[k];
         __syncthreads();
@@ -504,58 +281,23 @@ __device__ __forceinline__ void ada_step_tile_body(const AdaArgs& a, int bid) {
             const long o = ((long)ci2 * taps + tapf) * nrows + co2;
             if (a.wd) *reinterpret_cast<vec_t*>(a.wd + o) = t4;
             int bad = 0;
-            if (a.lin_bwd && !ADA_ABL(2)) {
-                unsigned hh, ll;
-                u32x2 ph, pl;
-                rdo::h2_split_pk(t4[0], t4[1], a.lin_pscale, hh, ll, bad); ph[0] = hh; pl[0] = ll;
-                rdo::h2_split_pk(t4[2], t4[3], a.lin_pscale, hh, ll, bad); ph[1] = hh; pl[1] = ll;
-                const long f = lin_frag_index(ci2, co2, Cin >> 4);
-                *reinterpret_cast<u32x2*>(a.lin_bwd + f) = ph;
-                *reinterpret_cast<u32x2*>(a.lin_bwd + (long)nrows * Cin + f) = pl;
-            }
+            if (a.lin_bwd && !ADA_ABL(2)) h2_store4(t4, a.lin_pscale, a.lin_bwd, (long)nrows * Cin, lin_frag_index(ci2, co2, Cin >> 4), bad);
             if (a.wd && a.wd_planes && !ADA_ABL(2)) {
                 // wd is the weight [Cin][KH][KW][Cout] of the dgrad conv: its planes go in THAT conv's fragment order (slices of 16 co)
                 const long f0 = (nrows & 15) ? o : (((((long)(co2 >> 4) * taps + tapf) * Cin + ci2) << 4) + (co2 & 15));
-                if (a.wd_pscale > 0.f) {
-                    unsigned hh, ll;
-                    u32x2 ph, pl;
-                    rdo::h2_split_pk(t4[0], t4[1], a.wd_pscale, hh, ll, bad); ph[0] = hh; pl[0] = ll;
-                    rdo::h2_split_pk(t4[2], t4[3], a.wd_pscale, hh, ll, bad); ph[1] = hh; pl[1] = ll;
-                    *reinterpret_cast<u32x2*>(a.wd_planes + f0) = ph;
-                    *reinterpret_cast<u32x2*>(a.wd_planes + d.numel + f0) = pl;
-                } else {
-                    u16x4 ph, pm, pl;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const __bf16 hb = (__bf16)t4[k];
-                        const float r1 = t4[k] - (float)hb;
-                        const __bf16 mb = (__bf16)r1;
-                        const __bf16 lb = (__bf16)(r1 - (float)mb);
-                        ph[k] = __builtin_bit_cast(unsigned short, hb);
-                        pm[k] = __builtin_bit_cast(unsigned short, mb);
-                        pl[k] = __builtin_bit_cast(unsigned short, lb);
-                    }
-                    *reinterpret_cast<u16x4*>(a.wd_planes + f0) = ph;
-                    *reinterpret_cast<u16x4*>(a.wd_planes + d.numel + f0) = pm;
-                    *reinterpret_cast<u16x4*>(a.wd_planes + 2 * d.numel + f0) = pl;
-                }
+                if (a.wd_pscale > 0.f) h2_store4(t4, a.wd_pscale, a.wd_planes, d.numel, f0, bad);
+                else split3_store4(t4, a.wd_planes, d.numel, f0);
             }
             rdo::h2_report(bad, a.ovf);
         }
     }
-    if (a.round_loss_out && round_on != 0.f) {
-        const float t = rdo::block_sum(rl_local);           // as in the flat form: a uniform condition
-        if (threadIdx.x == 0) {
-            if (t != 0.f) atomicAdd(a.round_loss_out + (long)it * RDO_LOG_SLOTS + (bid0 & (RDO_LOG_SLOTS - 1)), t);
-        }
-    }
+    publish_round_loss(a.round_loss_out, sc.round_on, it, bid0, rl_local);
 }
 
 // Does a tensor's fused step / apply run in the tile form?  (host side; the kernel gets the answer as `tile` in the batch descriptor)
 inline bool tile_ok(const rdo_ada_desc& d, int mode) {
     return mode != 1 && d.Cin > 0 && d.Cin % 4 == 0 && d.rows % 4 == 0 && (long)d.rows * d.KH * d.KW * d.Cin == d.numel && d.numel < (1L << 31);
 }
-inline long tile_blocks(const rdo_ada_desc& d) { return rdo::ceil_div(d.rows, 32) * d.KH * d.KW * rdo::ceil_div(d.Cin, 32); }
 
 template <int W>
 __global__ __launch_bounds__(256) void ada_step_kernel(AdaArgs a) {
@@ -598,41 +340,7 @@ __global__ __launch_bounds__(256) void ada_step_batch_kernel(AdaBatch b) {
     else ada_step_body<4>(b.a[t], (long)blockIdx.x - beg, (long)b.blk_end[t] - beg);
 }
 
-// wd[ci][KH-1-kh][KW-1-kw][co] = wq[co][kh][kw][ci]: 32x32 tiles through LDS, 128-byte segments on both sides
-__device__ __forceinline__ void wd_transpose_body(const rdo_ada_desc& d, const float* wq, float* wd, unsigned short* wd_planes, float pscale,
-                                                  int* ovf, int bid) {
-    const int taps = d.KH * d.KW, cdim = d.Cin;
-    const int ctiles = (cdim + 31) / 32;
-    const int ct = bid % ctiles; bid /= ctiles;
-    const int tap = bid % taps;
-    const int rt = bid / taps;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    __shared__ float tile[32][33];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int row = rt * 32 + ty + 8 * k, c = ct * 32 + tx;
-        if (row < d.rows && c < cdim) tile[ty + 8 * k][tx] = wq[((long)row * taps + tap) * cdim + c];
-    }
-    __syncthreads();
-    const int kh = tap / d.KW, kw = tap - kh * d.KW;
-    const int tapf = (d.KH - 1 - kh) * d.KW + (d.KW - 1 - kw);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int ci = ct * 32 + ty + 8 * k, co = rt * 32 + tx;
-        if (ci < cdim && co < d.rows) {
-            const long o = ((long)ci * taps + tapf) * d.rows + co;
-            wd[o] = tile[tx][ty + 8 * k];
-            // wd is the weight [Cin][KH][KW][Cout] of the dgrad conv: its planes go in that conv's fragment order
-            if (wd_planes && pscale > 0.f) {
-                int bad = 0;
-                rdo::h2_split_store(tile[tx][ty + 8 * k], pscale, wd_planes, d.numel, rdo::frag_index(o, d.Cin, d.KH, d.KW, d.rows), bad);
-                rdo::h2_report(bad, ovf);
-            } else if (wd_planes) {
-                split3_store(tile[tx][ty + 8 * k], wd_planes, d.numel, rdo::frag_index(o, d.Cin, d.KH, d.KW, d.rows));
-            }
-        }
-    }
-}
+// the dgrad layout of the flat form, a second launch (wd_transpose_body, ada_device.h)
 __global__ __launch_bounds__(256) void wd_transpose_kernel(rdo_ada_desc d, const float* wq, float* wd, unsigned short* wd_planes, float pscale,
                                                            int* ovf) {
     wd_transpose_body(d, wq, wd, wd_planes, pscale, ovf, blockIdx.x);
@@ -661,15 +369,8 @@ __global__ __launch_bounds__(256) void ada_fwd_kernel(rdo_ada_desc d, const floa
             emit(d, e, rdo::uaq_nearest(wv, dl, z, Lm1), wq, wd);
             continue;
         }
-        const float xf = floorf(wv / dl);
-        float h;
-        if (mode == 1) {
-            h = fminf(fmaxf(sigmoidf_(alpha[e]) * (kZeta - kGamma) + kGamma, 0.f), 1.f);
-        } else {
-            h = alpha[e] >= 0.f ? 1.f : 0.f;
-        }
-        const float xint = xf + h + z;
-        emit(d, e, (fminf(fmaxf(xint, 0.f), Lm1) - z) * dl, wq, wd);
+        const IntGrid grid{floorf(wv / dl), z, dl, Lm1};
+        emit(d, e, grid.q(ada_h(alpha[e], mode == 1)), wq, wd);
     }
 }
 
@@ -678,8 +379,7 @@ __global__ __launch_bounds__(256) void ada_init_kernel(rdo_ada_desc d, const flo
     for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < d.numel; e += (long)gridDim.x * blockDim.x) {
         const float dl = delta[e / inner];
         const float r = w[e] / dl;
-        const float rest = r - floorf(r);
-        alpha[e] = -logf((kZeta - kGamma) / (rest - kGamma) - 1.f);
+        alpha[e] = ada_alpha0(r - floorf(r));
     }
 }
 
@@ -707,20 +407,21 @@ __global__ __launch_bounds__(256) void reduce_slabs_kernel(const float* slabs, i
 
 using rdo::grid_for;
 
-int check_desc(const rdo_ada_desc* d, const char* who) {
-    RDO_REQUIRE(d != nullptr, "%s: null descriptor", who);
-    RDO_REQUIRE(d->numel > 0 && d->rows > 0 && d->numel % d->rows == 0, "%s: numel %ld not divisible by rows %d", who,
-                (long)d->numel, d->rows);
-    RDO_REQUIRE(d->n_levels >= 4 && d->n_levels <= 65536, "%s: n_levels %d unsupported", who, d->n_levels);
-    if (d->Cin > 0)
-        RDO_REQUIRE(d->KH > 0 && d->KW > 0 && (long)d->rows * d->KH * d->KW * d->Cin == d->numel,
-                    "%s: conv layout [%d][%d][%d][%d] does not match numel %ld", who, d->rows, d->KH, d->KW, d->Cin,
-                    (long)d->numel);
-    return RDO_OK;
+// the arguments that rdo_adaround_step (mode 0: slabs) and rdo_adaround_apply (mode 2: dalpha) share
+AdaArgs step_args(const rdo_ada_desc* d, int mode, const float* w, const float* delta, const float* zp, float grad_scale, float round_weight,
+                  const rdo_sched_row* sched, const int32_t* iter_ptr, float* alpha, float* adam_m, float* adam_v, float* wq, float* wd,
+                  float* round_loss_out, void* wq_planes, void* wd_planes, float wq_plane_scale, float wd_plane_scale) {
+    AdaArgs a{};
+    a.d = *d; a.w = w; a.delta = delta; a.zp = zp; a.grad_scale = grad_scale;
+    a.round_weight = round_weight; a.sched = sched; a.iter_ptr = iter_ptr; a.alpha = alpha; a.m = adam_m; a.v = adam_v;
+    a.wq = wq; a.wd = wd; a.round_loss_out = round_loss_out; a.mode = mode;
+    a.wq_planes = static_cast<unsigned short*>(wq_planes);
+    a.wd_planes = wd ? static_cast<unsigned short*>(wd_planes) : nullptr;
+    a.wq_pscale = wq_plane_scale; a.wd_pscale = wd_plane_scale; a.ovf = rdo::h2_overflow_flag();
+    return a;
 }
 
 int run_step(AdaArgs a, void* stream) {
-
     return rdo::dispatch(
         [a](hipStream_t s) {
             if (a.d.numel % 4 == 0)
@@ -728,9 +429,8 @@ int run_step(AdaArgs a, void* stream) {
             else
                 hipLaunchKernelGGL(ada_step_kernel<1>, dim3(grid_for(a.d.numel)), dim3(256), 0, s, a);
             if (a.mode != 1 && a.wd && a.d.Cin > 0) {
-                const long blocks = rdo::ceil_div(a.d.rows, 32) * a.d.KH * a.d.KW * rdo::ceil_div(a.d.Cin, 32);
-                hipLaunchKernelGGL(wd_transpose_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a.d, (const float*)a.wq, a.wd, a.wd_planes, a.wd_pscale,
-                                   a.ovf);
+                hipLaunchKernelGGL(wd_transpose_kernel, dim3((unsigned)tile_blocks(a.d)), dim3(256), 0, s, a.d, (const float*)a.wq, a.wd, a.wd_planes,
+                                   a.wd_pscale, a.ovf);
             }
             return rdo::check_launch("ada_step");
         },
@@ -814,13 +514,9 @@ int rdo_adaround_step(const rdo_ada_desc* d, const float* w, const float* delta,
     if (int rc = check_desc(d, "rdo_adaround_step")) return rc;
     RDO_REQUIRE(w && delta && zp && slabs && nsplit >= 1 && sched && iter_ptr && alpha && adam_m && adam_v && wq,
                 "rdo_adaround_step: null pointer");
-    AdaArgs a{};
-    a.d = *d; a.w = w; a.delta = delta; a.zp = zp; a.slabs = slabs; a.nsplit = nsplit; a.grad_scale = grad_scale;
-    a.round_weight = round_weight; a.sched = sched; a.iter_ptr = iter_ptr; a.alpha = alpha; a.m = adam_m; a.v = adam_v;
-    a.wq = wq; a.wd = wd; a.round_loss_out = round_loss_out; a.mode = 0;
-    a.wq_planes = static_cast<unsigned short*>(wq_planes);
-    a.wd_planes = wd ? static_cast<unsigned short*>(wd_planes) : nullptr;
-    a.wq_pscale = wq_plane_scale; a.wd_pscale = wd_plane_scale; a.ovf = rdo::h2_overflow_flag();
+    AdaArgs a = step_args(d, 0, w, delta, zp, grad_scale, round_weight, sched, iter_ptr, alpha, adam_m, adam_v, wq, wd, round_loss_out, wq_planes,
+                          wd_planes, wq_plane_scale, wd_plane_scale);
+    a.slabs = slabs; a.nsplit = nsplit;
     return run_step(a, stream);
 }
 
@@ -874,7 +570,7 @@ static int step_batch_impl(const rdo_ada_step_item* items, int32_t n, int32_t mo
         bytes += 4.0 * it.d.numel * ((mode == 2 ? 1 : it.nsplit) + (mode == 1 ? 3.0 : 9.0));
         if (mode != 1 && it.wd && it.d.Cin > 0 && !b.tile[i]) {
             bw.a[bw.n] = a;
-            wblocks += (int)(rdo::ceil_div(it.d.rows, 32) * it.d.KH * it.d.KW * rdo::ceil_div(it.d.Cin, 32));
+            wblocks += (int)tile_blocks(it.d);
             bw.blk_end[bw.n++] = wblocks;
         }
     }
@@ -950,13 +646,9 @@ int rdo_adaround_apply(const rdo_ada_desc* d, const float* w, const float* delta
     if (int rc = check_desc(d, "rdo_adaround_apply")) return rc;
     RDO_REQUIRE(w && delta && zp && dalpha && sched && iter_ptr && alpha && adam_m && adam_v && wq,
                 "rdo_adaround_apply: null pointer");
-    AdaArgs a{};
-    a.d = *d; a.w = w; a.delta = delta; a.zp = zp; a.dalpha_in = dalpha; a.grad_scale = grad_scale;
-    a.round_weight = round_weight; a.sched = sched; a.iter_ptr = iter_ptr; a.alpha = alpha; a.m = adam_m; a.v = adam_v;
-    a.wq = wq; a.wd = wd; a.round_loss_out = round_loss_out; a.mode = 2;
-    a.wq_planes = static_cast<unsigned short*>(wq_planes);
-    a.wd_planes = wd ? static_cast<unsigned short*>(wd_planes) : nullptr;
-    a.wq_pscale = wq_plane_scale; a.wd_pscale = wd_plane_scale; a.ovf = rdo::h2_overflow_flag();
+    AdaArgs a = step_args(d, 2, w, delta, zp, grad_scale, round_weight, sched, iter_ptr, alpha, adam_m, adam_v, wq, wd, round_loss_out, wq_planes,
+                          wd_planes, wq_plane_scale, wd_plane_scale);
+    a.dalpha_in = dalpha;
     return run_step(a, stream);
 }
 

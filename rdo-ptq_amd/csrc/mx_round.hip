@@ -8,27 +8,16 @@
 // and no level clamp in the step.  gap == 0 marks a pinned element (where round to nearest saturates): the step leaves its alpha, m and v
 // alone and keeps its weight at lo.
 //
-// rdo_mx_round_step restates the flat form of adaround.hip's fused step (ada_step_body: float4 streams where numel % 4 == 0, a scalar
-// form otherwise, the slab loads 16 / 8 / 4 at a time, the same summation order, the same Adam constants, pow_u on the transcendental
-// unit, the rounding loss by block_sum + one atomicAdd per workgroup) with `w, delta, zp` replaced by `lo, gap`; that file stays as it
-// is (its step has bit-for-bit tests), hence the restated sigmoidf_, pow_u and constants.  The dgrad layout is a second launch.
+// rdo_mx_round_step has the shape of the flat form of adaround.hip's fused step (ada_step_body: float4 streams where numel % 4 == 0, a
+// scalar form otherwise) with `w, delta, zp` replaced by `lo, gap`.  The element step -- slab sum, h(alpha), the LowerBound chain, the
+// rounding regulariser, Adam, the rounding-loss publish -- is the one of ada_device.h that adaround.hip runs too; this file supplies the
+// grid (MxGrid) and skips the pinned elements.  The dgrad layout is a second launch of that header's wd_transpose_body.
 #include "rdo_common.h"
 #include "../../include/rdo_ptq_mxround.h"
 #include "mx_device.h"
+#include "ada_device.h"
 
 namespace {
-
-constexpr float kGamma = -0.1f, kZeta = 1.1f;
-constexpr float kBeta2 = 0.999f, kAdamEps = 1e-8f;
-// 1 - beta as torch.optim.Adam forms it (in double, then one rounding), as in adaround.hip
-constexpr float kOmBeta1 = (float)(1.0 - 0.9), kOmBeta2 = (float)(1.0 - 0.999);
-
-__device__ __forceinline__ float sigmoidf_(float a) { return 1.0f / (1.0f + __expf(-a)); }
-
-// u^p for u in [0, 1], p in [1, 19] on the transcendental unit: exp2(p * log2 u) (adaround.hip states its error)
-__device__ __forceinline__ float pow_u(float u, float p) {
-    return (u > 0.f) ? __builtin_amdgcn_exp2f(__builtin_amdgcn_logf(u) * p) : 0.f;
-}
 
 // ---- neighbours ------------------------------------------------------------------------------------------------------------------------
 // the fp32 bit pattern of 2^e, -149 <= e <= 127
@@ -130,39 +119,25 @@ __global__ __launch_bounds__(256) void mx_init_kernel(const float* __restrict__ 
     for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < numel; e += (long)gridDim.x * blockDim.x) {
         const float gp = gap[e];
         float a = 0.f;
-        if (gp > 0.f) {
-            const float rest = (w[e] - lo[e]) / gp;
-            a = -logf((kZeta - kGamma) / (rest - kGamma) - 1.f);
-        }
+        if (gp > 0.f) a = ada_alpha0((w[e] - lo[e]) / gp);
         alpha[e] = a;
     }
 }
 
-__device__ __forceinline__ long wd_index(const rdo_ada_desc& d, long e) {
-    // e = ((co*KH + kh)*KW + kw)*Cin + ci  ->  ((ci*KH + KH-1-kh)*KW + KW-1-kw)*Cout + co
-    const int Cin = d.Cin, KW = d.KW, KH = d.KH;
-    long t = e / Cin;
-    const int ci = (int)(e - t * Cin);
-    const int kw = (int)(t % KW); t /= KW;
-    const int kh = (int)(t % KH);
-    const long co = t / KH;
-    return (((long)ci * KH + (KH - 1 - kh)) * KW + (KW - 1 - kw)) * d.rows + co;
-}
-
-__device__ __forceinline__ float reparam_of(const rdo_ada_desc& d, float q) {
-    if (!d.reparam) return q;
-    const float lb = fmaxf(q, d.reparam_bound);
-    return lb * lb - d.reparam_pedestal;
-}
+// The MX grid of one weight (ada_element's Grid): lo is on the grid and so is lo + gap -- no level clamp, dq/dh = gap everywhere
+struct MxGrid {
+    float lo, gap;
+    __device__ __forceinline__ float q(float h) const { return lo + gap * h; }
+    __device__ __forceinline__ float dq_dh(float g, float) const { return g * gap; }
+};
 
 __global__ __launch_bounds__(256) void mx_fwd_kernel(rdo_ada_desc d, const float* __restrict__ lo, const float* __restrict__ gap,
                                                      const float* __restrict__ alpha, int soft, float* __restrict__ wq, float* __restrict__ wd,
                                                      uint8_t* __restrict__ codes, const uint8_t* __restrict__ scales, long nb, MxFormat f) {
     const long inner = d.numel / d.rows;
     for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < d.numel; e += (long)gridDim.x * blockDim.x) {
-        const float al = alpha[e];
-        const float h = soft ? fminf(fmaxf(sigmoidf_(al) * (kZeta - kGamma) + kGamma, 0.f), 1.f) : (al >= 0.f ? 1.f : 0.f);
-        const float q = lo[e] + gap[e] * h;                                     // hard: lo or lo + gap, exact
+        const float h = ada_h(alpha[e], soft != 0);
+        const float q = MxGrid{lo[e], gap[e]}.q(h);                             // hard: lo or lo + gap, exact
         if (codes) {
             const long row = e / inner;
             const unsigned sc = scales[row * nb + (e - row * inner) / kBlock];
@@ -171,9 +146,7 @@ __global__ __launch_bounds__(256) void mx_fwd_kernel(rdo_ada_desc d, const float
             if (sc != 255u) code = mx_encode(qb & 0x7FFFFFFFu, (int)sc - 127, f) | ((qb & 0x80000000u) >> (32 - f.bits));
             codes[e] = (uint8_t)code;
         }
-        const float o = reparam_of(d, q);
-        wq[e] = o;
-        if (wd && d.Cin > 0) wd[wd_index(d, e)] = o;
+        emit(d, e, q, wq, wd);
     }
 }
 
@@ -201,87 +174,31 @@ __global__ __launch_bounds__(256) void mx_step_kernel(MxStepArgs a) {
     const rdo_ada_desc d = a.d;
     const int it = *a.iter_ptr;
     const rdo_sched_row sc = a.sched[it];
-    const float b = sc.b, round_on = sc.round_on, step_size = sc.step_size, bc2 = sc.bc2_sqrt;
     float rl_local = 0.f;
     const long nq = d.numel / W;
     for (long qi = (long)blockIdx.x * blockDim.x + threadIdx.x; qi < nq; qi += (long)gridDim.x * blockDim.x) {
+        // ---- load the streams
         const long e0 = qi * W;
         const vec_t lo4 = *reinterpret_cast<const vec_t*>(a.lo + e0);
         const vec_t gp4 = *reinterpret_cast<const vec_t*>(a.gap + e0);
         vec_t al4 = *reinterpret_cast<const vec_t*>(a.alpha + e0);
-        vec_t g4 = lo4 * 0.f;
-        {
-            // the slab loads in flight as in ada_step_body: a serial chain of nsplit dependent loads was that kernel's whole time
-            const float* sp = a.slabs + e0;
-            int s = 0;
-            for (; s + 16 <= a.nsplit; s += 16) {
-                vec_t t[16];
-#pragma unroll
-                for (int u = 0; u < 16; ++u) t[u] = *reinterpret_cast<const vec_t*>(sp + (long)(s + u) * d.numel);
-                g4 += (((t[0] + t[1]) + (t[2] + t[3])) + ((t[4] + t[5]) + (t[6] + t[7]))) +
-                      (((t[8] + t[9]) + (t[10] + t[11])) + ((t[12] + t[13]) + (t[14] + t[15])));
-            }
-            for (; s + 8 <= a.nsplit; s += 8) {
-                vec_t t[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) t[u] = *reinterpret_cast<const vec_t*>(sp + (long)(s + u) * d.numel);
-                g4 += ((t[0] + t[1]) + (t[2] + t[3])) + ((t[4] + t[5]) + (t[6] + t[7]));
-            }
-            if (s + 4 <= a.nsplit) {
-                vec_t t[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) t[u] = *reinterpret_cast<const vec_t*>(sp + (long)(s + u) * d.numel);
-                g4 += (t[0] + t[1]) + (t[2] + t[3]);
-                s += 4;
-            }
-            for (; s < a.nsplit; ++s) g4 += *reinterpret_cast<const vec_t*>(sp + (long)s * d.numel);
-        }
+        const vec_t g4 = slab_sum(lo4 * 0.f, a.slabs + e0, a.nsplit, d.numel);
         vec_t m4 = *reinterpret_cast<const vec_t*>(a.m + e0);
         vec_t v4 = *reinterpret_cast<const vec_t*>(a.v + e0);
         vec_t o4 = lo4;
         bool any_pinned = false;
+        // ---- the element step (mode 0)
 #pragma unroll
         for (int k = 0; k < W; ++k) {
-            const float lo = lo4[k], gp = gp4[k];
-            if (!(gp > 0.f)) {                                                  // pinned (or a non-finite block): the weight stays lo
+            const MxGrid grid{lo4[k], gp4[k]};
+            if (!(grid.gap > 0.f)) {                                            // pinned (or a non-finite block): the weight stays lo
                 any_pinned = true;
-                o4[k] = reparam_of(d, lo);
+                o4[k] = lower_bound_fwd(d, grid.lo);
                 continue;
             }
-            float al = al4[k];
-            const float sg = sigmoidf_(al);
-            const float hraw = sg * (kZeta - kGamma) + kGamma;
-            const float h = fminf(fmaxf(hraw, 0.f), 1.f);
-            const float pass_h = (hraw >= 0.f && hraw <= 1.f) ? 1.f : 0.f;
-            const float dh_da = pass_h * ((kZeta - kGamma) * (sg * (1.f - sg)));
-            float g = g4[k];
-            if (d.reparam) {
-                const float q = lo + gp * h;
-                const float lb = fmaxf(q, d.reparam_bound);
-                const float go = g * (2.f * lb);                                // d(lb^2)/dlb
-                g = (q >= d.reparam_bound || go < 0.f) ? go : 0.f;              // LowerBound backward
-            }
-            const float g_alpha = (g * gp) * dh_da;                             // hi is on the grid: no level clamp, no pass_q
-            // rounding regulariser (value of the current alpha, gradient through h)
-            float g_total = g_alpha * a.grad_scale;
-            if (round_on != 0.f) {
-                const float u = fabsf(h - 0.5f) * 2.f;
-                const float ub1 = pow_u(u, b - 1.f);                            // u^(b-1); u^b = u * u^(b-1)
-                rl_local += a.round_weight * (1.f - u * ub1);
-                const float sgn = (h > 0.5f) ? 1.f : ((h < 0.5f) ? -1.f : 0.f);
-                g_total += (-a.round_weight * (b * ub1) * 2.f * sgn) * dh_da;
-            }
-            // Adam (torch.optim.Adam defaults; alpha has no weight decay)
-            float mm = m4[k], vv = v4[k];
-            mm = fmaf(g_total - mm, kOmBeta1, mm);
-            vv = fmaf(vv, kBeta2, kOmBeta2 * g_total * g_total);
-            const float denom = sqrtf(vv) / bc2 + kAdamEps;
-            al = al - step_size * (mm / denom);
-            m4[k] = mm; v4[k] = vv; al4[k] = al;
-            // next iteration's soft weight
-            const float h2 = fminf(fmaxf(sigmoidf_(al) * (kZeta - kGamma) + kGamma, 0.f), 1.f);
-            o4[k] = reparam_of(d, lo + gp * h2);
+            ada_element(grid, d, 0, k, g4, al4, m4, v4, o4, a.grad_scale, a.round_weight, sc.b, sc.round_on, sc.step_size, sc.bc2_sqrt, rl_local);
         }
+        // ---- store the state and the next soft weight
         if (!any_pinned) {
             *reinterpret_cast<vec_t*>(a.m + e0) = m4;
             *reinterpret_cast<vec_t*>(a.v + e0) = v4;
@@ -298,52 +215,17 @@ __global__ __launch_bounds__(256) void mx_step_kernel(MxStepArgs a) {
         }
         *reinterpret_cast<vec_t*>(a.wq + e0) = o4;
     }
-    if (a.round_loss_out && round_on != 0.f) {
-        const float t = rdo::block_sum(rl_local);           // the condition holds kernel arguments only: uniform over the workgroup
-        if (threadIdx.x == 0) {
-            if (t != 0.f) atomicAdd(a.round_loss_out + (long)it * RDO_LOG_SLOTS + (blockIdx.x & (RDO_LOG_SLOTS - 1)), t);
-        }
-    }
+    publish_round_loss(a.round_loss_out, sc.round_on, it, blockIdx.x, rl_local);
 }
 
-// wd[ci][KH-1-kh][KW-1-kw][co] = wq[co][kh][kw][ci]: 32x32 tiles through LDS, 128-byte segments on both sides (wd_transpose_kernel
-// of adaround.hip without its plane outputs)
+// the dgrad layout, a second launch: wd_transpose_body without plane outputs
 __global__ __launch_bounds__(256) void mx_wd_transpose_kernel(rdo_ada_desc d, const float* __restrict__ wq, float* __restrict__ wd) {
-    const int taps = d.KH * d.KW, cdim = d.Cin;
-    const int ctiles = (cdim + 31) / 32;
-    int bid = blockIdx.x;
-    const int ct = bid % ctiles; bid /= ctiles;
-    const int tap = bid % taps;
-    const int rt = bid / taps;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    __shared__ float tile[32][33];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int row = rt * 32 + ty + 8 * k, c = ct * 32 + tx;
-        if (row < d.rows && c < cdim) tile[ty + 8 * k][tx] = wq[((long)row * taps + tap) * cdim + c];
-    }
-    __syncthreads();
-    const int kh = tap / d.KW, kw = tap - kh * d.KW;
-    const int tapf = (d.KH - 1 - kh) * d.KW + (d.KW - 1 - kw);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int ci = ct * 32 + ty + 8 * k, co = rt * 32 + tx;
-        if (ci < cdim && co < d.rows) wd[((long)ci * taps + tapf) * d.rows + co] = tile[tx][ty + 8 * k];
-    }
+    wd_transpose_body(d, wq, wd, nullptr, 0.f, nullptr, blockIdx.x);
 }
 
 using rdo::grid_for;
 
 inline bool aligned4(const void* p) { return reinterpret_cast<uintptr_t>(p) % 4 == 0; }
-
-int check_desc(const rdo_ada_desc* d, const char* who) {
-    RDO_REQUIRE(d != nullptr, "%s: null descriptor", who);
-    RDO_REQUIRE(d->numel > 0 && d->rows > 0 && d->numel % d->rows == 0, "%s: numel %ld not divisible by rows %d", who, (long)d->numel, d->rows);
-    if (d->Cin > 0)
-        RDO_REQUIRE(d->KH > 0 && d->KW > 0 && (long)d->rows * d->KH * d->KW * d->Cin == d->numel,
-                    "%s: conv layout [%d][%d][%d][%d] does not match numel %ld", who, d->rows, d->KH, d->KW, d->Cin, (long)d->numel);
-    return RDO_OK;
-}
 
 }  // namespace
 
@@ -382,7 +264,7 @@ int rdo_mx_round_init_alpha(const float* w, const float* lo, const float* gap, i
 
 int rdo_mx_round_fwd(const rdo_ada_desc* d, const float* lo, const float* gap, const float* alpha, int32_t soft, float* wq, float* wd,
                      uint8_t* codes, const uint8_t* scales_in, int32_t format, void* stream) {
-    if (int rc = check_desc(d, "rdo_mx_round_fwd")) return rc;
+    if (int rc = check_desc(d, "rdo_mx_round_fwd", false)) return rc;
     RDO_REQUIRE(lo && gap && alpha && wq, "rdo_mx_round_fwd: null pointer");
     MxFormat f;
     RDO_REQUIRE(mx_format(format, f), "rdo_mx_round_fwd: unknown format %d (0 .. %d)", format, RDO_MX_FORMATS - 1);
@@ -404,7 +286,7 @@ int rdo_mx_round_fwd(const rdo_ada_desc* d, const float* lo, const float* gap, c
 int rdo_mx_round_step(const rdo_ada_desc* d, const float* lo, const float* gap, const float* slabs, int32_t nsplit, float grad_scale,
                       float round_weight, const rdo_sched_row* sched, const int32_t* iter_ptr, float* alpha, float* adam_m, float* adam_v,
                       float* wq, float* wd, float* round_loss_out, void* stream) {
-    if (int rc = check_desc(d, "rdo_mx_round_step")) return rc;
+    if (int rc = check_desc(d, "rdo_mx_round_step", false)) return rc;
     RDO_REQUIRE(lo && gap && slabs && sched && iter_ptr && alpha && adam_m && adam_v && wq, "rdo_mx_round_step: null pointer");
     RDO_REQUIRE(nsplit >= 1, "rdo_mx_round_step: nsplit %d (at least one gradient slab)", nsplit);
     RDO_REQUIRE(aligned4(lo) && aligned4(gap) && aligned4(slabs) && aligned4(sched) && aligned4(iter_ptr) && aligned4(alpha) && aligned4(adam_m) &&
@@ -423,7 +305,7 @@ int rdo_mx_round_step(const rdo_ada_desc* d, const float* lo, const float* gap, 
             else
                 hipLaunchKernelGGL(mx_step_kernel<1>, dim3(grid_for(a.d.numel)), dim3(256), 0, s, a);
             if (wd && a.d.Cin > 0) {
-                const long blocks = rdo::ceil_div(a.d.rows, 32) * a.d.KH * a.d.KW * rdo::ceil_div(a.d.Cin, 32);
+                const long blocks = tile_blocks(a.d);
                 hipLaunchKernelGGL(mx_wd_transpose_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a.d, (const float*)a.wq, wd);
             }
             return rdo::check_launch("mx_round_step");

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The fused AdaRound step on an MX grid (`ops.mx_round_step`; mx_step_kernel + mx_wd_transpose_kernel of csrc/mx_round.hip) on one
-MI355X, next to the integer-grid step it restates (`ops.adaround_step`: the flat form of csrc/adaround.hip with its dgrad launch, no
+MI355X, next to the integer-grid step it mirrors (`ops.adaround_step`: the flat form of csrc/adaround.hip with its dgrad launch, no
 planes) on the same tensors in the same process, alternating: the two weights of the flagship codec's blocks, 192x3x3x192 and
 192x1x1x192, at the gradient-slab counts the engine uses for them on a 128 x 128 feature map at batch 4 (`ops.wgrad_nsplit`; --nsplit
 overrides).  The MX step reads one more fp32 stream per element (lo, gap against w) and does no per-row look-ups and no division.
