@@ -252,6 +252,15 @@ _SIGS_MXROUND = {
     "rdo_mx_round_step": (C.c_int, [C.POINTER(AdaDesc), P, P, P, C.c_int32, C.c_float, C.c_float, P, P, P, P, P, P, P, P, P]),
 }
 EXPORTS_MXROUND = tuple(_SIGS_MXROUND)
+# include/rdo_ptq_mxgemm.h: the packed MX operand, its producers and the GEMM on the block-scaled matrix instruction
+_SIGS_MXGEMM = {
+    "rdo_mx_packed_bytes": (C.c_int64, [C.c_int32, C.c_int64, C.c_int32]),
+    "rdo_mx_pack_codes": (C.c_int, [P, C.c_int32, C.c_int64, C.c_int32, P, P]),
+    "rdo_mx_quant_pack": (C.c_int, [P, C.c_int32, C.c_int64, C.c_int32, P, P, P, P]),
+    "rdo_mx_unpack_codes": (C.c_int, [P, C.c_int32, C.c_int64, C.c_int32, P, P]),
+    "rdo_mx_gemm": (C.c_int, [P, P, C.c_int32, P, P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, P, P, P]),
+}
+EXPORTS_MXGEMM = tuple(_SIGS_MXGEMM)
 
 _lib = None
 
@@ -270,7 +279,8 @@ def lib():
         h = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(_SIGS.items()) + list(_SIGS_GDN.items()) + list(_SIGS_BIAS.items()) + list(_SIGS_BITS.items())
                                   + list(_SIGS_PACK.items()) + list(_SIGS_SUBPEL.items()) + list(_SIGS_ACTBITS.items())
-                                  + list(_SIGS_ATTNQ.items()) + list(_SIGS_MX.items()) + list(_SIGS_MXROUND.items())):
+                                  + list(_SIGS_ATTNQ.items()) + list(_SIGS_MX.items()) + list(_SIGS_MXROUND.items())
+                                  + list(_SIGS_MXGEMM.items())):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         _lib = h

@@ -830,6 +830,105 @@ def mx_round_step(d, lo, gap, slabs, grad_scale, round_weight, sched, iter_ptr, 
             "rdo_mx_round_step")
 
 
+# ---- MX codes on the block-scaled matrix instruction (include/rdo_ptq_mxgemm.h) -------------------------------------------------------------
+class MXOperand:
+    """A packed MX operand of `mx_gemm`: `.packed` uint8 [rows, K / 32 * 4 b] (blocks of 4 b bytes, b the element bits of `.fmt`; the byte
+    image is stated in include/rdo_ptq_mxgemm.h), `.scales` uint8 [rows, K / 32] (E8M0 bytes), `.fmt` a name of `MX_FORMATS`, `.rows`, `.K`."""
+    __slots__ = ("packed", "scales", "fmt", "rows", "K")
+
+    def __init__(self, packed, scales, fmt, rows, K):
+        self.packed, self.scales, self.fmt, self.rows, self.K = packed, scales, fmt, int(rows), int(K)
+
+    @property
+    def device(self):
+        return self.packed.device
+
+    def __repr__(self):
+        return f"MXOperand({self.fmt}, rows={self.rows}, K={self.K}, device={self.packed.device})"
+
+
+def _mx_k(what, rows, K):
+    """blocks a row of a packed operand: K must be a whole number of blocks"""
+    if K % L.MX_BLOCK:
+        raise ValueError(f"{what}: K = {K} is no multiple of the MX block size {L.MX_BLOCK}")
+    return _mx_geometry(what, rows, K)
+
+
+def _mx_operand(what, name, op, device=None):
+    """an `MXOperand` whose tensors have the shapes its fields state; -> (format id, element bits, blocks a row)"""
+    if not isinstance(op, MXOperand):
+        raise ValueError(f"{what}: {name} must be an MXOperand, got {type(op).__name__}")
+    fid, bits = mx_format(what, op.fmt)
+    if op.rows < 1 or op.K < 1:
+        raise ValueError(f"{what}: {name} states rows {op.rows} and K {op.K}")
+    nb = _mx_k(what, op.rows, op.K)
+    A.tensor(what, f"{name}.packed", op.packed, torch.uint8, "uint8", shape=(op.rows, nb * 4 * bits), contiguous=True, device=device, oneshot=True)
+    A.tensor(what, f"{name}.scales", op.scales, torch.uint8, "uint8", shape=(op.rows, nb), contiguous=True, device=op.packed.device, oneshot=True)
+    return fid, bits, nb
+
+
+def mx_pack_codes(codes, scales, fmt):
+    """An `MXOperand` from one-code-per-byte element codes (contiguous uint8 [rows, K], K % 32 == 0: 'codes' of `mx_fakequant`, the codes of
+    `mx_round_fwd`) and their scale bytes (contiguous uint8 [rows, K / 32]; kept, not copied) (rdo_mx_pack_codes).  Checked on the host
+    before a pointer is taken."""
+    what = "mx_pack_codes"
+    A.tensor(what, "codes", codes, torch.uint8, "uint8", rank=2, layout="of rank 2 [rows, K]", contiguous=True)
+    fid, bits = mx_format(what, fmt)
+    rows, K, dev = int(codes.shape[0]), int(codes.shape[1]), codes.device
+    nb = _mx_k(what, rows, K)
+    A.tensor(what, "scales", scales, torch.uint8, "uint8", shape=(rows, nb), contiguous=True, device=dev, oneshot=True)
+    _mx_cuda(what, codes, "codes")
+    packed = torch.empty(rows, nb * 4 * bits, device=dev, dtype=torch.uint8)
+    L.check(L.lib().rdo_mx_pack_codes(_ptr(codes, *_U8), rows, K, fid, _ptr(packed, *_U8), _stream()), "rdo_mx_pack_codes")
+    return MXOperand(packed, scales, fmt, rows, K)
+
+
+def mx_quant_pack(x2d, fmt, want_xq=False):
+    """Quantise activation rows to the MX format `fmt` and pack them in one read (rdo_mx_quant_pack): x2d contiguous fp32 [rows, K], K % 32
+    == 0, blocks of 32 along K -> `MXOperand`; want_xq: -> (operand, xq), xq fp32 [rows, K] the decoded values.  Bit for bit `mx_fakequant`
+    followed by `mx_pack_codes`.  Checked on the host before a pointer is taken."""
+    what = "mx_quant_pack"
+    A.tensor(what, "x2d", x2d, rank=2, layout="of rank 2 [rows, K]", contiguous=True)
+    fid, bits = mx_format(what, fmt)
+    rows, K, dev = int(x2d.shape[0]), int(x2d.shape[1]), x2d.device
+    nb = _mx_k(what, rows, K)
+    _mx_cuda(what, x2d, "x2d")
+    packed = torch.empty(rows, nb * 4 * bits, device=dev, dtype=torch.uint8)
+    scales = torch.empty(rows, nb, device=dev, dtype=torch.uint8)
+    xq = torch.empty_like(x2d) if want_xq else None
+    L.check(L.lib().rdo_mx_quant_pack(_ptr(x2d), rows, K, fid, _ptr(packed, *_U8), _ptr(scales, *_U8), _ptr(xq), _stream()), "rdo_mx_quant_pack")
+    op = MXOperand(packed, scales, fmt, rows, K)
+    return (op, xq) if want_xq else op
+
+
+def mx_unpack_codes(op):
+    """codes uint8 [rows, K] of an `MXOperand`: the inverse of `mx_pack_codes` (rdo_mx_unpack_codes)"""
+    what = "mx_unpack_codes"
+    fid, _, _ = _mx_operand(what, "op", op)
+    _mx_cuda(what, op.packed, "op.packed")
+    codes = torch.empty(op.rows, op.K, device=op.packed.device, dtype=torch.uint8)
+    L.check(L.lib().rdo_mx_unpack_codes(_ptr(op.packed, *_U8), op.rows, op.K, fid, _ptr(codes, *_U8), _stream()), "rdo_mx_unpack_codes")
+    return codes
+
+
+def mx_gemm(a, b, bias=None):
+    """y fp32 [M, N] = A B^T (+ bias) on the block-scaled matrix instruction (rdo_mx_gemm): a an `MXOperand` [M, K], b an `MXOperand` [N, K]
+    of any two formats, bias contiguous fp32 [N] or None.  The products are exact; the sum is the instruction's fp32 accumulation.
+    Checked on the host before a pointer is taken."""
+    what = "mx_gemm"
+    fa, _, _ = _mx_operand(what, "a", a)
+    fb, _, _ = _mx_operand(what, "b", b, device=a.packed.device)
+    if a.K != b.K:
+        raise ValueError(f"{what}: a has K = {a.K}, b has K = {b.K}")
+    dev = a.packed.device
+    A.tensor(what, "bias", bias, shape=(b.rows,), contiguous=True, device=dev, optional=True, oneshot=True)
+    _mx_cuda(what, a.packed, "a.packed")
+    y = torch.empty(a.rows, b.rows, device=dev, dtype=torch.float32)
+    L.check(L.lib().rdo_mx_gemm(_ptr(a.packed, *_U8), _ptr(a.scales, *_U8), fa, _ptr(b.packed, *_U8), _ptr(b.scales, *_U8), fb, a.rows, b.rows,
+                                a.K, _ptr(bias), _ptr(y), _stream()), "rdo_mx_gemm")
+    return y
+
+
 def pack_row_words(inner, bits):
     """W = ceil(inner * bits / 32): the 32-bit words one row of `inner` codes of `bits` bits occupies (rdo_pack_row_words on the host)"""
     return -(-int(inner) * int(bits) // 32)

@@ -1,7 +1,14 @@
 """Weight quantisers on the OCP microscaling (MX) block formats (include/rdo_ptq_mx.h): blocks of 32 elements along the GEMM's K
 dimension, one shared power-of-two scale per block, FP4 / FP6 / FP8 elements.  `MXQuantizer` rounds to nearest (`ops.mx_fakequant`);
 `MXAdaRoundQuantizer` carries learned rounding on the same grids (include/rdo_ptq_mxround.h; `QuantModel.set_weight_format(...,
-rounding='learned')`, then `reconstruct`).  MX activations and a packed MX container are not built."""
+rounding='learned')`, then `reconstruct`).
+
+The codes on the matrix cores (include/rdo_ptq_mxgemm.h): `native_operand(module)` is a module's weight as a packed operand of the
+block-scaled matrix instruction, `native_linear(module, x, act_fmt)` the module's pre-activation output with the input quantised to an MX
+format as well -- for token-matrix Linears and 1x1 stride-1 convs whose input channels are a multiple of 32;
+`QuantModel.mx_native_report` measures it against the emulation, layer by layer.  The quantisers themselves serve weights only: an
+activation is put on an MX grid by `native_linear` (`ops.mx_quant_pack`), not by a quantiser call with act=True.  MX activations inside
+the modules' own forward and a packed MX container are not built."""
 import torch
 import torch.nn as nn
 
@@ -55,7 +62,8 @@ class _MXFields(nn.Module):
 
     def _refuse_act(self, act):
         if act:
-            raise NotImplementedError(f"{type(self).__name__}({self.fmt}): MX activations are not built; this quantiser serves weights only")
+            raise NotImplementedError(f"{type(self).__name__}({self.fmt}): MX activations are not built into the quantisers, which serve weights only; "
+                                      "`quantization.mx.native_linear` quantises a Linear's or 1x1 conv's input to an MX format")
 
     def _nearest(self, x):
         wr = to_rows(x.detach(), self.tconv)
@@ -88,7 +96,8 @@ class MXQuantizer(_MXFields):
     n_bits, delta = zero_point = None), `fmt`, and `size_bits(weight)` = element bits x elements + 8 x blocks.  `QuantModel.weight_bits()`
     reads n_bits and so counts the element bits only, not the scales.
 
-    Weights only: a call with act=True raises NotImplementedError (MX activations are not built)."""
+    Weights only: a call with act=True raises NotImplementedError (MX activations are not built into the quantisers; `native_linear` is the
+    path that quantises an input)."""
 
     def forward(self, x: torch.Tensor, act: bool = False, **kw):
         self._refuse_act(act)
@@ -103,7 +112,8 @@ class MXAdaRoundQuantizer(_MXFields):
     are those of round to nearest, a pinned element stays at +-max X.  `codes_and_scales(weight)` is the stored form: uint8 element codes
     and E8M0 scale bytes with `ops.mx_dequant(codes, scales, inner, fmt)` the forwarded rows bit for bit.
 
-    Weights only: a call with act=True raises NotImplementedError (MX activations are not built)."""
+    Weights only: a call with act=True raises NotImplementedError (MX activations are not built into the quantisers; `native_linear` is the
+    path that quantises an input)."""
 
     def __init__(self, fmt: str, tconv: bool = False):
         super().__init__(fmt, tconv)
@@ -137,3 +147,91 @@ class MXAdaRoundQuantizer(_MXFields):
 
     def extra_repr(self):
         return super().extra_repr() + f", rounding={'nearest' if self.alpha is None else 'learned'}"
+
+
+# ---- the codes on the block-scaled matrix instruction (include/rdo_ptq_mxgemm.h) --------------------------------------------------------------
+def native_refusal(module):
+    """None for a QuantModule `native_operand` serves, else the reason it does not: its weight quantiser is no MX class, or it is neither
+    a Linear nor a 1x1 stride-1 unpadded conv (dilation 1, groups 1), or its input channels are no multiple of 32"""
+    q = getattr(module, "weight_quantizer", None)
+    kind = getattr(module, "kind", None)
+    if kind not in ("linear", "conv"):
+        return f"a {kind} module is not GEMM-shaped: the native path serves Linears and 1x1 stride-1 convs"
+    w = module.weight
+    if kind == "conv":
+        kw = module.fwd_kwargs
+        one = lambda v, want: all(int(a) == want for a in ((v, v) if isinstance(v, int) else tuple(v)))
+        if tuple(w.shape[2:]) != (1, 1) or not one(kw["stride"], 1) or not one(kw["padding"], 0) or not one(kw["dilation"], 1) or kw["groups"] != 1:
+            return (f"a conv with kernel {tuple(w.shape[2:])}, stride {kw['stride']}, padding {kw['padding']}, dilation {kw['dilation']}, groups "
+                    f"{kw['groups']} is not a 1x1 stride-1 unpadded conv")
+    K = int(w.shape[1])
+    if K % L.MX_BLOCK:
+        return f"its {K} input channels are no multiple of the MX block size {L.MX_BLOCK}"
+    if not is_mx_any(q):
+        return f"its weight quantiser is a {type(q).__name__}, not an MXQuantizer or MXAdaRoundQuantizer"
+    return None
+
+
+def native_operand(module):
+    """The `ops.MXOperand` [out, in] of a QuantModule's weight as its MX quantiser forwards it: `mx_fakequant` codes and scales from an
+    `MXQuantizer`, `codes_and_scales(weight)` from an `MXAdaRoundQuantizer` (learned rounding included), both along `to_rows`, packed by
+    `ops.mx_pack_codes`.  Memoised next to `weight_pack()` (same weight, quantiser and alpha: same operand) and dropped by
+    `drop_weight_pack()`.  ValueError naming the module and the reason for a module `native_refusal` gives a reason for."""
+    why = native_refusal(module)
+    if why is not None:
+        raise ValueError(f"native_operand: module {_describe(module)}: {why}")
+    q, w = module.weight_quantizer, module.weight
+    alpha = getattr(q, "alpha", None)
+    key = ("mx_native", id(q), q.fmt, module._tkey(w), module._tkey(alpha))
+    memos = module.__dict__.get("_pack_memo")
+    if not isinstance(memos, dict):
+        memos = module.__dict__["_pack_memo"] = {}
+    memo = memos.get("mx_native")
+    if memo is not None and memo[0] == key and memo[2][0] is w and memo[2][1] is alpha:
+        return memo[1]
+    if is_mx_learned(q):
+        codes, scales = q.codes_and_scales(w)
+    else:
+        out = ops.mx_fakequant(q._rows(w.detach()), q.fmt, want=("codes", "scales"))
+        codes, scales = out["codes"], out["scales"]
+    op = ops.mx_pack_codes(codes, scales, q.fmt)
+    memos["mx_native"] = (key, op, (w, alpha))
+    return op
+
+
+def _describe(module):
+    return f"{type(module).__name__}({getattr(module, 'kind', '?')}, weight {tuple(module.weight.shape) if getattr(module, 'weight', None) is not None else None})"
+
+
+def native_rows(module, x):
+    """the activation operand of an eligible module's input as contiguous fp32 [rows, K] -- a Linear's [..., K] flattened, the
+    channels-last view of a 1x1 conv's NCHW input: one row per token or pixel -- and the shape of the module's output"""
+    K = int(module.weight.shape[1])
+    N = int(module.weight.shape[0])
+    if module.kind == "linear":
+        if x.dim() < 1 or x.shape[-1] != K:
+            raise ValueError(f"native_linear: the input must be [..., {K}], got {tuple(x.shape)}")
+        return x.reshape(-1, K).contiguous(), lambda y: y.reshape(*x.shape[:-1], N)
+    if x.dim() != 4 or x.shape[1] != K:
+        raise ValueError(f"native_linear: the input must be [B, {K}, H, W], got {tuple(x.shape)}")
+    B, _, H, W = x.shape
+    return x.permute(0, 2, 3, 1).reshape(-1, K).contiguous(), lambda y: y.reshape(B, H, W, N).permute(0, 3, 1, 2)
+
+
+def native_bias(module):
+    """the bias the module's forward uses in its present quant state (None for a module without one)"""
+    b = module.bias if module.use_weight_quant else module.org_bias
+    return None if b is None else b.detach().contiguous()
+
+
+def native_linear(module, x, act_fmt):
+    """The pre-activation output of an eligible QuantModule (`native_operand`) on the block-scaled matrix instruction: `x` is the
+    module's input ([..., K] for a Linear, NCHW for a 1x1 conv), the result has the module's output shape ([..., N]; a channels-last
+    view [B, N, H, W]).  The rows of the channels-last view of x are quantised to the MX format `act_fmt` in blocks of 32 along the input
+    channels -- the K of the product, along which `to_rows` lays the weight's blocks -- by one `ops.mx_quant_pack` launch; one
+    `ops.mx_gemm` launch multiplies them with the weight's codes and adds the bias of the module's present quant state.  Nothing else of
+    the module's forward is applied: no activation function or fused epilogue, no `se_module`, no output quantiser."""
+    b = native_operand(module)
+    rows, shape = native_rows(module, x)
+    a = ops.mx_quant_pack(rows, act_fmt)
+    return shape(ops.mx_gemm(a, b, native_bias(module)))

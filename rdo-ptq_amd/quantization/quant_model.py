@@ -159,6 +159,13 @@ class QuantModel(nn.Module):
         from .reports import format_report
         return format_report(self, images, formats=formats, lmbda=lmbda, batch=batch, units=units)
 
+    def mx_native_report(self, images, act_fmt="mxfp8_e4m3", batch=8, units=None):
+        """How far the MX codes on the matrix cores (`mx.native_linear`: the block-scaled matrix instruction, input quantised to
+        `act_fmt`) are from their fp32 emulation, for every eligible Linear / 1x1 conv of the chosen units, in one pass over `images`
+        in the state the model is in (`reports.mx_native_report`)."""
+        from .reports import mx_native_report
+        return mx_native_report(self, images, act_fmt=act_fmt, batch=batch, units=units)
+
     def set_weight_format(self, formats, rounding="nearest"):
         """Leave the weights of the units in an MX block format: `formats` is one name for every unit, or a mapping unit
         name -> name (units it does not name keep theirs); a name is one of `hipops._lib.MX_FORMATS` or 'int'.  A format swaps the

@@ -2,7 +2,7 @@
 `unit_report` (each unit's output error, learned rounding against round-to-nearest) and `bias_report` (what the bias correction did).
 Five measure on images: `rd_report` (rate and distortion cost of each unit), `bit_report` / `act_bit_report` (the same at several weight /
 activation widths: the tables `widths.allocate_bits` / `allocate_act_bits` choose from), `format_report` (the same in several MX block
-formats) and `act_width_report` (one-pass screening of activation widths).  The measuring ones are lists of states handed to one sweep driver, `_Sweep`, which owns the argument checks, the
+formats) and `act_width_report` (one-pass screening of activation widths); `mx_native_report` measures, layer by layer, the MX codes on the matrix cores against their emulation.  The measuring ones are lists of states handed to one sweep driver, `_Sweep`, which owns the argument checks, the
 rank sharding, the passes, the restore, the rank reduction and the rows."""
 import math
 from collections import OrderedDict
@@ -164,10 +164,11 @@ class _Sweep:
     those images in each, restores what the states changed, reduces the sums over the ranks and makes the rows (the columns `rd_report`
     documents); `width_table` arranges them per (unit, width)."""
 
-    def __init__(self, what, qnn, images, batch, rd=None):
+    def __init__(self, what, qnn, images, batch, rd=None, side=64):
         """Checks `images` and `batch` -- all `act_width_report` needs -- and with rd = (lmbda, act_quant, units) those three as well,
         reporting faults in the order images, lmbda, batch, act_quant, units; `chosen` is then the selected (name, unit) pairs in
-        `units()` order."""
+        `units()` order.  `side`: what the image sides must be a multiple of (64 for the codecs' rate and distortion; a report that
+        measures layers takes whatever the model runs)."""
         self.what, self.qnn, self.images = what, qnn, images
         if not torch.is_tensor(images) or images.dtype != torch.float32:
             raise ValueError(f"{what}: images must be an fp32 tensor [n, 3, H, W], got "
@@ -176,8 +177,8 @@ class _Sweep:
             raise ValueError(f"{what}: images must be [n, 3, H, W], got {tuple(images.shape)}")
         if images.numel() == 0:
             raise ValueError(f"{what}: images is empty: {tuple(images.shape)}")
-        if images.shape[2] % 64 or images.shape[3] % 64:
-            raise ValueError(f"{what}: the image sides must be multiples of 64 (the calibration crops; nothing is padded), got "
+        if images.shape[2] % side or images.shape[3] % side:
+            raise ValueError(f"{what}: the image sides must be multiples of {side} (the calibration crops; nothing is padded), got "
                              f"{tuple(images.shape[2:])}")
         lmbda, act_quant, units = (None, None, None) if rd is None else rd
         if rd is not None and (isinstance(lmbda, bool) or not isinstance(lmbda, (int, float)) or not math.isfinite(lmbda) or lmbda <= 0):
@@ -664,4 +665,103 @@ def act_bit_report(qnn, images, widths=(4, 6, 8), lmbda=0.01, weight_quant=False
     rep["elements"], rep["skipped"] = elements, skipped
     rep["widths"], rep["n"], rep["pixels"], rep["lmbda"] = list(widths), sweep.n, sweep.pixels, float(lmbda)
     rep["weight_quant"], rep["batch"] = weight_quant, sweep.bs
+    return rep
+
+
+def mx_native_report(qnn, images, act_fmt="mxfp8_e4m3", batch=8, units=None) -> "OrderedDict":
+    """How far the MX codes on the matrix cores are from the emulation a calibration runs under, layer by layer (include/rdo_ptq_mxgemm.h;
+    `mx.native_linear`), measured on `images` (fp32 [n, 3, H, W] of any size the model runs) under torch.no_grad() in ONE pass over the
+    images in the state the model is in: weights in their MX formats (`set_weight_format`), the quant-state flags as set.  Every
+    eligible module of the chosen units (`mx.native_refusal`: a Linear or 1x1 stride-1 conv on an MX weight quantiser with input
+    channels a multiple of 32) computes, under a forward pre-hook, from its actual input x:
+      native     `ops.mx_quant_pack(rows of x, act_fmt)` x `mx.native_operand(module)` + bias by `ops.mx_gemm`
+      emulated   xq of the same `mx_quant_pack` call and the decoded weight (`ops.mx_dequant` of the operand's own codes) through the
+                 fp32-accurate forward kernel the module's forward uses, epilogue EPI_NONE, same bias
+    The model's own forward goes on with x untouched.
+    -> OrderedDict:
+      'modules'  name -> {unit, rows (per pass, all images), K, N, w_fmt, act_fmt, max_abs_diff, rel_l2 = |native - emulated| /
+                 |emulated| from float64 sums over the batches (0 when both are zero), act_sqnr_db = 10 log10(sum x^2 / sum (x - xq)^2)
+                 in float64 (inf at zero error)}
+      'skipped'  name -> why a weighted module of the chosen units has no row
+      'act_fmt', 'n', 'batch'
+    State: every module's use_weight_quant | use_act_quant pair is put back in a `finally` and the hooks are removed whatever a forward
+    raises; quantisers, alpha and scales are not written; the operands made stay memoised next to the weight packs.
+    Raises ValueError before any GPU work for what `rd_report` refuses of images (but for their size), batch and units, for an unknown
+    act_fmt, and for a named unit without an eligible module; NotImplementedError for world_size > 1."""
+    from hipops import _lib as L
+    from hipops import ops
+    from . import dp, mx
+    what = "mx_native_report"
+    sweep = _Sweep(what, qnn, images, batch, side=1)
+    chosen = sweep._units(False, units)
+    ops.mx_format(what, act_fmt)
+    if dp.world()[1] > 1:
+        raise NotImplementedError(f"{what}: not built for data-parallel runs (world_size > 1)")
+    eligible, skipped = OrderedDict(), OrderedDict()
+    for uname, u in chosen:
+        found = False
+        for mn, m in u.named_modules():
+            if not isinstance(m, QuantModule) or m.org_weight is None:
+                continue
+            name = f"{uname}.{mn}" if mn else uname
+            why = mx.native_refusal(m)
+            if why is None:
+                eligible[name], found = (uname, m), True
+            else:
+                skipped[name] = why
+        if units is not None and not found:
+            raise ValueError(f"{what}: unit {uname!r} holds no eligible module: "
+                             f"{ {n: w for n, w in skipped.items() if n == uname or n.startswith(uname + '.')} }")
+    sweep.shard(batch)
+    flags = quant_state(qnn)                                                            # the flags as found: `run` clears them before `enter`
+    sums, packs, handles = {}, {}, []
+
+    def measure(name, m):
+        def hook(mod, args):
+            x = args[0].detach()
+            rows, _ = mx.native_rows(mod, x)
+            b = mx.native_operand(mod)
+            a, xq = ops.mx_quant_pack(rows, act_fmt, want_xq=True)
+            bias = mx.native_bias(mod)
+            native = ops.mx_gemm(a, b, bias)
+            pack = packs.get(name)
+            if pack is None or pack[0] is not b:
+                wdec = ops.mx_dequant(ops.mx_unpack_codes(b), b.scales, b.K, b.fmt)
+                pack = packs[name] = (b, ops.WeightPack(wdec.reshape(b.rows, 1, 1, b.K), bias))
+            emulated = ops.conv2d_fwd_pack(xq.reshape(1, 1, -1, b.K), pack[1], 1, 0, epilogue=L.EPI_NONE).reshape(native.shape)
+            d = (native - emulated).double()
+            x64, e64 = rows.double(), (rows - xq).double()
+            new = torch.stack([(d * d).sum(), (emulated.double() ** 2).sum(), (x64 * x64).sum(), (e64 * e64).sum(), d.abs().max()])
+            st = sums.get(name)
+            if st is None:
+                sums[name] = [new, int(rows.shape[0])]
+            else:
+                st[0] = torch.cat([st[0][:4] + new[:4], torch.maximum(st[0][4:], new[4:])])
+                st[1] += int(rows.shape[0])
+        return hook
+
+    def enter():
+        for m, (w, a) in zip(flags.mods, flags.held):
+            m.use_weight_quant, m.use_act_quant = w, a
+        for name, (_, m) in eligible.items():
+            handles.append(m.register_forward_pre_hook(measure(name, m)))
+    try:
+        sweep.run([("found", enter)], measure=False)
+    finally:
+        for h in handles:
+            h.remove()
+    rep = OrderedDict()
+    rep["modules"] = OrderedDict()
+    for name, (uname, m) in eligible.items():
+        if name not in sums:
+            skipped[name] = "the pass never called the module"
+            continue
+        t, rows = sums[name]
+        diff2, emu2, x2, e2, mad = (float(v) for v in t.cpu())
+        rep["modules"][name] = {"unit": uname, "rows": rows, "K": int(m.weight.shape[1]), "N": int(m.weight.shape[0]),
+                                "w_fmt": m.weight_quantizer.fmt, "act_fmt": act_fmt, "max_abs_diff": mad,
+                                "rel_l2": 0.0 if diff2 == 0 else math.sqrt(diff2 / emu2) if emu2 > 0 else float("inf"),
+                                "act_sqnr_db": _sqnr_db_float(x2, e2)}
+    rep["skipped"] = skipped
+    rep["act_fmt"], rep["n"], rep["batch"] = act_fmt, sweep.n, sweep.bs
     return rep
