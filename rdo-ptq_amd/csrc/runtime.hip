@@ -70,8 +70,8 @@ int32_t* take_iter_publish() {
     return p;
 }
 
-int* h2_overflow_flag() {
-    if (t_h2_bound) return t_h2_bound;
+// the per-device default pair: what rdo_h2_overflow reads, whatever this thread has bound
+static int* h2_default_flag() {
     static std::mutex mu;
     static int* ptr[64] = {};
     int dev = 0;
@@ -84,6 +84,8 @@ int* h2_overflow_flag() {
     }
     return p;
 }
+
+int* h2_overflow_flag() { return t_h2_bound ? t_h2_bound : h2_default_flag(); }
 
 }  // namespace rdo
 
@@ -145,7 +147,7 @@ int rdo_h2_bind_flag(int32_t* flag) {
 }
 
 int rdo_h2_overflow(int reset) {
-    int* p = rdo::h2_overflow_flag();
+    int* p = rdo::h2_default_flag();      // never a caller's bound pair: reading that one here would also reset it
     if (!p) return -1;
     int v[2] = {0, 0};
     if (hipMemcpy(v, p, sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return -1;

@@ -1818,7 +1818,9 @@ def h2_to_float(planes, shape):
 
 
 def h2_overflow(reset=True):
-    """True when a producer of H2 planes met a value outside fp16's range since the last reset (synchronises the device)."""
+    """True when a producer of H2 planes raised the per-device default flag -- met a value outside fp16's range with no word of its own
+    bound -- since the last reset (synchronises the device).  Words bound with `h2_flag` or carried by an output `H2` are the caller's to
+    read: this neither reads nor resets them."""
     rc = int(L.lib().rdo_h2_overflow(int(bool(reset))))
     if rc < 0:
         raise RuntimeError("rdo_h2_overflow failed")
@@ -2057,6 +2059,8 @@ def pixel_shuffle_h2(x, out=None, out_planes=None):
 def pixel_unshuffle2(x, out=None, out_planes=None):
     """[B,2H,2W,C] -> [B,H,W,4C]: gradient of the r = 2 pixel shuffle (16-byte accesses on both sides), as fp32 and / or H2 planes."""
     B, Hr, Wr, Cc = x.shape
+    if Hr % 2 or Wr % 2:
+        raise ValueError(f"pixel_unshuffle2: r = 2 needs an even height and width, got {Hr} x {Wr} (the odd last row / column would be dropped)")
     if out is None and out_planes is None:
         out = torch.empty((B, Hr // 2, Wr // 2, 4 * Cc), device=x.device, dtype=torch.float32)
     _bind_out(out_planes)

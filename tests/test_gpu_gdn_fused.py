@@ -1,6 +1,7 @@
 """rdo_gdn_fwd_bwd -- the GDN / IGDN block of a unit (norm pool, loss tail, gamma'^T GEMM, dx) in one launch -- against the chain of
-the four launches it replaces: linear_h2(square_input) -> loss_gdn_bwd -> linear_h2 -> gdn_bwd_dx_h2.  The chain is pinned to fp64 /
-torch / the oracle by the rest of the suite (test_gpu_h2.py, test_gpu_swin_kernels.py); the fused launch runs the same device
+the four launches it replaces: linear_h2(square_input) -> loss_gdn_bwd -> linear_h2 -> gdn_bwd_dx_h2.  The tail launches of the chain (loss_gdn_bwd, gdn_bwd_dx_h2) are pinned to float64 formulas with stated error
+bounds by test_gpu_tail_parity.py (reference: tail_reference.py, itself pinned to the oracle's f_gdn autograd by test_tail_reference.py),
+linear_h2 to fp64 by test_gpu_h2.py and test_gpu_swin_kernels.py; the fused launch runs the same device
 functions in the same order, so every fp32 output and the int16 planes must equal the chain's BIT FOR BIT.  Only the loss log is
 summed in another order (float atomics): rtol 1e-5, the bar of test_loss_gdn_bwd_equals_unfused_chain."""
 import pytest

@@ -59,6 +59,19 @@ def test_gdn_gate():
     assert not ops.gdn_fwd_bwd_px_supported((1, 6, 6, 192))                        # 36 tokens: no whole tile of 64
 
 
+def test_pixel_unshuffle2_refuses_odd_sizes():
+    """[B,2H,2W,C] -> [B,H,W,4C]: an odd height or width has no r = 2 unshuffle (the wrapper used to drop the last row / column); refused
+    before any pointer is taken, so a CPU tensor gets this far"""
+    import pytest
+    import torch
+    from hipops import ops
+    for shape in ((1, 5, 4, 16), (1, 4, 7, 16), (2, 3, 3, 4)):
+        with pytest.raises(ValueError, match="pixel_unshuffle2"):
+            ops.pixel_unshuffle2(torch.zeros(shape))
+    with pytest.raises(RuntimeError, match="no CPU path"):       # even sizes pass the check and reach the operand check
+        ops.pixel_unshuffle2(torch.zeros(1, 4, 6, 16), out=torch.zeros(1, 2, 3, 64))
+
+
 def test_bad_arguments_are_refused_before_any_launch():
     from hipops import _lib as L
     from hipops import ops
