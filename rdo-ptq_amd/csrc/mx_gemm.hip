@@ -18,14 +18,12 @@
 // the instruction's own sum over eight neighbouring FP8 products drops small ones, one product per sum drops nothing.
 // C/D: col = lane & 15, row = 4 (lane >> 4) + reg.
 // The kernel is a template over the (A, B) formats, whose numbers are immediates of the instruction: 25 instantiations.
+// load_fragment, keep_one_of_eight, the K step and the store are mx_mfma_device.h's, shared with the convolution (mx_conv.hip).
 #include "rdo_common.h"
 #include "../../include/rdo_ptq_mxgemm.h"
-#include "mx_device.h"
+#include "mx_mfma_device.h"
 
 namespace {
-
-using i32x8 = __attribute__((ext_vector_type(8))) int;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 // ---- packed operand -----------------------------------------------------------------------------------------------------------------
 // Called by all 64 lanes.  `code` (b bits) is the element `lane` of this half-wave's block; lane t < b puts together dword t of the
@@ -99,58 +97,6 @@ __global__ __launch_bounds__(256) void mx_quant_pack_kernel(const float* __restr
 }
 
 // ---- the GEMM -----------------------------------------------------------------------------------------------------------------------
-// the instruction's format numbers {0 E4M3, 1 E5M2, 2 E2M3, 3 E3M2, 4 FP4} and the operand dwords of each
-constexpr int hw_dwords(int hw) { return hw <= 1 ? 8 : (hw <= 3 ? 6 : 4); }
-
-inline int hw_format(int format) {
-    switch (format) {
-        case RDO_MX_FP4: return 4;
-        case RDO_MX_FP6_E2M3: return 2;
-        case RDO_MX_FP6_E3M2: return 3;
-        case RDO_MX_FP8_E4M3: return 0;
-        case RDO_MX_FP8_E5M2: return 1;
-    }
-    return -1;
-}
-
-// The operand registers of lane (row, k group kg) for the K step that starts at block k0 of the row whose packed blocks start at `row`.
-// FP4 / FP6 (4 / 6 dwords): the lane owns block k0 + kg, its dwords are the registers.  FP8 (8 dwords): registers 0 .. 3 are elements
-// 16 kg .. 16 kg + 15 of the step and registers 4 .. 7 elements 64 + 16 kg .. 64 + 16 kg + 15 -- the second (kg odd) or first half of
-// block k0 + kg / 2 and the same half of block k0 + 2 + kg / 2; the scale of lane kg is block k0 + kg's for every width.
-template <int DW>
-__device__ __forceinline__ i32x8 load_fragment(const uint32_t* __restrict__ row, long k0, int kg, long nb, bool row_ok) {
-    i32x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-    if constexpr (DW == 8) {
-        const long b0 = k0 + (kg >> 1), b1 = b0 + 2;
-        const int off = (kg & 1) * 4;
-        if (row_ok && b0 < nb) {
-#pragma unroll
-            for (int d = 0; d < 4; ++d) v[d] = (int)row[b0 * 8 + off + d];
-        }
-        if (row_ok && b1 < nb) {
-#pragma unroll
-            for (int d = 0; d < 4; ++d) v[4 + d] = (int)row[b1 * 8 + off + d];
-        }
-    } else {
-        const long kb = k0 + kg;
-        if (row_ok && kb < nb) {
-#pragma unroll
-            for (int d = 0; d < DW; ++d) v[d] = (int)row[kb * DW + d];
-        }
-    }
-    return v;
-}
-
-// An FP8 fragment with all but element t of every eight neighbouring elements cleared (t = 0 .. 7): the eight lie in a pair of VGPRs
-// (2 p, 2 p + 1), element t in byte t & 3 of the VGPR of parity t >> 2.
-__device__ __forceinline__ i32x8 keep_one_of_eight(const i32x8& v, int t) {
-    const int m = (int)(0xFFu << (8 * (t & 3)));
-    i32x8 o = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int p = 0; p < 4; ++p) o[2 * p + (t >> 2)] = v[2 * p + (t >> 2)] & m;
-    return o;
-}
-
 template <int FA, int FB>
 __global__ __launch_bounds__(256) void mx_gemm_kernel(const uint32_t* __restrict__ a, const uint8_t* __restrict__ sa,
                                                       const uint32_t* __restrict__ b, const uint8_t* __restrict__ sb, int M, int N, long nb,
@@ -187,45 +133,9 @@ __global__ __launch_bounds__(256) void mx_gemm_kernel(const uint32_t* __restrict
             xa[i] = aok[i] && kok ? (int)sa[arow[i] + kb] : 127;
             xb[i] = bok[i] && kok ? (int)sb[brow[i] + kb] : 127;
         }
-        if constexpr (DA == 8 || DB == 8) {
-            // With an FP8 operand the instruction adds the products of eight neighbouring k aligned to the largest of the eight and
-            // drops what lies some 14 bits below it.  Eight passes, each with one element of every eight of ONE FP8 operand kept and
-            // the rest cleared, leave a single product in every such sum: nothing is dropped, the sums between the groups are fp32's.
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                i32x8 ma[2], mb[2];
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    ma[i] = DA == 8 ? keep_one_of_eight(fa[i], t) : fa[i];
-                    mb[i] = DA == 8 ? fb[i] : keep_one_of_eight(fb[i], t);
-                }
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(ma[i], mb[j], acc[i][j], FA, FB, 0, xa[i], 0, xb[j]);
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fa[i], fb[j], acc[i][j], FA, FB, 0, xa[i], 0, xb[j]);
-        }
+        mx_mfma_step<FA, FB>(fa, fb, xa, xb, acc);
     }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const long col = n0 + 16 * j + r;
-        if (col >= N) continue;
-        const float bj = bias ? bias[col] : 0.f;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const long row = m0 + 16 * i + 4 * kg + q;
-                if (row < M) y[row * N + col] = acc[i][j][q] + bj;
-            }
-    }
+    mx_store_tiles(acc, bias, y, m0, n0, M, N, r, kg);
 }
 
 using GemmKernel = void (*)(const uint32_t*, const uint8_t*, const uint32_t*, const uint8_t*, int, int, long, int, const float*, float*);
@@ -240,8 +150,6 @@ inline long packed_blocks(int32_t rows, int64_t K) {
     long nb = 0;
     return mx_blocks(rows, K, nb);
 }
-
-inline bool aligned4(const void* p) { return reinterpret_cast<uintptr_t>(p) % 4 == 0; }
 
 }  // namespace
 

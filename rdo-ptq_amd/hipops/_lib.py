@@ -261,6 +261,12 @@ _SIGS_MXGEMM = {
     "rdo_mx_gemm": (C.c_int, [P, P, C.c_int32, P, P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, P, P, P]),
 }
 EXPORTS_MXGEMM = tuple(_SIGS_MXGEMM)
+# include/rdo_ptq_mxconv.h: k x k convolutions on the block-scaled matrix instruction from the packed MX operands
+_SIGS_MXCONV = {
+    "rdo_mx_conv2d_out_pixels": (C.c_int64, [C.c_int32] * 6),
+    "rdo_mx_conv2d": (C.c_int, [P, P, C.c_int32, P, P, C.c_int32] + [C.c_int32] * 8 + [P, P, P]),
+}
+EXPORTS_MXCONV = tuple(_SIGS_MXCONV)
 
 _lib = None
 
@@ -280,7 +286,7 @@ def lib():
         for name, (res, args) in (list(_SIGS.items()) + list(_SIGS_GDN.items()) + list(_SIGS_BIAS.items()) + list(_SIGS_BITS.items())
                                   + list(_SIGS_PACK.items()) + list(_SIGS_SUBPEL.items()) + list(_SIGS_ACTBITS.items())
                                   + list(_SIGS_ATTNQ.items()) + list(_SIGS_MX.items()) + list(_SIGS_MXROUND.items())
-                                  + list(_SIGS_MXGEMM.items())):
+                                  + list(_SIGS_MXGEMM.items()) + list(_SIGS_MXCONV.items())):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         _lib = h

@@ -929,6 +929,37 @@ def mx_gemm(a, b, bias=None):
     return y
 
 
+def mx_conv2d(x, w, shape, k, stride=1, pad=0, bias=None):
+    """y fp32 [B, Ho, Wo, N] = conv(x, w) (+ bias) on the block-scaled matrix instruction (rdo_mx_conv2d; include/rdo_ptq_mxconv.h): x an
+    `MXOperand` [B * H * W, C] -- an NHWC activation, one packed row per pixel, what `mx_quant_pack` makes of the NHWC rows --, shape =
+    (B, H, W), w an `MXOperand` [N, k * k * C] whose rows are in (kh, kw, in) order (`to_rows`), of any two formats; square kernel k, one
+    stride >= 1, one zero padding >= 0, dilation 1, groups 1; bias contiguous fp32 [N] or None.  Ho = (H + 2 pad - k) // stride + 1, Wo
+    likewise.  Bit for bit `mx_gemm` on the im2col matrix of x.  Checked on the host before a pointer is taken."""
+    what = "mx_conv2d"
+    fx, _, _ = _mx_operand(what, "x", x)
+    fw, _, _ = _mx_operand(what, "w", w, device=x.packed.device)
+    if isinstance(shape, (str, bytes)) or not hasattr(shape, "__len__") or len(shape) != 3:
+        raise ValueError(f"{what}: shape must be (B, H, W), got {shape!r}")
+    B, H, W = (A.whole(what, f"shape[{i}]", v, 1) for i, v in enumerate(shape))
+    k, stride, pad = A.whole(what, "k", k, 1), A.whole(what, "stride", stride, 1), A.whole(what, "pad", pad, 0)
+    if x.rows != B * H * W:
+        raise ValueError(f"{what}: x has {x.rows} rows, shape {(B, H, W)} states {B * H * W} pixels")
+    if w.K != k * k * x.K:
+        raise ValueError(f"{what}: w has K = {w.K}, a {k} x {k} kernel over x's {x.K} channels needs K = {k * k * x.K}")
+    if H + 2 * pad < k or W + 2 * pad < k:
+        raise ValueError(f"{what}: a {k} x {k} kernel does not fit the {H} x {W} input under padding {pad}")
+    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    if B * Ho * Wo > 0x7fffffff or max(k, stride, pad, x.K) > 0x7fffffff:
+        raise ValueError(f"{what}: {B} x {Ho} x {Wo} output pixels, {x.K} channels, k {k}, stride {stride} or pad {pad} is beyond 2^31 - 1")
+    dev = x.packed.device
+    A.tensor(what, "bias", bias, shape=(w.rows,), contiguous=True, device=dev, optional=True, oneshot=True)
+    _mx_cuda(what, x.packed, "x.packed")
+    y = torch.empty(B, Ho, Wo, w.rows, device=dev, dtype=torch.float32)
+    L.check(L.lib().rdo_mx_conv2d(_ptr(x.packed, *_U8), _ptr(x.scales, *_U8), fx, _ptr(w.packed, *_U8), _ptr(w.scales, *_U8), fw, B, H, W, x.K,
+                                  w.rows, k, stride, pad, _ptr(bias), _ptr(y), _stream()), "rdo_mx_conv2d")
+    return y
+
+
 def pack_row_words(inner, bits):
     """W = ceil(inner * bits / 32): the 32-bit words one row of `inner` codes of `bits` bits occupies (rdo_pack_row_words on the host)"""
     return -(-int(inner) * int(bits) // 32)

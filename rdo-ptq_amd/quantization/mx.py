@@ -8,7 +8,14 @@ block-scaled matrix instruction, `native_linear(module, x, act_fmt)` the module'
 format as well -- for token-matrix Linears and 1x1 stride-1 convs whose input channels are a multiple of 32;
 `QuantModel.mx_native_report` measures it against the emulation, layer by layer.  The quantisers themselves serve weights only: an
 activation is put on an MX grid by `native_linear` (`ops.mx_quant_pack`), not by a quantiser call with act=True.  MX activations inside
-the modules' own forward and a packed MX container are not built."""
+the modules' own forward and a packed MX container are not built.
+
+k x k convolutions (include/rdo_ptq_mxconv.h): `native_conv_operand(module)` is a conv's weight [Cout, k * k * Cin] as a packed operand,
+rows in `to_rows`' (kh, kw, in) order, `native_conv(module, x, act_fmt)` its pre-activation output from the NHWC pixels of x quantised
+to an MX format -- an implicit GEMM, bit for bit `ops.mx_gemm` on the im2col matrix -- for square kernels with one stride and one zero
+padding, dilation 1, groups 1 and input channels a multiple of 32 (`native_conv_refusal`); `mx_native_report(..., convs=True)` measures
+them too.  Not built: transposed convs, GDN, the native path inside the modules' forward or the calibration loop, a backward, a producer
+fused into the conv; no rate-distortion claim is made for it."""
 import torch
 import torch.nn as nn
 
@@ -180,13 +187,18 @@ def native_operand(module):
     why = native_refusal(module)
     if why is not None:
         raise ValueError(f"native_operand: module {_describe(module)}: {why}")
+    return _weight_operand(module, "mx_native")
+
+
+def _weight_operand(module, slot):
+    """the packed operand of a module's weight along `to_rows`, memoised in `_pack_memo[slot]`"""
     q, w = module.weight_quantizer, module.weight
     alpha = getattr(q, "alpha", None)
-    key = ("mx_native", id(q), q.fmt, module._tkey(w), module._tkey(alpha))
+    key = (slot, id(q), q.fmt, module._tkey(w), module._tkey(alpha))
     memos = module.__dict__.get("_pack_memo")
     if not isinstance(memos, dict):
         memos = module.__dict__["_pack_memo"] = {}
-    memo = memos.get("mx_native")
+    memo = memos.get(slot)
     if memo is not None and memo[0] == key and memo[2][0] is w and memo[2][1] is alpha:
         return memo[1]
     if is_mx_learned(q):
@@ -195,7 +207,7 @@ def native_operand(module):
         out = ops.mx_fakequant(q._rows(w.detach()), q.fmt, want=("codes", "scales"))
         codes, scales = out["codes"], out["scales"]
     op = ops.mx_pack_codes(codes, scales, q.fmt)
-    memos["mx_native"] = (key, op, (w, alpha))
+    memos[slot] = (key, op, (w, alpha))
     return op
 
 
@@ -235,3 +247,66 @@ def native_linear(module, x, act_fmt):
     rows, shape = native_rows(module, x)
     a = ops.mx_quant_pack(rows, act_fmt)
     return shape(ops.mx_gemm(a, b, native_bias(module)))
+
+
+# ---- k x k convolutions on the same instruction (include/rdo_ptq_mxconv.h) --------------------------------------------------------------------
+def _pair(v):
+    return (int(v), int(v)) if isinstance(v, int) else tuple(int(a) for a in v)
+
+
+def conv_geometry(module):
+    """(k, stride, pad) of a conv QuantModule `native_conv_refusal` accepts"""
+    kw = module.fwd_kwargs
+    return int(module.weight.shape[2]), _pair(kw["stride"])[0], _pair(kw["padding"])[0]
+
+
+def native_conv_refusal(module):
+    """None for a QuantModule `native_conv_operand` serves, else the reason it does not, looked for in this order: it is no conv; its
+    kernel, stride (>= 1) or padding (>= 0) is not square, or it is dilated or grouped; its input channels are no multiple of 32; its
+    weight quantiser is no MX class"""
+    q = getattr(module, "weight_quantizer", None)
+    kind = getattr(module, "kind", None)
+    if kind != "conv":
+        return f"a {kind} module is not a convolution: the native conv path serves square k x k convs"
+    w, kw = module.weight, module.fwd_kwargs
+    (kh, kwid), (sh, sw), (dh, dw), pad = tuple(int(a) for a in w.shape[2:]), _pair(kw["stride"]), _pair(kw["dilation"]), kw["padding"]
+    square_pad = not isinstance(pad, str) and _pair(pad)[0] == _pair(pad)[1] and _pair(pad)[0] >= 0
+    if kh != kwid or sh != sw or sh < 1 or not square_pad or (dh, dw) != (1, 1) or kw["groups"] != 1:
+        return (f"a conv with kernel {(kh, kwid)}, stride {kw['stride']}, padding {kw['padding']}, dilation {kw['dilation']}, groups "
+                f"{kw['groups']} is not a square-kernel conv with one stride, one zero padding, dilation 1 and groups 1")
+    K = int(w.shape[1])
+    if K % L.MX_BLOCK:
+        return f"its {K} input channels are no multiple of the MX block size {L.MX_BLOCK}"
+    if not is_mx_any(q):
+        return f"its weight quantiser is a {type(q).__name__}, not an MXQuantizer or MXAdaRoundQuantizer"
+    return None
+
+
+def native_conv_operand(module):
+    """The `ops.MXOperand` [Cout, k * k * Cin] of a conv QuantModule's weight as its MX quantiser forwards it, made along `to_rows` (rows
+    in (kh, kw, in) order) exactly as `native_operand` makes it, learned rounding included.  Memoised under a key of its own next to
+    `weight_pack()` and dropped by `drop_weight_pack()`; for a 1x1 stride-1 unpadded conv it is the object `native_operand` returns.
+    ValueError naming the module and the reason for a module `native_conv_refusal` gives a reason for."""
+    why = native_conv_refusal(module)
+    if why is not None:
+        raise ValueError(f"native_conv_operand: module {_describe(module)}: {why}")
+    if native_refusal(module) is None:
+        return native_operand(module)
+    return _weight_operand(module, "mx_native_conv")
+
+
+def native_conv(module, x, act_fmt):
+    """The pre-activation output of an eligible conv QuantModule (`native_conv_operand`) on the block-scaled matrix instruction: `x` is
+    the module's NCHW input, the result a channels-last view [B, N, Ho, Wo].  The rows of the channels-last view of x -- one per pixel --
+    are quantised to the MX format `act_fmt` in blocks of 32 along the input channels by one `ops.mx_quant_pack` launch; one
+    `ops.mx_conv2d` launch convolves them with the weight's codes at the module's stride and padding and adds the bias of the module's
+    present quant state.  Nothing else of the module's forward is applied: no activation function or fused epilogue, no `se_module`, no
+    output quantiser."""
+    b = native_conv_operand(module)
+    C = int(module.weight.shape[1])
+    if x.dim() != 4 or x.shape[1] != C:
+        raise ValueError(f"native_conv: the input must be [B, {C}, H, W], got {tuple(x.shape)}")
+    B, _, H, W = (int(v) for v in x.shape)
+    k, stride, pad = conv_geometry(module)
+    a = ops.mx_quant_pack(x.permute(0, 2, 3, 1).reshape(-1, C).contiguous(), act_fmt)
+    return ops.mx_conv2d(a, b, (B, H, W), k, stride, pad, native_bias(module)).permute(0, 3, 1, 2)

@@ -159,12 +159,13 @@ class QuantModel(nn.Module):
         from .reports import format_report
         return format_report(self, images, formats=formats, lmbda=lmbda, batch=batch, units=units)
 
-    def mx_native_report(self, images, act_fmt="mxfp8_e4m3", batch=8, units=None):
+    def mx_native_report(self, images, act_fmt="mxfp8_e4m3", batch=8, units=None, convs=False):
         """How far the MX codes on the matrix cores (`mx.native_linear`: the block-scaled matrix instruction, input quantised to
-        `act_fmt`) are from their fp32 emulation, for every eligible Linear / 1x1 conv of the chosen units, in one pass over `images`
-        in the state the model is in (`reports.mx_native_report`)."""
+        `act_fmt`) are from their fp32 emulation, for every eligible Linear / 1x1 conv of the chosen units -- with convs=True also for
+        every eligible k x k conv (`mx.native_conv`) --, in one pass over `images` in the state the model is in
+        (`reports.mx_native_report`)."""
         from .reports import mx_native_report
-        return mx_native_report(self, images, act_fmt=act_fmt, batch=batch, units=units)
+        return mx_native_report(self, images, act_fmt=act_fmt, batch=batch, units=units, convs=convs)
 
     def set_weight_format(self, formats, rounding="nearest"):
         """Leave the weights of the units in an MX block format: `formats` is one name for every unit, or a mapping unit

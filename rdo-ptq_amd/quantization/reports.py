@@ -668,7 +668,7 @@ def act_bit_report(qnn, images, widths=(4, 6, 8), lmbda=0.01, weight_quant=False
     return rep
 
 
-def mx_native_report(qnn, images, act_fmt="mxfp8_e4m3", batch=8, units=None) -> "OrderedDict":
+def mx_native_report(qnn, images, act_fmt="mxfp8_e4m3", batch=8, units=None, convs=False) -> "OrderedDict":
     """How far the MX codes on the matrix cores are from the emulation a calibration runs under, layer by layer (include/rdo_ptq_mxgemm.h;
     `mx.native_linear`), measured on `images` (fp32 [n, 3, H, W] of any size the model runs) under torch.no_grad() in ONE pass over the
     images in the state the model is in: weights in their MX formats (`set_weight_format`), the quant-state flags as set.  Every
@@ -678,6 +678,13 @@ def mx_native_report(qnn, images, act_fmt="mxfp8_e4m3", batch=8, units=None) -> 
       emulated   xq of the same `mx_quant_pack` call and the decoded weight (`ops.mx_dequant` of the operand's own codes) through the
                  fp32-accurate forward kernel the module's forward uses, epilogue EPI_NONE, same bias
     The model's own forward goes on with x untouched.
+    convs=True also measures every conv `mx.native_conv_refusal` accepts (include/rdo_ptq_mxconv.h: a square kernel, one stride, one
+    zero padding, dilation 1, groups 1, input channels a multiple of 32; a 1x1 conv among them goes this way too):
+      native     `ops.mx_quant_pack(NHWC pixels of x, act_fmt)`, then `ops.mx_conv2d` with `mx.native_conv_operand(module)` + bias
+      emulated   xq of the same call as NHWC and the decoded weight as [N, k, k, Cin] through `ops.conv2d_fwd_pack` at the module's
+                 stride and padding, epilogue EPI_NONE, same bias
+    Their rows gain k, stride and pad; K is k * k * Cin, rows counts output pixels, act_sqnr_db is taken over the input pixels; a conv
+    that is refused is skipped for the reason `native_conv_refusal` gives.  convs=False gives what it gave before convs existed.
     -> OrderedDict:
       'modules'  name -> {unit, rows (per pass, all images), K, N, w_fmt, act_fmt, max_abs_diff, rel_l2 = |native - emulated| /
                  |emulated| from float64 sums over the batches (0 when both are zero), act_sqnr_db = 10 log10(sum x^2 / sum (x - xq)^2)
@@ -687,7 +694,7 @@ def mx_native_report(qnn, images, act_fmt="mxfp8_e4m3", batch=8, units=None) -> 
     State: every module's use_weight_quant | use_act_quant pair is put back in a `finally` and the hooks are removed whatever a forward
     raises; quantisers, alpha and scales are not written; the operands made stay memoised next to the weight packs.
     Raises ValueError before any GPU work for what `rd_report` refuses of images (but for their size), batch and units, for an unknown
-    act_fmt, and for a named unit without an eligible module; NotImplementedError for world_size > 1."""
+    act_fmt, for convs not a bool, and for a named unit without an eligible module; NotImplementedError for world_size > 1."""
     from hipops import _lib as L
     from hipops import ops
     from . import dp, mx
@@ -695,6 +702,8 @@ def mx_native_report(qnn, images, act_fmt="mxfp8_e4m3", batch=8, units=None) -> 
     sweep = _Sweep(what, qnn, images, batch, side=1)
     chosen = sweep._units(False, units)
     ops.mx_format(what, act_fmt)
+    if not isinstance(convs, bool):
+        raise ValueError(f"{what}: convs must be True or False, got {convs!r}")
     if dp.world()[1] > 1:
         raise NotImplementedError(f"{what}: not built for data-parallel runs (world_size > 1)")
     eligible, skipped = OrderedDict(), OrderedDict()
@@ -704,7 +713,8 @@ def mx_native_report(qnn, images, act_fmt="mxfp8_e4m3", batch=8, units=None) -> 
             if not isinstance(m, QuantModule) or m.org_weight is None:
                 continue
             name = f"{uname}.{mn}" if mn else uname
-            why = mx.native_refusal(m)
+            as_conv = convs and m.kind == "conv"
+            why = mx.native_conv_refusal(m) if as_conv else mx.native_refusal(m)
             if why is None:
                 eligible[name], found = (uname, m), True
             else:
@@ -716,28 +726,52 @@ def mx_native_report(qnn, images, act_fmt="mxfp8_e4m3", batch=8, units=None) -> 
     flags = quant_state(qnn)                                                            # the flags as found: `run` clears them before `enter`
     sums, packs, handles = {}, {}, []
 
+    def decoded(name, b, bias, shape):
+        pack = packs.get(name)
+        if pack is None or pack[0] is not b:
+            wdec = ops.mx_dequant(ops.mx_unpack_codes(b), b.scales, b.K, b.fmt)
+            pack = packs[name] = (b, ops.WeightPack(wdec.reshape(shape), bias))
+        return pack[1]
+
+    def measure_conv(mod, name, x):
+        """(pixel rows, xq, native, emulated) of a conv on `ops.mx_conv2d`; native and emulated [output pixels, N]"""
+        C = int(mod.weight.shape[1])
+        if x.dim() != 4 or x.shape[1] != C:
+            raise ValueError(f"{what}: module {name!r}: the input must be [B, {C}, H, W], got {tuple(x.shape)}")
+        B, _, H, W = (int(v) for v in x.shape)
+        k, stride, pad = mx.conv_geometry(mod)
+        rows = x.permute(0, 2, 3, 1).reshape(-1, C).contiguous()
+        b = mx.native_conv_operand(mod)
+        a, xq = ops.mx_quant_pack(rows, act_fmt, want_xq=True)
+        bias = mx.native_bias(mod)
+        native = ops.mx_conv2d(a, b, (B, H, W), k, stride, pad, bias).reshape(-1, b.rows)
+        emulated = ops.conv2d_fwd_pack(xq.reshape(B, H, W, C), decoded(name, b, bias, (b.rows, k, k, C)), stride, pad, epilogue=L.EPI_NONE)
+        return rows, xq, native, emulated.reshape(native.shape)
+
     def measure(name, m):
+        as_conv = convs and m.kind == "conv"
+
         def hook(mod, args):
             x = args[0].detach()
-            rows, _ = mx.native_rows(mod, x)
-            b = mx.native_operand(mod)
-            a, xq = ops.mx_quant_pack(rows, act_fmt, want_xq=True)
-            bias = mx.native_bias(mod)
-            native = ops.mx_gemm(a, b, bias)
-            pack = packs.get(name)
-            if pack is None or pack[0] is not b:
-                wdec = ops.mx_dequant(ops.mx_unpack_codes(b), b.scales, b.K, b.fmt)
-                pack = packs[name] = (b, ops.WeightPack(wdec.reshape(b.rows, 1, 1, b.K), bias))
-            emulated = ops.conv2d_fwd_pack(xq.reshape(1, 1, -1, b.K), pack[1], 1, 0, epilogue=L.EPI_NONE).reshape(native.shape)
+            if as_conv:
+                rows, xq, native, emulated = measure_conv(mod, name, x)
+            else:
+                rows, _ = mx.native_rows(mod, x)
+                b = mx.native_operand(mod)
+                a, xq = ops.mx_quant_pack(rows, act_fmt, want_xq=True)
+                bias = mx.native_bias(mod)
+                native = ops.mx_gemm(a, b, bias)
+                emulated = ops.conv2d_fwd_pack(xq.reshape(1, 1, -1, b.K), decoded(name, b, bias, (b.rows, 1, 1, b.K)), 1, 0,
+                                               epilogue=L.EPI_NONE).reshape(native.shape)
             d = (native - emulated).double()
             x64, e64 = rows.double(), (rows - xq).double()
             new = torch.stack([(d * d).sum(), (emulated.double() ** 2).sum(), (x64 * x64).sum(), (e64 * e64).sum(), d.abs().max()])
             st = sums.get(name)
             if st is None:
-                sums[name] = [new, int(rows.shape[0])]
+                sums[name] = [new, int(native.shape[0])]
             else:
                 st[0] = torch.cat([st[0][:4] + new[:4], torch.maximum(st[0][4:], new[4:])])
-                st[1] += int(rows.shape[0])
+                st[1] += int(native.shape[0])
         return hook
 
     def enter():
@@ -762,6 +796,9 @@ def mx_native_report(qnn, images, act_fmt="mxfp8_e4m3", batch=8, units=None) -> 
                                 "w_fmt": m.weight_quantizer.fmt, "act_fmt": act_fmt, "max_abs_diff": mad,
                                 "rel_l2": 0.0 if diff2 == 0 else math.sqrt(diff2 / emu2) if emu2 > 0 else float("inf"),
                                 "act_sqnr_db": _sqnr_db_float(x2, e2)}
+        if convs and m.kind == "conv":
+            k, stride, pad = mx.conv_geometry(m)
+            rep["modules"][name].update(k=k, stride=stride, pad=pad, K=k * k * int(m.weight.shape[1]))
     rep["skipped"] = skipped
     rep["act_fmt"], rep["n"], rep["batch"] = act_fmt, sweep.n, sweep.bs
     return rep
