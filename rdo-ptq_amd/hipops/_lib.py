@@ -267,6 +267,12 @@ _SIGS_MXCONV = {
     "rdo_mx_conv2d": (C.c_int, [P, P, C.c_int32, P, P, C.c_int32] + [C.c_int32] * 8 + [P, P, P]),
 }
 EXPORTS_MXCONV = tuple(_SIGS_MXCONV)
+# include/rdo_ptq_mxtconv.h: transposed k x k convolutions on the block-scaled matrix instruction from the packed MX operands
+_SIGS_MXTCONV = {
+    "rdo_mx_conv_transpose2d_out_pixels": (C.c_int64, [C.c_int32] * 7),
+    "rdo_mx_conv_transpose2d": (C.c_int, [P, P, C.c_int32, P, P, C.c_int32] + [C.c_int32] * 9 + [P, P, P]),
+}
+EXPORTS_MXTCONV = tuple(_SIGS_MXTCONV)
 
 _lib = None
 
@@ -286,7 +292,7 @@ def lib():
         for name, (res, args) in (list(_SIGS.items()) + list(_SIGS_GDN.items()) + list(_SIGS_BIAS.items()) + list(_SIGS_BITS.items())
                                   + list(_SIGS_PACK.items()) + list(_SIGS_SUBPEL.items()) + list(_SIGS_ACTBITS.items())
                                   + list(_SIGS_ATTNQ.items()) + list(_SIGS_MX.items()) + list(_SIGS_MXROUND.items())
-                                  + list(_SIGS_MXGEMM.items()) + list(_SIGS_MXCONV.items())):
+                                  + list(_SIGS_MXGEMM.items()) + list(_SIGS_MXCONV.items()) + list(_SIGS_MXTCONV.items())):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         _lib = h

@@ -960,6 +960,42 @@ def mx_conv2d(x, w, shape, k, stride=1, pad=0, bias=None):
     return y
 
 
+def mx_conv_transpose2d(x, w, shape, k, stride=1, pad=0, output_padding=0, bias=None):
+    """y fp32 [B, Ho, Wo, N] = conv_transpose(x, w) (+ bias) on the block-scaled matrix instruction (rdo_mx_conv_transpose2d;
+    include/rdo_ptq_mxtconv.h): x an `MXOperand` [B * H * W, C] -- an NHWC activation, one packed row per pixel, what `mx_quant_pack`
+    makes of the NHWC rows --, shape = (B, H, W), w an `MXOperand` [N, k * k * C] whose rows are those of `to_rows(W, tconv=True)`
+    ((kh, kw, in) order, taps un-flipped), of any two formats; square kernel k, one stride >= 1, one padding >= 0, one output padding
+    in 0 .. stride - 1, dilation 1, groups 1; bias contiguous fp32 [N] or None.  Ho = (H - 1) stride - 2 pad + k + output_padding, Wo
+    likewise.  Phase by phase bit for bit `mx_gemm` on the gathered operands.  Checked on the host before a pointer is taken."""
+    what = "mx_conv_transpose2d"
+    fx, _, _ = _mx_operand(what, "x", x)
+    fw, _, _ = _mx_operand(what, "w", w, device=x.packed.device)
+    if isinstance(shape, (str, bytes)) or not hasattr(shape, "__len__") or len(shape) != 3:
+        raise ValueError(f"{what}: shape must be (B, H, W), got {shape!r}")
+    B, H, W = (A.whole(what, f"shape[{i}]", v, 1) for i, v in enumerate(shape))
+    k, stride, pad = A.whole(what, "k", k, 1), A.whole(what, "stride", stride, 1), A.whole(what, "pad", pad, 0)
+    opad = A.whole(what, "output_padding", output_padding, 0)
+    if opad >= stride:
+        raise ValueError(f"{what}: output_padding {opad} must be below the stride {stride}")
+    if x.rows != B * H * W:
+        raise ValueError(f"{what}: x has {x.rows} rows, shape {(B, H, W)} states {B * H * W} pixels")
+    if w.K != k * k * x.K:
+        raise ValueError(f"{what}: w has K = {w.K}, a {k} x {k} kernel over x's {x.K} channels needs K = {k * k * x.K}")
+    Ho, Wo = (H - 1) * stride - 2 * pad + k + opad, (W - 1) * stride - 2 * pad + k + opad
+    if Ho <= 0 or Wo <= 0:
+        raise ValueError(f"{what}: a {k} x {k} kernel at stride {stride}, padding {pad} and output padding {opad} leaves no output of the "
+                         f"{H} x {W} input")
+    if B * Ho * Wo > 0x7fffffff or max(k, stride, pad, x.K) > 0x7fffffff:
+        raise ValueError(f"{what}: {B} x {Ho} x {Wo} output pixels, {x.K} channels, k {k}, stride {stride} or pad {pad} is beyond 2^31 - 1")
+    dev = x.packed.device
+    A.tensor(what, "bias", bias, shape=(w.rows,), contiguous=True, device=dev, optional=True, oneshot=True)
+    _mx_cuda(what, x.packed, "x.packed")
+    y = torch.empty(B, Ho, Wo, w.rows, device=dev, dtype=torch.float32)
+    L.check(L.lib().rdo_mx_conv_transpose2d(_ptr(x.packed, *_U8), _ptr(x.scales, *_U8), fx, _ptr(w.packed, *_U8), _ptr(w.scales, *_U8), fw, B, H,
+                                            W, x.K, w.rows, k, stride, pad, opad, _ptr(bias), _ptr(y), _stream()), "rdo_mx_conv_transpose2d")
+    return y
+
+
 def pack_row_words(inner, bits):
     """W = ceil(inner * bits / 32): the 32-bit words one row of `inner` codes of `bits` bits occupies (rdo_pack_row_words on the host)"""
     return -(-int(inner) * int(bits) // 32)

@@ -7,15 +7,26 @@ The codes on the matrix cores (include/rdo_ptq_mxgemm.h): `native_operand(module
 block-scaled matrix instruction, `native_linear(module, x, act_fmt)` the module's pre-activation output with the input quantised to an MX
 format as well -- for token-matrix Linears and 1x1 stride-1 convs whose input channels are a multiple of 32;
 `QuantModel.mx_native_report` measures it against the emulation, layer by layer.  The quantisers themselves serve weights only: an
-activation is put on an MX grid by `native_linear` (`ops.mx_quant_pack`), not by a quantiser call with act=True.  MX activations inside
-the modules' own forward and a packed MX container are not built.
+activation is put on an MX grid by `native_linear` (`ops.mx_quant_pack`), not by a quantiser call with act=True.
 
 k x k convolutions (include/rdo_ptq_mxconv.h): `native_conv_operand(module)` is a conv's weight [Cout, k * k * Cin] as a packed operand,
 rows in `to_rows`' (kh, kw, in) order, `native_conv(module, x, act_fmt)` its pre-activation output from the NHWC pixels of x quantised
 to an MX format -- an implicit GEMM, bit for bit `ops.mx_gemm` on the im2col matrix -- for square kernels with one stride and one zero
 padding, dilation 1, groups 1 and input channels a multiple of 32 (`native_conv_refusal`); `mx_native_report(..., convs=True)` measures
-them too.  Not built: transposed convs, GDN, the native path inside the modules' forward or the calibration loop, a backward, a producer
-fused into the conv; no rate-distortion claim is made for it."""
+them too.
+
+Transposed convs (include/rdo_ptq_mxtconv.h): `native_tconv_operand(module)` is a transposed conv's weight [Cout, k * k * Cin] along
+`to_rows(W, tconv=True)` as a packed operand, `native_tconv(module, x, act_fmt)` its pre-activation output -- phase by phase bit for bit
+`ops.mx_gemm` on the gathered operands -- for square kernels with one stride, one padding and one output padding, dilation 1, groups 1
+and input channels (`weight.shape[0]`) a multiple of 32 (`native_tconv_refusal`); `mx_native_report(..., tconvs=True)` measures them.
+
+MX activations inside the modules' own forward: `QuantModel.set_mx_activations(act_fmt, mode)` sets `mx_activations = (act_fmt, mode)` on
+every module one of the three refusals accepts; `QuantModule.forward` (no-grad path, weight quantisation on) then takes its
+pre-activation output from `mx_forward`: mode 'native' runs `native_linear` / `native_conv` / `native_tconv`, mode 'emulated' the
+module's fp32 kernel on the decoded `xq` of the same producer; the module's tail (se_module, activation function, output quantiser)
+follows un-fused.  Not built: GDN and LayerNorm on the native path, fused activation epilogues, a producer fused into the previous
+layer's store, calibration or a backward under MX activations (`reconstruct` refuses such a model), data-parallel runs, a packed MX
+container; no rate-distortion claim is made for any of it."""
 import torch
 import torch.nn as nn
 
@@ -310,3 +321,121 @@ def native_conv(module, x, act_fmt):
     k, stride, pad = conv_geometry(module)
     a = ops.mx_quant_pack(x.permute(0, 2, 3, 1).reshape(-1, C).contiguous(), act_fmt)
     return ops.mx_conv2d(a, b, (B, H, W), k, stride, pad, native_bias(module)).permute(0, 3, 1, 2)
+
+
+# ---- transposed convolutions on the same instruction (include/rdo_ptq_mxtconv.h) ---------------------------------------------------------------
+def tconv_geometry(module):
+    """(k, stride, pad, output_padding) of a transposed-conv QuantModule `native_tconv_refusal` accepts"""
+    kw = module.fwd_kwargs
+    return int(module.weight.shape[2]), _pair(kw["stride"])[0], _pair(kw["padding"])[0], _pair(kw["output_padding"])[0]
+
+
+def native_tconv_refusal(module):
+    """None for a QuantModule `native_tconv_operand` serves, else the reason it does not, looked for in this order: it is no transposed
+    conv; its kernel, stride (>= 1), padding (>= 0) or output padding is not square, or it is dilated or grouped; its input channels
+    (`weight.shape[0]`) are no multiple of 32; its weight quantiser is no MX class, or one made with tconv=False"""
+    q = getattr(module, "weight_quantizer", None)
+    kind = getattr(module, "kind", None)
+    if kind != "tconv":
+        return f"a {kind} module is not a transposed convolution: the native tconv path serves square k x k transposed convs"
+    w, kw = module.weight, module.fwd_kwargs
+    (kh, kwid), (sh, sw), (dh, dw) = tuple(int(a) for a in w.shape[2:]), _pair(kw["stride"]), _pair(kw["dilation"])
+    (ph, pw), (oh, ow) = _pair(kw["padding"]), _pair(kw["output_padding"])
+    if kh != kwid or sh != sw or sh < 1 or ph != pw or ph < 0 or oh != ow or (dh, dw) != (1, 1) or kw["groups"] != 1:
+        return (f"a transposed conv with kernel {(kh, kwid)}, stride {kw['stride']}, padding {kw['padding']}, output padding "
+                f"{kw['output_padding']}, dilation {kw['dilation']}, groups {kw['groups']} is not a square-kernel transposed conv with one "
+                "stride, one padding, one output padding, dilation 1 and groups 1")
+    K = int(w.shape[0])
+    if K % L.MX_BLOCK:
+        return f"its {K} input channels are no multiple of the MX block size {L.MX_BLOCK}"
+    if not is_mx_any(q):
+        return f"its weight quantiser is a {type(q).__name__}, not an MXQuantizer or MXAdaRoundQuantizer"
+    if not q.tconv:
+        return f"its {type(q).__name__} was made with tconv=False: its blocks do not run along the rows of to_rows(W, tconv=True)"
+    return None
+
+
+def native_tconv_operand(module):
+    """The `ops.MXOperand` [Cout, k * k * Cin] of a transposed-conv QuantModule's weight as its MX quantiser forwards it, made along
+    `to_rows(W, tconv=True)` (row n, tap (kh, kw), channel c holds W[c, n, kh, kw]; taps un-flipped) exactly as `native_operand` makes
+    it, learned rounding included.  Memoised under a key of its own next to `weight_pack()` and dropped by `drop_weight_pack()`.
+    ValueError naming the module and the reason for a module `native_tconv_refusal` gives a reason for."""
+    why = native_tconv_refusal(module)
+    if why is not None:
+        raise ValueError(f"native_tconv_operand: module {_describe(module)}: {why}")
+    return _weight_operand(module, "mx_native_tconv")
+
+
+def native_tconv(module, x, act_fmt):
+    """The pre-activation output of an eligible transposed-conv QuantModule (`native_tconv_operand`) on the block-scaled matrix
+    instruction: `x` is the module's NCHW input, the result a channels-last view [B, N, Ho, Wo].  The rows of the channels-last view of
+    x -- one per pixel -- are quantised to the MX format `act_fmt` in blocks of 32 along the input channels by one `ops.mx_quant_pack`
+    launch; one `ops.mx_conv_transpose2d` launch applies the weight's codes at the module's stride, padding and output padding and adds
+    the bias of the module's present quant state.  Nothing else of the module's forward is applied."""
+    why = native_tconv_refusal(module)
+    if why is not None:
+        raise ValueError(f"native_tconv_operand: module {_describe(module)}: {why}")
+    C = int(module.weight.shape[0])
+    if x.dim() != 4 or x.shape[1] != C:
+        raise ValueError(f"native_tconv: the input must be [B, {C}, H, W], got {tuple(x.shape)}")
+    b = native_tconv_operand(module)
+    B, _, H, W = (int(v) for v in x.shape)
+    k, stride, pad, opad = tconv_geometry(module)
+    a = ops.mx_quant_pack(x.permute(0, 2, 3, 1).reshape(-1, C).contiguous(), act_fmt)
+    return ops.mx_conv_transpose2d(a, b, (B, H, W), k, stride, pad, opad, native_bias(module)).permute(0, 3, 1, 2)
+
+
+# ---- MX activations inside the modules' own forward (QuantModel.set_mx_activations) ------------------------------------------------------------
+MX_ACT_MODES = ("native", "emulated")
+
+
+def native_kind(module):
+    """('linear' | 'conv' | 'tconv', None) for a module one of the three refusals accepts -- a 1x1 stride-1 conv counts as 'conv' --,
+    else (None, the reason of the refusal that speaks for the module's kind)"""
+    kind = getattr(module, "kind", None)
+    if kind == "tconv":
+        why = native_tconv_refusal(module)
+    elif kind == "conv":
+        why = native_conv_refusal(module)
+    else:
+        why = native_refusal(module)
+    return (kind, None) if why is None else (None, why)
+
+
+def refuse_mx_activations(what, named_modules, why):
+    """NotImplementedError naming the first module of (name, module) pairs that carries `mx_activations`"""
+    for name, m in named_modules:
+        on = getattr(m, "mx_activations", None)
+        if on is not None:
+            raise NotImplementedError(f"{what}: module {name!r} runs on MX activations ({on[0]}, {on[1]}): {why}")
+
+
+def mx_forward(module, x):
+    """The pre-activation output of a module whose `mx_activations` = (act_fmt, mode) is set (`QuantModel.set_mx_activations`), from its
+    input quantised to act_fmt in blocks of 32 along the input channels.  'native': `native_linear`, `native_conv` or `native_tconv`.
+    'emulated': xq of `ops.mx_quant_pack(rows, act_fmt, want_xq=True)`, reshaped to the input, through the module's fp32 forward kernel
+    with its quantised weight pack and EPI_NONE."""
+    act_fmt, mode = module.mx_activations
+    kind = module.kind
+    if mode == "native":
+        if kind == "linear":
+            return native_linear(module, x, act_fmt)
+        return (native_conv if kind == "conv" else native_tconv)(module, x, act_fmt)
+    pack = module.weight_pack()
+    if kind == "linear":
+        rows, shape = native_rows(module, x)
+        _, xq = ops.mx_quant_pack(rows, act_fmt, want_xq=True)
+        return shape(ops.conv2d_fwd_pack(xq.reshape(1, 1, -1, rows.shape[1]), pack, 1, 0, epilogue=L.EPI_NONE))
+    C = int(module.weight.shape[0 if kind == "tconv" else 1])
+    if x.dim() != 4 or x.shape[1] != C:
+        raise ValueError(f"mx_forward: the input must be [B, {C}, H, W], got {tuple(x.shape)}")
+    B, _, H, W = (int(v) for v in x.shape)
+    _, xq = ops.mx_quant_pack(x.permute(0, 2, 3, 1).reshape(-1, C).contiguous(), act_fmt, want_xq=True)
+    xq = xq.reshape(B, H, W, C)
+    if kind == "conv":
+        _, stride, pad = conv_geometry(module)
+        y = ops.conv2d_fwd_pack(xq, pack, stride, pad, epilogue=L.EPI_NONE)
+    else:
+        _, stride, pad, opad = tconv_geometry(module)
+        y = ops.conv_transpose2d(xq, None, None, stride, pad, opad, epilogue=L.EPI_NONE, pack=pack)
+    return y.permute(0, 3, 1, 2)

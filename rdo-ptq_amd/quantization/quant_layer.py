@@ -206,6 +206,7 @@ class QuantModule(nn.Module):
         opt-in R + lambda*D task loss differentiates through the modules behind a unit.  The reference's dynamic activation
         quantiser works on a detached clone (quantizer.py:99-100), so an activation-quantised output has no gradient there either."""
         from hipops import autograd as A
+        self._refuse_mx_grad()
         if self.is_ps:
             y = torch.nn.functional.pixel_shuffle(input, int(self.fwd_kwargs))
             return torch.nn.functional.leaky_relu(y, 0.01) if isinstance(self.activation_function, nn.LeakyReLU) else y
@@ -245,11 +246,34 @@ class QuantModule(nn.Module):
             out = self.act_quantizer(out, True)
         return out
 
+    def _refuse_mx_grad(self):
+        on = getattr(self, "mx_activations", None)
+        if on is not None:
+            raise NotImplementedError(f"QuantModule({self.kind}, weight {tuple(self.weight.shape)}) runs on MX activations ({on[0]}, {on[1]}) "
+                                      "and its input requires grad: no backward is built under MX activations "
+                                      "(QuantModel.set_mx_activations(None) switches them off)")
+
+    def _forward_mx(self, input):
+        """the forward under `mx_activations` (`QuantModel.set_mx_activations`): the pre-activation output of `mx.mx_forward`, then the
+        module's tail, un-fused"""
+        from .mx import mx_forward
+        out = mx_forward(self, input)
+        if self.se_module is not None:
+            out = self.se_module(out)
+        out = self.activation_function(out)
+        if self.disable_act_quant:
+            return out
+        if self.use_act_quant and self.trained:
+            out = self.act_quantizer(out, True)
+        return out
+
     def forward(self, input: torch.Tensor):
         if not input.is_cuda:
             raise RuntimeError("QuantModule.forward runs on librdoptq_hip only: move the model and data to the GPU")
         if torch.is_grad_enabled() and input.requires_grad:
             return self._forward_autograd(input)
+        if self.use_weight_quant and getattr(self, "mx_activations", None) is not None:
+            return self._forward_mx(input)
         if self.is_ps:
             y = ops.pixel_shuffle(_nhwc(input), int(self.fwd_kwargs))
             return _nchw_view(ops.lrelu(y) if isinstance(self.activation_function, nn.LeakyReLU) else y)

@@ -159,13 +159,65 @@ class QuantModel(nn.Module):
         from .reports import format_report
         return format_report(self, images, formats=formats, lmbda=lmbda, batch=batch, units=units)
 
-    def mx_native_report(self, images, act_fmt="mxfp8_e4m3", batch=8, units=None, convs=False):
+    def mx_native_report(self, images, act_fmt="mxfp8_e4m3", batch=8, units=None, convs=False, tconvs=False):
         """How far the MX codes on the matrix cores (`mx.native_linear`: the block-scaled matrix instruction, input quantised to
         `act_fmt`) are from their fp32 emulation, for every eligible Linear / 1x1 conv of the chosen units -- with convs=True also for
-        every eligible k x k conv (`mx.native_conv`) --, in one pass over `images` in the state the model is in
-        (`reports.mx_native_report`)."""
+        every eligible k x k conv (`mx.native_conv`), with tconvs=True for every eligible transposed conv (`mx.native_tconv`) --, in
+        one pass over `images` in the state the model is in (`reports.mx_native_report`)."""
         from .reports import mx_native_report
-        return mx_native_report(self, images, act_fmt=act_fmt, batch=batch, units=units, convs=convs)
+        return mx_native_report(self, images, act_fmt=act_fmt, batch=batch, units=units, convs=convs, tconvs=tconvs)
+
+    def set_mx_activations(self, act_fmt, mode="native", units=None):
+        """Run the modules' own forward on MX activations: every weighted QuantModule of the chosen units (`units`: a list of names of
+        `units()`, None for all) that `mx.native_refusal`, `native_conv_refusal` or `native_tconv_refusal` accepts gets the plain
+        attribute `mx_activations = (act_fmt, mode)`.  Its no-grad forward, while `use_weight_quant` is on, then takes the
+        pre-activation output from its input quantised to the MX format `act_fmt` in blocks of 32 along the input channels --
+        mode 'native': the MX codes of input and weight on the block-scaled matrix instruction (`mx.native_linear` / `native_conv` /
+        `native_tconv`); mode 'emulated': the decoded input through the module's fp32 kernel -- followed by the module's tail
+        (se_module, activation function, output quantiser), un-fused.  With `use_weight_quant` off the forward is what it was.
+        act_fmt=None clears the attribute on every weighted module of the chosen units.  Whether a unit is trained does not matter.
+        -> OrderedDict: 'native' module name -> 'linear' | 'conv' | 'tconv'; 'left' module name -> why the module keeps its forward
+        (GDN, LayerNorm, a 3-channel stem, ragged channel counts, a weight that is in no MX format).
+        ValueError before anything is written for an unknown act_fmt or mode, an unknown unit, and (act_fmt not None) a named unit
+        without an eligible module.  An input that requires grad raises NotImplementedError in a switched module; `reconstruct`
+        refuses a model that holds one."""
+        from collections import OrderedDict
+        from . import mx
+        from hipops import ops
+        what, known = "set_mx_activations", self.units()
+        if act_fmt is not None:
+            ops.mx_format(what, act_fmt)
+        if not isinstance(mode, str) or mode not in mx.MX_ACT_MODES:
+            raise ValueError(f"{what}: mode must be one of {list(mx.MX_ACT_MODES)}, got {mode!r}")
+        if units is None:
+            chosen = list(known)
+        else:
+            if isinstance(units, (str, bytes)) or not hasattr(units, "__iter__"):
+                raise ValueError(f"{what}: units must be None or a list of unit names, got {units!r}")
+            chosen = list(units)
+            unknown = [n for n in chosen if n not in known]
+            if unknown:
+                raise ValueError(f"{what}: unknown unit name(s) {unknown}; QuantModel.units() has {list(known)}")
+        rep = OrderedDict(native=OrderedDict(), left=OrderedDict())
+        plan = []
+        for uname in chosen:
+            found = False
+            for mn, m in known[uname].named_modules():
+                if not isinstance(m, QuantModule) or m.org_weight is None:
+                    continue
+                name = f"{uname}.{mn}" if mn else uname
+                kind, why = mx.native_kind(m)
+                plan.append((m, kind))
+                if kind is None:
+                    rep["left"][name] = why
+                else:
+                    rep["native"][name], found = kind, True
+            if units is not None and act_fmt is not None and not found:
+                raise ValueError(f"{what}: unit {uname!r} holds no eligible module: "
+                                 f"{ {n: w for n, w in rep['left'].items() if n == uname or n.startswith(uname + '.')} }")
+        for m, kind in plan:
+            m.mx_activations = None if (act_fmt is None or kind is None) else (act_fmt, mode)
+        return rep
 
     def set_weight_format(self, formats, rounding="nearest"):
         """Leave the weights of the units in an MX block format: `formats` is one name for every unit, or a mapping unit

@@ -248,8 +248,10 @@ def reconstruct(model, unit, unit_name, cali_data, *a, **kw):
     quantisers that `_reconstruct` put on torch's tape for the unit (`act_ste`: loss_mode='rd' behind frozen activation quantisers) are
     taken off it again, whatever happened.  A unit that holds an `MXQuantizer` is refused (NotImplementedError) before any cache is
     built; one whose weighted modules all hold an `MXAdaRoundQuantizer` is calibrated on its MX grid (`_check_mx_learned` has what that
-    path refuses)."""
-    from .mx import refuse_mx
+    path refuses).  A model in which any module runs on MX activations (`QuantModel.set_mx_activations`) is refused the same way."""
+    from .mx import refuse_mx, refuse_mx_activations
+    refuse_mx_activations("reconstruct", model.named_modules() if isinstance(model, torch.nn.Module) else (),
+                          "calibration under MX activations is not built (QuantModel.set_mx_activations(None) switches them off)")
     inside = unit.named_modules() if isinstance(unit, torch.nn.Module) else ()
     named = [(f"{unit_name}.{n}" if n else unit_name, m) for n, m in inside]
     refuse_mx("reconstruct", named, NotImplementedError,

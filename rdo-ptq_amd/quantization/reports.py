@@ -668,7 +668,7 @@ def act_bit_report(qnn, images, widths=(4, 6, 8), lmbda=0.01, weight_quant=False
     return rep
 
 
-def mx_native_report(qnn, images, act_fmt="mxfp8_e4m3", batch=8, units=None, convs=False) -> "OrderedDict":
+def mx_native_report(qnn, images, act_fmt="mxfp8_e4m3", batch=8, units=None, convs=False, tconvs=False) -> "OrderedDict":
     """How far the MX codes on the matrix cores are from the emulation a calibration runs under, layer by layer (include/rdo_ptq_mxgemm.h;
     `mx.native_linear`), measured on `images` (fp32 [n, 3, H, W] of any size the model runs) under torch.no_grad() in ONE pass over the
     images in the state the model is in: weights in their MX formats (`set_weight_format`), the quant-state flags as set.  Every
@@ -685,6 +685,12 @@ def mx_native_report(qnn, images, act_fmt="mxfp8_e4m3", batch=8, units=None, con
                  stride and padding, epilogue EPI_NONE, same bias
     Their rows gain k, stride and pad; K is k * k * Cin, rows counts output pixels, act_sqnr_db is taken over the input pixels; a conv
     that is refused is skipped for the reason `native_conv_refusal` gives.  convs=False gives what it gave before convs existed.
+    tconvs=True also measures every transposed conv `mx.native_tconv_refusal` accepts (include/rdo_ptq_mxtconv.h):
+      native     `ops.mx_quant_pack(NHWC pixels of x, act_fmt)`, then `ops.mx_conv_transpose2d` with `mx.native_tconv_operand(module)` + bias
+      emulated   xq of the same call as NHWC and the decoded weight as [N, k, k, Cin] through `ops.conv_transpose2d` at the module's
+                 stride, padding and output padding, epilogue EPI_NONE, same bias
+    Their rows gain k, stride, pad and output_padding; K is k * k * Cin, N the output channels (`weight.shape[1]`).  tconvs=False gives
+    what it gave before tconvs existed, the 'skipped' reasons included.
     -> OrderedDict:
       'modules'  name -> {unit, rows (per pass, all images), K, N, w_fmt, act_fmt, max_abs_diff, rel_l2 = |native - emulated| /
                  |emulated| from float64 sums over the batches (0 when both are zero), act_sqnr_db = 10 log10(sum x^2 / sum (x - xq)^2)
@@ -694,7 +700,7 @@ def mx_native_report(qnn, images, act_fmt="mxfp8_e4m3", batch=8, units=None, con
     State: every module's use_weight_quant | use_act_quant pair is put back in a `finally` and the hooks are removed whatever a forward
     raises; quantisers, alpha and scales are not written; the operands made stay memoised next to the weight packs.
     Raises ValueError before any GPU work for what `rd_report` refuses of images (but for their size), batch and units, for an unknown
-    act_fmt, for convs not a bool, and for a named unit without an eligible module; NotImplementedError for world_size > 1."""
+    act_fmt, for convs or tconvs not a bool, and for a named unit without an eligible module; NotImplementedError for world_size > 1."""
     from hipops import _lib as L
     from hipops import ops
     from . import dp, mx
@@ -704,6 +710,8 @@ def mx_native_report(qnn, images, act_fmt="mxfp8_e4m3", batch=8, units=None, con
     ops.mx_format(what, act_fmt)
     if not isinstance(convs, bool):
         raise ValueError(f"{what}: convs must be True or False, got {convs!r}")
+    if not isinstance(tconvs, bool):
+        raise ValueError(f"{what}: tconvs must be True or False, got {tconvs!r}")
     if dp.world()[1] > 1:
         raise NotImplementedError(f"{what}: not built for data-parallel runs (world_size > 1)")
     eligible, skipped = OrderedDict(), OrderedDict()
@@ -714,7 +722,8 @@ def mx_native_report(qnn, images, act_fmt="mxfp8_e4m3", batch=8, units=None, con
                 continue
             name = f"{uname}.{mn}" if mn else uname
             as_conv = convs and m.kind == "conv"
-            why = mx.native_conv_refusal(m) if as_conv else mx.native_refusal(m)
+            as_tconv = tconvs and m.kind == "tconv"
+            why = mx.native_tconv_refusal(m) if as_tconv else mx.native_conv_refusal(m) if as_conv else mx.native_refusal(m)
             if why is None:
                 eligible[name], found = (uname, m), True
             else:
@@ -748,12 +757,31 @@ def mx_native_report(qnn, images, act_fmt="mxfp8_e4m3", batch=8, units=None, con
         emulated = ops.conv2d_fwd_pack(xq.reshape(B, H, W, C), decoded(name, b, bias, (b.rows, k, k, C)), stride, pad, epilogue=L.EPI_NONE)
         return rows, xq, native, emulated.reshape(native.shape)
 
+    def measure_tconv(mod, name, x):
+        """(pixel rows, xq, native, emulated) of a transposed conv on `ops.mx_conv_transpose2d`; native and emulated [output pixels, N]"""
+        C = int(mod.weight.shape[0])
+        if x.dim() != 4 or x.shape[1] != C:
+            raise ValueError(f"{what}: module {name!r}: the input must be [B, {C}, H, W], got {tuple(x.shape)}")
+        B, _, H, W = (int(v) for v in x.shape)
+        k, stride, pad, opad = mx.tconv_geometry(mod)
+        rows = x.permute(0, 2, 3, 1).reshape(-1, C).contiguous()
+        b = mx.native_tconv_operand(mod)
+        a, xq = ops.mx_quant_pack(rows, act_fmt, want_xq=True)
+        bias = mx.native_bias(mod)
+        native = ops.mx_conv_transpose2d(a, b, (B, H, W), k, stride, pad, opad, bias).reshape(-1, b.rows)
+        emulated = ops.conv_transpose2d(xq.reshape(B, H, W, C), None, None, stride, pad, opad, epilogue=L.EPI_NONE,
+                                        pack=decoded(name, b, bias, (b.rows, k, k, C)))
+        return rows, xq, native, emulated.reshape(native.shape)
+
     def measure(name, m):
         as_conv = convs and m.kind == "conv"
+        as_tconv = tconvs and m.kind == "tconv"
 
         def hook(mod, args):
             x = args[0].detach()
-            if as_conv:
+            if as_tconv:
+                rows, xq, native, emulated = measure_tconv(mod, name, x)
+            elif as_conv:
                 rows, xq, native, emulated = measure_conv(mod, name, x)
             else:
                 rows, _ = mx.native_rows(mod, x)
@@ -799,6 +827,10 @@ def mx_native_report(qnn, images, act_fmt="mxfp8_e4m3", batch=8, units=None, con
         if convs and m.kind == "conv":
             k, stride, pad = mx.conv_geometry(m)
             rep["modules"][name].update(k=k, stride=stride, pad=pad, K=k * k * int(m.weight.shape[1]))
+        if tconvs and m.kind == "tconv":
+            k, stride, pad, opad = mx.tconv_geometry(m)
+            rep["modules"][name].update(k=k, stride=stride, pad=pad, output_padding=opad, K=k * k * int(m.weight.shape[0]),
+                                        N=int(m.weight.shape[1]))
     rep["skipped"] = skipped
     rep["act_fmt"], rep["n"], rep["batch"] = act_fmt, sweep.n, sweep.bs
     return rep
