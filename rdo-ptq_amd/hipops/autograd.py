@@ -64,7 +64,8 @@ class Conv2dFn(torch.autograd.Function):
             dx = ops.conv2d_fwd_pack(gr, pack.flipped(), 1, K - 1 - pad)     # [Cin][KH'][KW'][Cout], taps flipped
         else:
             # dgrad of a strided conv = the transposed conv with the same weight tensor read as [Cin_t = Cout][Cout_t = Cin][K][K]
-            out_pad = (xs[1] + 2 * pad - K) % stride
+            # (the rows / columns the strided conv never reached, per axis: H and W may leave different remainders)
+            out_pad = ((xs[1] + 2 * pad - K) % stride, (xs[2] + 2 * pad - K) % stride)
             dx = ops.conv_transpose2d(gr, None, None, stride, pad, out_pad, pack=pack.transposed())
         return _nchw(dx), None, None, None, None, None
 

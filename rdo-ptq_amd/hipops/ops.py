@@ -1376,12 +1376,15 @@ def conv2d_fwd_pack(x, pack, stride=1, pad=0, bias=True, **kw):
 def conv_transpose2d(x, w_iohw_rows, bias, stride, pad, output_padding, epilogue=L.EPI_NONE, pack=None):
     """x [B,H,W,Cin]; w_iohw_rows = to_rows(W, tconv=True) = [Cout,KH,KW,Cin] (un-flipped taps of the [Cin,Cout,KH,KW] weight), or
     `pack` = a WeightPack of it (weight-derived tensors are then built once).  Output = stride x input (the deconv of the LIC
-    decoders): stride-1 conv with the phase weight + pixel shuffle, no zero insertion; other geometries: zero insertion + dense conv."""
+    decoders): stride-1 conv with the phase weight + pixel shuffle, no zero insertion; other geometries: zero insertion + dense conv.
+    `output_padding`: one int for both axes or an (h, w) pair (the input gradient of a strided conv whose height and width leave
+    different remainders); the phase form needs output = stride x input on both."""
     if pack is None:
         pack = WeightPack(w_iohw_rows, bias)
     Cout, KH, KW, Cin = pack.w.shape
     B, H, W, _ = x.shape
-    ph = TconvPhase.get(KH, stride, pad, output_padding, False, x.device) if KH == KW else None
+    oph, opw = (int(v) for v in output_padding) if isinstance(output_padding, (tuple, list)) else (int(output_padding),) * 2
+    ph = TconvPhase.get(KH, stride, pad, oph, False, x.device) if KH == KW and oph == opw else None
     if ph is not None:
         # LeakyReLU / ReLU commute with the pixel shuffle; large problems on the split-precision path
         yp = conv2d_fwd_pack(x, pack.phase(ph), 1, ph.pad, epilogue=epilogue)
@@ -1389,7 +1392,7 @@ def conv_transpose2d(x, w_iohw_rows, bias, stride, pad, output_padding, epilogue
     q = KH - 1 - pad
     if q < 0:
         raise ValueError("conv_transpose2d: padding larger than kernel_size - 1 is not supported")
-    Hup, Wup = (H - 1) * stride + 1 + 2 * q + output_padding, (W - 1) * stride + 1 + 2 * q + output_padding
+    Hup, Wup = (H - 1) * stride + 1 + 2 * q + oph, (W - 1) * stride + 1 + 2 * q + opw
     xu = zero_insert(x, stride, q, q, Hup, Wup)
     return conv2d_fwd_pack(xu, pack.get("zi", lambda: WeightPack(pack.w.flip(1, 2), pack.bias)), 1, 0, epilogue=epilogue)
 
