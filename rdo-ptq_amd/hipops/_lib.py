@@ -273,6 +273,13 @@ _SIGS_MXTCONV = {
     "rdo_mx_conv_transpose2d": (C.c_int, [P, P, C.c_int32, P, P, C.c_int32] + [C.c_int32] * 9 + [P, P, P]),
 }
 EXPORTS_MXTCONV = tuple(_SIGS_MXTCONV)
+# include/rdo_ptq_mxfile.h: the bytes a packed MX checkpoint stores for a weight (rows of any length), and back to the weight in one launch
+_SIGS_MXFILE = {
+    "rdo_mx_row_bytes": (C.c_int64, [C.c_int64, C.c_int32]),
+    "rdo_mx_pack_rows": (C.c_int, [P, C.c_int32, C.c_int64, C.c_int32, P, P]),
+    "rdo_mx_unpack_dequant": (C.c_int, [P, P, C.c_int32, C.c_int64, C.c_int32, P, P, P]),
+}
+EXPORTS_MXFILE = tuple(_SIGS_MXFILE)
 
 _lib = None
 
@@ -292,7 +299,8 @@ def lib():
         for name, (res, args) in (list(_SIGS.items()) + list(_SIGS_GDN.items()) + list(_SIGS_BIAS.items()) + list(_SIGS_BITS.items())
                                   + list(_SIGS_PACK.items()) + list(_SIGS_SUBPEL.items()) + list(_SIGS_ACTBITS.items())
                                   + list(_SIGS_ATTNQ.items()) + list(_SIGS_MX.items()) + list(_SIGS_MXROUND.items())
-                                  + list(_SIGS_MXGEMM.items()) + list(_SIGS_MXCONV.items()) + list(_SIGS_MXTCONV.items())):
+                                  + list(_SIGS_MXGEMM.items()) + list(_SIGS_MXCONV.items()) + list(_SIGS_MXTCONV.items())
+                                  + list(_SIGS_MXFILE.items())):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         _lib = h

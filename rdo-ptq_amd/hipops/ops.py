@@ -911,6 +911,63 @@ def mx_unpack_codes(op):
     return codes
 
 
+# ---- the stored rows of a packed MX checkpoint (include/rdo_ptq_mxfile.h) ----------------------------------------------------------------
+MX_UNPACK_OUTPUTS = ("w", "codes")      # what `mx_unpack_dequant` can be asked for
+
+
+def mx_pack_rows(codes, fmt, out=None):
+    """The bytes a packed MX checkpoint stores for a weight (rdo_mx_pack_rows): codes contiguous uint8 [rows, inner] of any inner >= 1,
+    one code per byte (upper bits ignored) -> uint8 [rows, ceil(inner / 32) * 4 b]; the missing elements of a short last block are zero
+    codes.  For inner % 32 == 0 it is `mx_pack_codes(...).packed` bit for bit.  `out`: a contiguous uint8 tensor of that shape on the
+    codes' device, 4-byte aligned, to write into.  Checked on the host before a pointer is taken."""
+    what = "mx_pack_rows"
+    A.tensor(what, "codes", codes, torch.uint8, "uint8", rank=2, layout="of rank 2 [rows, inner]", contiguous=True)
+    fid, bits = mx_format(what, fmt)
+    rows, inner, dev = int(codes.shape[0]), int(codes.shape[1]), codes.device
+    nb = _mx_geometry(what, rows, inner)
+    A.tensor(what, "out", out, torch.uint8, "uint8", shape=(rows, nb * 4 * bits), contiguous=True, device=dev, optional=True, oneshot=True)
+    _mx_cuda(what, codes, "codes")
+    packed = torch.empty(rows, nb * 4 * bits, device=dev, dtype=torch.uint8) if out is None else out
+    L.check(L.lib().rdo_mx_pack_rows(_ptr(codes, *_U8), rows, inner, fid, _ptr(packed, *_U8), _stream()), "rdo_mx_pack_rows")
+    return packed
+
+
+def mx_unpack_dequant(packed, scales, inner, fmt, want=("w",), w_out=None, codes_out=None):
+    """From the stored rows back to the weight in one launch (rdo_mx_unpack_dequant): packed contiguous uint8 [rows, ceil(inner / 32) *
+    4 b] (what `mx_pack_rows` gives), scales contiguous uint8 [rows, ceil(inner / 32)] on its device, want a non-empty sequence of
+    distinct names out of `MX_UNPACK_OUTPUTS` -> dict: 'w' fp32 [rows, inner], bit for bit `mx_dequant` of the codes (a scale code of
+    255 gives NaN), 'codes' uint8 [rows, inner] with zero upper bits.  `w_out` / `codes_out`: contiguous tensors of those shapes on
+    packed's device to write a wanted output into.  Checked on the host before a pointer is taken."""
+    what = "mx_unpack_dequant"
+    A.tensor(what, "packed", packed, torch.uint8, "uint8", rank=2, layout="of rank 2 [rows, row bytes]", contiguous=True)
+    fid, bits = mx_format(what, fmt)
+    inner = A.whole(what, "inner", inner, 1)
+    if isinstance(want, (str, bytes)) or not hasattr(want, "__iter__"):
+        raise ValueError(f"{what}: want must be a sequence of names out of {list(MX_UNPACK_OUTPUTS)}, got {want!r}")
+    want = list(want)
+    if not want or any(n not in MX_UNPACK_OUTPUTS for n in want) or len(set(want)) != len(want):
+        raise ValueError(f"{what}: want must hold at least one and only distinct names out of {list(MX_UNPACK_OUTPUTS)}, got {want!r}")
+    rows, dev = int(packed.shape[0]), packed.device
+    nb = _mx_geometry(what, rows, inner)
+    if packed.shape[1] != nb * 4 * bits:
+        raise ValueError(f"{what}: packed is {tuple(packed.shape)}; a row of inner {inner} in {fmt} has {nb * 4 * bits} bytes")
+    A.tensor(what, "scales", scales, torch.uint8, "uint8", shape=(rows, nb), contiguous=True, device=dev, oneshot=True)
+    for name, given in (("w", w_out), ("codes", codes_out)):
+        if given is not None and name not in want:
+            raise ValueError(f"{what}: {name}_out is given but {name!r} is not wanted")
+    A.tensor(what, "w_out", w_out, shape=(rows, inner), contiguous=True, device=dev, optional=True, oneshot=True)
+    A.tensor(what, "codes_out", codes_out, torch.uint8, "uint8", shape=(rows, inner), contiguous=True, device=dev, optional=True, oneshot=True)
+    _mx_cuda(what, packed, "packed")
+    out = {}
+    if "w" in want:
+        out["w"] = torch.empty(rows, inner, device=dev, dtype=torch.float32) if w_out is None else w_out
+    if "codes" in want:
+        out["codes"] = torch.empty(rows, inner, device=dev, dtype=torch.uint8) if codes_out is None else codes_out
+    L.check(L.lib().rdo_mx_unpack_dequant(_ptr(packed, *_U8), _ptr(scales, *_U8), rows, inner, fid, _ptr(out.get("w")),
+                                          _ptr(out.get("codes"), *_U8), _stream()), "rdo_mx_unpack_dequant")
+    return {n: out[n] for n in want}
+
+
 def mx_gemm(a, b, bias=None):
     """y fp32 [M, N] = A B^T (+ bias) on the block-scaled matrix instruction (rdo_mx_gemm): a an `MXOperand` [M, K], b an `MXOperand` [N, K]
     of any two formats, bias contiguous fp32 [N] or None.  The products are exact; the sum is the instruction's fp32 accumulation.

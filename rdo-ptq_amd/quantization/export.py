@@ -54,4 +54,4 @@ def dequantize(entry) -> torch.Tensor:
 
 
 from .reports import act_bit_report, act_width_report, activation_report, bias_report, bit_report, format_report, rd_report, unit_report  # noqa: E402,F401
-from .widths import act_applied, act_modules, allocate_act_bits, allocate_bits, is_trained, weighted_modules  # noqa: E402,F401
+from .widths import act_applied, act_modules, allocate_act_bits, allocate_bits, allocate_formats, is_trained, weighted_modules  # noqa: E402,F401

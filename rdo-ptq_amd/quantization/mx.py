@@ -25,8 +25,9 @@ every module one of the three refusals accepts; `QuantModule.forward` (no-grad p
 pre-activation output from `mx_forward`: mode 'native' runs `native_linear` / `native_conv` / `native_tconv`, mode 'emulated' the
 module's fp32 kernel on the decoded `xq` of the same producer; the module's tail (se_module, activation function, output quantiser)
 follows un-fused.  Not built: GDN and LayerNorm on the native path, fused activation epilogues, a producer fused into the previous
-layer's store, calibration or a backward under MX activations (`reconstruct` refuses such a model), data-parallel runs, a packed MX
-container; no rate-distortion claim is made for any of it."""
+layer's store, calibration or a backward under MX activations (`reconstruct` refuses such a model), data-parallel runs; no
+rate-distortion claim is made for any of it.  A model on these quantisers is stored by `mx_packed.save_mx_packed`, the `mx_activations`
+pairs included."""
 import torch
 import torch.nn as nn
 

@@ -322,6 +322,20 @@ class QuantModel(nn.Module):
         from .packed import load_packed
         return load_packed(self, path)
 
+    def save_mx_packed(self, path):
+        """Write the packed checkpoint of a model whose weights stand on MX block formats, on integer grids, or on both: per MX module
+        the element codes packed at their own width and the blocks' scale bytes, learned rounding included -- no fp32 weight
+        (`mx_packed.save_mx_packed`).  -> the sizes written."""
+        from .mx_packed import save_mx_packed
+        return save_mx_packed(self, path)
+
+    def load_mx_packed(self, path):
+        """Install a checkpoint of `save_mx_packed` into this model, which must be of the file's architecture, on the GPU and not
+        calibrated; it then computes bit for bit what the saved model computed (`mx_packed.load_mx_packed`).  A refusal leaves the
+        model as it was."""
+        from .mx_packed import load_mx_packed
+        return load_mx_packed(self, path)
+
     def forward(self, input):
         return self.model(input)
 

@@ -169,6 +169,98 @@ def allocate_bits(report, budget_bits=None, avg_bits=None, fixed=None) -> dict:
             "cost": cost, "budget_bits": budget, "steps": steps}
 
 
+def allocate_formats(format_report, bit_report=None, budget_bits=None, avg_bits=None, fixed=None) -> dict:
+    """Choose one weight format per unit from a `format_report` table -- with a `bit_report`, one MX format or one integer width --
+    under a size budget: `allocate_bits`'s rule, guarantee and result on options keyed by name.  Pure host code.
+    Options.  A unit's options are the formats of its `format_report` row under their names and, with a `bit_report`, its widths under
+    "int<b>".  Sizes are the tables' own `size_bits`, and they are not of one kind: an integer width counts n_bits x elements, the
+    per-channel delta and zero point of the grid not included; an MX format counts element bits x elements + 8 x blocks, its scale
+    bytes included (4.25 / 6.25 / 8.25 bits a weight on rows that are whole blocks).  Costs are the rows' `d_loss`.
+    The two reports must be tables of one measurement: the same unit names in the same order, the same 'weights', 'n', 'pixels' and
+    'lmbda', and the same 'loss' of the 'fp' row; otherwise ValueError saying what differs.
+    Equal sizes.  `allocate_bits` refuses two options of one size (mxfp6_e2m3 and mxfp6_e3m2, mxfp8_e4m3 and mxfp8_e5m2).  Among the
+    options of a unit with equal size_bits only the one with the least d_loss is kept, ties to the earlier one (formats in the order
+    of the row, then widths); the others can be in no cheapest assignment of any size and are listed under 'dominated'.
+    `budget_bits` / `avg_bits`: as in `allocate_bits`.  `fixed`: name -> option key, a unit that has that one option (no other option
+    of the unit is looked at, none is listed as dominated).
+    -> `allocate_bits`'s keys with 'choice' (OrderedDict name -> option key) in place of 'bits' -- 'steps' name option keys --, and
+    'formats': OrderedDict name -> format name, or 'int' (what `QuantModel.set_weight_format` takes), 'bits': OrderedDict name -> width
+    for the units on 'int' (what `QuantModel.set_weight_bits` takes), 'dominated': OrderedDict name -> [option keys] (units that
+    have any).  With a `format_report` of distinct sizes alone, 'choice' and every shared key are `allocate_bits` of that table."""
+    from hipops._lib import MX_FORMATS
+    what = "allocate_formats"
+    try:
+        names = list(format_report["units"])
+        table = OrderedDict((n, OrderedDict((f, format_report["units"][n][f]) for f in format_report["units"][n])) for n in names)
+        weights = format_report["weights"]
+        for n in names:
+            for f, row in table[n].items():
+                row["size_bits"], row["d_loss"]
+    except (KeyError, TypeError, IndexError) as e:
+        raise ValueError(f"{what}: format_report must be a `format_report` table ('units': name -> format -> row with size_bits and "
+                         f"d_loss; 'weights'): {e!r}")
+    unknown = [f for n in names for f in table[n] if f not in MX_FORMATS]
+    if unknown:
+        raise ValueError(f"{what}: format_report holds the unknown format(s) {sorted(set(map(str, unknown)))}; the formats are {list(MX_FORMATS)}")
+    width_of = {}
+    if bit_report is not None:
+        try:
+            theirs = list(bit_report["units"])
+            if theirs != names:
+                raise ValueError(f"{what}: the reports differ in their units: format_report has {names}, bit_report has {theirs}")
+            if dict(bit_report["weights"]) != dict(weights) or list(bit_report["weights"]) != list(weights):
+                raise ValueError(f"{what}: the reports differ in 'weights': {dict(weights)} and {dict(bit_report['weights'])}")
+            for key in ("n", "pixels", "lmbda"):
+                if bit_report[key] != format_report[key]:
+                    raise ValueError(f"{what}: the reports differ in {key!r}: format_report has {format_report[key]!r}, bit_report has "
+                                     f"{bit_report[key]!r}")
+            if bit_report["fp"]["loss"] != format_report["fp"]["loss"]:
+                raise ValueError(f"{what}: the reports differ in the loss of their 'fp' rows: {format_report['fp']['loss']!r} and "
+                                 f"{bit_report['fp']['loss']!r}: they were not measured on the same model and images")
+            for n in names:
+                for b, row in bit_report["units"][n].items():
+                    if isinstance(b, bool) or not isinstance(b, Integral):
+                        raise ValueError(f"{what}: bit_report gives unit {n!r} the width {b!r}, which is no whole number")
+                    row["size_bits"], row["d_loss"]
+                    table[n][f"int{int(b)}"] = row
+                    width_of[f"int{int(b)}"] = int(b)
+        except (KeyError, TypeError, IndexError) as e:
+            raise ValueError(f"{what}: bit_report must be a `bit_report` table of the same measurement ('units', 'weights', 'fp', 'n', "
+                             f"'pixels', 'lmbda'): {e!r}")
+    fixed = {} if fixed is None else fixed
+    if not isinstance(fixed, dict):
+        raise ValueError(f"{what}: fixed must be None or a dict name -> option, got {fixed!r}")
+    for n, k in fixed.items():
+        if n not in table:
+            raise ValueError(f"{what}: fixed names the unknown unit {n!r}; the table has {names}")
+        if not isinstance(k, str) or k not in table[n]:
+            raise ValueError(f"{what}: fixed gives unit {n!r} the option {k!r}; the table has {list(table[n])}")
+    kept, dominated = OrderedDict(), OrderedDict()
+    for n in names:
+        rows = OrderedDict((k, r) for k, r in table[n].items() if n not in fixed or k == fixed[n])
+        best = {}                                                                # size -> the key kept at that size
+        for k, r in rows.items():
+            size, cost = r["size_bits"], r["d_loss"]
+            if isinstance(size, bool) or not isinstance(size, int) or size < 1 or isinstance(cost, bool) or \
+                    not isinstance(cost, (int, float)) or not math.isfinite(cost):
+                raise ValueError(f"{what}: unit {n!r} at option {k!r}: size_bits {size!r} must be a positive whole number and d_loss {cost!r} finite")
+            if size not in best or float(cost) < float(rows[best[size]]["d_loss"]):
+                best[size] = k
+        kept[n] = OrderedDict((k, {"size_bits": r["size_bits"], "d_loss": r["d_loss"]}) for k, r in rows.items() if best[r["size_bits"]] == k)
+        if len(kept[n]) != len(rows):
+            dominated[n] = [k for k in rows if k not in kept[n]]
+    try:
+        out = allocate_bits({"units": kept, "weights": weights}, budget_bits=budget_bits, avg_bits=avg_bits)
+    except ValueError as e:
+        raise ValueError(str(e).replace("allocate_bits:", f"{what}:", 1).replace("at width", "at option").replace("`bit_report`", "`format_report`"))
+    choice = out.pop("bits")
+    out["choice"] = choice
+    out["formats"] = OrderedDict((n, "int" if k in width_of else k) for n, k in choice.items())
+    out["bits"] = OrderedDict((n, width_of[k]) for n, k in choice.items() if k in width_of)
+    out["dominated"] = dominated
+    return out
+
+
 def allocate_act_bits(report, budget_bits=None, avg_bits=None, fixed=None) -> dict:
     """Choose one activation width per unit from an `act_bit_report` table under a size budget: `allocate_bits` on the table with the
     units' elements (activation values per image) in the place of the weight counts -- its rule, its guarantees and its result, with
