@@ -280,6 +280,11 @@ _SIGS_MXFILE = {
     "rdo_mx_unpack_dequant": (C.c_int, [P, P, C.c_int32, C.c_int64, C.c_int32, P, P, P]),
 }
 EXPORTS_MXFILE = tuple(_SIGS_MXFILE)
+# tuning hooks the library exports beside its headers (csrc/conv_wgrad.hip): tile choice (-1 = the library's, 0 = 64 x 64, 1 = 192 x 192)
+# and slab count (-1 = the library's) of rdo_conv2d_wgrad, process-wide; ops.forced_wgrad sets and restores them
+_SIGS_DEBUG = {
+    "rdo_debug_force_wgrad_choice": (None, [C.c_int, C.c_int]),
+}
 
 _lib = None
 
@@ -300,7 +305,7 @@ def lib():
                                   + list(_SIGS_PACK.items()) + list(_SIGS_SUBPEL.items()) + list(_SIGS_ACTBITS.items())
                                   + list(_SIGS_ATTNQ.items()) + list(_SIGS_MX.items()) + list(_SIGS_MXROUND.items())
                                   + list(_SIGS_MXGEMM.items()) + list(_SIGS_MXCONV.items()) + list(_SIGS_MXTCONV.items())
-                                  + list(_SIGS_MXFILE.items())):
+                                  + list(_SIGS_MXFILE.items()) + list(_SIGS_DEBUG.items())):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         _lib = h

@@ -6,6 +6,7 @@ When a plan is being recorded (hipops.plan.Plan.record()), the same calls are ca
 A wrapper that checks its arguments does so with the functions of `_args` (one tensor check, one whole-number check), and every check
 runs before a pointer is taken (`_ptr`, `_ptr64`) or a library call made.  Workspaces a wrapper keeps between calls come from
 `_workspace`; the convolutions' split-K scratch has its own rule (`_scratch`)."""
+import contextlib
 import ctypes as C
 import math
 import threading
@@ -178,6 +179,18 @@ def wgrad_nsplit(x_shape, w_shape, stride, pad):
 def wgrad_uses_bf16x6(x_shape, w_shape, stride, pad):
     d = conv_desc(x_shape, w_shape, stride, pad)
     return bool(L.lib().rdo_conv2d_wgrad_uses_bf16x6(C.byref(d)))
+
+
+@contextlib.contextmanager
+def forced_wgrad(big=-1, nsplit=-1):
+    """Inside the block rdo_conv2d_wgrad and its predicates (wgrad_nsplit, wgrad_uses_bf16x6) take the given tile (0: 64 x 64, 1: 192 x 192;
+    this also switches the thin-Cout kernel off) and / or slab count instead of their own choice; -1 leaves a choice to the library.
+    Process-wide (rdo_debug_force_wgrad_choice): a tuning and test hook, restored to (-1, -1) on exit."""
+    L.lib().rdo_debug_force_wgrad_choice(int(big), int(nsplit))
+    try:
+        yield
+    finally:
+        L.lib().rdo_debug_force_wgrad_choice(-1, -1)
 
 
 def conv2d_wgrad(x, dy, w_shape, stride=1, pad=0, square_input=False, slabs=None):
