@@ -101,40 +101,13 @@ template <int FA, int FB>
 __global__ __launch_bounds__(256) void mx_gemm_kernel(const uint32_t* __restrict__ a, const uint8_t* __restrict__ sa,
                                                       const uint32_t* __restrict__ b, const uint8_t* __restrict__ sb, int M, int N, long nb,
                                                       int tiles_n, const float* __restrict__ bias, float* __restrict__ y) {
-    constexpr int DA = hw_dwords(FA), DB = hw_dwords(FB);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = lane & 15, kg = lane >> 4;
     const long tm = blockIdx.x / tiles_n, tn = blockIdx.x - tm * tiles_n;
     const long m0 = tm * 64 + (wave >> 1) * 32, n0 = tn * 64 + (wave & 1) * 32;
     if (m0 >= M || n0 >= N) return;                                             // uniform over the wave; the kernel has no barrier
-    long arow[2], brow[2];
-    bool aok[2], bok[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        aok[i] = m0 + 16 * i + r < M;
-        bok[i] = n0 + 16 * i + r < N;
-        arow[i] = (m0 + 16 * i + r) * nb;
-        brow[i] = (n0 + 16 * i + r) * nb;
-    }
     f32x4 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (long k0 = 0; k0 < nb; k0 += 4) {
-        const long kb = k0 + kg;
-        const bool kok = kb < nb;
-        i32x8 fa[2], fb[2];
-        int xa[2], xb[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            fa[i] = load_fragment<DA>(a + arow[i] * DA, k0, kg, nb, aok[i]);
-            fb[i] = load_fragment<DB>(b + brow[i] * DB, k0, kg, nb, bok[i]);
-            xa[i] = aok[i] && kok ? (int)sa[arow[i] + kb] : 127;
-            xb[i] = bok[i] && kok ? (int)sb[brow[i] + kb] : 127;
-        }
-        mx_mfma_step<FA, FB>(fa, fb, xa, xb, acc);
-    }
+    mx_gemm_accumulate<FA, FB>(a, sa, b, sb, M, N, nb, m0, n0, r, kg, acc);
     mx_store_tiles(acc, bias, y, m0, n0, M, N, r, kg);
 }
 
@@ -144,23 +117,7 @@ using GemmKernel = void (*)(const uint32_t*, const uint8_t*, const uint32_t*, co
 const GemmKernel kGemm[5][5] = {RDO_MXG_ROW(0), RDO_MXG_ROW(1), RDO_MXG_ROW(2), RDO_MXG_ROW(3), RDO_MXG_ROW(4)};
 #undef RDO_MXG_ROW
 
-// blocks of a packed [rows][K]; 0 for a refused geometry
-inline long packed_blocks(int32_t rows, int64_t K) {
-    if (K <= 0 || K % kBlock != 0) return 0;
-    long nb = 0;
-    return mx_blocks(rows, K, nb);
-}
-
 }  // namespace
-
-// the argument checks every entry shares: sizes, K % 32, the format, the block count
-#define RDO_MXG_GEOMETRY(who, rows, K, format, f, total)                                                                            \
-    RDO_REQUIRE((rows) > 0 && (K) > 0, who ": non-positive size rows %d K %lld", (int)(rows), (long long)(K));                      \
-    RDO_REQUIRE((K) % kBlock == 0, who ": K %lld is no multiple of the block size %d", (long long)(K), kBlock);                     \
-    MxFormat f;                                                                                                                     \
-    RDO_REQUIRE(mx_format(format, f), who ": unknown format %d (0 .. %d)", (int)(format), RDO_MX_FORMATS - 1);                      \
-    const long total = packed_blocks(rows, K);                                                                                      \
-    RDO_REQUIRE(total > 0, who ": rows %d of K %lld make more than 2^40 blocks", (int)(rows), (long long)(K))
 
 extern "C" {
 
@@ -213,25 +170,20 @@ int rdo_mx_quant_pack(const float* x, int32_t rows, int64_t K, int32_t format, v
 
 int rdo_mx_gemm(const void* a, const uint8_t* a_scales, int32_t a_format, const void* b, const uint8_t* b_scales, int32_t b_format,
                 int32_t M, int32_t N, int64_t K, const float* bias, float* y, void* stream) {
-    RDO_REQUIRE(a && a_scales && b && b_scales && y, "rdo_mx_gemm: null pointer");
-    RDO_MXG_GEOMETRY("rdo_mx_gemm", M, K, a_format, fa, total_a);
-    RDO_MXG_GEOMETRY("rdo_mx_gemm", N, K, b_format, fb, total_b);
-    RDO_REQUIRE(aligned4(a) && aligned4(b) && aligned4(bias) && aligned4(y), "rdo_mx_gemm: a, b, bias and y must be 4-byte aligned");
-    const long tiles_m = rdo::ceil_div(M, 64), tiles_n = rdo::ceil_div(N, 64);
-    RDO_REQUIRE(tiles_m * tiles_n <= 0x7fffffffL, "rdo_mx_gemm: M %d x N %d make more than 2^31 - 1 output tiles", M, N);
+    RDO_REQUIRE(y, "rdo_mx_gemm: null pointer");
+    GemmPlan p;
+    if (const int rc = mx_gemm_check("rdo_mx_gemm", a, a_scales, a_format, b, b_scales, b_format, M, N, K, bias, p)) return rc;
+    RDO_REQUIRE(aligned4(y), "rdo_mx_gemm: a, b, bias and y must be 4-byte aligned");
     const GemmKernel kern = kGemm[hw_format(a_format)][hw_format(b_format)];
     const uint32_t* pa = static_cast<const uint32_t*>(a);
     const uint32_t* pb = static_cast<const uint32_t*>(b);
-    const long nb = (long)(K / kBlock);
-    const int tn = (int)tiles_n;
-    const unsigned grid = (unsigned)(tiles_m * tiles_n);
     return rdo::dispatch(
         [=](hipStream_t s) {
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, pa, a_scales, pb, b_scales, M, N, nb, tn, bias, y);
+            hipLaunchKernelGGL(kern, dim3(p.grid), dim3(256), 0, s, pa, a_scales, pb, b_scales, M, N, p.nb, p.tiles_n, bias, y);
             return rdo::check_launch("mx_gemm");
         },
         stream, "mx_gemm", 2.0 * (double)M * (double)N * (double)K,
-        (double)total_a * (4.0 * fa.bits + 1.0) + (double)total_b * (4.0 * fb.bits + 1.0) + (double)M * (double)N * 4.0);
+        (double)p.total_a * (4.0 * p.bits_a + 1.0) + (double)p.total_b * (4.0 * p.bits_b + 1.0) + (double)M * (double)N * 4.0);
 }
 
 }  // extern "C"

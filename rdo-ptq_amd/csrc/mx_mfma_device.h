@@ -1,7 +1,7 @@
 // What mx_gemm.hip (the GEMM) and mx_conv.hip (the implicit-GEMM convolution) share of the block-scaled matrix instruction
 // v_mfma_scale_f32_16x16x128_f8f6f4 on packed MX operands (include/rdo_ptq_mxgemm.h states the operand format and what a lane holds):
 // the instruction's format numbers, a lane's operand registers from the packed blocks it owns in a K step, the FP8 one-of-eight mask,
-// the K step itself and the store of a wave's 32 x 32 outputs.  Both kernels run one K step as mx_mfma_step on fragments made by
+// the K step itself, the GEMM's K loop and argument checks, and the store of a wave's 32 x 32 outputs.  Both kernels run one K step as mx_mfma_step on fragments made by
 // load_blocks, in ascending K order: equal fragments and scales give equal bits, which is what makes the convolution the GEMM on the
 // im2col matrix bit for bit.  Included once per translation unit, hence the unnamed namespace.
 #pragma once
@@ -128,6 +128,77 @@ __device__ __forceinline__ void mx_store_tiles(const f32x4 (&acc)[2][2], const f
     }
 }
 
+// The K loop of the GEMM for the wave's 32 x 32 outputs at (m0, n0) of A [M][nb blocks] x B [N][nb blocks]^T: what mx_gemm_kernel
+// stores and mx_gemm_packed_kernel (mx_chain.hip) quantises -- one statement, equal accumulators.
+template <int FA, int FB>
+__device__ __forceinline__ void mx_gemm_accumulate(const uint32_t* __restrict__ a, const uint8_t* __restrict__ sa,
+                                                   const uint32_t* __restrict__ b, const uint8_t* __restrict__ sb, int M, int N, long nb, long m0,
+                                                   long n0, int r, int kg, f32x4 (&acc)[2][2]) {
+    constexpr int DA = hw_dwords(FA), DB = hw_dwords(FB);
+    long arow[2], brow[2];
+    bool aok[2], bok[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        aok[i] = m0 + 16 * i + r < M;
+        bok[i] = n0 + 16 * i + r < N;
+        arow[i] = (m0 + 16 * i + r) * nb;
+        brow[i] = (n0 + 16 * i + r) * nb;
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (long k0 = 0; k0 < nb; k0 += 4) {
+        const long kb = k0 + kg;
+        const bool kok = kb < nb;
+        i32x8 fa[2], fb[2];
+        int xa[2], xb[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            fa[i] = load_fragment<DA>(a + arow[i] * DA, k0, kg, nb, aok[i]);
+            fb[i] = load_fragment<DB>(b + brow[i] * DB, k0, kg, nb, bok[i]);
+            xa[i] = aok[i] && kok ? (int)sa[arow[i] + kb] : 127;
+            xb[i] = bok[i] && kok ? (int)sb[brow[i] + kb] : 127;
+        }
+        mx_mfma_step<FA, FB>(fa, fb, xa, xb, acc);
+    }
+}
+
 inline bool aligned4(const void* p) { return reinterpret_cast<uintptr_t>(p) % 4 == 0; }
+
+// blocks of a packed [rows][K]; 0 for a refused geometry
+inline long packed_blocks(int32_t rows, int64_t K) {
+    if (K <= 0 || K % kBlock != 0) return 0;
+    long nb = 0;
+    return mx_blocks(rows, K, nb);
+}
+
+// the argument checks every entry on a packed [rows][K] shares: sizes, K % 32, the format, the block count (`who`: the entry's name)
+#define RDO_MXG_GEOMETRY(who, rows, K, format, f, total)                                                                            \
+    RDO_REQUIRE((rows) > 0 && (K) > 0, "%s: non-positive size rows %d K %lld", who, (int)(rows), (long long)(K));                   \
+    RDO_REQUIRE((K) % kBlock == 0, "%s: K %lld is no multiple of the block size %d", who, (long long)(K), kBlock);                  \
+    MxFormat f;                                                                                                                     \
+    RDO_REQUIRE(mx_format(format, f), "%s: unknown format %d (0 .. %d)", who, (int)(format), RDO_MX_FORMATS - 1);                   \
+    const long total = packed_blocks(rows, K);                                                                                      \
+    RDO_REQUIRE(total > 0, "%s: rows %d of K %lld make more than 2^40 blocks", who, (int)(rows), (long long)(K))
+
+// what rdo_mx_gemm and rdo_mx_gemm_packed check of their operands, and the launch they share
+struct GemmPlan {
+    long total_a, total_b, nb;
+    int bits_a, bits_b, tiles_n;
+    unsigned grid;
+};
+
+inline int mx_gemm_check(const char* who, const void* a, const uint8_t* a_scales, int32_t a_format, const void* b, const uint8_t* b_scales,
+                         int32_t b_format, int32_t M, int32_t N, int64_t K, const float* bias, GemmPlan& p) {
+    RDO_REQUIRE(a && a_scales && b && b_scales, "%s: null pointer", who);
+    RDO_MXG_GEOMETRY(who, M, K, a_format, fa, total_a);
+    RDO_MXG_GEOMETRY(who, N, K, b_format, fb, total_b);
+    RDO_REQUIRE(aligned4(a) && aligned4(b) && aligned4(bias), "%s: a, b, bias and y must be 4-byte aligned", who);
+    const long tiles_m = rdo::ceil_div(M, 64), tiles_n = rdo::ceil_div(N, 64);
+    RDO_REQUIRE(tiles_m * tiles_n <= 0x7fffffffL, "%s: M %d x N %d make more than 2^31 - 1 output tiles", who, M, N);
+    p = GemmPlan{total_a, total_b, (long)(K / kBlock), fa.bits, fb.bits, (int)tiles_n, (unsigned)(tiles_m * tiles_n)};
+    return RDO_OK;
+}
 
 }  // namespace

@@ -280,6 +280,14 @@ _SIGS_MXFILE = {
     "rdo_mx_unpack_dequant": (C.c_int, [P, P, C.c_int32, C.c_int64, C.c_int32, P, P, P]),
 }
 EXPORTS_MXFILE = tuple(_SIGS_MXFILE)
+# include/rdo_ptq_mxchain.h: the GEMM and the convolutions with a packed MX output (bias, activation, quantise and pack in the epilogue)
+_SIGS_MXCHAIN = {
+    "rdo_mx_gemm_packed": (C.c_int, [P, P, C.c_int32, P, P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, P, C.c_int32, C.c_int32, P, P, P]),
+    "rdo_mx_conv2d_packed": (C.c_int, [P, P, C.c_int32, P, P, C.c_int32] + [C.c_int32] * 8 + [P, C.c_int32, C.c_int32, P, P, P]),
+    "rdo_mx_conv_transpose2d_packed": (C.c_int, [P, P, C.c_int32, P, P, C.c_int32] + [C.c_int32] * 9 + [P, C.c_int32, C.c_int32, P, P, P]),
+}
+EXPORTS_MXCHAIN = tuple(_SIGS_MXCHAIN)
+MX_ACTS = {"none": 0, "lrelu": 1, "relu": 2}      # RDO_MX_ACT_* of include/rdo_ptq_mxchain.h
 # tuning hooks the library exports beside its headers (csrc/conv_wgrad.hip): tile choice (-1 = the library's, 0 = 64 x 64, 1 = 192 x 192)
 # and slab count (-1 = the library's) of rdo_conv2d_wgrad, process-wide; ops.forced_wgrad sets and restores them
 _SIGS_DEBUG = {
@@ -305,7 +313,7 @@ def lib():
                                   + list(_SIGS_PACK.items()) + list(_SIGS_SUBPEL.items()) + list(_SIGS_ACTBITS.items())
                                   + list(_SIGS_ATTNQ.items()) + list(_SIGS_MX.items()) + list(_SIGS_MXROUND.items())
                                   + list(_SIGS_MXGEMM.items()) + list(_SIGS_MXCONV.items()) + list(_SIGS_MXTCONV.items())
-                                  + list(_SIGS_MXFILE.items()) + list(_SIGS_DEBUG.items())):
+                                  + list(_SIGS_MXFILE.items()) + list(_SIGS_MXCHAIN.items()) + list(_SIGS_DEBUG.items())):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         _lib = h

@@ -981,33 +981,64 @@ def mx_unpack_dequant(packed, scales, inner, fmt, want=("w",), w_out=None, codes
     return {n: out[n] for n in want}
 
 
-def mx_gemm(a, b, bias=None):
+def _mx_packed_out(what, out_fmt, act, N):
+    """None for the fp32 output (out_fmt None; an act other than 'none' is refused there), else (format id, element bits, activation id)
+    of a packed output [rows, N] (include/rdo_ptq_mxchain.h): ValueError for an unknown name and for N % 32 != 0"""
+    if not isinstance(act, str) or act not in L.MX_ACTS:
+        raise ValueError(f"{what}: unknown act {act!r}; the activations are {list(L.MX_ACTS)}")
+    if out_fmt is None:
+        if act != "none":
+            raise ValueError(f"{what}: act {act!r} needs out_fmt: the fp32 output has no fused activation")
+        return None
+    fid, bits = mx_format(what, out_fmt)
+    if N % L.MX_BLOCK:
+        raise ValueError(f"{what}: N = {N} is no multiple of the MX block size {L.MX_BLOCK}: the packed output's blocks run along N")
+    return fid, bits, L.MX_ACTS[act]
+
+
+def _mx_packed_empty(rows, N, bits, dev):
+    """the tensors of a packed [rows, N] output"""
+    nb = N // L.MX_BLOCK
+    return torch.empty(rows, nb * 4 * bits, device=dev, dtype=torch.uint8), torch.empty(rows, nb, device=dev, dtype=torch.uint8)
+
+
+def mx_gemm(a, b, bias=None, out_fmt=None, act="none"):
     """y fp32 [M, N] = A B^T (+ bias) on the block-scaled matrix instruction (rdo_mx_gemm): a an `MXOperand` [M, K], b an `MXOperand` [N, K]
     of any two formats, bias contiguous fp32 [N] or None.  The products are exact; the sum is the instruction's fp32 accumulation.
-    Checked on the host before a pointer is taken."""
+    out_fmt (a name of `MX_FORMATS`; N % 32 == 0): one launch (rdo_mx_gemm_packed) -> `MXOperand` [M, N] of act(y), act 'none' | 'lrelu'
+    (slope 0.01) | 'relu', bit for bit `mx_quant_pack(act(y), out_fmt)`; act needs out_fmt.  Checked on the host before a pointer is taken."""
     what = "mx_gemm"
     fa, _, _ = _mx_operand(what, "a", a)
     fb, _, _ = _mx_operand(what, "b", b, device=a.packed.device)
     if a.K != b.K:
         raise ValueError(f"{what}: a has K = {a.K}, b has K = {b.K}")
+    out = _mx_packed_out(what, out_fmt, act, b.rows)
     dev = a.packed.device
     A.tensor(what, "bias", bias, shape=(b.rows,), contiguous=True, device=dev, optional=True, oneshot=True)
     _mx_cuda(what, a.packed, "a.packed")
+    if out is not None:
+        packed, scales = _mx_packed_empty(a.rows, b.rows, out[1], dev)
+        L.check(L.lib().rdo_mx_gemm_packed(_ptr(a.packed, *_U8), _ptr(a.scales, *_U8), fa, _ptr(b.packed, *_U8), _ptr(b.scales, *_U8), fb, a.rows,
+                                           b.rows, a.K, _ptr(bias), out[0], out[2], _ptr(packed, *_U8), _ptr(scales, *_U8), _stream()),
+                "rdo_mx_gemm_packed")
+        return MXOperand(packed, scales, out_fmt, a.rows, b.rows)
     y = torch.empty(a.rows, b.rows, device=dev, dtype=torch.float32)
     L.check(L.lib().rdo_mx_gemm(_ptr(a.packed, *_U8), _ptr(a.scales, *_U8), fa, _ptr(b.packed, *_U8), _ptr(b.scales, *_U8), fb, a.rows, b.rows,
                                 a.K, _ptr(bias), _ptr(y), _stream()), "rdo_mx_gemm")
     return y
 
 
-def mx_conv2d(x, w, shape, k, stride=1, pad=0, bias=None):
+def mx_conv2d(x, w, shape, k, stride=1, pad=0, bias=None, out_fmt=None, act="none"):
     """y fp32 [B, Ho, Wo, N] = conv(x, w) (+ bias) on the block-scaled matrix instruction (rdo_mx_conv2d; include/rdo_ptq_mxconv.h): x an
     `MXOperand` [B * H * W, C] -- an NHWC activation, one packed row per pixel, what `mx_quant_pack` makes of the NHWC rows --, shape =
     (B, H, W), w an `MXOperand` [N, k * k * C] whose rows are in (kh, kw, in) order (`to_rows`), of any two formats; square kernel k, one
     stride >= 1, one zero padding >= 0, dilation 1, groups 1; bias contiguous fp32 [N] or None.  Ho = (H + 2 pad - k) // stride + 1, Wo
-    likewise.  Bit for bit `mx_gemm` on the im2col matrix of x.  Checked on the host before a pointer is taken."""
+    likewise.  Bit for bit `mx_gemm` on the im2col matrix of x.  out_fmt / act as in `mx_gemm` (rdo_mx_conv2d_packed): -> `MXOperand`
+    [B * Ho * Wo, N], one packed row per output pixel -- the next conv's x.  Checked on the host before a pointer is taken."""
     what = "mx_conv2d"
     fx, _, _ = _mx_operand(what, "x", x)
     fw, _, _ = _mx_operand(what, "w", w, device=x.packed.device)
+    out = _mx_packed_out(what, out_fmt, act, w.rows)
     if isinstance(shape, (str, bytes)) or not hasattr(shape, "__len__") or len(shape) != 3:
         raise ValueError(f"{what}: shape must be (B, H, W), got {shape!r}")
     B, H, W = (A.whole(what, f"shape[{i}]", v, 1) for i, v in enumerate(shape))
@@ -1024,22 +1055,31 @@ def mx_conv2d(x, w, shape, k, stride=1, pad=0, bias=None):
     dev = x.packed.device
     A.tensor(what, "bias", bias, shape=(w.rows,), contiguous=True, device=dev, optional=True, oneshot=True)
     _mx_cuda(what, x.packed, "x.packed")
+    if out is not None:
+        packed, scales = _mx_packed_empty(B * Ho * Wo, w.rows, out[1], dev)
+        L.check(L.lib().rdo_mx_conv2d_packed(_ptr(x.packed, *_U8), _ptr(x.scales, *_U8), fx, _ptr(w.packed, *_U8), _ptr(w.scales, *_U8), fw, B, H, W,
+                                             x.K, w.rows, k, stride, pad, _ptr(bias), out[0], out[2], _ptr(packed, *_U8), _ptr(scales, *_U8),
+                                             _stream()), "rdo_mx_conv2d_packed")
+        return MXOperand(packed, scales, out_fmt, B * Ho * Wo, w.rows)
     y = torch.empty(B, Ho, Wo, w.rows, device=dev, dtype=torch.float32)
     L.check(L.lib().rdo_mx_conv2d(_ptr(x.packed, *_U8), _ptr(x.scales, *_U8), fx, _ptr(w.packed, *_U8), _ptr(w.scales, *_U8), fw, B, H, W, x.K,
                                   w.rows, k, stride, pad, _ptr(bias), _ptr(y), _stream()), "rdo_mx_conv2d")
     return y
 
 
-def mx_conv_transpose2d(x, w, shape, k, stride=1, pad=0, output_padding=0, bias=None):
+def mx_conv_transpose2d(x, w, shape, k, stride=1, pad=0, output_padding=0, bias=None, out_fmt=None, act="none"):
     """y fp32 [B, Ho, Wo, N] = conv_transpose(x, w) (+ bias) on the block-scaled matrix instruction (rdo_mx_conv_transpose2d;
     include/rdo_ptq_mxtconv.h): x an `MXOperand` [B * H * W, C] -- an NHWC activation, one packed row per pixel, what `mx_quant_pack`
     makes of the NHWC rows --, shape = (B, H, W), w an `MXOperand` [N, k * k * C] whose rows are those of `to_rows(W, tconv=True)`
     ((kh, kw, in) order, taps un-flipped), of any two formats; square kernel k, one stride >= 1, one padding >= 0, one output padding
     in 0 .. stride - 1, dilation 1, groups 1; bias contiguous fp32 [N] or None.  Ho = (H - 1) stride - 2 pad + k + output_padding, Wo
-    likewise.  Phase by phase bit for bit `mx_gemm` on the gathered operands.  Checked on the host before a pointer is taken."""
+    likewise.  Phase by phase bit for bit `mx_gemm` on the gathered operands.  out_fmt / act as in `mx_gemm`
+    (rdo_mx_conv_transpose2d_packed): -> `MXOperand` [B * Ho * Wo, N], one packed row per output pixel.  Checked on the host before a
+    pointer is taken."""
     what = "mx_conv_transpose2d"
     fx, _, _ = _mx_operand(what, "x", x)
     fw, _, _ = _mx_operand(what, "w", w, device=x.packed.device)
+    out = _mx_packed_out(what, out_fmt, act, w.rows)
     if isinstance(shape, (str, bytes)) or not hasattr(shape, "__len__") or len(shape) != 3:
         raise ValueError(f"{what}: shape must be (B, H, W), got {shape!r}")
     B, H, W = (A.whole(what, f"shape[{i}]", v, 1) for i, v in enumerate(shape))
@@ -1060,6 +1100,12 @@ def mx_conv_transpose2d(x, w, shape, k, stride=1, pad=0, output_padding=0, bias=
     dev = x.packed.device
     A.tensor(what, "bias", bias, shape=(w.rows,), contiguous=True, device=dev, optional=True, oneshot=True)
     _mx_cuda(what, x.packed, "x.packed")
+    if out is not None:
+        packed, scales = _mx_packed_empty(B * Ho * Wo, w.rows, out[1], dev)
+        L.check(L.lib().rdo_mx_conv_transpose2d_packed(_ptr(x.packed, *_U8), _ptr(x.scales, *_U8), fx, _ptr(w.packed, *_U8), _ptr(w.scales, *_U8), fw,
+                                                       B, H, W, x.K, w.rows, k, stride, pad, opad, _ptr(bias), out[0], out[2],
+                                                       _ptr(packed, *_U8), _ptr(scales, *_U8), _stream()), "rdo_mx_conv_transpose2d_packed")
+        return MXOperand(packed, scales, out_fmt, B * Ho * Wo, w.rows)
     y = torch.empty(B, Ho, Wo, w.rows, device=dev, dtype=torch.float32)
     L.check(L.lib().rdo_mx_conv_transpose2d(_ptr(x.packed, *_U8), _ptr(x.scales, *_U8), fx, _ptr(w.packed, *_U8), _ptr(w.scales, *_U8), fw, B, H,
                                             W, x.K, w.rows, k, stride, pad, opad, _ptr(bias), _ptr(y), _stream()), "rdo_mx_conv_transpose2d")

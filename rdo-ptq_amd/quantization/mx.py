@@ -24,10 +24,14 @@ MX activations inside the modules' own forward: `QuantModel.set_mx_activations(a
 every module one of the three refusals accepts; `QuantModule.forward` (no-grad path, weight quantisation on) then takes its
 pre-activation output from `mx_forward`: mode 'native' runs `native_linear` / `native_conv` / `native_tconv`, mode 'emulated' the
 module's fp32 kernel on the decoded `xq` of the same producer; the module's tail (se_module, activation function, output quantiser)
-follows un-fused.  Not built: GDN and LayerNorm on the native path, fused activation epilogues, a producer fused into the previous
-layer's store, calibration or a backward under MX activations (`reconstruct` refuses such a model), data-parallel runs; no
-rate-distortion claim is made for any of it.  A model on these quantisers is stored by `mx_packed.save_mx_packed`, the `mx_activations`
-pairs included."""
+follows un-fused.  Not built: GDN and LayerNorm on the native path, calibration or a backward under MX activations (`reconstruct`
+refuses such a model), data-parallel runs; no rate-distortion claim is made for any of it.  A model on these quantisers is stored by
+`mx_packed.save_mx_packed`, the `mx_activations` pairs included.
+
+Chains (include/rdo_ptq_mxchain.h): `native_chain(first, second, x, act_fmt, act)` runs two convs of the kinds above in three launches
+-- `first` writes act(its output) packed in `act_fmt`, the operand `second` reads -- for pairs `native_chain_refusal` accepts;
+`set_mx_activations(..., chain=True)` switches the conv1 -> LReLU -> conv2 pair of `QuantRB` / `QuantRBWS` blocks to it (`mx_chain`, not
+stored by `save_mx_packed`).  The same bits as the un-chained forward."""
 import torch
 import torch.nn as nn
 
@@ -384,6 +388,67 @@ def native_tconv(module, x, act_fmt):
     k, stride, pad, opad = tconv_geometry(module)
     a = ops.mx_quant_pack(x.permute(0, 2, 3, 1).reshape(-1, C).contiguous(), act_fmt)
     return ops.mx_conv_transpose2d(a, b, (B, H, W), k, stride, pad, opad, native_bias(module)).permute(0, 3, 1, 2)
+
+
+# ---- two convs chained through a packed MX tensor (include/rdo_ptq_mxchain.h) ---------------------------------------------------------------
+def _chain_channels(module):
+    """(input channels, output channels) of a conv or transposed-conv QuantModule"""
+    w = module.weight
+    return (int(w.shape[0]), int(w.shape[1])) if module.kind == "tconv" else (int(w.shape[1]), int(w.shape[0]))
+
+
+def native_chain_refusal(first, second):
+    """None for a pair of QuantModules `native_chain` serves, else the reason it does not, looked for in this order: `first`, then
+    `second`, is no module `native_conv_refusal` / `native_tconv_refusal` accepts; `first` has an `se_module`, an activation function of
+    its own that is not the identity, or an active output quantiser (the chain applies bias and `act` alone between the two convs);
+    its output channels are no multiple of 32 (they are the blocks of `second`'s K); they are not `second`'s input channels"""
+    from .quantizer import StraightThrough
+    for name, m in (("first", first), ("second", second)):
+        why = (native_tconv_refusal if getattr(m, "kind", None) == "tconv" else native_conv_refusal)(m)
+        if why is not None:
+            return f"{name}: {why}"
+    if first.se_module is not None:
+        return "first has an se_module between its convolution and its output"
+    if not isinstance(first.activation_function, (StraightThrough, nn.Identity)):
+        return f"first has an activation function of its own ({type(first.activation_function).__name__}), not the identity"
+    if not first.disable_act_quant and first.use_act_quant and first.trained:
+        return "first has an active output quantiser"
+    n, c = _chain_channels(first)[1], _chain_channels(second)[0]
+    if n % L.MX_BLOCK:
+        return f"first's {n} output channels are no multiple of the MX block size {L.MX_BLOCK}"
+    if n != c:
+        return f"first's {n} output channels are not second's {c} input channels"
+    return None
+
+
+def _chain_step(module, a, shape, **out):
+    """one conv or transposed conv of a chain on the packed NHWC pixels `a` of a (B, H, W) input -> (result, (B, Ho, Wo))"""
+    B, H, W = shape
+    if module.kind == "tconv":
+        k, stride, pad, opad = tconv_geometry(module)
+        y = ops.mx_conv_transpose2d(a, native_tconv_operand(module), shape, k, stride, pad, opad, native_bias(module), **out)
+        return y, (B, (H - 1) * stride - 2 * pad + k + opad, (W - 1) * stride - 2 * pad + k + opad)
+    k, stride, pad = conv_geometry(module)
+    y = ops.mx_conv2d(a, native_conv_operand(module), shape, k, stride, pad, native_bias(module), **out)
+    return y, (B, (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1)
+
+
+def native_chain(first, second, x, act_fmt, act="lrelu"):
+    """The pre-activation output of `second` from the NCHW input `x` of `first` in three launches: `ops.mx_quant_pack` on the NHWC pixels
+    of x, `first` with its bias and `act` ('none' | 'lrelu' | 'relu') writing its output packed in `act_fmt` (`out_fmt=` of
+    `ops.mx_conv2d` / `mx_conv_transpose2d`), and `second` on that operand with its bias and the fp32 output, a channels-last view
+    [B, N, Ho, Wo].  Bit for bit second's `native_conv` / `native_tconv` on act(first's): no fp32 tensor lies between the two convs.
+    ValueError naming the modules and the reason for a pair `native_chain_refusal` gives a reason for."""
+    why = native_chain_refusal(first, second)
+    if why is not None:
+        raise ValueError(f"native_chain: modules {_describe(first)} -> {_describe(second)}: {why}")
+    C = _chain_channels(first)[0]
+    if x.dim() != 4 or x.shape[1] != C:
+        raise ValueError(f"native_chain: the input must be [B, {C}, H, W], got {tuple(x.shape)}")
+    B, _, H, W = (int(v) for v in x.shape)
+    a = ops.mx_quant_pack(x.permute(0, 2, 3, 1).reshape(-1, C).contiguous(), act_fmt)
+    mid, shape = _chain_step(first, a, (B, H, W), out_fmt=act_fmt, act=act)
+    return _chain_step(second, mid, shape)[0].permute(0, 3, 1, 2)
 
 
 # ---- MX activations inside the modules' own forward (QuantModel.set_mx_activations) ------------------------------------------------------------

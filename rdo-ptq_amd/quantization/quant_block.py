@@ -38,6 +38,21 @@ class BaseQuantBlock(nn.Module):
         return self.act_quantizer(x, True, site=site) if (self.use_act_quant and self.trained) else x
 
 
+    def _conv_pair(self, x):
+        """conv2(_aq(LReLU(conv1(x)))) of a block with such a pair.  Where `mx_chain` is set (`QuantModel.set_mx_activations(...,
+        chain=True)`), both convs run on the same native MX activations with their quantised weights, the input is not tracked and the
+        block's activation quantiser is inactive between them, the pair is `mx.native_chain`: conv1 writes LReLU(conv1(x)) packed in
+        the activation format and conv2 reads it -- the same bits without the fp32 tensor, the LReLU launch and the quantise launch
+        between them --, then conv2's own tail."""
+        c1, c2 = self.conv1, self.conv2
+        on = getattr(c1, "mx_activations", None)
+        if (getattr(self, "mx_chain", False) and on is not None and on[1] == "native" and on == getattr(c2, "mx_activations", None)
+                and c1.use_weight_quant and c2.use_weight_quant and not _tracked(x) and not (self.use_act_quant and self.trained)):
+            from .mx import native_chain
+            return c2._mx_tail(native_chain(c1, c2, x, on[0], "lrelu"))
+        return c2(self._aq(_lrelu(c1(x))))
+
+
 def _tracked(*ts):
     return torch.is_grad_enabled() and any(t.requires_grad for t in ts)
 
@@ -67,8 +82,7 @@ class QuantRBWS(BaseQuantBlock):
         self.skip = None if basic_block.skip is None else QuantModule(basic_block.skip, weight_quant_params, act_quant_params)
 
     def forward(self, x):
-        out = self._aq(_lrelu(self.conv1(x)))
-        out = self.gdn(self.conv2(out))
+        out = self.gdn(self._conv_pair(x))
         out = _add(out, x if self.skip is None else self.skip(x))
         return self._aq(out, 1)
 
@@ -114,8 +128,7 @@ class QuantRB(BaseQuantBlock):
         self.skip = None if basic_block.skip is None else QuantModule(basic_block.skip, weight_quant_params, act_quant_params)
 
     def forward(self, x):
-        out = self._aq(_lrelu(self.conv1(x)))
-        out = self._aq(_lrelu(self.conv2(out)), 1)
+        out = self._aq(_lrelu(self._conv_pair(x)), 1)
         out = _add(out, x if self.skip is None else self.skip(x))
         return self._aq(out, 2)
 

@@ -257,7 +257,11 @@ class QuantModule(nn.Module):
         """the forward under `mx_activations` (`QuantModel.set_mx_activations`): the pre-activation output of `mx.mx_forward`, then the
         module's tail, un-fused"""
         from .mx import mx_forward
-        out = mx_forward(self, input)
+        return self._mx_tail(mx_forward(self, input))
+
+    def _mx_tail(self, out):
+        """the module's tail behind a pre-activation output of the MX paths (`_forward_mx`; a block's `mx.native_chain`): se_module,
+        activation function, output quantiser, un-fused"""
         if self.se_module is not None:
             out = self.se_module(out)
         out = self.activation_function(out)

@@ -5,7 +5,7 @@ import torch.nn as nn
 from lic import EntropyBottleneck
 
 from .fold_bn import search_fold_and_remove_bn
-from .quant_block import BaseQuantBlock, specials
+from .quant_block import BaseQuantBlock, QuantRB, QuantRBWS, specials
 from .quant_layer import GDN_TYPES, QuantModule, StraightThrough
 from .widths import act_applied, act_modules, format_plan, is_trained, weighted_modules, width_plan
 
@@ -167,7 +167,7 @@ class QuantModel(nn.Module):
         from .reports import mx_native_report
         return mx_native_report(self, images, act_fmt=act_fmt, batch=batch, units=units, convs=convs, tconvs=tconvs)
 
-    def set_mx_activations(self, act_fmt, mode="native", units=None):
+    def set_mx_activations(self, act_fmt, mode="native", units=None, chain=False):
         """Run the modules' own forward on MX activations: every weighted QuantModule of the chosen units (`units`: a list of names of
         `units()`, None for all) that `mx.native_refusal`, `native_conv_refusal` or `native_tconv_refusal` accepts gets the plain
         attribute `mx_activations = (act_fmt, mode)`.  Its no-grad forward, while `use_weight_quant` is on, then takes the
@@ -178,8 +178,14 @@ class QuantModel(nn.Module):
         act_fmt=None clears the attribute on every weighted module of the chosen units.  Whether a unit is trained does not matter.
         -> OrderedDict: 'native' module name -> 'linear' | 'conv' | 'tconv'; 'left' module name -> why the module keeps its forward
         (GDN, LayerNorm, a 3-channel stem, ragged channel counts, a weight that is in no MX format).
-        ValueError before anything is written for an unknown act_fmt or mode, an unknown unit, and (act_fmt not None) a named unit
-        without an eligible module.  An input that requires grad raises NotImplementedError in a switched module; `reconstruct`
+        chain=True (mode 'native' only) also sets the plain attribute `mx_chain` on every `QuantRB` / `QuantRBWS` block of the chosen
+        units whose (conv1, conv2) `mx.native_chain_refusal` accepts: its no-grad forward then runs the pair as `mx.native_chain` --
+        conv1 writes LReLU(conv1(x)) packed in act_fmt, conv2 reads it; the same bits in three launches instead of five -- while both
+        convs carry this (act_fmt, 'native'), `use_weight_quant` is on and the block's activation quantiser is inactive.  The result
+        then gains 'chained': block name -> (conv1 name, conv2 name).  chain=False and act_fmt=None clear `mx_chain` on the chosen units'
+        blocks.  `mx_chain` is not stored by `save_mx_packed`: a loaded model is un-chained and computes the same bits.
+        ValueError before anything is written for an unknown act_fmt or mode, an unknown unit, a chain that is no bool or is True in
+        another mode than 'native', and (act_fmt not None) a named unit without an eligible module.  An input that requires grad raises NotImplementedError in a switched module; `reconstruct`
         refuses a model that holds one."""
         from collections import OrderedDict
         from . import mx
@@ -189,6 +195,8 @@ class QuantModel(nn.Module):
             ops.mx_format(what, act_fmt)
         if not isinstance(mode, str) or mode not in mx.MX_ACT_MODES:
             raise ValueError(f"{what}: mode must be one of {list(mx.MX_ACT_MODES)}, got {mode!r}")
+        if not isinstance(chain, bool) or (chain and mode != "native"):
+            raise ValueError(f"{what}: chain must be True or False, and True in mode 'native' only; got chain={chain!r}, mode={mode!r}")
         if units is None:
             chosen = list(known)
         else:
@@ -199,13 +207,20 @@ class QuantModel(nn.Module):
             if unknown:
                 raise ValueError(f"{what}: unknown unit name(s) {unknown}; QuantModel.units() has {list(known)}")
         rep = OrderedDict(native=OrderedDict(), left=OrderedDict())
-        plan = []
+        if chain:
+            rep["chained"] = OrderedDict()
+        plan, blocks = [], []
         for uname in chosen:
             found = False
             for mn, m in known[uname].named_modules():
+                name = f"{uname}.{mn}" if mn else uname
+                if isinstance(m, (QuantRB, QuantRBWS)):
+                    on = chain and act_fmt is not None and mx.native_chain_refusal(m.conv1, m.conv2) is None
+                    blocks.append((m, on))
+                    if on:
+                        rep["chained"][name] = (f"{name}.conv1", f"{name}.conv2")
                 if not isinstance(m, QuantModule) or m.org_weight is None:
                     continue
-                name = f"{uname}.{mn}" if mn else uname
                 kind, why = mx.native_kind(m)
                 plan.append((m, kind))
                 if kind is None:
@@ -217,6 +232,8 @@ class QuantModel(nn.Module):
                                  f"{ {n: w for n, w in rep['left'].items() if n == uname or n.startswith(uname + '.')} }")
         for m, kind in plan:
             m.mx_activations = None if (act_fmt is None or kind is None) else (act_fmt, mode)
+        for b, on in blocks:
+            b.mx_chain = on
         return rep
 
     def set_weight_format(self, formats, rounding="nearest"):
