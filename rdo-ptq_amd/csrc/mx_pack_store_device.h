@@ -127,6 +127,47 @@ __device__ __forceinline__ void mx_pack_store(const f32x4 (&acc)[2][2], const fl
     if (h == 0) o.scales[blk] = (uint8_t)scale;
 }
 
+// The row-major form of the same quantiser, for a kernel whose lanes hold four consecutive channels of a row (mx_gdn.hip: the x o x
+// producer and the packed epilogue): the eight lanes 8 t .. 8 t + 7 of a wave hold one block, lane s = lane & 7 its elements 4 s ..
+// 4 s + 3 in v.  Block maximum by three xor shuffles inside the eight; mx_block_exponent / mx_encode as above; the lane's four codes are
+// 16 / 24 / 32 consecutive bits of the block's bit string, put into whole dwords by one more shuffle (FP4: a lane pair makes a dword;
+// FP6: four lanes make three) and stored to dst[0 .. bits - 1], the block's packed image in global memory or LDS.  Returns the scale
+// byte (255 and zero codes for a block that holds a NaN or an infinity).  Called by all 64 lanes; `live` guards the stores alone.
+__device__ __forceinline__ unsigned mx_quad_quant_store(const float (&v)[4], const MxFormat& f, uint32_t* dst, bool live) {
+    const int lane = threadIdx.x & 63, s = lane & 7;
+    unsigned pat[4], amax = 0u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        pat[k] = __builtin_bit_cast(unsigned, v[k]);
+        const unsigned m = pat[k] & 0x7FFFFFFFu;
+        amax = m > amax ? m : amax;
+    }
+#pragma unroll
+    for (int o = 1; o < 8; o <<= 1) {
+        const unsigned u = __shfl_xor(amax, o, 64);
+        amax = u > amax ? u : amax;
+    }
+    const bool finite = amax < 0x7F800000u;
+    const int E = finite ? mx_block_exponent(amax, f) : -127;
+    unsigned w = 0u;
+    if (finite) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            w |= (mx_encode(pat[k] & 0x7FFFFFFFu, E, f) | ((pat[k] & 0x80000000u) >> (32 - f.bits))) << (k * f.bits);
+    }
+    if (f.bits == 8) {
+        if (live) dst[s] = w;
+    } else if (f.bits == 4) {
+        const unsigned hi = __shfl_xor(w, 1, 64);
+        if (live && !(s & 1)) dst[s >> 1] = w | (hi << 16);
+    } else {
+        const unsigned next = __shfl(w, (lane + 1) & 63, 64);                   // (lane 3 of a four stores nothing: its `next` is unused)
+        const int i = s & 3;
+        if (live && i < 3) dst[3 * (s >> 2) + i] = (w >> (8 * i)) | (next << (24 - 8 * i));
+    }
+    return finite ? (unsigned)(E + 127) : 255u;
+}
+
 // what every packed entry checks beyond its fp32 twin; the message starts with `who`
 inline int mx_packed_out_check(const char* who, int32_t out_format, int32_t act, int64_t N, void* y_packed, uint8_t* y_scales,
                                MxPackedOut& o) {

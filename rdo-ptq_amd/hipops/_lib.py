@@ -288,6 +288,13 @@ _SIGS_MXCHAIN = {
 }
 EXPORTS_MXCHAIN = tuple(_SIGS_MXCHAIN)
 MX_ACTS = {"none": 0, "lrelu": 1, "relu": 2}      # RDO_MX_ACT_* of include/rdo_ptq_mxchain.h
+# include/rdo_ptq_mxgdn.h: the GDN / IGDN forward with its norm pool on the block-scaled matrix instruction, fp32 or packed output
+_SIGS_MXGDN = {
+    "rdo_mx_gdn": (C.c_int, [P, C.c_int32, C.c_int32, C.c_int32, P, P, C.c_int32, P, C.c_int32, P, P, P]),
+    "rdo_mx_gdn_packed": (C.c_int, [P, C.c_int32, C.c_int32, C.c_int32, P, P, C.c_int32, P, C.c_int32, C.c_int32, P, P, P, P]),
+}
+EXPORTS_MXGDN = tuple(_SIGS_MXGDN)
+MXGDN_MAX_C = 512         # RDO_MXGDN_MAX_C of include/rdo_ptq_mxgdn.h
 # tuning hooks the library exports beside its headers (csrc/conv_wgrad.hip): tile choice (-1 = the library's, 0 = 64 x 64, 1 = 192 x 192)
 # and slab count (-1 = the library's) of rdo_conv2d_wgrad, process-wide; ops.forced_wgrad sets and restores them
 _SIGS_DEBUG = {
@@ -313,7 +320,8 @@ def lib():
                                   + list(_SIGS_PACK.items()) + list(_SIGS_SUBPEL.items()) + list(_SIGS_ACTBITS.items())
                                   + list(_SIGS_ATTNQ.items()) + list(_SIGS_MX.items()) + list(_SIGS_MXROUND.items())
                                   + list(_SIGS_MXGEMM.items()) + list(_SIGS_MXCONV.items()) + list(_SIGS_MXTCONV.items())
-                                  + list(_SIGS_MXFILE.items()) + list(_SIGS_MXCHAIN.items()) + list(_SIGS_DEBUG.items())):
+                                  + list(_SIGS_MXFILE.items()) + list(_SIGS_MXCHAIN.items()) + list(_SIGS_MXGDN.items())
+                                  + list(_SIGS_DEBUG.items())):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         _lib = h

@@ -1112,6 +1112,40 @@ def mx_conv_transpose2d(x, w, shape, k, stride=1, pad=0, output_padding=0, bias=
     return y
 
 
+def mx_gdn(x2d, g, beta, fmt, inverse=False, out_fmt=None, want_norm=False):
+    """The GDN / IGDN forward with its norm pool on the block-scaled matrix instruction, one launch (rdo_mx_gdn; include/rdo_ptq_mxgdn.h):
+    x2d contiguous fp32 [rows, C] (the NHWC pixels), g an `MXOperand` [C, C] (gamma', blocks along the input channel), beta contiguous
+    fp32 [C] (beta'), fmt the MX format of x o x; C % 32 == 0 and C <= `MXGDN_MAX_C`.  norm = `mx_gemm(mx_quant_pack(x2d * x2d, fmt), g,
+    beta)` bit for bit, y = x * norm^-1/2 (inverse: x * norm^1/2) -> fp32 [rows, C]; out_fmt (a name of `MX_FORMATS`): -> `MXOperand`
+    [rows, C], bit for bit `mx_quant_pack(y, out_fmt)` (rdo_mx_gdn_packed).  want_norm: -> (y, norm).  Checked on the host before a
+    pointer is taken."""
+    what = "mx_gdn"
+    A.tensor(what, "x2d", x2d, rank=2, layout="of rank 2 [rows, C]", contiguous=True)
+    fx, _ = mx_format(what, fmt)
+    rows, Cc, dev = int(x2d.shape[0]), int(x2d.shape[1]), x2d.device
+    _mx_k(what, rows, Cc)
+    if Cc > L.MXGDN_MAX_C:
+        raise ValueError(f"{what}: C = {Cc} is above {L.MXGDN_MAX_C}, the most the kernel's LDS serves")
+    fg, _, _ = _mx_operand(what, "g", g, device=dev)
+    if (g.rows, g.K) != (Cc, Cc):
+        raise ValueError(f"{what}: g is [{g.rows}, {g.K}], x2d's {Cc} channels need [{Cc}, {Cc}]")
+    A.tensor(what, "beta", beta, shape=(Cc,), contiguous=True, device=dev, oneshot=True)
+    out = None if out_fmt is None else mx_format(what, out_fmt)
+    _mx_cuda(what, x2d, "x2d")
+    inverse = 1 if inverse else 0
+    norm = torch.empty_like(x2d) if want_norm else None
+    if out is not None:
+        packed, scales = _mx_packed_empty(rows, Cc, out[1], dev)
+        L.check(L.lib().rdo_mx_gdn_packed(_ptr(x2d), rows, Cc, fx, _ptr(g.packed, *_U8), _ptr(g.scales, *_U8), fg, _ptr(beta), inverse, out[0],
+                                          _ptr(packed, *_U8), _ptr(scales, *_U8), _ptr(norm), _stream()), "rdo_mx_gdn_packed")
+        y = MXOperand(packed, scales, out_fmt, rows, Cc)
+    else:
+        y = torch.empty_like(x2d)
+        L.check(L.lib().rdo_mx_gdn(_ptr(x2d), rows, Cc, fx, _ptr(g.packed, *_U8), _ptr(g.scales, *_U8), fg, _ptr(beta), inverse, _ptr(y),
+                                   _ptr(norm), _stream()), "rdo_mx_gdn")
+    return (y, norm) if want_norm else y
+
+
 def pack_row_words(inner, bits):
     """W = ceil(inner * bits / 32): the 32-bit words one row of `inner` codes of `bits` bits occupies (rdo_pack_row_words on the host)"""
     return -(-int(inner) * int(bits) // 32)

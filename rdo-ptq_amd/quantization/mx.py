@@ -24,7 +24,10 @@ MX activations inside the modules' own forward: `QuantModel.set_mx_activations(a
 every module one of the three refusals accepts; `QuantModule.forward` (no-grad path, weight quantisation on) then takes its
 pre-activation output from `mx_forward`: mode 'native' runs `native_linear` / `native_conv` / `native_tconv`, mode 'emulated' the
 module's fp32 kernel on the decoded `xq` of the same producer; the module's tail (se_module, activation function, output quantiser)
-follows un-fused.  Not built: GDN and LayerNorm on the native path, calibration or a backward under MX activations (`reconstruct`
+follows un-fused.  GDN / IGDN (include/rdo_ptq_mxgdn.h): `native_gdn(module, x, act_fmt)` squares, quantises, runs the norm pool on the
+instruction and forms x * norm^-+1/2 in one launch, with gamma' re-quantised onto the MX grid (`native_gdn_operand`: a second
+rounding); `set_mx_activations(..., gdn=True)` switches eligible GDNs to it, `native_gdn_chain` hands its packed output to a following
+conv.  Not built: LayerNorm on the native path, calibration or a backward under MX activations (`reconstruct`
 refuses such a model), data-parallel runs; no rate-distortion claim is made for any of it.  A model on these quantisers is stored by
 `mx_packed.save_mx_packed`, the `mx_activations` pairs included.
 
@@ -451,6 +454,110 @@ def native_chain(first, second, x, act_fmt, act="lrelu"):
     return _chain_step(second, mid, shape)[0].permute(0, 3, 1, 2)
 
 
+# ---- GDN / IGDN with the norm pool on the same instruction (include/rdo_ptq_mxgdn.h) -----------------------------------------------------------
+def native_gdn_refusal(module):
+    """None for a QuantModule `native_gdn` serves, else the reason it does not, looked for in this order: it is no GDN / IGDN; its
+    channels are no multiple of 32; they are above `hipops._lib.MXGDN_MAX_C`; its weight quantiser is no MX class"""
+    q = getattr(module, "weight_quantizer", None)
+    kind = getattr(module, "kind", None)
+    if kind != "gdn":
+        return f"a {kind} module is not a GDN: the native GDN path serves GDN and IGDN modules"
+    C = int(module.weight.shape[0])
+    if C % L.MX_BLOCK:
+        return f"its {C} channels are no multiple of the MX block size {L.MX_BLOCK}"
+    if C > L.MXGDN_MAX_C:
+        return f"its {C} channels are above {L.MXGDN_MAX_C}, the most the kernel's LDS serves"
+    if not is_mx_any(q):
+        return f"its weight quantiser is a {type(q).__name__}, not an MXQuantizer or MXAdaRoundQuantizer"
+    return None
+
+
+def _gdn_operands(module):
+    """(packed operand, decoded `ops.WeightPack`) of a GDN module's effective gamma' on the MX grid, memoised in
+    `_pack_memo['mx_native_gdn']` for as long as `weight_pack()` returns the same pack"""
+    why = native_gdn_refusal(module)
+    if why is not None:
+        raise ValueError(f"native_gdn_operand: module {_describe(module)}: {why}")
+    pack, fmt = module.weight_pack(), module.weight_quantizer.fmt
+    memos = module.__dict__.get("_pack_memo")
+    if not isinstance(memos, dict):
+        memos = module.__dict__["_pack_memo"] = {}
+    memo = memos.get("mx_native_gdn")
+    if memo is not None and memo[0] is pack and memo[1] == fmt:
+        return memo[2]
+    C = int(pack.w.shape[0])
+    out = ops.mx_fakequant(pack.w.reshape(C, C), fmt, want=("wq", "codes", "scales"))
+    both = (ops.mx_pack_codes(out["codes"], out["scales"], fmt), ops.WeightPack(out["wq"].reshape(C, 1, 1, C), pack.bias))
+    memos["mx_native_gdn"] = (pack, fmt, both)
+    return both
+
+
+def native_gdn_operand(module):
+    """The `ops.MXOperand` [C, C] of a GDN QuantModule's effective gamma' in its present quant state: `module.weight_pack().w` --
+    reparam(weight_quantizer(gamma)) = max(., bound)^2 - pedestal of the quantised gamma -- put on the MX grid of the quantiser's format
+    by `ops.mx_fakequant` (round to nearest), blocks along the input channel, and packed.  This is a SECOND rounding: the
+    re-parametrisation takes the quantised gamma off its grid, and the instruction needs codes.  Rounding keeps signs and zeros, so
+    gamma' >= 0 stays so, and beta' > 0 is not rounded: norm > 0.  Memoised in `_pack_memo` under a slot of its own and dropped by
+    `drop_weight_pack()`.  ValueError naming the module and the reason for a module `native_gdn_refusal` gives a reason for."""
+    return _gdn_operands(module)[0]
+
+
+def _gdn_rows(what, module, x):
+    C = int(module.weight.shape[0])
+    if x.dim() != 4 or x.shape[1] != C:
+        raise ValueError(f"{what}: the input must be [B, {C}, H, W], got {tuple(x.shape)}")
+    B, _, H, W = (int(v) for v in x.shape)
+    return x.permute(0, 2, 3, 1).reshape(-1, C).contiguous(), (B, H, W)
+
+
+def native_gdn(module, x, act_fmt, out_fmt=None):
+    """The output of an eligible GDN / IGDN QuantModule (`native_gdn_operand`) in one `ops.mx_gdn` launch: `x` is the module's NCHW
+    input; the squares of its NHWC pixels are quantised to `act_fmt` in blocks of 32 channels, the norm pool beta' + gamma' x^2 runs on
+    the block-scaled matrix instruction with `module.weight_pack().bias` as beta', and y = x * norm^-1/2 (IGDN: x * norm^1/2) comes
+    back as a channels-last view [B, C, H, W] -- or, with out_fmt, as the `ops.MXOperand` [B * H * W, C] of the NHWC pixels, the
+    operand of a following conv.  Nothing else of the module's forward is applied."""
+    g = native_gdn_operand(module)
+    rows, (B, H, W) = _gdn_rows("native_gdn", module, x)
+    y = ops.mx_gdn(rows, g, module.weight_pack().bias, act_fmt, inverse=bool(module.fwd_kwargs["inverse"]), out_fmt=out_fmt)
+    return y if out_fmt is not None else y.reshape(B, H, W, -1).permute(0, 3, 1, 2)
+
+
+def native_gdn_chain_refusal(gdn, second):
+    """None for a (GDN, conv or transposed conv) pair `native_gdn_chain` serves, else the reason it does not, looked for in this order:
+    `gdn` is no module `native_gdn_refusal` accepts; `second` none `native_conv_refusal` / `native_tconv_refusal` accepts; `gdn` has an
+    `se_module`, an activation function that is not the identity, or an active output quantiser; its channels are not `second`'s input
+    channels"""
+    from .quantizer import StraightThrough
+    why = native_gdn_refusal(gdn)
+    if why is not None:
+        return f"gdn: {why}"
+    why = (native_tconv_refusal if getattr(second, "kind", None) == "tconv" else native_conv_refusal)(second)
+    if why is not None:
+        return f"second: {why}"
+    if gdn.se_module is not None:
+        return "gdn has an se_module between its output and second"
+    if not isinstance(gdn.activation_function, (StraightThrough, nn.Identity)):
+        return f"gdn has an activation function of its own ({type(gdn.activation_function).__name__}), not the identity"
+    if not gdn.disable_act_quant and gdn.use_act_quant and gdn.trained:
+        return "gdn has an active output quantiser"
+    n, c = int(gdn.weight.shape[0]), _chain_channels(second)[0]
+    if n != c:
+        return f"gdn's {n} channels are not second's {c} input channels"
+    return None
+
+
+def native_gdn_chain(gdn, second, x, act_fmt):
+    """The pre-activation output of `second` from the NCHW input `x` of `gdn` in two launches: `ops.mx_gdn` writing the GDN's output
+    packed in `act_fmt`, and `second` (`_chain_step`) on that operand.  Bit for bit second's `native_conv` / `native_tconv` on
+    `native_gdn(gdn, x, act_fmt)`: no fp32 tensor lies between the two.  ValueError naming the modules and the reason for a pair
+    `native_gdn_chain_refusal` gives a reason for."""
+    why = native_gdn_chain_refusal(gdn, second)
+    if why is not None:
+        raise ValueError(f"native_gdn_chain: modules {_describe(gdn)} -> {_describe(second)}: {why}")
+    _, shape = _gdn_rows("native_gdn_chain", gdn, x)
+    return _chain_step(second, native_gdn(gdn, x, act_fmt, out_fmt=act_fmt), shape)[0].permute(0, 3, 1, 2)
+
+
 # ---- MX activations inside the modules' own forward (QuantModel.set_mx_activations) ------------------------------------------------------------
 MX_ACT_MODES = ("native", "emulated")
 
@@ -480,9 +587,21 @@ def mx_forward(module, x):
     """The pre-activation output of a module whose `mx_activations` = (act_fmt, mode) is set (`QuantModel.set_mx_activations`), from its
     input quantised to act_fmt in blocks of 32 along the input channels.  'native': `native_linear`, `native_conv` or `native_tconv`.
     'emulated': xq of `ops.mx_quant_pack(rows, act_fmt, want_xq=True)`, reshaped to the input, through the module's fp32 forward kernel
-    with its quantised weight pack and EPI_NONE."""
+    with its quantised weight pack and EPI_NONE.
+    A GDN / IGDN (`set_mx_activations(..., gdn=True)`): 'native' is `native_gdn`; 'emulated' the fp32 GDN kernel on the decoded operands --
+    xq of `ops.mx_quant_pack(x o x, act_fmt, want_xq=True)` as the pool's input (square_input=False), the decoded gamma' of
+    `native_gdn_operand` with beta' as its weight pack, EPI_GDN / EPI_IGDN with aux = x."""
     act_fmt, mode = module.mx_activations
     kind = module.kind
+    if kind == "gdn":
+        if mode == "native":
+            return native_gdn(module, x, act_fmt)
+        rows, (B, H, W) = _gdn_rows("mx_forward", module, x)
+        _, xq = ops.mx_quant_pack(rows * rows, act_fmt, want_xq=True)
+        y = ops.conv2d_fwd_pack(xq.reshape(B, H, W, -1), _gdn_operands(module)[1], 1, 0,
+                                epilogue=L.EPI_IGDN if module.fwd_kwargs["inverse"] else L.EPI_GDN, aux=rows.reshape(B, H, W, -1),
+                                square_input=False)
+        return y.permute(0, 3, 1, 2)
     if mode == "native":
         if kind == "linear":
             return native_linear(module, x, act_fmt)

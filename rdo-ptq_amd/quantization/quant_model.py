@@ -167,7 +167,7 @@ class QuantModel(nn.Module):
         from .reports import mx_native_report
         return mx_native_report(self, images, act_fmt=act_fmt, batch=batch, units=units, convs=convs, tconvs=tconvs)
 
-    def set_mx_activations(self, act_fmt, mode="native", units=None, chain=False):
+    def set_mx_activations(self, act_fmt, mode="native", units=None, chain=False, gdn=False):
         """Run the modules' own forward on MX activations: every weighted QuantModule of the chosen units (`units`: a list of names of
         `units()`, None for all) that `mx.native_refusal`, `native_conv_refusal` or `native_tconv_refusal` accepts gets the plain
         attribute `mx_activations = (act_fmt, mode)`.  Its no-grad forward, while `use_weight_quant` is on, then takes the
@@ -176,7 +176,7 @@ class QuantModel(nn.Module):
         `native_tconv`); mode 'emulated': the decoded input through the module's fp32 kernel -- followed by the module's tail
         (se_module, activation function, output quantiser), un-fused.  With `use_weight_quant` off the forward is what it was.
         act_fmt=None clears the attribute on every weighted module of the chosen units.  Whether a unit is trained does not matter.
-        -> OrderedDict: 'native' module name -> 'linear' | 'conv' | 'tconv'; 'left' module name -> why the module keeps its forward
+        -> OrderedDict: 'native' module name -> 'linear' | 'conv' | 'tconv' (| 'gdn'); 'left' module name -> why the module keeps its forward
         (GDN, LayerNorm, a 3-channel stem, ragged channel counts, a weight that is in no MX format).
         chain=True (mode 'native' only) also sets the plain attribute `mx_chain` on every `QuantRB` / `QuantRBWS` block of the chosen
         units whose (conv1, conv2) `mx.native_chain_refusal` accepts: its no-grad forward then runs the pair as `mx.native_chain` --
@@ -184,7 +184,11 @@ class QuantModel(nn.Module):
         convs carry this (act_fmt, 'native'), `use_weight_quant` is on and the block's activation quantiser is inactive.  The result
         then gains 'chained': block name -> (conv1 name, conv2 name).  chain=False and act_fmt=None clear `mx_chain` on the chosen units'
         blocks.  `mx_chain` is not stored by `save_mx_packed`: a loaded model is un-chained and computes the same bits.
-        ValueError before anything is written for an unknown act_fmt or mode, an unknown unit, a chain that is no bool or is True in
+        gdn=True also switches every GDN / IGDN module `mx.native_gdn_refusal` accepts, reported under 'native' as 'gdn': mode 'native'
+        runs `mx.native_gdn` (one launch, the norm pool on the block-scaled instruction from the squares quantised to act_fmt and
+        gamma' re-quantised onto the MX grid), mode 'emulated' the fp32 GDN kernel on the decoded operands.  gdn=False (the default)
+        leaves every GDN under 'left' as before.
+        ValueError before anything is written for an unknown act_fmt or mode, an unknown unit, a gdn that is no bool, a chain that is no bool or is True in
         another mode than 'native', and (act_fmt not None) a named unit without an eligible module.  An input that requires grad raises NotImplementedError in a switched module; `reconstruct`
         refuses a model that holds one."""
         from collections import OrderedDict
@@ -197,6 +201,8 @@ class QuantModel(nn.Module):
             raise ValueError(f"{what}: mode must be one of {list(mx.MX_ACT_MODES)}, got {mode!r}")
         if not isinstance(chain, bool) or (chain and mode != "native"):
             raise ValueError(f"{what}: chain must be True or False, and True in mode 'native' only; got chain={chain!r}, mode={mode!r}")
+        if not isinstance(gdn, bool):
+            raise ValueError(f"{what}: gdn must be True or False, got {gdn!r}")
         if units is None:
             chosen = list(known)
         else:
@@ -222,6 +228,9 @@ class QuantModel(nn.Module):
                 if not isinstance(m, QuantModule) or m.org_weight is None:
                     continue
                 kind, why = mx.native_kind(m)
+                if gdn and m.kind == "gdn":
+                    why = mx.native_gdn_refusal(m)
+                    kind = "gdn" if why is None else None
                 plan.append((m, kind))
                 if kind is None:
                     rep["left"][name] = why
