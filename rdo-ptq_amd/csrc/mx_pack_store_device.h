@@ -70,24 +70,24 @@ __device__ __forceinline__ unsigned squeeze6(unsigned w) {
     return (w & 0x3Fu) | ((w >> 2) & 0xFC0u) | ((w >> 4) & 0x3F000u) | ((w >> 6) & 0xFC0000u);
 }
 
-template <class RowOf>
-__device__ __forceinline__ void mx_pack_store(const f32x4 (&acc)[2][2], const float* __restrict__ bias, const MxPackedOut& o, long n0, int N,
-                                              RowOf row_of) {
+// Steps 2 .. 4 on the wave's 32 x 32 values v (the register layout above): lane L ends with the bits / 2 dwords d[] of half h = L & 1 of
+// tile row t = L >> 1 and the row's scale byte, and hands them to put(t, h, d, scale) -- step 5, or an LDS operand tile (mx_swin.hip).
+template <class Put>
+__device__ __forceinline__ void mx_pack_tile(const f32x4 (&v)[2][2], const MxFormat& f, Put put) {
     __shared__ uint32_t tiles[4][32 * kPackRowDwords];                         // one tile a wave, 4608 bytes a workgroup
     const int lane = threadIdx.x & 63, r = lane & 15, kg = lane >> 4;
     uint32_t* tile = tiles[threadIdx.x >> 6];
     uint8_t* bytes = reinterpret_cast<uint8_t*>(tile);
-    const MxFormat f = o.f;
-    float bj[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) bj[j] = bias ? bias[n0 + 16 * j + r] : 0.f;     // n0 + 31 < N: N % 32 == 0
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             unsigned pat[2];
 #pragma unroll
-            for (int j = 0; j < 2; ++j) pat[j] = __builtin_bit_cast(unsigned, mx_act(acc[i][j][q] + bj[j], o.act));
+            for (int j = 0; j < 2; ++j) {
+                const float e = v[i][j][q];                                     // a copy: bit_cast of a vector element takes the vector's address
+                pat[j] = __builtin_bit_cast(unsigned, e);
+            }
             const unsigned m0 = pat[0] & 0x7FFFFFFFu, m1 = pat[1] & 0x7FFFFFFFu;
             const unsigned amax = row16_max(m0 > m1 ? m0 : m1);
             const bool finite = amax < 0x7F800000u;
@@ -108,23 +108,47 @@ __device__ __forceinline__ void mx_pack_store(const f32x4 (&acc)[2][2], const fl
 #pragma unroll
     for (int d = 0; d < 4; ++d) c[d] = src[4 * h + d];
     const unsigned scale = src[8] & 0xFFu;
-    const long row = row_of(t);
-    if (row < 0) return;
-    const long blk = row * (N / kBlock) + n0 / kBlock;
-    uint32_t* dst = o.packed + blk * f.bits + h * (f.bits >> 1);
+    unsigned d[4] = {c[0], c[1], c[2], c[3]};
     if (f.bits == 4) {
-        dst[0] = squeeze4(c[0]) | (squeeze4(c[1]) << 16);
-        dst[1] = squeeze4(c[2]) | (squeeze4(c[3]) << 16);
+        d[0] = squeeze4(c[0]) | (squeeze4(c[1]) << 16);
+        d[1] = squeeze4(c[2]) | (squeeze4(c[3]) << 16);
     } else if (f.bits == 6) {
         const unsigned p0 = squeeze6(c[0]), p1 = squeeze6(c[1]), p2 = squeeze6(c[2]), p3 = squeeze6(c[3]);
-        dst[0] = p0 | (p1 << 24);
-        dst[1] = (p1 >> 8) | (p2 << 16);
-        dst[2] = (p2 >> 16) | (p3 << 8);
-    } else {
-#pragma unroll
-        for (int d = 0; d < 4; ++d) dst[d] = c[d];
+        d[0] = p0 | (p1 << 24);
+        d[1] = (p1 >> 8) | (p2 << 16);
+        d[2] = (p2 >> 16) | (p3 << 8);
     }
-    if (h == 0) o.scales[blk] = (uint8_t)scale;
+    put(t, h, d, scale);
+}
+
+// the lane's bits / 2 dwords of mx_pack_tile to dst[0 ..]
+__device__ __forceinline__ void mx_put_dwords(uint32_t* dst, const unsigned (&d)[4], int bits) {
+    dst[0] = d[0];
+    dst[1] = d[1];
+    if (bits >= 6) dst[2] = d[2];
+    if (bits == 8) dst[3] = d[3];
+}
+
+template <class RowOf>
+__device__ __forceinline__ void mx_pack_store(const f32x4 (&acc)[2][2], const float* __restrict__ bias, const MxPackedOut& o, long n0, int N,
+                                              RowOf row_of) {
+    const int r = threadIdx.x & 15;
+    f32x4 v[2][2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const float bj = bias ? bias[n0 + 16 * j + r] : 0.f;                    // n0 + 31 < N: N % 32 == 0
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[i][j][q] = mx_act(acc[i][j][q] + bj, o.act);
+    }
+    mx_pack_tile(v, o.f, [&](int t, int h, const unsigned (&d)[4], unsigned scale) {
+        const long row = row_of(t);
+        if (row < 0) return;
+        const long blk = row * (N / kBlock) + n0 / kBlock;
+        mx_put_dwords(o.packed + blk * o.f.bits + h * (o.f.bits >> 1), d, o.f.bits);
+        if (h == 0) o.scales[blk] = (uint8_t)scale;
+    });
 }
 
 // The row-major form of the same quantiser, for a kernel whose lanes hold four consecutive channels of a row (mx_gdn.hip: the x o x

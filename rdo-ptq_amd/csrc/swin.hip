@@ -580,12 +580,7 @@ __global__ __launch_bounds__(256) void layer_norm_bwd_kernel(const float* x, con
 // Layout: 16 lanes per row, VPL float4 per lane (C / 4 <= 16 * VPL), four rows per wave: every load instruction of a 16-lane group is
 // 256 contiguous bytes; the two row statistics are four-step butterflies inside the group.  Same arithmetic as the scalar kernels
 // (two-pass mean / variance).
-typedef float ln4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float ln_sum4(ln4 v) { return (v.x + v.y) + (v.z + v.w); }
-__device__ __forceinline__ float ln_red16(float v) {
-    v += __shfl_xor(v, 8, 16); v += __shfl_xor(v, 4, 16); v += __shfl_xor(v, 2, 16); v += __shfl_xor(v, 1, 16);
-    return v;
-}
+#include "ln_row_device.h"
 
 template <int VPL>
 __global__ __launch_bounds__(256) void add_ln_kernel(const ln4* __restrict__ a, const ln4* __restrict__ b, const ln4* __restrict__ w,
@@ -594,43 +589,11 @@ __global__ __launch_bounds__(256) void add_ln_kernel(const ln4* __restrict__ a, 
     const int l16 = threadIdx.x & 15, grp = threadIdx.x >> 4;
     const float invC = 1.f / (float)(4 * C4);
     ln4 wv[VPL], bv[VPL];
-#pragma unroll
-    for (int k = 0; k < VPL; ++k) {
-        const int c = l16 + 16 * k;
-        wv[k] = (w && c < C4) ? w[c] : ln4{1.f, 1.f, 1.f, 1.f};
-        bv[k] = (bias && c < C4) ? bias[c] : ln4{0.f, 0.f, 0.f, 0.f};
-    }
+    ln_row_params<VPL>(w, bias, C4, l16, wv, bv);
     for (long row = (long)blockIdx.x * 16 + grp; row < rows; row += (long)gridDim.x * 16) {
         const long base = row * C4;
-        ln4 v[VPL];
-        float s1 = 0.f;
-#pragma unroll
-        for (int k = 0; k < VPL; ++k) {
-            const int c = l16 + 16 * k;
-            if (c < C4) {
-                v[k] = a[base + c];
-                if (b) v[k] += b[base + c];
-                if (s_out) s_out[base + c] = v[k];
-                s1 += ln_sum4(v[k]);
-            } else {
-                v[k] = ln4{0.f, 0.f, 0.f, 0.f};
-            }
-        }
-        const float mean = ln_red16(s1) * invC;
-        float s2 = 0.f;
-#pragma unroll
-        for (int k = 0; k < VPL; ++k) {
-            if (l16 + 16 * k < C4) {
-                v[k] -= mean;
-                s2 += ln_sum4(v[k] * v[k]);
-            }
-        }
-        const float rstd = rsqrtf(ln_red16(s2) * invC + eps);
-#pragma unroll
-        for (int k = 0; k < VPL; ++k) {
-            const int c = l16 + 16 * k;
-            if (c < C4) y_out[base + c] = v[k] * rstd * wv[k] + bv[k];
-        }
+        ln_row<VPL>(a, b, base, C4, l16, invC, eps, s_out, [&](int k, ln4& wk, ln4& bk) { wk = wv[k]; bk = bv[k]; },
+                    [&](int k, ln4 y) { y_out[base + l16 + 16 * k] = y; });
     }
 }
 

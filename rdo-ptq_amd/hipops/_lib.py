@@ -295,6 +295,13 @@ _SIGS_MXGDN = {
 }
 EXPORTS_MXGDN = tuple(_SIGS_MXGDN)
 MXGDN_MAX_C = 512         # RDO_MXGDN_MAX_C of include/rdo_ptq_mxgdn.h
+# include/rdo_ptq_mxswin.h: the LayerNorm producer and the MLP half of a Swin block on the block-scaled matrix instruction, one launch each
+_SIGS_MXSWIN = {
+    "rdo_mx_layer_norm_pack": (C.c_int, [P, P, P, P, C.c_int32, C.c_int32, C.c_float, C.c_int32, P, P, P, P, P]),
+    "rdo_mx_swin_mlp": (C.c_int, [P, P, P, P, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P, P, P, P, P, P, C.c_int32, P, P, P, P, P, P]),
+}
+EXPORTS_MXSWIN = tuple(_SIGS_MXSWIN)
+MXSWIN_MAX_C, MXSWIN_MAX_HIDDEN = 512, 1024         # RDO_MXSWIN_MAX_C / RDO_MXSWIN_MAX_HIDDEN of include/rdo_ptq_mxswin.h
 # tuning hooks the library exports beside its headers (csrc/conv_wgrad.hip): tile choice (-1 = the library's, 0 = 64 x 64, 1 = 192 x 192)
 # and slab count (-1 = the library's) of rdo_conv2d_wgrad, process-wide; ops.forced_wgrad sets and restores them
 _SIGS_DEBUG = {
@@ -320,7 +327,7 @@ def lib():
                                   + list(_SIGS_PACK.items()) + list(_SIGS_SUBPEL.items()) + list(_SIGS_ACTBITS.items())
                                   + list(_SIGS_ATTNQ.items()) + list(_SIGS_MX.items()) + list(_SIGS_MXROUND.items())
                                   + list(_SIGS_MXGEMM.items()) + list(_SIGS_MXCONV.items()) + list(_SIGS_MXTCONV.items())
-                                  + list(_SIGS_MXFILE.items()) + list(_SIGS_MXCHAIN.items()) + list(_SIGS_MXGDN.items())
+                                  + list(_SIGS_MXFILE.items()) + list(_SIGS_MXCHAIN.items()) + list(_SIGS_MXGDN.items()) + list(_SIGS_MXSWIN.items())
                                   + list(_SIGS_DEBUG.items())):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args

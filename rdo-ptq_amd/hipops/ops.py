@@ -1146,6 +1146,84 @@ def mx_gdn(x2d, g, beta, fmt, inverse=False, out_fmt=None, want_norm=False):
     return (y, norm) if want_norm else y
 
 
+MX_SWIN_OUTPUTS = ("ln", "pre", "hidden")      # what `mx_swin_mlp` can be asked for beside `out`
+
+
+def _mx_ln_operands(what, a, b, weight, bias, max_c):
+    """(rows, C, device) of the fp32 [rows, C] input of the MX LayerNorm kernels, its optional addend and LayerNorm parameters"""
+    A.tensor(what, "a", a, rank=2, layout="of rank 2 [rows, C]", contiguous=True)
+    rows, Cc, dev = int(a.shape[0]), int(a.shape[1]), a.device
+    _mx_k(what, rows, Cc)
+    if Cc > max_c:
+        raise ValueError(f"{what}: C = {Cc} is above {max_c}, the most the kernel serves")
+    A.tensor(what, "b", b, shape=(rows, Cc), contiguous=True, device=dev, optional=True, oneshot=True)
+    A.tensor(what, "weight", weight, shape=(Cc,), contiguous=True, device=dev, optional=True, oneshot=True)
+    A.tensor(what, "bias", bias, shape=(Cc,), contiguous=True, device=dev, optional=True, oneshot=True)
+    return rows, Cc, dev
+
+
+def mx_layer_norm_pack(a, b, weight, bias, fmt, eps=1e-5, want_sum=False, want_ln=False):
+    """LayerNorm over the last dimension of a (+ b), quantised to the MX format `fmt` and packed, one launch (rdo_mx_layer_norm_pack;
+    include/rdo_ptq_mxswin.h): a contiguous fp32 [rows, C], b like a or None, weight / bias contiguous fp32 [C] or None; C % 32 == 0 and C
+    <= `MXSWIN_MAX_C` -> `MXOperand` [rows, C], bit for bit `mx_quant_pack(add_layer_norm(a, b, weight, bias, eps), fmt)`.  want_sum (needs
+    b): also a + b as `add` writes it; want_ln: also the fp32 LayerNorm; -> (operand, [sum], [ln]).  Checked on the host before a pointer
+    is taken."""
+    what = "mx_layer_norm_pack"
+    rows, Cc, dev = _mx_ln_operands(what, a, b, weight, bias, L.MXSWIN_MAX_C)
+    fid, bits = mx_format(what, fmt)
+    if want_sum and b is None:
+        raise ValueError(f"{what}: want_sum without a second addend b")
+    _mx_cuda(what, a, "a")
+    packed, scales = _mx_packed_empty(rows, Cc, bits, dev)
+    s = torch.empty_like(a) if want_sum else None
+    ln = torch.empty_like(a) if want_ln else None
+    L.check(L.lib().rdo_mx_layer_norm_pack(_ptr(a), _ptr(b), _ptr(weight), _ptr(bias), rows, Cc, float(eps), fid, _ptr(packed, *_U8),
+                                           _ptr(scales, *_U8), _ptr(s), _ptr(ln), _stream()), "rdo_mx_layer_norm_pack")
+    op = MXOperand(packed, scales, fmt, rows, Cc)
+    extras = [t for t in (s, ln) if t is not None]
+    return (op, *extras) if extras else op
+
+
+def mx_swin_mlp(a, b, ln_weight, ln_bias, w1, b1, w2, b2, act_fmt, eps=1e-5, want=()):
+    """The MLP half of a Swin block on the block-scaled matrix instruction, one launch (rdo_mx_swin_mlp; include/rdo_ptq_mxswin.h): out =
+    s + fc2(gelu(fc1(LN(s)))) with s = a (+ b); a contiguous fp32 [rows, C], b like a or None, ln_weight / ln_bias fp32 [C] or None, w1
+    an `MXOperand` [Hd, C] and w2 an `MXOperand` [C, Hd] of one format, b1 fp32 [Hd] / b2 fp32 [C] or None, act_fmt the MX format of both
+    activations; C, Hd % 32 == 0, C <= `MXSWIN_MAX_C`, Hd <= `MXSWIN_MAX_HIDDEN`.  Bit for bit `add(s, mx_gemm(mx_quant_pack(gelu(mx_gemm(
+    mx_quant_pack(add_layer_norm(a, b, ln_weight, ln_bias, eps), act_fmt), w1, b1)), act_fmt), w2, b2))`.  want: distinct names out of
+    `MX_SWIN_OUTPUTS` -> (out, *wanted): 'ln' fp32 [rows, C], 'pre' fp32 [rows, Hd] (fc1's output), 'hidden' the packed `MXOperand`
+    [rows, Hd] of gelu(pre).  Checked on the host before a pointer is taken."""
+    what = "mx_swin_mlp"
+    rows, Cc, dev = _mx_ln_operands(what, a, b, ln_weight, ln_bias, L.MXSWIN_MAX_C)
+    fa, abits = mx_format(what, act_fmt)
+    fw, _, _ = _mx_operand(what, "w1", w1, device=dev)
+    fw2, _, _ = _mx_operand(what, "w2", w2, device=dev)
+    Hd = w1.rows
+    if w1.K != Cc or (w2.rows, w2.K) != (Cc, Hd):
+        raise ValueError(f"{what}: w1 is [{w1.rows}, {w1.K}] and w2 [{w2.rows}, {w2.K}]; a's {Cc} channels need [Hd, {Cc}] and [{Cc}, Hd]")
+    if Hd > L.MXSWIN_MAX_HIDDEN:
+        raise ValueError(f"{what}: Hd = {Hd} is above {L.MXSWIN_MAX_HIDDEN}, the most the kernel's LDS serves")
+    if fw != fw2:
+        raise ValueError(f"{what}: w1 is in {w1.fmt} and w2 in {w2.fmt}; the kernel takes one weight format")
+    A.tensor(what, "b1", b1, shape=(Hd,), contiguous=True, device=dev, optional=True, oneshot=True)
+    A.tensor(what, "b2", b2, shape=(Cc,), contiguous=True, device=dev, optional=True, oneshot=True)
+    if isinstance(want, (str, bytes)) or not hasattr(want, "__iter__"):
+        raise ValueError(f"{what}: want must be a sequence of names out of {list(MX_SWIN_OUTPUTS)}, got {want!r}")
+    want = list(want)
+    if any(n not in MX_SWIN_OUTPUTS for n in want) or len(set(want)) != len(want):
+        raise ValueError(f"{what}: want must hold only distinct names out of {list(MX_SWIN_OUTPUTS)}, got {want!r}")
+    _mx_cuda(what, a, "a")
+    out = torch.empty_like(a)
+    got = {"ln": torch.empty_like(a) if "ln" in want else None,
+           "pre": torch.empty(rows, Hd, device=dev, dtype=torch.float32) if "pre" in want else None}
+    hp, hs = _mx_packed_empty(rows, Hd, abits, dev) if "hidden" in want else (None, None)
+    L.check(L.lib().rdo_mx_swin_mlp(_ptr(a), _ptr(b), _ptr(ln_weight), _ptr(ln_bias), float(eps), rows, Cc, Hd, fa, _ptr(w1.packed, *_U8),
+                                    _ptr(w1.scales, *_U8), _ptr(b1), _ptr(w2.packed, *_U8), _ptr(w2.scales, *_U8), _ptr(b2), fw, _ptr(out),
+                                    _ptr(got["ln"]), _ptr(got["pre"]), _ptr(hp, *_U8), _ptr(hs, *_U8), _stream()), "rdo_mx_swin_mlp")
+    if hp is not None:
+        got["hidden"] = MXOperand(hp, hs, act_fmt, rows, Hd)
+    return (out, *[got[n] for n in want]) if want else out
+
+
 def pack_row_words(inner, bits):
     """W = ceil(inner * bits / 32): the 32-bit words one row of `inner` codes of `bits` bits occupies (rdo_pack_row_words on the host)"""
     return -(-int(inner) * int(bits) // 32)

@@ -27,8 +27,10 @@ module's fp32 kernel on the decoded `xq` of the same producer; the module's tail
 follows un-fused.  GDN / IGDN (include/rdo_ptq_mxgdn.h): `native_gdn(module, x, act_fmt)` squares, quantises, runs the norm pool on the
 instruction and forms x * norm^-+1/2 in one launch, with gamma' re-quantised onto the MX grid (`native_gdn_operand`: a second
 rounding); `set_mx_activations(..., gdn=True)` switches eligible GDNs to it, `native_gdn_chain` hands its packed output to a following
-conv.  Not built: LayerNorm on the native path, calibration or a backward under MX activations (`reconstruct`
-refuses such a model), data-parallel runs; no rate-distortion claim is made for any of it.  A model on these quantisers is stored by
+conv.  Swin blocks (include/rdo_ptq_mxswin.h): `native_ln_linear(norm, linear, x, act_fmt)` runs norm1 -> qkv in two launches,
+`native_swin_mlp(block, x, a, act_fmt)` the half x + a + fc2(gelu(fc1(norm2(x + a)))) in one; `set_mx_activations(..., swin=True)` switches
+the blocks `native_swin_refusal` accepts (`mx_swin`, not stored by `save_mx_packed`).  Not built: calibration or a backward under MX
+activations (`reconstruct` refuses such a model), data-parallel runs; no rate-distortion claim is made for any of it.  A model on these quantisers is stored by
 `mx_packed.save_mx_packed`, the `mx_activations` pairs included.
 
 Chains (include/rdo_ptq_mxchain.h): `native_chain(first, second, x, act_fmt, act)` runs two convs of the kinds above in three launches
@@ -556,6 +558,85 @@ def native_gdn_chain(gdn, second, x, act_fmt):
         raise ValueError(f"native_gdn_chain: modules {_describe(gdn)} -> {_describe(second)}: {why}")
     _, shape = _gdn_rows("native_gdn_chain", gdn, x)
     return _chain_step(second, native_gdn(gdn, x, act_fmt, out_fmt=act_fmt), shape)[0].permute(0, 3, 1, 2)
+
+
+# ---- Swin blocks: LayerNorm producer and the MLP half (include/rdo_ptq_mxswin.h) ---------------------------------------------------------------
+def _act_quant_on(m):
+    """whether the output quantiser of a QuantModule, or the `_aq` of a block, rounds in the present state"""
+    return not getattr(m, "disable_act_quant", False) and m.use_act_quant and m.trained
+
+
+def swin_quantisers_idle(block):
+    """no activation quantiser rounds between the launches `native_ln_linear` and `native_swin_mlp` fuse"""
+    return not any(_act_quant_on(m) for m in (block.norm1, block.norm2, block.mlp.fc2, block.mlp))
+
+
+def native_swin_refusal(block):
+    """None for a `QuantSwinTransformerBlock` whose forward `native_ln_linear` and `native_swin_mlp` serve, else the reason it keeps its
+    forward, looked for in this order: a LayerNorm not over the last dimension only; C or the hidden width no multiple of 32 or above
+    `hipops._lib.MXSWIN_MAX_C` / `MXSWIN_MAX_HIDDEN`; qkv, fc1 or fc2 not native-eligible (`native_refusal`), or fc1 and fc2 in different
+    weight formats; an activation that is not the exact-erf `nn.GELU`; an `se_module` or an activation function on one of the five
+    modules; an active activation quantiser on norm1, norm2, fc2 or the MLP's `_aq`."""
+    from .quantizer import StraightThrough
+    fc1, fc2, qkv = block.mlp.fc1, block.mlp.fc2, block.attn.qkv
+    Hd, C = (int(v) for v in fc1.weight.shape)
+    for name, n in (("norm1", block.norm1), ("norm2", block.norm2)):
+        ns = tuple(n.fwd_kwargs["normalized_shape"])
+        if n.kind != "layernorm" or ns != (C,):
+            return f"{name} normalises over {ns}, not over the last dimension of {C} channels alone"
+    if C % L.MX_BLOCK or Hd % L.MX_BLOCK:
+        return f"its {C} channels or its hidden width {Hd} are no multiple of the MX block size {L.MX_BLOCK}"
+    if C > L.MXSWIN_MAX_C or Hd > L.MXSWIN_MAX_HIDDEN:
+        return f"its {C} channels are above {L.MXSWIN_MAX_C} or its hidden width {Hd} above {L.MXSWIN_MAX_HIDDEN}, the most the kernel's LDS serves"
+    for name, m in (("attn.qkv", qkv), ("mlp.fc1", fc1), ("mlp.fc2", fc2)):
+        why = native_refusal(m)
+        if why is not None:
+            return f"{name}: {why}"
+    if fc1.weight_quantizer.fmt != fc2.weight_quantizer.fmt:
+        return f"fc1's weights are in {fc1.weight_quantizer.fmt} and fc2's in {fc2.weight_quantizer.fmt}: the kernel takes one weight format"
+    act = block.mlp.act
+    if not isinstance(act, nn.GELU) or getattr(act, "approximate", "none") != "none":
+        return f"the MLP's activation is {act!r}, not the exact-erf nn.GELU"
+    for name, m in (("norm1", block.norm1), ("norm2", block.norm2), ("attn.qkv", qkv), ("mlp.fc1", fc1), ("mlp.fc2", fc2)):
+        if m.se_module is not None or not isinstance(m.activation_function, (StraightThrough, nn.Identity)):
+            return f"{name} has an se_module or an activation function of its own"
+    if not swin_quantisers_idle(block):
+        return "an activation quantiser is active on norm1, norm2, fc2 or between GELU and fc2"
+    return None
+
+
+def _ln_params(norm):
+    """(weight, bias, eps) of a LayerNorm QuantModule in its present quant state, as the module's forward takes them"""
+    w, b = norm._weights()
+    return (None if w is None else w.detach().contiguous(), None if b is None else b.detach().contiguous(),
+            float(norm.fwd_kwargs.get("eps", 1e-5)))
+
+
+def native_ln_linear(norm, linear, x, act_fmt):
+    """The pre-activation output of the eligible Linear `linear` on LayerNorm(x) of the QuantModule `norm` in two launches:
+    `ops.mx_layer_norm_pack` writes the LayerNorm packed in `act_fmt`, `ops.mx_gemm` reads it.  Bit for bit `native_linear(linear,
+    ops.add_layer_norm(x, None, weight, bias), act_fmt)`: no fp32 LayerNorm reaches memory.  Neither module's tail is applied."""
+    w = native_operand(linear)
+    rows, shape = native_rows(linear, x)
+    lw, lb, eps = _ln_params(norm)
+    return shape(ops.mx_gemm(ops.mx_layer_norm_pack(rows, None, lw, lb, act_fmt, eps=eps), w, native_bias(linear)))
+
+
+def native_swin_mlp(block, x, a, act_fmt):
+    """The second half of a `QuantSwinTransformerBlock` `native_swin_refusal` accepts, before the block's `_aq`, in one
+    `ops.mx_swin_mlp` launch: x [B, L, C] is the block's input, a the attention branch; -> t + fc2(gelu(fc1(norm2(t)))) with t = x + a,
+    both activations quantised to `act_fmt`, the weights the memoised `native_operand`s of fc1 and fc2."""
+    why = native_swin_refusal(block)
+    if why is not None:
+        raise ValueError(f"native_swin_mlp: {why}")
+    fc1, fc2 = block.mlp.fc1, block.mlp.fc2
+    C = int(fc1.weight.shape[1])
+    if x.shape[-1] != C or a.shape != x.shape:
+        raise ValueError(f"native_swin_mlp: x must be [..., {C}] and a like x, got {tuple(x.shape)} and {tuple(a.shape)}")
+    lw, lb, eps = _ln_params(block.norm2)
+    out = ops.mx_swin_mlp(x.reshape(-1, C).contiguous(), a.reshape(-1, C).contiguous(), lw, lb, native_operand(fc1), native_bias(fc1),
+                          native_operand(fc2), native_bias(fc2), act_fmt, eps=eps)
+    return out.reshape(x.shape)
 
 
 # ---- MX activations inside the modules' own forward (QuantModel.set_mx_activations) ------------------------------------------------------------

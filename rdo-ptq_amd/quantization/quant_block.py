@@ -204,10 +204,11 @@ class QuantWindowAttention(BaseQuantBlock):
         t = self.relative_position_bias_table.detach()[self.relative_position_index.view(-1)]
         return t.view(n, n, -1).permute(2, 0, 1).contiguous()
 
-    def attend(self, tokens, B, H, W, window, shift):
-        """tokens [B, H*W, C] in natural order -> same shape: qkv linear, attention core, projection."""
-        C = tokens.shape[-1]
-        qkv = self.qkv(tokens).contiguous()
+    def attend(self, tokens, B, H, W, window, shift, qkv=None):
+        """tokens [B, H*W, C] in natural order -> same shape: qkv linear, attention core, projection.  `qkv`: the qkv linear's output
+        [B, H*W, 3C] where the caller has computed it (`mx.native_ln_linear`); `tokens` is then not read."""
+        C = self.dim
+        qkv = (self.qkv(tokens) if qkv is None else qkv).contiguous()
         d = ops.attn_desc(B, H, W, C, self.num_heads, window, shift, self.scale)
         bias = self.position_bias()
         if self.use_act_quant and self.trained:
@@ -271,10 +272,33 @@ class QuantSwinTransformerBlock(BaseQuantBlock):
         self.mlp = QuantMlp(basic_block.mlp, weight_quant_params, act_quant_params)
         self.attn_mask = basic_block.attn_mask
 
+    def _mx_swin_format(self):
+        """the activation format where `mx_swin` is set (`QuantModel.set_mx_activations(..., swin=True)`), qkv, fc1 and fc2 carry the
+        same (act_fmt, 'native') with their quantised weights and no activation quantiser rounds inside the fused launches; else None"""
+        if not getattr(self, "mx_swin", False):
+            return None
+        from . import mx
+        lin = (self.attn.qkv, self.mlp.fc1, self.mlp.fc2)
+        on = getattr(lin[0], "mx_activations", None)
+        if (on is None or on[1] != "native" or any(getattr(m, "mx_activations", None) != on or not m.use_weight_quant for m in lin)
+                or not mx.swin_quantisers_idle(self)):
+            return None
+        return on[0]
+
     def forward(self, x, x_size):
         H, W = int(x_size[0]), int(x_size[1])
         B, L, C = x.shape
         x = x.contiguous()
+        fmt = self._mx_swin_format()
+        if fmt is not None:
+            # norm1 -> qkv in two launches, the half behind the attention in one (mx.native_ln_linear, mx.native_swin_mlp): the bits of
+            # the module-by-module forward with `ops.add_layer_norm` as the LayerNorm
+            from . import mx
+            if _tracked(x):
+                self.attn.qkv._refuse_mx_grad()
+            qkv = self.attn.qkv._mx_tail(mx.native_ln_linear(self.norm1, self.attn.qkv, x, fmt))
+            a = self.attn.attend(None, B, H, W, self.window_size, self.shift_size, qkv=qkv)
+            return self._aq(mx.native_swin_mlp(self, x, a.contiguous(), fmt))
         a = self.attn.attend(self.norm1(x), B, H, W, self.window_size, self.shift_size)
         if _tracked(x, a):                             # torch's tape is driving (the R + lambda*D tail of the calibration loop): its own adds
             x = x + a

@@ -5,7 +5,7 @@ import torch.nn as nn
 from lic import EntropyBottleneck
 
 from .fold_bn import search_fold_and_remove_bn
-from .quant_block import BaseQuantBlock, QuantRB, QuantRBWS, specials
+from .quant_block import BaseQuantBlock, QuantRB, QuantRBWS, QuantSwinTransformerBlock, specials
 from .quant_layer import GDN_TYPES, QuantModule, StraightThrough
 from .widths import act_applied, act_modules, format_plan, is_trained, weighted_modules, width_plan
 
@@ -167,7 +167,7 @@ class QuantModel(nn.Module):
         from .reports import mx_native_report
         return mx_native_report(self, images, act_fmt=act_fmt, batch=batch, units=units, convs=convs, tconvs=tconvs)
 
-    def set_mx_activations(self, act_fmt, mode="native", units=None, chain=False, gdn=False):
+    def set_mx_activations(self, act_fmt, mode="native", units=None, chain=False, gdn=False, swin=False):
         """Run the modules' own forward on MX activations: every weighted QuantModule of the chosen units (`units`: a list of names of
         `units()`, None for all) that `mx.native_refusal`, `native_conv_refusal` or `native_tconv_refusal` accepts gets the plain
         attribute `mx_activations = (act_fmt, mode)`.  Its no-grad forward, while `use_weight_quant` is on, then takes the
@@ -188,8 +188,14 @@ class QuantModel(nn.Module):
         runs `mx.native_gdn` (one launch, the norm pool on the block-scaled instruction from the squares quantised to act_fmt and
         gamma' re-quantised onto the MX grid), mode 'emulated' the fp32 GDN kernel on the decoded operands.  gdn=False (the default)
         leaves every GDN under 'left' as before.
-        ValueError before anything is written for an unknown act_fmt or mode, an unknown unit, a gdn that is no bool, a chain that is no bool or is True in
-        another mode than 'native', and (act_fmt not None) a named unit without an eligible module.  An input that requires grad raises NotImplementedError in a switched module; `reconstruct`
+        swin=True (mode 'native' only) also sets the plain attribute `mx_swin` on every `QuantSwinTransformerBlock` of the chosen units that
+        `mx.native_swin_refusal` accepts: its no-grad forward then runs norm1 -> qkv as `mx.native_ln_linear` (two launches instead of
+        three) and everything behind the attention as one `mx.native_swin_mlp` launch instead of eight, while qkv, fc1 and fc2 carry this
+        (act_fmt, 'native'), `use_weight_quant` is on and no activation quantiser rounds in between.  The result gains 'swin': block
+        name -> (norm2, fc1, fc2 names); the block's norm1 / norm2 are reported under 'native' as 'layernorm', a refused block under
+        'left' with the reason.  swin=False and act_fmt=None clear `mx_swin`; it is not stored by `save_mx_packed`.
+        ValueError before anything is written for an unknown act_fmt or mode, an unknown unit, a gdn that is no bool, a chain or swin that
+        is no bool or is True in another mode than 'native', and (act_fmt not None) a named unit without an eligible module.  An input that requires grad raises NotImplementedError in a switched module; `reconstruct`
         refuses a model that holds one."""
         from collections import OrderedDict
         from . import mx
@@ -203,6 +209,8 @@ class QuantModel(nn.Module):
             raise ValueError(f"{what}: chain must be True or False, and True in mode 'native' only; got chain={chain!r}, mode={mode!r}")
         if not isinstance(gdn, bool):
             raise ValueError(f"{what}: gdn must be True or False, got {gdn!r}")
+        if not isinstance(swin, bool) or (swin and mode != "native"):
+            raise ValueError(f"{what}: swin must be True or False, and True in mode 'native' only; got swin={swin!r}, mode={mode!r}")
         if units is None:
             chosen = list(known)
         else:
@@ -215,7 +223,9 @@ class QuantModel(nn.Module):
         rep = OrderedDict(native=OrderedDict(), left=OrderedDict())
         if chain:
             rep["chained"] = OrderedDict()
-        plan, blocks = [], []
+        if swin:
+            rep["swin"] = OrderedDict()
+        plan, blocks, swin_blocks, swin_norms = [], [], [], set()
         for uname in chosen:
             found = False
             for mn, m in known[uname].named_modules():
@@ -225,7 +235,19 @@ class QuantModel(nn.Module):
                     blocks.append((m, on))
                     if on:
                         rep["chained"][name] = (f"{name}.conv1", f"{name}.conv2")
+                if isinstance(m, QuantSwinTransformerBlock):
+                    why = mx.native_swin_refusal(m) if (swin and act_fmt is not None) else "not asked for"
+                    swin_blocks.append((m, why is None))
+                    if why is None:
+                        rep["swin"][name] = (f"{name}.norm2", f"{name}.mlp.fc1", f"{name}.mlp.fc2")
+                        swin_norms.update((f"{name}.norm1", f"{name}.norm2"))
+                    elif swin and act_fmt is not None:
+                        rep["left"][name] = why
                 if not isinstance(m, QuantModule) or m.org_weight is None:
+                    continue
+                if name in swin_norms:                  # the LayerNorms of an accepted block run inside its fused launches
+                    rep["native"][name] = "layernorm"
+                    plan.append((m, None))
                     continue
                 kind, why = mx.native_kind(m)
                 if gdn and m.kind == "gdn":
@@ -243,6 +265,8 @@ class QuantModel(nn.Module):
             m.mx_activations = None if (act_fmt is None or kind is None) else (act_fmt, mode)
         for b, on in blocks:
             b.mx_chain = on
+        for b, on in swin_blocks:
+            b.mx_swin = on
         return rep
 
     def set_weight_format(self, formats, rounding="nearest"):
