@@ -1,5 +1,6 @@
-// What the window attention kernels of swin.hip and attn_tape.hip share: the geometry of a launch and its host-side check, the token ->
-// pixel map (the header comment of swin.hip states the token order) and the 32 x 32 fp32 MFMA tile product on LDS images.
+// What the window attention kernels of swin.hip, attn_tape.hip and mx_attn.hip share: the geometry of a launch and its host-side check, the
+// token -> pixel and token -> mask-region maps (the header comment of swin.hip states the token order), the work-item order of a
+// persistent grid and the 32 x 32 fp32 MFMA tile product on LDS images.
 #pragma once
 #include "rdo_common.h"
 
@@ -30,6 +31,34 @@ __device__ __forceinline__ int token_pixel(const AttnGeom& g, int win, int tok) 
     if (h >= g.H) h -= g.H;
     if (w >= g.W) w -= g.W;
     return (b * g.H + h) * g.W + w;
+}
+
+// region id of a token in the SHIFTED image (layers.py:239-250): 3 bands per axis
+__device__ __forceinline__ int token_region(const AttnGeom& g, int win, int tok) {
+    const int nww = g.W / g.ws, nwh = g.H / g.ws;
+    const int r = win % (nwh * nww);
+    const int wh = r / nww, ww = r - wh * nww;
+    const int ih = tok / g.ws, iw = tok - ih * g.ws;
+    const int sh = wh * g.ws + ih, sw = ww * g.ws + iw;
+    const int rh = sh < g.H - g.ws ? 0 : (sh < g.H - g.shift ? 1 : 2);
+    const int rw = sw < g.W - g.ws ? 0 : (sw < g.W - g.shift ? 1 : 2);
+    return rh * 3 + rw;
+}
+
+// (window, head) of work item `id` of a persistent attention grid (swin.hip, mx_attn.hip).  Launch ids go round-robin over the 8 XCDs
+// (id % 8), each with its own L2: the heads of one window read interleaved pieces of the same qkv rows (head h of a token is hd floats
+// inside a 3C-float row: neighbouring heads share cache lines), so they are numbered next to each other INSIDE one XCD -- slot = id / 8
+// walks (window of this XCD, head) with the head fastest.  Window counts that are not a multiple of 8 (toy shapes): plain order.
+__device__ __forceinline__ void attn_item(int id, int windows, int heads, int& win, int& head) {
+    if (windows & 7) {
+        win = id / heads;
+        head = id - win * heads;
+        return;
+    }
+    const int xcd = id & 7, slot = id >> 3;
+    const int lw = slot / heads;
+    head = slot - lw * heads;
+    win = xcd * (windows >> 3) + lw;
 }
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));

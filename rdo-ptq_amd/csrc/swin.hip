@@ -12,18 +12,6 @@
 
 namespace {
 
-// region id of a token in the SHIFTED image (layers.py:239-250): 3 bands per axis
-__device__ __forceinline__ int token_region(const AttnGeom& g, int win, int tok) {
-    const int nww = g.W / g.ws, nwh = g.H / g.ws;
-    const int r = win % (nwh * nww);
-    const int wh = r / nww, ww = r - wh * nww;
-    const int ih = tok / g.ws, iw = tok - ih * g.ws;
-    const int sh = wh * g.ws + ih, sw = ww * g.ws + iw;
-    const int rh = sh < g.H - g.ws ? 0 : (sh < g.H - g.shift ? 1 : 2);
-    const int rw = sw < g.W - g.ws ? 0 : (sw < g.W - g.shift ? 1 : 2);
-    return rh * 3 + rw;
-}
-
 // cooperative load of one of q/k/v (or a gradient w.r.t. the output) of this (window, head) into LDS rows of stride hs
 __device__ __forceinline__ void load_tile(const AttnGeom& g, const float* src, int row_stride, int ch0, int win, float* dst, float mul) {
     for (int e = threadIdx.x; e < g.N * g.hd; e += 64) {
@@ -261,22 +249,6 @@ __device__ __forceinline__ void softmax_rows256(const AttnGeom& g, float* S, flo
 #pragma unroll
         for (int k = 0; k < 16; ++k) dP[i * SS + part + 4 * k] = v[k] * (dp[k] - D);
     }
-}
-
-// (window, head) of work item `id`.  Launch ids go round-robin over the 8 XCDs (id % 8), each with its own L2: the heads of one window
-// read interleaved pieces of the same qkv rows (head h of a token is hd floats inside a 3C-float row: neighbouring heads share cache
-// lines), so they are numbered next to each other INSIDE one XCD -- slot = id / 8 walks (window of this XCD, head) with the head
-// fastest.  Window counts that are not a multiple of 8 (toy shapes): plain order.
-__device__ __forceinline__ void attn_item(int id, int windows, int heads, int& win, int& head) {
-    if (windows & 7) {
-        win = id / heads;
-        head = id - win * heads;
-        return;
-    }
-    const int xcd = id & 7, slot = id >> 3;
-    const int lw = slot / heads;
-    head = slot - lw * heads;
-    win = xcd * (windows >> 3) + lw;
 }
 
 // One tile (Q, K, V or dO of a (window, head) pair) travels global -> registers -> LDS in two steps, so that the loads of the NEXT work

@@ -302,6 +302,11 @@ _SIGS_MXSWIN = {
 }
 EXPORTS_MXSWIN = tuple(_SIGS_MXSWIN)
 MXSWIN_MAX_C, MXSWIN_MAX_HIDDEN = 512, 1024         # RDO_MXSWIN_MAX_C / RDO_MXSWIN_MAX_HIDDEN of include/rdo_ptq_mxswin.h
+# include/rdo_ptq_mxattn.h: the window attention core with Q K^T and P V on the block-scaled matrix instruction, one launch
+_SIGS_MXATTN = {
+    "rdo_mx_window_attention": (C.c_int, [C.POINTER(AttnDesc), P, P, C.c_int32, C.c_int32, P, P, P, P]),
+}
+EXPORTS_MXATTN = tuple(_SIGS_MXATTN)
 # tuning hooks the library exports beside its headers (csrc/conv_wgrad.hip): tile choice (-1 = the library's, 0 = 64 x 64, 1 = 192 x 192)
 # and slab count (-1 = the library's) of rdo_conv2d_wgrad, process-wide; ops.forced_wgrad sets and restores them
 _SIGS_DEBUG = {
@@ -328,7 +333,7 @@ def lib():
                                   + list(_SIGS_ATTNQ.items()) + list(_SIGS_MX.items()) + list(_SIGS_MXROUND.items())
                                   + list(_SIGS_MXGEMM.items()) + list(_SIGS_MXCONV.items()) + list(_SIGS_MXTCONV.items())
                                   + list(_SIGS_MXFILE.items()) + list(_SIGS_MXCHAIN.items()) + list(_SIGS_MXGDN.items()) + list(_SIGS_MXSWIN.items())
-                                  + list(_SIGS_DEBUG.items())):
+                                  + list(_SIGS_MXATTN.items()) + list(_SIGS_DEBUG.items())):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         _lib = h

@@ -1224,6 +1224,42 @@ def mx_swin_mlp(a, b, ln_weight, ln_bias, w1, b1, w2, b2, act_fmt, eps=1e-5, wan
     return (out, *[got[n] for n in want]) if want else out
 
 
+MX_ATTN_OUTPUTS = ("scores", "probs")      # what `mx_window_attention` can be asked for beside `out`
+
+
+def mx_window_attention(d, qkv, bias, fmt, p_fmt=None, out=None, want=()):
+    """The (S)W-MSA core with both products on the block-scaled matrix instruction, one launch (rdo_mx_window_attention;
+    include/rdo_ptq_mxattn.h states the arithmetic): d an `attn_desc` whose head dim is a multiple of 4, qkv fp32 [B, H, W, 3C] and bias fp32
+    [heads, N, N] as `window_attention` takes them, fmt the MX format of Q, K (blocks of 32 along the head dim) and V (blocks of 32 along
+    the window's tokens), p_fmt that of the probabilities (None: fmt).  Not what `window_attention` computes: Q, K, P and V are each rounded
+    to an MX grid.  `out`: a contiguous fp32 [B, H, W, C] to write into.  want: distinct names out of `MX_ATTN_OUTPUTS` -> (out, *wanted):
+    'scores' / 'probs' fp32 [windows, N, N, heads], the logits after scale, bias and mask and their softmax before its quantisation.
+    Checked on the host before a pointer is taken."""
+    what = "mx_window_attention"
+    pixels, N, windows = _attn_geometry(what, d)
+    if (d.C // d.heads) % 4:
+        raise ValueError(f"{what}: the head dim {d.C // d.heads} (C={d.C}, heads={d.heads}) is no multiple of 4")
+    A.tensor(what, "qkv", qkv, numel=pixels * 3 * d.C, contiguous=True)
+    dev = qkv.device
+    A.tensor(what, "bias", bias, device=dev, numel=d.heads * N * N, contiguous=True)
+    fid, _ = mx_format(what, fmt)
+    pid, _ = mx_format(what, fmt if p_fmt is None else p_fmt)
+    A.tensor(what, "out", out, shape=(d.B, d.H, d.W, d.C), contiguous=True, device=dev, optional=True, oneshot=True)
+    if isinstance(want, (str, bytes)) or not hasattr(want, "__iter__"):
+        raise ValueError(f"{what}: want must be a sequence of names out of {list(MX_ATTN_OUTPUTS)}, got {want!r}")
+    want = list(want)
+    if any(n not in MX_ATTN_OUTPUTS for n in want) or len(set(want)) != len(want):
+        raise ValueError(f"{what}: want must hold only distinct names out of {list(MX_ATTN_OUTPUTS)}, got {want!r}")
+    _mx_cuda(what, qkv, "qkv")
+    if out is None:
+        out = torch.empty((d.B, d.H, d.W, d.C), device=dev, dtype=torch.float32)
+    # (a wanted stage output starts as NaN: an element the kernel does not write cannot pass for a result)
+    got = {n: torch.full((windows, N, N, d.heads), float("nan"), device=dev, dtype=torch.float32) if n in want else None for n in MX_ATTN_OUTPUTS}
+    L.check(L.lib().rdo_mx_window_attention(C.byref(d), _ptr(qkv), _ptr(bias), fid, pid, _ptr(out), _ptr(got["scores"]), _ptr(got["probs"]),
+                                            _stream()), "rdo_mx_window_attention")
+    return (out, *[got[n] for n in want]) if want else out
+
+
 def pack_row_words(inner, bits):
     """W = ceil(inner * bits / 32): the 32-bit words one row of `inner` codes of `bits` bits occupies (rdo_pack_row_words on the host)"""
     return -(-int(inner) * int(bits) // 32)

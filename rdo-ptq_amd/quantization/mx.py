@@ -29,7 +29,9 @@ instruction and forms x * norm^-+1/2 in one launch, with gamma' re-quantised ont
 rounding); `set_mx_activations(..., gdn=True)` switches eligible GDNs to it, `native_gdn_chain` hands its packed output to a following
 conv.  Swin blocks (include/rdo_ptq_mxswin.h): `native_ln_linear(norm, linear, x, act_fmt)` runs norm1 -> qkv in two launches,
 `native_swin_mlp(block, x, a, act_fmt)` the half x + a + fc2(gelu(fc1(norm2(x + a)))) in one; `set_mx_activations(..., swin=True)` switches
-the blocks `native_swin_refusal` accepts (`mx_swin`, not stored by `save_mx_packed`).  Not built: calibration or a backward under MX
+the blocks `native_swin_refusal` accepts (`mx_swin`, not stored by `save_mx_packed`).  The attention core (include/rdo_ptq_mxattn.h):
+`native_attention(attn, qkv, ...)` runs Q K^T, the softmax and P V in one launch with Q, K, P and V on MX grids;
+`set_mx_activations(..., attention=True)` switches the attentions `native_attention_refusal` accepts (`mx_attention`, not stored).  Not built: calibration or a backward under MX
 activations (`reconstruct` refuses such a model), data-parallel runs; no rate-distortion claim is made for any of it.  A model on these quantisers is stored by
 `mx_packed.save_mx_packed`, the `mx_activations` pairs included.
 
@@ -637,6 +639,38 @@ def native_swin_mlp(block, x, a, act_fmt):
     out = ops.mx_swin_mlp(x.reshape(-1, C).contiguous(), a.reshape(-1, C).contiguous(), lw, lb, native_operand(fc1), native_bias(fc1),
                           native_operand(fc2), native_bias(fc2), act_fmt, eps=eps)
     return out.reshape(x.shape)
+
+
+# ---- window attention with both products on the instruction (include/rdo_ptq_mxattn.h) ----------------------------------------------------------
+def native_attention_refusal(attn):
+    """None for a module whose attention core `native_attention` serves, else the reason it keeps its fp32 core, looked for in this order:
+    it is no `QuantWindowAttention`; its head dim is no multiple of 4 (the kernel has no scalar path); its activation quantiser would
+    round the probabilities and attn @ v (`use_act_quant` and `trained`: that path has its own two-launch split)."""
+    from .quant_block import QuantWindowAttention
+    if not isinstance(attn, QuantWindowAttention):
+        return f"a {type(attn).__name__} is no QuantWindowAttention"
+    hd = attn.dim // attn.num_heads
+    if hd % 4:
+        return f"its head dim {hd} ({attn.dim} channels, {attn.num_heads} heads) is no multiple of 4"
+    if attn.use_act_quant and attn.trained:
+        return "its activation quantiser rounds the probabilities and attn @ v between the two products"
+    return None
+
+
+def native_attention(attn, qkv, B, H, W, window, shift, fmt, p_fmt=None):
+    """The attention core of a `QuantWindowAttention` `native_attention_refusal` accepts in one `ops.mx_window_attention` launch: qkv [B,
+    H * W, 3C] the qkv linear's output in natural token order -> [B, H * W, C], the input of `proj`.  Q and K are quantised to `fmt` in
+    blocks of 32 along the head dim, the probabilities to `p_fmt` (None: fmt) along the keys and V to `fmt` along the window's tokens; both
+    products run on the block-scaled matrix instruction.  This is not the fp32 attention on rounded inputs of a Linear: four tensors are
+    rounded, V along another axis than any Linear would round it."""
+    why = native_attention_refusal(attn)
+    if why is not None:
+        raise ValueError(f"native_attention: {why}")
+    C = attn.dim
+    if qkv.dim() != 3 or tuple(qkv.shape) != (B, H * W, 3 * C):
+        raise ValueError(f"native_attention: qkv must be [{B}, {H * W}, {3 * C}], got {tuple(qkv.shape)}")
+    d = ops.attn_desc(B, H, W, C, attn.num_heads, window, shift, attn.scale)
+    return ops.mx_window_attention(d, qkv.contiguous().view(B, H, W, 3 * C), attn.position_bias(), fmt, p_fmt).view(B, H * W, C)
 
 
 # ---- MX activations inside the modules' own forward (QuantModel.set_mx_activations) ------------------------------------------------------------

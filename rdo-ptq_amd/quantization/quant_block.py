@@ -209,6 +209,13 @@ class QuantWindowAttention(BaseQuantBlock):
         [B, H*W, 3C] where the caller has computed it (`mx.native_ln_linear`); `tokens` is then not read."""
         C = self.dim
         qkv = (self.qkv(tokens) if qkv is None else qkv).contiguous()
+        mx_fmts = None if (self.use_act_quant and self.trained) else self._mx_attention_formats()
+        if mx_fmts is not None:
+            # Q K^T, softmax and P V in one launch with Q, K, P and V on MX grids (mx.native_attention): not the bits of the fp32 core
+            from . import mx
+            if _tracked(qkv):
+                self.qkv._refuse_mx_grad()
+            return self.proj(mx.native_attention(self, qkv, B, H, W, window, shift, *mx_fmts))
         d = ops.attn_desc(B, H, W, C, self.num_heads, window, shift, self.scale)
         bias = self.position_bias()
         if self.use_act_quant and self.trained:
@@ -242,6 +249,14 @@ class QuantWindowAttention(BaseQuantBlock):
         else:
             o = ops.window_attention(d, qkv, bias).view(B, H * W, C)
         return self.proj(o)
+
+    def _mx_attention_formats(self):
+        """(fmt, p_fmt) where `mx_attention` is set (`QuantModel.set_mx_activations(..., attention=True)`) and qkv carries (fmt, 'native')
+        with its quantised weight: the attention core then runs on the block-scaled matrix instruction; else None"""
+        on = getattr(self, "mx_attention", None)
+        if on is None or not self.qkv.use_weight_quant or getattr(self.qkv, "mx_activations", None) != (on[0], "native"):
+            return None
+        return on
 
     def forward(self, x, mask=None):
         """Reference signature: x [num_windows*B, N, C] already partitioned.  Without a mask every window is independent and

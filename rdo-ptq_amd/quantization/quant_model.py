@@ -5,7 +5,7 @@ import torch.nn as nn
 from lic import EntropyBottleneck
 
 from .fold_bn import search_fold_and_remove_bn
-from .quant_block import BaseQuantBlock, QuantRB, QuantRBWS, QuantSwinTransformerBlock, specials
+from .quant_block import BaseQuantBlock, QuantRB, QuantRBWS, QuantSwinTransformerBlock, QuantWindowAttention, specials
 from .quant_layer import GDN_TYPES, QuantModule, StraightThrough
 from .widths import act_applied, act_modules, format_plan, is_trained, weighted_modules, width_plan
 
@@ -167,7 +167,7 @@ class QuantModel(nn.Module):
         from .reports import mx_native_report
         return mx_native_report(self, images, act_fmt=act_fmt, batch=batch, units=units, convs=convs, tconvs=tconvs)
 
-    def set_mx_activations(self, act_fmt, mode="native", units=None, chain=False, gdn=False, swin=False):
+    def set_mx_activations(self, act_fmt, mode="native", units=None, chain=False, gdn=False, swin=False, attention=False, p_fmt=None):
         """Run the modules' own forward on MX activations: every weighted QuantModule of the chosen units (`units`: a list of names of
         `units()`, None for all) that `mx.native_refusal`, `native_conv_refusal` or `native_tconv_refusal` accepts gets the plain
         attribute `mx_activations = (act_fmt, mode)`.  Its no-grad forward, while `use_weight_quant` is on, then takes the
@@ -194,8 +194,15 @@ class QuantModel(nn.Module):
         (act_fmt, 'native'), `use_weight_quant` is on and no activation quantiser rounds in between.  The result gains 'swin': block
         name -> (norm2, fc1, fc2 names); the block's norm1 / norm2 are reported under 'native' as 'layernorm', a refused block under
         'left' with the reason.  swin=False and act_fmt=None clear `mx_swin`; it is not stored by `save_mx_packed`.
-        ValueError before anything is written for an unknown act_fmt or mode, an unknown unit, a gdn that is no bool, a chain or swin that
-        is no bool or is True in another mode than 'native', and (act_fmt not None) a named unit without an eligible module.  An input that requires grad raises NotImplementedError in a switched module; `reconstruct`
+        attention=True (mode 'native' only; independent of swin) also sets the plain attribute `mx_attention = (act_fmt, p_fmt)` (p_fmt None:
+        act_fmt) on every `QuantWindowAttention` of the chosen units that `mx.native_attention_refusal` accepts and whose qkv is switched:
+        its no-grad forward then runs Q K^T, the softmax and P V as one `mx.native_attention` launch -- Q, K and V quantised to act_fmt, the
+        probabilities to p_fmt, both products on the block-scaled matrix instruction -- while qkv carries this (act_fmt, 'native') and
+        `use_weight_quant` is on.  A switched attention does NOT compute what the fp32 attention computes: four more tensors are rounded.
+        The result gains 'attention': attention name -> (act_fmt, p_fmt); a refused one goes under 'left' with the reason.
+        attention=False and act_fmt=None clear `mx_attention`; it is not stored by `save_mx_packed`.
+        ValueError before anything is written for an unknown act_fmt, p_fmt or mode, an unknown unit, a gdn that is no bool, a chain, swin
+        or attention that is no bool or is True in another mode than 'native', a p_fmt without attention=True, and (act_fmt not None) a named unit without an eligible module.  An input that requires grad raises NotImplementedError in a switched module; `reconstruct`
         refuses a model that holds one."""
         from collections import OrderedDict
         from . import mx
@@ -211,6 +218,12 @@ class QuantModel(nn.Module):
             raise ValueError(f"{what}: gdn must be True or False, got {gdn!r}")
         if not isinstance(swin, bool) or (swin and mode != "native"):
             raise ValueError(f"{what}: swin must be True or False, and True in mode 'native' only; got swin={swin!r}, mode={mode!r}")
+        if not isinstance(attention, bool) or (attention and mode != "native"):
+            raise ValueError(f"{what}: attention must be True or False, and True in mode 'native' only; got attention={attention!r}, mode={mode!r}")
+        if p_fmt is not None:
+            ops.mx_format(what, p_fmt)
+            if not attention:
+                raise ValueError(f"{what}: p_fmt={p_fmt!r} is the format of the attention's probabilities and needs attention=True")
         if units is None:
             chosen = list(known)
         else:
@@ -225,7 +238,9 @@ class QuantModel(nn.Module):
             rep["chained"] = OrderedDict()
         if swin:
             rep["swin"] = OrderedDict()
-        plan, blocks, swin_blocks, swin_norms = [], [], [], set()
+        if attention:
+            rep["attention"] = OrderedDict()
+        plan, blocks, swin_blocks, swin_norms, attentions = [], [], [], set(), []
         for uname in chosen:
             found = False
             for mn, m in known[uname].named_modules():
@@ -243,6 +258,17 @@ class QuantModel(nn.Module):
                         swin_norms.update((f"{name}.norm1", f"{name}.norm2"))
                     elif swin and act_fmt is not None:
                         rep["left"][name] = why
+                if isinstance(m, QuantWindowAttention):
+                    why = "not asked for"
+                    if attention and act_fmt is not None:
+                        why = mx.native_attention_refusal(m)
+                        if why is None and mx.native_refusal(m.qkv) is not None:
+                            why = f"qkv keeps its fp32 operands: {mx.native_refusal(m.qkv)}"
+                        if why is None:
+                            rep["attention"][name] = (act_fmt, act_fmt if p_fmt is None else p_fmt)
+                        else:
+                            rep["left"][name] = why
+                    attentions.append((m, rep["attention"][name] if why is None else None))
                 if not isinstance(m, QuantModule) or m.org_weight is None:
                     continue
                 if name in swin_norms:                  # the LayerNorms of an accepted block run inside its fused launches
@@ -267,6 +293,8 @@ class QuantModel(nn.Module):
             b.mx_chain = on
         for b, on in swin_blocks:
             b.mx_swin = on
+        for a, on in attentions:
+            a.mx_attention = on
         return rep
 
     def set_weight_format(self, formats, rounding="nearest"):
