@@ -129,7 +129,7 @@ __device__ __forceinline__ void mx_store_tiles(const f32x4 (&acc)[2][2], const f
 }
 
 // The K loop of the GEMM for the wave's 32 x 32 outputs at (m0, n0) of A [M][nb blocks] x B [N][nb blocks]^T: what mx_gemm_kernel
-// stores and mx_gemm_packed_kernel (mx_chain.hip) quantises -- one statement, equal accumulators.  mx_swin.hip's unit_accumulate is
+// stores and mx_gemm_packed_kernel (mx_chain.hip) quantises -- one statement, equal accumulators.  mx_swin_device.h's unit_accumulate is
 // this loop with the A rows in an LDS tile of its own row stride (no row test, int offsets): a change of the K order, of the trailing
 // blocks' scale or of mx_mfma_step's passes here has to be made there too; tests/test_gpu_mx_swin.py holds the two to equal bits.
 template <int FA, int FB>

@@ -4,7 +4,7 @@
 // Built with -ffp-contract=off like mx_gemm.hip, mx_chain.hip and mx_gdn.hip: acc + bias, gelu's products and s + y are separate fp32
 // operations; the LayerNorm row states its own arithmetic (ln_row_device.h).
 //
-// Row phase, shared by both kernels (ln_pack_row).  add_ln_kernel's layout: 16 lanes a row, lane l16 holds float4 l16 + 16 k.  A 32-channel
+// Row phase, shared by both kernels (ln_pack_row, mx_swin_device.h; unit_accumulate is there as well).  add_ln_kernel's layout: 16 lanes a row, lane l16 holds float4 l16 + 16 k.  A 32-channel
 //   MX block is then the eight neighbouring lanes 8 t .. 8 t + 7 of one k -- block 2 k + (l16 >> 3) -- which is what mx_quad_quant_store
 //   (mx_pack_store_device.h) quantises and places: the LayerNorm never leaves the registers between ln_row and the packed dwords.  A row
 //   past `rows` is not read; its codes in an LDS image are zeros.
@@ -29,8 +29,7 @@
 // (its rows of image H are then neither written nor read); rows past `rows` inside a unit are zero codes and store nothing.
 #include "rdo_common.h"
 #include "../../include/rdo_ptq_mxswin.h"
-#include "mx_pack_store_device.h"
-#include "ln_row_device.h"
+#include "mx_swin_device.h"
 
 namespace {
 
@@ -43,36 +42,6 @@ struct LnPackArgs {
     uint8_t* scales;
     ln4 *sum_out, *ln;                                                          // nullable
 };
-
-// One row by its 16 lanes: LN(a + b) -> `ln` (if asked), its MX blocks -> dst_row (the row's packed dwords, global or LDS) and sc_row,
-// block by block as ln_row hands the float4 out (weight and bias are loaded there: L1 lines, not 64 registers).  A row that is not live
-// is not read; where keep_dead (the LDS image) its codes and scale bytes are zeros.  `live` is uniform over the row's 16 lanes.
-template <int VPL>
-__device__ __forceinline__ void ln_pack_row(const ln4* __restrict__ a, const ln4* __restrict__ b, const ln4* w, const ln4* bias, int C4, int l16,
-                                            float invC, float eps, long row, bool live, bool keep_dead, ln4* __restrict__ sum_out, ln4* ln,
-                                            const MxFormat& f, uint32_t* dst_row, uint8_t* sc_row) {
-    if (live) {
-        ln_row<VPL>(
-            a, b, row * C4, C4, l16, invC, eps, sum_out,
-            [&](int k, ln4& wk, ln4& bk) {
-                wk = w ? w[l16 + 16 * k] : ln4{1.f, 1.f, 1.f, 1.f};
-                bk = bias ? bias[l16 + 16 * k] : ln4{0.f, 0.f, 0.f, 0.f};
-            },
-            [&](int k, ln4 y) {                                                 // the eight lanes of block kb together: C4 % 8 == 0
-                const int c = l16 + 16 * k, kb = c >> 3;
-                if (ln) ln[row * C4 + c] = y;
-                const float v[4] = {y.x, y.y, y.z, y.w};
-                const unsigned sc = mx_quad_quant_store(v, f, dst_row + kb * f.bits, true);
-                if ((l16 & 7) == 0) sc_row[kb] = (uint8_t)sc;
-            });
-    } else if (keep_dead) {
-        const int s = l16 & 7;
-        for (int c = l16; c < C4; c += 16) {
-            if (s < f.bits) dst_row[(c >> 3) * f.bits + s] = 0u;
-            if (s == 0) sc_row[c >> 3] = 0;
-        }
-    }
-}
 
 template <int VPL>
 __global__ __launch_bounds__(256) void mx_ln_pack_kernel(LnPackArgs p) {
@@ -97,40 +66,6 @@ struct SwinMlpArgs {
     uint32_t* hidden;                                                           // nullable, with hs
     uint8_t* hs;
 };
-
-// mx_gemm_accumulate's loop for the wave's 32 x 32 outputs at (m0, n0) with the A rows in an LDS image (all 64 rows exist: no row test)
-template <int FA, int FB>
-__device__ __forceinline__ void unit_accumulate(const uint32_t* image, int stride, const uint8_t* scales, int nb, const uint32_t* __restrict__ w,
-                                                const uint8_t* __restrict__ sw, int m0, int n0, int r, int kg, f32x4 (&acc)[2][2]) {
-    constexpr int DA = hw_dwords(FA), DB = hw_dwords(FB);
-    const uint32_t* arow[2];
-    long brow[2];
-    int srow[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        arow[i] = image + (m0 + 16 * i + r) * stride;
-        srow[i] = (m0 + 16 * i + r) * nb;
-        brow[i] = (long)(n0 + 16 * i + r) * nb;
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int k0 = 0; k0 < nb; k0 += 4) {
-        const int kb = k0 + kg;
-        const bool kok = kb < nb;
-        i32x8 fa[2], fb[2];
-        int xa[2], xb[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            fa[i] = load_fragment<DA>(arow[i], k0, kg, nb, true);
-            fb[i] = load_fragment<DB>(w + brow[i] * DB, k0, kg, nb, true);
-            xa[i] = kok ? (int)scales[srow[i] + kb] : 127;
-            xb[i] = kok ? (int)sw[brow[i] + kb] : 127;
-        }
-        mx_mfma_step<FA, FB>(fa, fb, xa, xb, acc);
-    }
-}
 
 template <int VPL, int FA, int FB>
 __global__ __launch_bounds__(256) void mx_swin_mlp_kernel(SwinMlpArgs p) {
@@ -236,13 +171,6 @@ const MlpKernel kMlp[3][5][5] = {RDO_MXSWIN_VPL(3), RDO_MXSWIN_VPL(5), RDO_MXSWI
 constexpr size_t kStaticLds = 4 * 32 * kPackRowDwords * sizeof(uint32_t);
 
 inline bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
-
-// dwords of an LDS operand row of nb blocks: a multiple of four, an odd number of 16-byte units (mx_gdn.hip's rule)
-inline int lds_row_dwords(int nb, int bits) {
-    int stride = (nb * bits + 3) & ~3;
-    if (((stride >> 2) & 1) == 0) stride += 4;
-    return stride;
-}
 
 }  // namespace
 

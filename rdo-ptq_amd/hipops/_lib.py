@@ -307,6 +307,12 @@ _SIGS_MXATTN = {
     "rdo_mx_window_attention": (C.c_int, [C.POINTER(AttnDesc), P, P, C.c_int32, C.c_int32, P, P, P, P]),
 }
 EXPORTS_MXATTN = tuple(_SIGS_MXATTN)
+# include/rdo_ptq_mxswinattn.h: the attention half of a Swin block -- LayerNorm, qkv, window attention, proj, residual add -- in one launch
+_SIGS_MXSWINATTN = {
+    "rdo_mx_swin_attn": (C.c_int, [C.POINTER(AttnDesc), P, P, P, C.c_float, C.c_int32, P, P, P, P, P, P, C.c_int32, P, P, P, P, P, P, P]),
+}
+EXPORTS_MXSWINATTN = tuple(_SIGS_MXSWINATTN)
+MXSWINATTN_MAX_C = 320         # RDO_MXSWINATTN_MAX_C of include/rdo_ptq_mxswinattn.h
 # tuning hooks the library exports beside its headers (csrc/conv_wgrad.hip): tile choice (-1 = the library's, 0 = 64 x 64, 1 = 192 x 192)
 # and slab count (-1 = the library's) of rdo_conv2d_wgrad, process-wide; ops.forced_wgrad sets and restores them
 _SIGS_DEBUG = {
@@ -333,7 +339,7 @@ def lib():
                                   + list(_SIGS_ATTNQ.items()) + list(_SIGS_MX.items()) + list(_SIGS_MXROUND.items())
                                   + list(_SIGS_MXGEMM.items()) + list(_SIGS_MXCONV.items()) + list(_SIGS_MXTCONV.items())
                                   + list(_SIGS_MXFILE.items()) + list(_SIGS_MXCHAIN.items()) + list(_SIGS_MXGDN.items()) + list(_SIGS_MXSWIN.items())
-                                  + list(_SIGS_MXATTN.items()) + list(_SIGS_DEBUG.items())):
+                                  + list(_SIGS_MXATTN.items()) + list(_SIGS_MXSWINATTN.items()) + list(_SIGS_DEBUG.items())):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         _lib = h

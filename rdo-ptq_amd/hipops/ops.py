@@ -1260,6 +1260,65 @@ def mx_window_attention(d, qkv, bias, fmt, p_fmt=None, out=None, want=()):
     return (out, *[got[n] for n in want]) if want else out
 
 
+MX_SWIN_ATTN_OUTPUTS = ("ln", "qkv", "attn", "branch")      # what `mx_swin_attn` can be asked for beside `out`
+
+
+def mx_swin_attn(d, x, ln_weight, ln_bias, wqkv, bqkv, wproj, bproj, bias, act_fmt, eps=1e-5, want=(), out=None):
+    """The attention half of a Swin block on the block-scaled matrix instruction, one launch (rdo_mx_swin_attn;
+    include/rdo_ptq_mxswinattn.h): out = x + proj(attention(qkv(LN(x)))) with d an `attn_desc` whose head dim is a multiple of 4 and whose C
+    is a multiple of 32, at most `MXSWINATTN_MAX_C`; x contiguous fp32 with B * H * W * C elements in natural pixel order ([B, H, W, C],
+    [B, L, C] or [rows, C]); ln_weight / ln_bias fp32 [C] or None; wqkv an `MXOperand` [3C, C] and wproj an `MXOperand` [C, C] of one
+    format; bqkv fp32 [3C] / bproj fp32 [C] or None; bias fp32 [heads, N, N]; act_fmt the MX format of every activation (the
+    probabilities included: another p_fmt keeps the five launches).  Bit for bit `add(x, mx_gemm(mx_quant_pack(mx_window_attention(d,
+    mx_gemm(mx_quant_pack(add_layer_norm(x, None, ln_weight, ln_bias, eps), act_fmt), wqkv, bqkv), bias, act_fmt), act_fmt), wproj,
+    bproj))`.  `out`: a contiguous fp32 tensor of x's shape to write into.  want: distinct names out of `MX_SWIN_ATTN_OUTPUTS` -> (out,
+    *wanted): 'ln', 'attn', 'branch' fp32 of x's shape, 'qkv' fp32 [..., 3C] -- the stages of the composition above.  Checked on the
+    host before a pointer is taken."""
+    what = "mx_swin_attn"
+    pixels, N, windows = _attn_geometry(what, d)
+    Cc = d.C
+    if (Cc // d.heads) % 4:
+        raise ValueError(f"{what}: the head dim {Cc // d.heads} (C={Cc}, heads={d.heads}) is no multiple of 4")
+    if Cc % L.MX_BLOCK:
+        raise ValueError(f"{what}: C = {Cc} is no multiple of the MX block size {L.MX_BLOCK}")
+    if Cc > L.MXSWINATTN_MAX_C:
+        raise ValueError(f"{what}: C = {Cc} is above {L.MXSWINATTN_MAX_C}, the most the kernel's LDS serves")
+    A.tensor(what, "x", x, numel=pixels * Cc, contiguous=True)
+    dev = x.device
+    if x.dim() < 2 or x.shape[-1] != Cc:
+        raise ValueError(f"{what}: x must be [..., {Cc}], got {tuple(x.shape)}")
+    A.tensor(what, "ln_weight", ln_weight, shape=(Cc,), contiguous=True, device=dev, optional=True, oneshot=True)
+    A.tensor(what, "ln_bias", ln_bias, shape=(Cc,), contiguous=True, device=dev, optional=True, oneshot=True)
+    fa, _ = mx_format(what, act_fmt)
+    fw, _, _ = _mx_operand(what, "wqkv", wqkv, device=dev)
+    fw2, _, _ = _mx_operand(what, "wproj", wproj, device=dev)
+    if (wqkv.rows, wqkv.K) != (3 * Cc, Cc) or (wproj.rows, wproj.K) != (Cc, Cc):
+        raise ValueError(f"{what}: wqkv is [{wqkv.rows}, {wqkv.K}] and wproj [{wproj.rows}, {wproj.K}]; the descriptor's {Cc} channels need "
+                         f"[{3 * Cc}, {Cc}] and [{Cc}, {Cc}]")
+    if fw != fw2:
+        raise ValueError(f"{what}: wqkv is in {wqkv.fmt} and wproj in {wproj.fmt}; the kernel takes one weight format")
+    A.tensor(what, "bqkv", bqkv, shape=(3 * Cc,), contiguous=True, device=dev, optional=True, oneshot=True)
+    A.tensor(what, "bproj", bproj, shape=(Cc,), contiguous=True, device=dev, optional=True, oneshot=True)
+    A.tensor(what, "bias", bias, device=dev, numel=d.heads * N * N, contiguous=True)
+    A.tensor(what, "out", out, shape=tuple(x.shape), contiguous=True, device=dev, optional=True, oneshot=True)
+    if isinstance(want, (str, bytes)) or not hasattr(want, "__iter__"):
+        raise ValueError(f"{what}: want must be a sequence of names out of {list(MX_SWIN_ATTN_OUTPUTS)}, got {want!r}")
+    want = list(want)
+    if any(n not in MX_SWIN_ATTN_OUTPUTS for n in want) or len(set(want)) != len(want):
+        raise ValueError(f"{what}: want must hold only distinct names out of {list(MX_SWIN_ATTN_OUTPUTS)}, got {want!r}")
+    _mx_cuda(what, x, "x")
+    if out is None:
+        out = torch.empty_like(x)
+    # (a wanted stage output starts as NaN: an element the kernel does not write cannot pass for a result)
+    got = {n: torch.full((*x.shape[:-1], (3 if n == "qkv" else 1) * Cc), float("nan"), device=dev, dtype=torch.float32) if n in want else None
+           for n in MX_SWIN_ATTN_OUTPUTS}
+    L.check(L.lib().rdo_mx_swin_attn(C.byref(d), _ptr(x), _ptr(ln_weight), _ptr(ln_bias), float(eps), fa, _ptr(wqkv.packed, *_U8),
+                                     _ptr(wqkv.scales, *_U8), _ptr(bqkv), _ptr(wproj.packed, *_U8), _ptr(wproj.scales, *_U8), _ptr(bproj), fw,
+                                     _ptr(bias), _ptr(out), _ptr(got["ln"]), _ptr(got["qkv"]), _ptr(got["attn"]), _ptr(got["branch"]),
+                                     _stream()), "rdo_mx_swin_attn")
+    return (out, *[got[n] for n in want]) if want else out
+
+
 def pack_row_words(inner, bits):
     """W = ceil(inner * bits / 32): the 32-bit words one row of `inner` codes of `bits` bits occupies (rdo_pack_row_words on the host)"""
     return -(-int(inner) * int(bits) // 32)

@@ -31,7 +31,10 @@ conv.  Swin blocks (include/rdo_ptq_mxswin.h): `native_ln_linear(norm, linear, x
 `native_swin_mlp(block, x, a, act_fmt)` the half x + a + fc2(gelu(fc1(norm2(x + a)))) in one; `set_mx_activations(..., swin=True)` switches
 the blocks `native_swin_refusal` accepts (`mx_swin`, not stored by `save_mx_packed`).  The attention core (include/rdo_ptq_mxattn.h):
 `native_attention(attn, qkv, ...)` runs Q K^T, the softmax and P V in one launch with Q, K, P and V on MX grids;
-`set_mx_activations(..., attention=True)` switches the attentions `native_attention_refusal` accepts (`mx_attention`, not stored).  Not built: calibration or a backward under MX
+`set_mx_activations(..., attention=True)` switches the attentions `native_attention_refusal` accepts (`mx_attention`, not stored).  The
+attention half (include/rdo_ptq_mxswinattn.h): `native_swin_attn(block, x, H, W, act_fmt)` runs norm1, qkv, the attention, proj and the
+residual add in one launch; `set_mx_activations(..., swin=True, attention=True, fused_attention=True)` switches the blocks
+`native_swin_attn_refusal` accepts (`mx_swin_attn`, not stored): a switched block is two launches.  Not built: calibration or a backward under MX
 activations (`reconstruct` refuses such a model), data-parallel runs; no rate-distortion claim is made for any of it.  A model on these quantisers is stored by
 `mx_packed.save_mx_packed`, the `mx_activations` pairs included.
 
@@ -627,16 +630,17 @@ def native_ln_linear(norm, linear, x, act_fmt):
 def native_swin_mlp(block, x, a, act_fmt):
     """The second half of a `QuantSwinTransformerBlock` `native_swin_refusal` accepts, before the block's `_aq`, in one
     `ops.mx_swin_mlp` launch: x [B, L, C] is the block's input, a the attention branch; -> t + fc2(gelu(fc1(norm2(t)))) with t = x + a,
-    both activations quantised to `act_fmt`, the weights the memoised `native_operand`s of fc1 and fc2."""
+    both activations quantised to `act_fmt`, the weights the memoised `native_operand`s of fc1 and fc2.  a = None: x is t itself, the
+    output of `native_swin_attn`."""
     why = native_swin_refusal(block)
     if why is not None:
         raise ValueError(f"native_swin_mlp: {why}")
     fc1, fc2 = block.mlp.fc1, block.mlp.fc2
     C = int(fc1.weight.shape[1])
-    if x.shape[-1] != C or a.shape != x.shape:
+    if x.shape[-1] != C or (a is not None and a.shape != x.shape):
         raise ValueError(f"native_swin_mlp: x must be [..., {C}] and a like x, got {tuple(x.shape)} and {tuple(a.shape)}")
     lw, lb, eps = _ln_params(block.norm2)
-    out = ops.mx_swin_mlp(x.reshape(-1, C).contiguous(), a.reshape(-1, C).contiguous(), lw, lb, native_operand(fc1), native_bias(fc1),
+    out = ops.mx_swin_mlp(x.reshape(-1, C).contiguous(), None if a is None else a.reshape(-1, C).contiguous(), lw, lb, native_operand(fc1), native_bias(fc1),
                           native_operand(fc2), native_bias(fc2), act_fmt, eps=eps)
     return out.reshape(x.shape)
 
@@ -671,6 +675,54 @@ def native_attention(attn, qkv, B, H, W, window, shift, fmt, p_fmt=None):
         raise ValueError(f"native_attention: qkv must be [{B}, {H * W}, {3 * C}], got {tuple(qkv.shape)}")
     d = ops.attn_desc(B, H, W, C, attn.num_heads, window, shift, attn.scale)
     return ops.mx_window_attention(d, qkv.contiguous().view(B, H, W, 3 * C), attn.position_bias(), fmt, p_fmt).view(B, H * W, C)
+
+
+# ---- the attention half of a Swin block in one launch (include/rdo_ptq_mxswinattn.h) ------------------------------------------------------------
+def native_swin_attn_refusal(block):
+    """None for a `QuantSwinTransformerBlock` whose attention half `native_swin_attn` serves, else the reason it keeps its five launches,
+    looked for in this order: `native_swin_refusal`'s reason; `native_attention_refusal`'s for its attention; proj not native-eligible
+    (`native_refusal`), or qkv and proj in different weight formats; C above `hipops._lib.MXSWINATTN_MAX_C`; an `se_module` or an
+    activation function on proj; an active activation quantiser on qkv or proj."""
+    from .quantizer import StraightThrough
+    why = native_swin_refusal(block)
+    if why is None:
+        why = native_attention_refusal(block.attn)
+    if why is not None:
+        return why
+    qkv, proj = block.attn.qkv, block.attn.proj
+    why = native_refusal(proj)
+    if why is not None:
+        return f"attn.proj: {why}"
+    if qkv.weight_quantizer.fmt != proj.weight_quantizer.fmt:
+        return f"qkv's weights are in {qkv.weight_quantizer.fmt} and proj's in {proj.weight_quantizer.fmt}: the kernel takes one weight format"
+    C = int(proj.weight.shape[1])
+    if C > L.MXSWINATTN_MAX_C:
+        return f"its {C} channels are above {L.MXSWINATTN_MAX_C}, the most the kernel's LDS serves"
+    if proj.se_module is not None or not isinstance(proj.activation_function, (StraightThrough, nn.Identity)):
+        return "attn.proj has an se_module or an activation function of its own"
+    if _act_quant_on(qkv) or _act_quant_on(proj):
+        return "an activation quantiser is active on qkv or proj"
+    return None
+
+
+def native_swin_attn(block, x, H, W, act_fmt):
+    """The first half of a `QuantSwinTransformerBlock` `native_swin_attn_refusal` accepts in one `ops.mx_swin_attn` launch: x [B, L, C]
+    is the block's input, L = H * W -> x + proj(attention(qkv(norm1(x)))) as [B, L, C], every activation -- the LayerNorm, Q, K, V, the
+    probabilities, the attention output -- quantised to `act_fmt`, the weights the memoised `native_operand`s of qkv and proj.  The bits of
+    `native_ln_linear`, `native_attention` (p_fmt = act_fmt), proj's `native_linear` and `ops.add`, without their round trips through
+    memory."""
+    why = native_swin_attn_refusal(block)
+    if why is not None:
+        raise ValueError(f"native_swin_attn: {why}")
+    attn = block.attn
+    C = attn.dim
+    if x.dim() != 3 or x.shape[1] != H * W or x.shape[2] != C:
+        raise ValueError(f"native_swin_attn: x must be [B, {H * W}, {C}], got {tuple(x.shape)}")
+    B = int(x.shape[0])
+    lw, lb, eps = _ln_params(block.norm1)
+    d = ops.attn_desc(B, H, W, C, attn.num_heads, block.window_size, block.shift_size, attn.scale)
+    return ops.mx_swin_attn(d, x.contiguous(), lw, lb, native_operand(attn.qkv), native_bias(attn.qkv), native_operand(attn.proj),
+                            native_bias(attn.proj), attn.position_bias(), act_fmt, eps=eps)
 
 
 # ---- MX activations inside the modules' own forward (QuantModel.set_mx_activations) ------------------------------------------------------------

@@ -300,11 +300,29 @@ class QuantSwinTransformerBlock(BaseQuantBlock):
             return None
         return on[0]
 
+    def _mx_swin_attn_on(self, fmt):
+        """whether `mx_swin_attn` is set (`QuantModel.set_mx_activations(..., fused_attention=True)`) and the five launches it replaces
+        would run on `fmt` alone: the attention core on (fmt, fmt), proj on (fmt, 'native') with its quantised weight, and no activation
+        quantiser rounding on qkv or proj"""
+        if not getattr(self, "mx_swin_attn", False):
+            return False
+        from . import mx
+        a, proj = self.attn, self.attn.proj
+        return (not (a.use_act_quant and a.trained) and a._mx_attention_formats() == (fmt, fmt) and proj.use_weight_quant
+                and getattr(proj, "mx_activations", None) == (fmt, "native") and not mx._act_quant_on(a.qkv) and not mx._act_quant_on(proj))
+
     def forward(self, x, x_size):
         H, W = int(x_size[0]), int(x_size[1])
         B, L, C = x.shape
         x = x.contiguous()
         fmt = self._mx_swin_format()
+        if fmt is not None and self._mx_swin_attn_on(fmt):
+            # two launches: everything up to x + attention branch (mx.native_swin_attn), then the MLP half on that sum -- the bits of the
+            # path below
+            from . import mx
+            if _tracked(x):
+                self.attn.qkv._refuse_mx_grad()
+            return self._aq(mx.native_swin_mlp(self, mx.native_swin_attn(self, x, H, W, fmt), None, fmt))
         if fmt is not None:
             # norm1 -> qkv in two launches, the half behind the attention in one (mx.native_ln_linear, mx.native_swin_mlp): the bits of
             # the module-by-module forward with `ops.add_layer_norm` as the LayerNorm

@@ -167,7 +167,7 @@ class QuantModel(nn.Module):
         from .reports import mx_native_report
         return mx_native_report(self, images, act_fmt=act_fmt, batch=batch, units=units, convs=convs, tconvs=tconvs)
 
-    def set_mx_activations(self, act_fmt, mode="native", units=None, chain=False, gdn=False, swin=False, attention=False, p_fmt=None):
+    def set_mx_activations(self, act_fmt, mode="native", units=None, chain=False, gdn=False, swin=False, attention=False, p_fmt=None, fused_attention=False):
         """Run the modules' own forward on MX activations: every weighted QuantModule of the chosen units (`units`: a list of names of
         `units()`, None for all) that `mx.native_refusal`, `native_conv_refusal` or `native_tconv_refusal` accepts gets the plain
         attribute `mx_activations = (act_fmt, mode)`.  Its no-grad forward, while `use_weight_quant` is on, then takes the
@@ -201,7 +201,17 @@ class QuantModel(nn.Module):
         `use_weight_quant` is on.  A switched attention does NOT compute what the fp32 attention computes: four more tensors are rounded.
         The result gains 'attention': attention name -> (act_fmt, p_fmt); a refused one goes under 'left' with the reason.
         attention=False and act_fmt=None clear `mx_attention`; it is not stored by `save_mx_packed`.
-        ValueError before anything is written for an unknown act_fmt, p_fmt or mode, an unknown unit, a gdn that is no bool, a chain, swin
+        fused_attention=True (needs swin=True and attention=True, and p_fmt None or act_fmt) also sets the plain attribute `mx_swin_attn` on
+        every accepted Swin block that `mx.native_swin_attn_refusal` accepts too: its no-grad forward then runs norm1, qkv, the attention
+        core, proj and the residual add as one `mx.native_swin_attn` launch instead of five, so the block is two launches, with the bits of
+        the five -- while the conditions of swin and attention hold and proj carries this (act_fmt, 'native').  The result gains
+        'swin_attn': block name -> (norm1, qkv, proj names); a refused block keeps the five launches and goes under 'left' with the
+        reason.  Cleared like `mx_swin`; not stored by `save_mx_packed`.  Measured at the Lu2022 width (B = 4, 128 x 128, C = 192, 8 heads,
+        window 8, shift 0 and 4, FP8 and FP4; profiles/mx_swin_attn_bench.log): the one launch is SLOWER at every one
+        of those shapes, 2.05-2.18 x the five launches' time -- one workgroup a CU by LDS.  The keyword is for a forward in two launches
+        a block with the same bits, not for speed; it is off by default.
+        ValueError before anything is written for an unknown act_fmt, p_fmt or mode, a fused_attention that is no bool, is True without
+        swin=True and attention=True or with a p_fmt other than act_fmt, an unknown unit, a gdn that is no bool, a chain, swin
         or attention that is no bool or is True in another mode than 'native', a p_fmt without attention=True, and (act_fmt not None) a named unit without an eligible module.  An input that requires grad raises NotImplementedError in a switched module; `reconstruct`
         refuses a model that holds one."""
         from collections import OrderedDict
@@ -224,6 +234,9 @@ class QuantModel(nn.Module):
             ops.mx_format(what, p_fmt)
             if not attention:
                 raise ValueError(f"{what}: p_fmt={p_fmt!r} is the format of the attention's probabilities and needs attention=True")
+        if not isinstance(fused_attention, bool) or (fused_attention and not (swin and attention and p_fmt in (None, act_fmt))):
+            raise ValueError(f"{what}: fused_attention must be True or False, and True only with swin=True, attention=True and a p_fmt that is "
+                             f"None or act_fmt; got fused_attention={fused_attention!r}, swin={swin!r}, attention={attention!r}, p_fmt={p_fmt!r}")
         if units is None:
             chosen = list(known)
         else:
@@ -240,6 +253,8 @@ class QuantModel(nn.Module):
             rep["swin"] = OrderedDict()
         if attention:
             rep["attention"] = OrderedDict()
+        if fused_attention:
+            rep["swin_attn"] = OrderedDict()
         plan, blocks, swin_blocks, swin_norms, attentions = [], [], [], set(), []
         for uname in chosen:
             found = False
@@ -252,12 +267,20 @@ class QuantModel(nn.Module):
                         rep["chained"][name] = (f"{name}.conv1", f"{name}.conv2")
                 if isinstance(m, QuantSwinTransformerBlock):
                     why = mx.native_swin_refusal(m) if (swin and act_fmt is not None) else "not asked for"
-                    swin_blocks.append((m, why is None))
+                    fused = why is None and fused_attention
                     if why is None:
                         rep["swin"][name] = (f"{name}.norm2", f"{name}.mlp.fc1", f"{name}.mlp.fc2")
                         swin_norms.update((f"{name}.norm1", f"{name}.norm2"))
                     elif swin and act_fmt is not None:
                         rep["left"][name] = why
+                    if fused:
+                        why_not = mx.native_swin_attn_refusal(m)
+                        fused = why_not is None
+                        if fused:
+                            rep["swin_attn"][name] = (f"{name}.norm1", f"{name}.attn.qkv", f"{name}.attn.proj")
+                        else:
+                            rep["left"][name] = f"the attention half keeps its five launches: {why_not}"
+                    swin_blocks.append((m, why is None, fused))
                 if isinstance(m, QuantWindowAttention):
                     why = "not asked for"
                     if attention and act_fmt is not None:
@@ -291,8 +314,8 @@ class QuantModel(nn.Module):
             m.mx_activations = None if (act_fmt is None or kind is None) else (act_fmt, mode)
         for b, on in blocks:
             b.mx_chain = on
-        for b, on in swin_blocks:
-            b.mx_swin = on
+        for b, on, fused in swin_blocks:
+            b.mx_swin, b.mx_swin_attn = on, fused
         for a, on in attentions:
             a.mx_attention = on
         return rep
