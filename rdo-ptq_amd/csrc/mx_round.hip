@@ -16,6 +16,7 @@
 #include "../../include/rdo_ptq_mxround.h"
 #include "mx_device.h"
 #include "ada_device.h"
+#include "mx_grid_device.h"
 
 namespace {
 
@@ -123,13 +124,6 @@ __global__ __launch_bounds__(256) void mx_init_kernel(const float* __restrict__ 
         alpha[e] = a;
     }
 }
-
-// The MX grid of one weight (ada_element's Grid): lo is on the grid and so is lo + gap -- no level clamp, dq/dh = gap everywhere
-struct MxGrid {
-    float lo, gap;
-    __device__ __forceinline__ float q(float h) const { return lo + gap * h; }
-    __device__ __forceinline__ float dq_dh(float g, float) const { return g * gap; }
-};
 
 __global__ __launch_bounds__(256) void mx_fwd_kernel(rdo_ada_desc d, const float* __restrict__ lo, const float* __restrict__ gap,
                                                      const float* __restrict__ alpha, int soft, float* __restrict__ wq, float* __restrict__ wd,

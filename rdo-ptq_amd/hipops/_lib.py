@@ -37,6 +37,14 @@ class GatherDesc(C.Structure):
                 ("out", C.c_void_p), ("out_planes", C.c_void_p), ("out_scale", C.c_float), ("overflow_flag", C.c_void_p)]
 
 
+class MxRoundStepItem(C.Structure):
+    """rdo_mx_round_step_item of include/rdo_ptq_mxroundbatch.h"""
+    _fields_ = [("d", AdaDesc), ("lo", C.c_void_p), ("gap", C.c_void_p), ("slabs", C.c_void_p), ("nsplit", C.c_int32),
+                ("alpha", C.c_void_p), ("adam_m", C.c_void_p), ("adam_v", C.c_void_p), ("wq", C.c_void_p), ("wd", C.c_void_p),
+                ("wq_planes", C.c_void_p), ("wd_planes", C.c_void_p), ("wq_plane_scale", C.c_float), ("wd_plane_scale", C.c_float),
+                ("lin_fwd_planes", C.c_void_p), ("lin_bwd_planes", C.c_void_p), ("lin_plane_scale", C.c_float)]
+
+
 class AttnDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("B", "H", "W", "C", "heads", "window", "shift")] + [("scale", C.c_float)]
 
@@ -313,6 +321,12 @@ _SIGS_MXSWINATTN = {
 }
 EXPORTS_MXSWINATTN = tuple(_SIGS_MXSWINATTN)
 MXSWINATTN_MAX_C = 320         # RDO_MXSWINATTN_MAX_C of include/rdo_ptq_mxswinattn.h
+# include/rdo_ptq_mxroundbatch.h: the learned-rounding step on the MX grids for every weight tensor of a unit, planes and next mini-batch included
+_SIGS_MXROUNDBATCH = {
+    "rdo_mx_round_step_batch": (C.c_int, [C.POINTER(MxRoundStepItem), C.c_int32, C.c_float, C.c_float, P, P, P, P, P, C.POINTER(GatherDesc), P]),
+}
+EXPORTS_MXROUNDBATCH = tuple(_SIGS_MXROUNDBATCH)
+MXROUNDBATCH_MAX = 8           # tensors a launch of rdo_mx_round_step_batch takes
 # tuning hooks the library exports beside its headers (csrc/conv_wgrad.hip): tile choice (-1 = the library's, 0 = 64 x 64, 1 = 192 x 192)
 # and slab count (-1 = the library's) of rdo_conv2d_wgrad, process-wide; ops.forced_wgrad sets and restores them
 _SIGS_DEBUG = {
@@ -339,7 +353,8 @@ def lib():
                                   + list(_SIGS_ATTNQ.items()) + list(_SIGS_MX.items()) + list(_SIGS_MXROUND.items())
                                   + list(_SIGS_MXGEMM.items()) + list(_SIGS_MXCONV.items()) + list(_SIGS_MXTCONV.items())
                                   + list(_SIGS_MXFILE.items()) + list(_SIGS_MXCHAIN.items()) + list(_SIGS_MXGDN.items()) + list(_SIGS_MXSWIN.items())
-                                  + list(_SIGS_MXATTN.items()) + list(_SIGS_MXSWINATTN.items()) + list(_SIGS_DEBUG.items())):
+                                  + list(_SIGS_MXATTN.items()) + list(_SIGS_MXSWINATTN.items()) + list(_SIGS_MXROUNDBATCH.items())
+                                  + list(_SIGS_DEBUG.items())):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         _lib = h

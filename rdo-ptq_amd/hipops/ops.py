@@ -292,6 +292,20 @@ def iter_bind_publish(word):
     return bool(L.lib().rdo_iter_bind_publish(_ptr(word)))
 
 
+def _gather_desc(gather):
+    """the rdo_gather_desc of a step launch that also assembles the next mini-batch, from dict(cache_q, cache_fp, idx_table, B,
+    batch_offset, prob, seed, out, out_planes)"""
+    dp = lambda t: None if t is None else _ptr(t).value
+    cq, pl = gather["cache_q"], gather.get("out_planes")
+    g = L.GatherDesc()
+    g.cache_q, g.cache_fp, g.idx_table = dp(cq), dp(gather["cache_fp"]), dp(gather["idx_table"])
+    g.n_iters, g.B, g.batch_offset = int(gather["idx_table"].shape[0]), int(gather["B"]), int(gather.get("batch_offset", 0))
+    g.per_image, g.C, g.prob, g.seed = cq[0].numel(), int(cq.shape[-1]), float(gather["prob"]), int(gather["seed"])
+    g.out, g.out_planes, g.out_scale = dp(gather.get("out")), dp(pl), (float(pl.scale) if pl is not None else 0.0)
+    g.overflow_flag = dp(getattr(pl, "flag", None))      # the gathered planes raise their own overflow word
+    return g
+
+
 def adaround_step_batch(items, grad_scale, round_weight, sched, iter_ptr, round_log, advance_iter=None, mode=0, iter_shadow=None, gather=None,
                         row_groups=None):
     """items: list of dicts(d, w, delta, zp, slabs, alpha, m, v, wq, wd, wq_planes, wd_planes[, dalpha, lin_fwd, lin_bwd]) -- one launch for every
@@ -328,13 +342,7 @@ def adaround_step_batch(items, grad_scale, round_weight, sched, iter_ptr, round_
     if gather is not None:
         if advance_iter is not None:
             raise ValueError("adaround_step_batch: the gather form moves the counter by hand-over (iter_shadow), not advance_iter")
-        cq, pl = gather["cache_q"], gather.get("out_planes")
-        g = L.GatherDesc()
-        g.cache_q, g.cache_fp, g.idx_table = dp(cq), dp(gather["cache_fp"]), dp(gather["idx_table"])
-        g.n_iters, g.B, g.batch_offset = int(gather["idx_table"].shape[0]), int(gather["B"]), int(gather.get("batch_offset", 0))
-        g.per_image, g.C, g.prob, g.seed = cq[0].numel(), int(cq.shape[-1]), float(gather["prob"]), int(gather["seed"])
-        g.out, g.out_planes, g.out_scale = dp(gather.get("out")), dp(pl), (float(pl.scale) if pl is not None else 0.0)
-        g.overflow_flag = dp(getattr(pl, "flag", None))      # the gathered planes raise their own overflow word
+        g = _gather_desc(gather)
         if px:
             rg = (C.c_int32 * len(items))(*[int(v) for v in row_groups])
             L.check(L.lib().rdo_adaround_step_batch_gather_px(arr, len(items), int(mode), grad_scale, round_weight, _ptr(sched), _ptr(iter_ptr),
@@ -841,6 +849,118 @@ def mx_round_step(d, lo, gap, slabs, grad_scale, round_weight, sched, iter_ptr, 
     L.check(L.lib().rdo_mx_round_step(C.byref(d), _ptr(lo), _ptr(gap), _ptr(slabs), int(slabs.shape[0]), float(grad_scale), float(round_weight),
                                       _ptr(sched), _ptr(iter_ptr), _ptr(alpha), _ptr(m), _ptr(v), _ptr(wq), _ptr(wd), _ptr(round_log), _stream()),
             "rdo_mx_round_step")
+
+
+# ---- the MX step of a whole unit (include/rdo_ptq_mxroundbatch.h) --------------------------------------------------------------------------
+def _mx_planes(what, name, planes, n, dev, h2_only=False):
+    """a plane output of `mx_round_step_batch`: None, an `H2` (fp16 two-way, 2 n halves) or, unless h2_only, an int16 tensor of 3 n
+    elements (bf16 three-way)"""
+    if planes is None:
+        return
+    if h2_only and not isinstance(planes, H2):
+        raise ValueError(f"{what}: {name} must be an H2 (fp16 planes with their scale), got {type(planes).__name__}")
+    t, k = (planes.t, 2) if isinstance(planes, H2) else (planes, 3)
+    A.tensor(what, name, t, torch.int16, "int16", numel=k * n, contiguous=True, device=dev, oneshot=True)
+
+
+def mx_round_step_batch(items, grad_scale, round_weight, sched, iter_ptr, round_log, advance_iter=None, iter_shadow=None, gather=None):
+    """The fused AdaRound step on MX grids for every weight tensor of a unit in ONE launch, and their dgrad layouts in a second one
+    (rdo_mx_round_step_batch, include/rdo_ptq_mxroundbatch.h): `mx_round_step` per item, bit for bit, plus the planes that the split
+    wrappers would make of the new weights.
+    items: 1 .. 8 dicts(d, lo, gap, slabs, alpha, m, v, wq[, wd, wq_planes, wd_planes, lin_fwd, lin_bwd]) with numel % 4 == 0 -- the
+    tensors of `mx_round_step`; wq_planes / wd_planes an int16 [3, numel] tensor (bf16 three-way split) or an `H2` (fp16 two-way split of
+    w * scale) in the conv fragment order, lin_fwd / lin_bwd `H2`s of one scale in the fragment order of `linear_h2` (1 x 1 layout, rows
+    and inner multiples of 32).  sched, iter_ptr, round_log as in `mx_round_step`.
+    advance_iter: the counter to increment afterwards; iter_shadow (the alternative): the word that receives *iter_ptr + 1;
+    gather: dict(cache_q, cache_fp, idx_table, B, batch_offset, prob, seed, out, out_planes) -- the launch also assembles the NEXT
+    iteration's mini-batch, as `adaround_step_batch` does.  Everything is checked on the host before a pointer is taken."""
+    what = "mx_round_step_batch"
+    if not isinstance(items, (list, tuple)) or not 1 <= len(items) <= L.MXROUNDBATCH_MAX or not all(isinstance(it, dict) for it in items):
+        raise ValueError(f"{what}: items must be a list of 1 .. {L.MXROUNDBATCH_MAX} dicts, got "
+                         f"{len(items) if isinstance(items, (list, tuple)) else type(items).__name__}")
+    first = items[0].get("lo")
+    A.tensor(what, "lo of item 0", first, contiguous=True)
+    dev = first.device
+    for k, it in enumerate(items):
+        at = lambda name: f"{name} of item {k}"
+        lo = it.get("lo")
+        A.tensor(what, at("lo"), lo, contiguous=True, device=dev, other="lo of item 0")
+        n = lo.numel()
+        for name in ("gap", "alpha", "m", "v", "wq"):
+            A.tensor(what, at(name), it.get(name), numel=n, contiguous=True, device=dev, other=at("lo"))
+        if n % 4:
+            raise ValueError(f"{what}: {at('lo')} holds {n} elements, no multiple of 4 (`mx_round_step` takes such a tensor)")
+        _mx_desc(f"{what}: item {k}", it.get("d"), lo)
+        d, wd = it["d"], it.get("wd")
+        A.tensor(what, at("wd"), wd, numel=n, contiguous=True, device=dev, optional=True, oneshot=True)
+        slabs = it.get("slabs")
+        A.tensor(what, at("slabs"), slabs, contiguous=True, device=dev, other=at("lo"))
+        if slabs.dim() < 1 or slabs.numel() != slabs.shape[0] * n:
+            raise ValueError(f"{what}: {at('slabs')} must be [nsplit, ...] with {n} elements a slab, got {tuple(slabs.shape)}")
+        _mx_planes(what, at("wq_planes"), it.get("wq_planes"), n, dev)
+        _mx_planes(what, at("wd_planes"), it.get("wd_planes"), n, dev)
+        if it.get("wd_planes") is not None and wd is None:
+            raise ValueError(f"{what}: {at('wd_planes')} needs wd")
+        lf, lb = it.get("lin_fwd"), it.get("lin_bwd")
+        _mx_planes(what, at("lin_fwd"), lf, n, dev, h2_only=True)
+        _mx_planes(what, at("lin_bwd"), lb, n, dev, h2_only=True)
+        if (wd is not None or lf is not None or lb is not None) and d.Cin <= 0:
+            raise ValueError(f"{what}: item {k}: wd and the Linear planes need a descriptor with a conv layout (`ada_desc`)")
+        if lf is not None or lb is not None:
+            if d.rows % 32 or d.Cin % 32 or d.KH * d.KW != 1:
+                raise ValueError(f"{what}: item {k}: Linear planes need a 1 x 1 layout with rows and inner multiples of 32, got "
+                                 f"[{d.rows}, {d.KH}, {d.KW}, {d.Cin}]")
+            if lf is not None and lb is not None and lf.scale != lb.scale:
+                raise ValueError(f"{what}: item {k}: lin_fwd and lin_bwd have the scales {lf.scale} and {lb.scale}, expected one")
+    A.tensor(what, "sched", sched, rank=2, layout="of rank 2 [iters, 4]", contiguous=True, device=dev, other="lo of item 0")
+    if sched.shape[1] != 4:
+        raise ValueError(f"{what}: sched must be [iters, 4], got {tuple(sched.shape)}")
+    A.tensor(what, "iter_ptr", iter_ptr, torch.int32, "int32", numel=1, device=dev, other="lo of item 0")
+    A.tensor(what, "round_log", round_log, shape=(sched.shape[0], L.LOG_SLOTS), contiguous=True, device=dev, optional=True, oneshot=True)
+    if advance_iter is not None and iter_shadow is not None:
+        raise ValueError(f"{what}: advance_iter and iter_shadow are alternatives")
+    for name, word in (("advance_iter", advance_iter), ("iter_shadow", iter_shadow)):
+        A.tensor(what, name, word, torch.int32, "int32", numel=1, device=dev, optional=True, oneshot=True)
+    if iter_shadow is not None and (iter_shadow is iter_ptr or (iter_shadow.device.type != "meta" and iter_shadow.data_ptr() == iter_ptr.data_ptr())):
+        raise ValueError(f"{what}: iter_shadow must be another word than iter_ptr")
+    if gather is not None:
+        if not isinstance(gather, dict) or not {"cache_q", "cache_fp", "idx_table", "B", "prob", "seed"} <= set(gather):
+            raise ValueError(f"{what}: gather must be a dict with cache_q, cache_fp, idx_table, B, prob, seed and out and / or out_planes")
+        cq, B = gather["cache_q"], gather["B"]
+        A.tensor(what, "gather cache_q", cq, contiguous=True, device=dev, other="lo of item 0")
+        A.tensor(what, "gather cache_fp", gather["cache_fp"], shape=tuple(cq.shape), contiguous=True, device=dev, oneshot=True)
+        A.whole(what, "gather B", B, 1)
+        A.tensor(what, "gather idx_table", gather["idx_table"], torch.int32, "int32", rank=2, layout="of rank 2 [iters, B]", contiguous=True, device=dev,
+                 other="lo of item 0")
+        if gather["idx_table"].shape[1] != B:
+            raise ValueError(f"{what}: gather idx_table must be [iters, {B}], got {tuple(gather['idx_table'].shape)}")
+        per = cq[0].numel()
+        out, pl = gather.get("out"), gather.get("out_planes")
+        if out is None and pl is None:
+            raise ValueError(f"{what}: gather has neither out nor out_planes")
+        if per % 4 or (pl is not None and cq.shape[-1] % 16):
+            raise ValueError(f"{what}: gather needs images of a multiple of 4 elements, and channels in 16s for planes, got {tuple(cq.shape)}")
+        A.tensor(what, "gather out", out, numel=B * per, contiguous=True, device=dev, optional=True, oneshot=True)
+        _mx_planes(what, "gather out_planes", pl, B * per, dev, h2_only=True)
+        if not 0.0 <= float(gather["prob"]) <= 1.0:
+            raise ValueError(f"{what}: gather prob must lie in [0, 1], got {gather['prob']!r}")
+    _mx_cuda(what, first, "lo of item 0")
+    _bind_out(None)            # weight planes raise the enclosing block's word
+    arr = (L.MxRoundStepItem * len(items))()
+    dp = lambda t: None if t is None else _ptr(t).value
+    for k, it in enumerate(items):
+        a = arr[k]
+        a.d = it["d"]
+        a.lo, a.gap, a.slabs, a.nsplit = dp(it["lo"]), dp(it["gap"]), dp(it["slabs"]), int(it["slabs"].shape[0])
+        a.alpha, a.adam_m, a.adam_v, a.wq, a.wd = dp(it["alpha"]), dp(it["m"]), dp(it["v"]), dp(it["wq"]), dp(it.get("wd"))
+        a.wq_planes, a.wd_planes = dp(it.get("wq_planes")), dp(it.get("wd_planes"))
+        a.wq_plane_scale, a.wd_plane_scale = _pscale(it.get("wq_planes")), _pscale(it.get("wd_planes"))
+        lf, lb = it.get("lin_fwd"), it.get("lin_bwd")
+        a.lin_fwd_planes, a.lin_bwd_planes = dp(lf), dp(lb)
+        a.lin_plane_scale = float((lf if lf is not None else lb).scale) if (lf is not None or lb is not None) else 0.0
+    g = None if gather is None else C.byref(_gather_desc(gather))
+    L.check(L.lib().rdo_mx_round_step_batch(arr, len(items), float(grad_scale), float(round_weight), _ptr(sched), _ptr(iter_ptr), _ptr(round_log),
+                                            _ptr(advance_iter), _ptr(iter_shadow), g, _stream()), "rdo_mx_round_step_batch")
 
 
 # ---- MX codes on the block-scaled matrix instruction (include/rdo_ptq_mxgemm.h) -------------------------------------------------------------

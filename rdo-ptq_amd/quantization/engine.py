@@ -419,7 +419,7 @@ def _make_op(name, qm, need_dgrad):
 class UnitEngine(DpLoop, RdTask):
     def __init__(self, kind, modules, cache_q, cache_fp, cache_out, *, batch_size, iters, weight=0.01, b_range=(20, 2),
                  warmup=0.2, input_prob=0.5, lr=1e-3, seed=0, idx_table=None, include_act_func=True, group=None,
-                 use_graph=True, force_dp_split=False, task_p=2.0, batch_offset=0, dp_overlap=None, fuse_tail=True, batch_step=True, use_h2=True, rd=None):
+                 use_graph=True, force_dp_split=False, task_p=2.0, batch_offset=0, dp_overlap=None, fuse_tail=True, batch_step=None, use_h2=True, rd=None):
         if kind not in UNIT_KINDS:
             raise NotImplementedError(f"calibration engine: unit kind '{kind}'")
         for t in (cache_q, cache_fp, cache_out):
@@ -438,7 +438,10 @@ class UnitEngine(DpLoop, RdTask):
             use_h2 = os.environ["RDO_USE_H2"] != "0"      # A/B switch for whole runs (bench.py)
         self.use_h2 = bool(use_h2)             # big units on H2 tensors (plane-input LDS-DMA GEMM kernels); False: fp32 activations only
         self.P = {}                            # name -> planes of the H2 form of an activation buffer
-        self.batch_step = bool(batch_step)     # one AdaRound-step launch per unit (False: one per weight tensor)
+        # one AdaRound-step launch per unit (False: one per weight tensor).  None, the default: units on integer grids take it, units on MX
+        # grids keep the per-tensor launches they had before rdo_mx_round_step_batch existed; True asks for it on both kinds of grid
+        self.batch_step = batch_step is None or bool(batch_step)
+        self.batch_step_mx = batch_step is not None and bool(batch_step)
         self.fuse_splitk = os.environ.get("RDO_FUSE_SPLITK", "1") != "0"   # split-K conv + unit tail: the conv's second pass inside the tail
         self.fuse_h2_tail = os.environ.get("RDO_H2_TAIL", "1") != "0"       # last conv of a H2 ResidualBlock unit + its tail in one launch
         self.fold_iter = os.environ.get("RDO_FOLD_ITER", "1") != "0"     # iteration-counter hand-over instead of an increment launch
@@ -540,7 +543,7 @@ class UnitEngine(DpLoop, RdTask):
             raise NotImplementedError(f"calibration engine: ops {mx} are on MX grids and {[n for n in o if n not in mx]} on integer grids: "
                                       "a unit is calibrated on one kind of grid")
         if mx and (self.split or self.rd is not None):
-            # the MX step is the per-op fused launch only (rdo_mx_round_step): no gradient-only / apply pair, no batched form
+            # the MX step is the fused launch only (rdo_mx_round_step, rdo_mx_round_step_batch): no gradient-only / apply pair
             raise NotImplementedError("calibration engine: learned rounding on MX grids is not built for " +
                                       ("data-parallel calibration (world_size > 1)" if self.split else "loss_mode='rd'"))
         self.ops = o
@@ -1147,6 +1150,7 @@ class UnitEngine(DpLoop, RdTask):
         for op in self.ops.values():
             op.row_groups, op.bias_g = 0, None
         if not (self.subpel_fused and not self._probing and self.h2_plan == "rbu" and self.r == 2 and one and not self.split and self._handover
+                and not first.is_mx                      # (the batched step on MX grids reads the slabs in logical row order)
                 and x.planes is not None and h1.planes is not None and dc.planes is not None
                 and self.forms.get("dup") == PLANES and self.forms.get("dsp") == PLANES):
             return False
@@ -1322,6 +1326,9 @@ class UnitEngine(DpLoop, RdTask):
 
     def _items(self, opl):
         # (lin_fwd / lin_bwd: the fragment-ordered planes of a Linear / GDN gamma on rdo_linear_h2 -- written by the step's own launch)
+        if opl[0].is_mx:
+            return [dict(d=op.desc, lo=op.lo, gap=op.gap, slabs=op.slabs, alpha=op.alpha, m=op.m, v=op.v, wq=op.wq, wd=op.wd,
+                         wq_planes=op.wq_planes, wd_planes=op.wd_planes, lin_fwd=op.lin_fwd, lin_bwd=op.lin_bwd) for op in opl]
         return [dict(d=op.desc, w=op.w, delta=op.delta, zp=op.zp, slabs=op.slabs, alpha=op.alpha, m=op.m, v=op.v, wq=op.wq, wd=op.wd,
                      wq_planes=op.wq_planes, wd_planes=op.wd_planes, dalpha=op.dalpha,
                      lin_fwd=op.lin_fwd, lin_bwd=op.lin_bwd) for op in opl]
@@ -1331,7 +1338,13 @@ class UnitEngine(DpLoop, RdTask):
     def _batchable(self, opl):
         """The tensors can go through rdo_adaround_step_batch: in ONE launch up to STEP_BATCH of them, else in ceil(n / STEP_BATCH) launches
         (an RSTB with six blocks has 37 trainable tensors: 37 single-tensor steps, 24 transposes and 48 plane splits per iteration before)."""
-        return self.batch_step and len(opl) >= 1 and all(op.numel() % 4 == 0 and not op.is_mx for op in opl)
+        if not (self.batch_step and len(opl) >= 1 and all(op.numel() % 4 == 0 for op in opl)):
+            return False
+        if not any(op.is_mx for op in opl):
+            return True
+        # rdo_mx_round_step_batch: every tensor on an MX grid (a unit never mixes the grids).  It has the plain step only (no
+        # data-parallel modes) and no rows in 4 groups (`_subpel_plan` leaves such a unit on the plan with the shuffle launches)
+        return self.batch_step_mx and all(op.is_mx for op in opl)
 
     def _step_batches(self, opl, scale, mode):
         """The batched step (mode 0) / update (mode 2) of `opl`.  The iteration counter moves by hand-over (the FIRST launch leaves
@@ -1346,6 +1359,11 @@ class UnitEngine(DpLoop, RdTask):
                 it, kw = self.it, dict(iter_shadow=self.it_shadow if i == 0 else None)
             else:
                 it, kw = self.it, dict(advance_iter=self.it if last else None)
+            if opl[0].is_mx:
+                if mode != 0:
+                    raise NotImplementedError("calibration engine: the batched MX step has no data-parallel modes")
+                ops.mx_round_step_batch(self._items(opl[i:i + self.STEP_BATCH]), scale, self.weight, self.sched, it, self.round_log, **kw)
+                continue
             ops.adaround_step_batch(self._items(opl[i:i + self.STEP_BATCH]), scale, self.weight, self.sched, it, self.round_log, mode=mode,
                                     row_groups=[op.row_groups for op in opl[i:i + self.STEP_BATCH]] if any(op.row_groups for op in opl) else None,
                                     **kw)
@@ -1405,8 +1423,8 @@ class UnitEngine(DpLoop, RdTask):
 
     def _step_ops(self, apply=False):
         """AdaRound step of every op of the unit + iteration counter: one batched launch (+ one for the dgrad layouts) when the
-        tensors allow it, else one launch per op.  The bf16 planes of the new weights are written by the same launches -- except for
-        ops on an MX grid (`_MxOp`: never batchable), whose step writes no planes: the split kernels follow it.
+        tensors allow it, else one launch per op.  The planes of the new weights are written by the same launches -- except on the per-op
+        path of ops on an MX grid (`_MxOp`), whose single-tensor step writes no planes: the split kernels follow it.
         apply (data parallel, plan B): the step from the all-reduced gradient bucket instead of from the weight-gradient slabs."""
         opl = list(self.ops.values())
         scale = self.bucket.scale if apply else 1.0

@@ -358,6 +358,13 @@ def _reconstruct(model, unit, unit_name, cali_data, batch_size=32, iters=20000, 
     common = dict(batch_size=batch_size, iters=iters, weight=weight, b_range=b_range, warmup=warmup, input_prob=input_prob,
                   lr=1e-3, seed=unit_seed(unit_name), include_act_func=include_act_func, batch_offset=rank * batch_size,
                   task_p=float(task_p))
+    # args.batch_step (optional): the engine's switch of the same name -- True asks for the one-launch AdaRound step on MX grids too,
+    # False for one launch per weight tensor on every grid; absent, integer grids take the batched step and MX grids the per-tensor one
+    batch_step = _arg(args, "batch_step", None)
+    if batch_step is not None:
+        if not isinstance(batch_step, bool):
+            raise ValueError(f"reconstruct: args.batch_step must be True or False, got {batch_step!r}")
+        common["batch_step"] = batch_step
     if rd is not None:
         # The rate-distortion task term replaces the lp term through the rest of the sub-coder: the whole wrapped model behind the unit
         # runs under torch's tape (hipops.autograd; Swin blocks included), so the Lu2022 units need no recorded FP tail here
