@@ -38,19 +38,21 @@ __device__ __forceinline__ void ln_pack_row(const ln4* __restrict__ a, const ln4
 }
 
 // mx_gemm_accumulate's loop for the wave's 32 x 32 outputs at (m0, n0) with the A rows in an LDS image (all 64 rows exist: no row test).
-// A B row past `nlast` reads row nlast instead: its column's accumulators are the caller's to drop (a unit that overhangs the matrix).
+// A B row past `nlast` reads row nlast instead: its column's accumulators are the caller's to drop (a unit that overhangs the matrix);
+// likewise an A row past `mlast` (an image of fewer rows than its units cover: mx_resunit.hip's 100-row halo).
 template <int FA, int FB>
 __device__ __forceinline__ void unit_accumulate(const uint32_t* image, int stride, const uint8_t* scales, int nb, const uint32_t* __restrict__ w,
                                                 const uint8_t* __restrict__ sw, int m0, int n0, int r, int kg, f32x4 (&acc)[2][2],
-                                                int nlast = 0x7fffffff) {
+                                                int nlast = 0x7fffffff, int mlast = 0x7fffffff) {
     constexpr int DA = hw_dwords(FA), DB = hw_dwords(FB);
     const uint32_t* arow[2];
     long brow[2];
     int srow[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-        arow[i] = image + (m0 + 16 * i + r) * stride;
-        srow[i] = (m0 + 16 * i + r) * nb;
+        const int m = m0 + 16 * i + r < mlast ? m0 + 16 * i + r : mlast;
+        arow[i] = image + m * stride;
+        srow[i] = m * nb;
         const int n = n0 + 16 * i + r;
         brow[i] = (long)(n < nlast ? n : nlast) * nb;
     }

@@ -327,6 +327,12 @@ _SIGS_MXROUNDBATCH = {
 }
 EXPORTS_MXROUNDBATCH = tuple(_SIGS_MXROUNDBATCH)
 MXROUNDBATCH_MAX = 8           # tensors a launch of rdo_mx_round_step_batch takes
+# include/rdo_ptq_mxresunit.h: the residual unit of the Cheng2020 attention block -- 1x1, ReLU, 3x3, ReLU, 1x1, identity add, ReLU -- in one launch
+_SIGS_MXRESUNIT = {
+    "rdo_mx_residual_unit": (C.c_int, [P] + [C.c_int32] * 5 + [P] * 9 + [C.c_int32] + [P] * 9),
+}
+EXPORTS_MXRESUNIT = tuple(_SIGS_MXRESUNIT)
+MXRESUNIT_MAX_N = 320          # RDO_MXRESUNIT_MAX_N of include/rdo_ptq_mxresunit.h
 # tuning hooks the library exports beside its headers (csrc/conv_wgrad.hip): tile choice (-1 = the library's, 0 = 64 x 64, 1 = 192 x 192)
 # and slab count (-1 = the library's) of rdo_conv2d_wgrad, process-wide; ops.forced_wgrad sets and restores them
 _SIGS_DEBUG = {
@@ -353,7 +359,7 @@ def lib():
                                   + list(_SIGS_ATTNQ.items()) + list(_SIGS_MX.items()) + list(_SIGS_MXROUND.items())
                                   + list(_SIGS_MXGEMM.items()) + list(_SIGS_MXCONV.items()) + list(_SIGS_MXTCONV.items())
                                   + list(_SIGS_MXFILE.items()) + list(_SIGS_MXCHAIN.items()) + list(_SIGS_MXGDN.items()) + list(_SIGS_MXSWIN.items())
-                                  + list(_SIGS_MXATTN.items()) + list(_SIGS_MXSWINATTN.items()) + list(_SIGS_MXROUNDBATCH.items())
+                                  + list(_SIGS_MXATTN.items()) + list(_SIGS_MXSWINATTN.items()) + list(_SIGS_MXROUNDBATCH.items()) + list(_SIGS_MXRESUNIT.items())
                                   + list(_SIGS_DEBUG.items())):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args

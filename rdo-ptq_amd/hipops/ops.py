@@ -1439,6 +1439,65 @@ def mx_swin_attn(d, x, ln_weight, ln_bias, wqkv, bqkv, wproj, bproj, bias, act_f
     return (out, *[got[n] for n in want]) if want else out
 
 
+MX_RESUNIT_OUTPUTS = ("xp", "h1", "h2", "branch")      # what `mx_residual_unit` can be asked for beside `out`
+
+
+def mx_residual_unit(x, shape, w1, b1, w2, b2, w3, b3, act_fmt, want=(), out=None):
+    """The residual unit of the Cheng2020 attention block on the block-scaled matrix instruction, one launch (rdo_mx_residual_unit;
+    include/rdo_ptq_mxresunit.h): out = relu(x + conv1x1(relu(conv3x3(relu(conv1x1(x)))))) with x contiguous fp32 [B * H * W, N] -- the
+    NHWC pixels --, shape = (B, H, W), w1 an `MXOperand` [N/2, N], w2 an `MXOperand` [N/2, 9 N/2] whose rows are in (kh, kw, in) order
+    (`to_rows`) and w3 an `MXOperand` [N, N/2] of one format, b1 / b2 fp32 [N/2] and b3 fp32 [N] or None, act_fmt the MX format of the
+    three activations; N % 64 == 0 and N <= `MXRESUNIT_MAX_N`; the 3x3 has stride 1 and zero padding 1.  Bit for bit `relu(add(x, mx_gemm(
+    mx_conv2d(mx_gemm(mx_quant_pack(x, act_fmt), w1, b1, out_fmt=act_fmt, act='relu'), w2, (B, H, W), 3, 1, 1, b2, out_fmt=act_fmt,
+    act='relu'), w3, b3)))`.  `out`: a contiguous fp32 tensor of x's shape to write into.  want: distinct names out of
+    `MX_RESUNIT_OUTPUTS` -> (out, *wanted): 'xp', 'h1', 'h2' the packed `MXOperand`s [B * H * W, N | N/2 | N/2] of the composition above,
+    'branch' fp32 of x's shape, the last conv's output.  Checked on the host before a pointer is taken."""
+    what = "mx_residual_unit"
+    A.tensor(what, "x", x, rank=2, layout="of rank 2 [B * H * W, N]", contiguous=True)
+    rows, N, dev = int(x.shape[0]), int(x.shape[1]), x.device
+    if isinstance(shape, (str, bytes)) or not hasattr(shape, "__len__") or len(shape) != 3:
+        raise ValueError(f"{what}: shape must be (B, H, W), got {shape!r}")
+    B, H, W = (A.whole(what, f"shape[{i}]", v, 1) for i, v in enumerate(shape))
+    if rows != B * H * W or rows > 0x7fffffff:
+        raise ValueError(f"{what}: x has {rows} rows, shape {(B, H, W)} states {B * H * W} pixels (at most 2^31 - 1)")
+    if N % (2 * L.MX_BLOCK):
+        raise ValueError(f"{what}: N = {N} is no multiple of {2 * L.MX_BLOCK}: N / 2 must be whole MX blocks of {L.MX_BLOCK}")
+    if N > L.MXRESUNIT_MAX_N:
+        raise ValueError(f"{what}: N = {N} is above {L.MXRESUNIT_MAX_N}, the most the kernel's LDS serves")
+    fa, abits = mx_format(what, act_fmt)
+    fw, _, _ = _mx_operand(what, "w1", w1, device=dev)
+    fw2, _, _ = _mx_operand(what, "w2", w2, device=dev)
+    fw3, _, _ = _mx_operand(what, "w3", w3, device=dev)
+    Nh = N // 2
+    if (w1.rows, w1.K) != (Nh, N) or (w2.rows, w2.K) != (Nh, 9 * Nh) or (w3.rows, w3.K) != (N, Nh):
+        raise ValueError(f"{what}: w1 is [{w1.rows}, {w1.K}], w2 [{w2.rows}, {w2.K}] and w3 [{w3.rows}, {w3.K}]; x's {N} channels need "
+                         f"[{Nh}, {N}], [{Nh}, {9 * Nh}] and [{N}, {Nh}]")
+    if not fw == fw2 == fw3:
+        raise ValueError(f"{what}: w1 is in {w1.fmt}, w2 in {w2.fmt} and w3 in {w3.fmt}; the kernel takes one weight format")
+    A.tensor(what, "b1", b1, shape=(Nh,), contiguous=True, device=dev, optional=True, oneshot=True)
+    A.tensor(what, "b2", b2, shape=(Nh,), contiguous=True, device=dev, optional=True, oneshot=True)
+    A.tensor(what, "b3", b3, shape=(N,), contiguous=True, device=dev, optional=True, oneshot=True)
+    A.tensor(what, "out", out, shape=(rows, N), contiguous=True, device=dev, optional=True, oneshot=True)
+    if isinstance(want, (str, bytes)) or not hasattr(want, "__iter__"):
+        raise ValueError(f"{what}: want must be a sequence of names out of {list(MX_RESUNIT_OUTPUTS)}, got {want!r}")
+    want = list(want)
+    if any(n not in MX_RESUNIT_OUTPUTS for n in want) or len(set(want)) != len(want):
+        raise ValueError(f"{what}: want must hold only distinct names out of {list(MX_RESUNIT_OUTPUTS)}, got {want!r}")
+    _mx_cuda(what, x, "x")
+    if out is None:
+        out = torch.empty_like(x)
+    packed = {n: _mx_packed_empty(rows, k, abits, dev) if n in want else (None, None) for n, k in (("xp", N), ("h1", Nh), ("h2", Nh))}
+    # (the wanted fp32 output starts as NaN: an element the kernel does not write cannot pass for a result)
+    branch = torch.full_like(x, float("nan")) if "branch" in want else None
+    L.check(L.lib().rdo_mx_residual_unit(_ptr(x), B, H, W, N, fa, _ptr(w1.packed, *_U8), _ptr(w1.scales, *_U8), _ptr(b1), _ptr(w2.packed, *_U8),
+                                         _ptr(w2.scales, *_U8), _ptr(b2), _ptr(w3.packed, *_U8), _ptr(w3.scales, *_U8), _ptr(b3), fw, _ptr(out),
+                                         *[_ptr(t, *_U8) for n in ("xp", "h1", "h2") for t in packed[n]], _ptr(branch), _stream()),
+            "rdo_mx_residual_unit")
+    got = {n: MXOperand(*packed[n], act_fmt, rows, k) for n, k in (("xp", N), ("h1", Nh), ("h2", Nh)) if n in want}
+    got["branch"] = branch
+    return (out, *[got[n] for n in want]) if want else out
+
+
 def pack_row_words(inner, bits):
     """W = ceil(inner * bits / 32): the 32-bit words one row of `inner` codes of `bits` bits occupies (rdo_pack_row_words on the host)"""
     return -(-int(inner) * int(bits) // 32)

@@ -124,7 +124,13 @@ class _ResidualUnit(nn.Module):
                                   conv1x1(N // 2, N))
         self.relu = nn.ReLU(inplace=True)
 
+    fused_forward = None      # a hook a quantisation package may install: (unit, x) -> the unit's output, or None to decline
+
     def forward(self, x):
+        if self.fused_forward is not None:
+            y = self.fused_forward(x)
+            if y is not None:
+                return y
         return self.relu(self.conv(x) + x)
 
 

@@ -41,7 +41,12 @@ activations (`reconstruct` refuses such a model), data-parallel runs; no rate-di
 Chains (include/rdo_ptq_mxchain.h): `native_chain(first, second, x, act_fmt, act)` runs two convs of the kinds above in three launches
 -- `first` writes act(its output) packed in `act_fmt`, the operand `second` reads -- for pairs `native_chain_refusal` accepts;
 `set_mx_activations(..., chain=True)` switches the conv1 -> LReLU -> conv2 pair of `QuantRB` / `QuantRBWS` blocks to it (`mx_chain`, not
-stored by `save_mx_packed`).  The same bits as the un-chained forward."""
+stored by `save_mx_packed`).  The same bits as the un-chained forward.
+
+The residual unit of the Cheng2020 attention block (include/rdo_ptq_mxresunit.h): `native_residual_unit(unit, x, act_fmt)` runs 1x1,
+ReLU, 3x3, ReLU, 1x1, the identity add and the last ReLU of a `lic.layers._ResidualUnit` in one launch for units
+`native_residual_unit_refusal` accepts; `set_mx_activations(..., residual_units=True)` switches them (`mx_resunit`, not stored).  The same
+bits as the three modules' forwards with the eager add and ReLU."""
 import torch
 import torch.nn as nn
 
@@ -723,6 +728,101 @@ def native_swin_attn(block, x, H, W, act_fmt):
     d = ops.attn_desc(B, H, W, C, attn.num_heads, block.window_size, block.shift_size, attn.scale)
     return ops.mx_swin_attn(d, x.contiguous(), lw, lb, native_operand(attn.qkv), native_bias(attn.qkv), native_operand(attn.proj),
                             native_bias(attn.proj), attn.position_bias(), act_fmt, eps=eps)
+
+
+# ---- the residual unit of the Cheng2020 attention block in one launch (include/rdo_ptq_mxresunit.h) ---------------------------------------------
+def _residual_unit_convs(unit):
+    """the three conv QuantModules of a `lic.layers._ResidualUnit` after the surgery: `unit.conv` is (conv, StraightThrough, conv,
+    StraightThrough, conv) -- `quant_module_refactor` folds each ReLU into the QuantModule before it --; None for anything else"""
+    seq = getattr(unit, "conv", None)
+    if not isinstance(seq, nn.Sequential) or len(seq) != 5:
+        return None
+    convs = (seq[0], seq[2], seq[4])
+    return convs if all(getattr(m, "kind", None) == "conv" for m in convs) else None
+
+
+def native_residual_unit_refusal(unit):
+    """None for a `_ResidualUnit` whose forward `native_residual_unit` serves, else the reason it keeps its forward, looked for in this
+    order: its three convs are not 1x1 / 3x3 stride 1 padding 1 / 1x1 (dilation 1, groups 1) with N -> N/2 -> N/2 -> N channels; a weight
+    is on no MX grid, or the three weight formats differ; N is no multiple of 64 or above `hipops._lib.MXRESUNIT_MAX_N`; a conv has an
+    `se_module`, or the activation functions are not exactly ReLU, ReLU, none; an activation quantiser is active on one of the three."""
+    from .quantizer import StraightThrough
+    convs = _residual_unit_convs(unit)
+    if convs is None:
+        return f"a {type(unit).__name__} does not hold the three convs of a residual unit"
+    c1, c2, c3 = convs
+    N = int(c1.weight.shape[1])
+    if N % 2:
+        return f"its {N} channels are odd"
+    want = (((N // 2, N, 1, 1), 0), ((N // 2, N // 2, 3, 3), 1), ((N, N // 2, 1, 1), 0))
+    for name, m, (shape, pad) in zip(("conv.0", "conv.2", "conv.4"), convs, want):
+        kw = m.fwd_kwargs
+        if (tuple(m.weight.shape) != shape or isinstance(kw["padding"], str) or _pair(kw["stride"]) != (1, 1) or _pair(kw["padding"]) != (pad, pad)
+                or _pair(kw["dilation"]) != (1, 1) or kw["groups"] != 1):
+            return (f"{name} has weight {tuple(m.weight.shape)}, stride {kw['stride']}, padding {kw['padding']}, dilation {kw['dilation']}, groups "
+                    f"{kw['groups']}, not weight {shape}, stride 1, padding {pad}")
+    for name, m in zip(("conv.0", "conv.2", "conv.4"), convs):
+        if not is_mx_any(m.weight_quantizer):
+            return f"{name}: its weight quantiser is a {type(m.weight_quantizer).__name__}, not an MXQuantizer or MXAdaRoundQuantizer"
+    fmts = [m.weight_quantizer.fmt for m in convs]
+    if len(set(fmts)) != 1:
+        return f"its weights are in {fmts[0]}, {fmts[1]} and {fmts[2]}: the kernel takes one weight format"
+    if N % (2 * L.MX_BLOCK):
+        return f"its {N} channels are no multiple of {2 * L.MX_BLOCK}: N / 2 must be whole MX blocks"
+    if N > L.MXRESUNIT_MAX_N:
+        return f"its {N} channels are above {L.MXRESUNIT_MAX_N}, the most the kernel's LDS serves"
+    if any(m.se_module is not None for m in convs):
+        return "one of its convs has an se_module"
+    if (type(c1.activation_function) is not nn.ReLU or type(c2.activation_function) is not nn.ReLU
+            or not isinstance(c3.activation_function, (StraightThrough, nn.Identity))):
+        return (f"its activation functions are {type(c1.activation_function).__name__}, {type(c2.activation_function).__name__} and "
+                f"{type(c3.activation_function).__name__}, not ReLU, ReLU and none")
+    if any(_act_quant_on(m) for m in convs):
+        return "an activation quantiser is active on one of its three convs"
+    return None
+
+
+def residual_unit_format(unit, x):
+    """the activation format where `mx_resunit` is set on a `_ResidualUnit` (`QuantModel.set_mx_activations(..., residual_units=True)`),
+    its three convs carry the same (act_fmt, 'native') with their quantised weights, no activation quantiser rounds between them and the
+    input is not tracked; else None: the unit keeps its module-by-module forward"""
+    convs = _residual_unit_convs(unit) if getattr(unit, "mx_resunit", False) else None
+    if convs is None or (torch.is_grad_enabled() and x.requires_grad):
+        return None
+    on = getattr(convs[0], "mx_activations", None)
+    if on is None or on[1] != "native" or any(getattr(m, "mx_activations", None) != on or not m.use_weight_quant or _act_quant_on(m) for m in convs):
+        return None
+    return on[0]
+
+
+def _residual_unit_forward(unit, x):
+    """`_ResidualUnit.fused_forward`: the one launch where `residual_unit_format` gives a format, else None -- the unit's own forward"""
+    fmt = residual_unit_format(unit, x)
+    return None if fmt is None else native_residual_unit(unit, x, fmt)
+
+
+def native_residual_unit(unit, x, act_fmt):
+    """The output of a `_ResidualUnit` `native_residual_unit_refusal` accepts in one `ops.mx_residual_unit` launch: x is the unit's NCHW
+    input -> relu(x + conv1x1(relu(conv3x3(relu(conv1x1(x)))))) as a channels-last view [B, N, H, W], with x and the two intermediate
+    tensors quantised to `act_fmt` in LDS, the weights the memoised `native_conv_operand`s and the biases those of the modules' present
+    quant state.  The bits of the three modules' `native_conv` forwards with their un-fused ReLUs, the add and the last ReLU."""
+    why = native_residual_unit_refusal(unit)
+    if why is not None:
+        raise ValueError(f"native_residual_unit: {why}")
+    c1, c2, c3 = _residual_unit_convs(unit)
+    N = int(c1.weight.shape[1])
+    if x.dim() != 4 or x.shape[1] != N:
+        raise ValueError(f"native_residual_unit: the input must be [B, {N}, H, W], got {tuple(x.shape)}")
+    B, _, H, W = (int(v) for v in x.shape)
+    out = ops.mx_residual_unit(x.permute(0, 2, 3, 1).reshape(-1, N).contiguous(), (B, H, W), native_conv_operand(c1), native_bias(c1),
+                               native_conv_operand(c2), native_bias(c2), native_conv_operand(c3), native_bias(c3), act_fmt)
+    return out.reshape(B, H, W, N).permute(0, 3, 1, 2)
+
+
+# the model package does not know this one: the unit's class gets the hook here, `set_mx_activations` sets `mx_resunit` per unit
+from lic.layers import _ResidualUnit  # noqa: E402
+
+_ResidualUnit.fused_forward = _residual_unit_forward
 
 
 # ---- MX activations inside the modules' own forward (QuantModel.set_mx_activations) ------------------------------------------------------------

@@ -167,7 +167,8 @@ class QuantModel(nn.Module):
         from .reports import mx_native_report
         return mx_native_report(self, images, act_fmt=act_fmt, batch=batch, units=units, convs=convs, tconvs=tconvs)
 
-    def set_mx_activations(self, act_fmt, mode="native", units=None, chain=False, gdn=False, swin=False, attention=False, p_fmt=None, fused_attention=False):
+    def set_mx_activations(self, act_fmt, mode="native", units=None, chain=False, gdn=False, swin=False, attention=False, p_fmt=None, fused_attention=False,
+                           residual_units=False):
         """Run the modules' own forward on MX activations: every weighted QuantModule of the chosen units (`units`: a list of names of
         `units()`, None for all) that `mx.native_refusal`, `native_conv_refusal` or `native_tconv_refusal` accepts gets the plain
         attribute `mx_activations = (act_fmt, mode)`.  Its no-grad forward, while `use_weight_quant` is on, then takes the
@@ -210,13 +211,28 @@ class QuantModel(nn.Module):
         window 8, shift 0 and 4, FP8 and FP4; profiles/mx_swin_attn_bench.log): the one launch is SLOWER at every one
         of those shapes, 2.05-2.18 x the five launches' time -- one workgroup a CU by LDS.  The keyword is for a forward in two launches
         a block with the same bits, not for speed; it is off by default.
-        ValueError before anything is written for an unknown act_fmt, p_fmt or mode, a fused_attention that is no bool, is True without
+        residual_units=True (mode 'native' only) also sets the plain attribute `mx_resunit` on every `_ResidualUnit` of an `AttentionBlock`
+        (Cheng2020-attn) whose three convs are among the chosen units and switched and which `mx.native_residual_unit_refusal` accepts: its
+        no-grad forward then runs relu(x + conv1x1(relu(conv3x3(relu(conv1x1(x)))))) as one `mx.native_residual_unit` launch instead of
+        eleven (three per conv, the eager add and ReLU), the two intermediate tensors packed in LDS, with the bits of the eleven -- while
+        the three convs carry this (act_fmt, 'native'), `use_weight_quant` is on, no activation quantiser rounds on them and the input is
+        not tracked.  The result gains 'residual_units': unit name -> the three conv names; a refused unit goes under 'left' with the
+        reason.  residual_units=False and act_fmt=None clear `mx_resunit`; it is not stored by `save_mx_packed`.  An input that is
+        not a channels-last view costs one layout copy before the launch; switched units hand each other channels-last views.  Measured
+        against the six `ops` launches the kernel is bit for bit (B = 4, 16 x 16 and 64 x 64, N = 128 and 192, FP8 and FP4;
+        profiles/mx_resunit_bench.log): called from Python 0.49-0.94 x their time (1.04 x for FP8 at N = 192, 64 x
+        64), which is the host issuing one launch for six; both replayed as graphs, kernels only, the one launch is SLOWER at six of the
+        eight shapes (1.09-2.06 x) and faster only at N = 128, 64 x 64 (0.82 x).  The keyword is for a unit in one launch with the same
+        bits, not for a faster kernel; it is off by default.
+        ValueError before anything is written for an unknown act_fmt, p_fmt or mode, a residual_units that is no bool or is True in another
+        mode than 'native', a fused_attention that is no bool, is True without
         swin=True and attention=True or with a p_fmt other than act_fmt, an unknown unit, a gdn that is no bool, a chain, swin
         or attention that is no bool or is True in another mode than 'native', a p_fmt without attention=True, and (act_fmt not None) a named unit without an eligible module.  An input that requires grad raises NotImplementedError in a switched module; `reconstruct`
         refuses a model that holds one."""
         from collections import OrderedDict
         from . import mx
         from hipops import ops
+        from lic.layers import _ResidualUnit
         what, known = "set_mx_activations", self.units()
         if act_fmt is not None:
             ops.mx_format(what, act_fmt)
@@ -237,6 +253,9 @@ class QuantModel(nn.Module):
         if not isinstance(fused_attention, bool) or (fused_attention and not (swin and attention and p_fmt in (None, act_fmt))):
             raise ValueError(f"{what}: fused_attention must be True or False, and True only with swin=True, attention=True and a p_fmt that is "
                              f"None or act_fmt; got fused_attention={fused_attention!r}, swin={swin!r}, attention={attention!r}, p_fmt={p_fmt!r}")
+        if not isinstance(residual_units, bool) or (residual_units and mode != "native"):
+            raise ValueError(f"{what}: residual_units must be True or False, and True in mode 'native' only; got residual_units={residual_units!r}, "
+                             f"mode={mode!r}")
         if units is None:
             chosen = list(known)
         else:
@@ -310,6 +329,23 @@ class QuantModel(nn.Module):
             if units is not None and act_fmt is not None and not found:
                 raise ValueError(f"{what}: unit {uname!r} holds no eligible module: "
                                  f"{ {n: w for n, w in rep['left'].items() if n == uname or n.startswith(uname + '.')} }")
+        resunits = []
+        if residual_units:
+            rep["residual_units"] = OrderedDict()
+        for rname, r in self.model.named_modules():
+            names = tuple(f"{rname}.conv.{i}" for i in (0, 2, 4))
+            if not isinstance(r, _ResidualUnit) or not any(n in chosen for n in names):
+                continue
+            why = "not asked for"
+            if residual_units and act_fmt is not None:
+                why = mx.native_residual_unit_refusal(r)
+                if why is None and not all(n in chosen and n in rep["native"] for n in names):
+                    why = "its three convs are not all among the chosen units and switched"
+                if why is None:
+                    rep["residual_units"][rname] = names
+                else:
+                    rep["left"][rname] = why
+            resunits.append((r, why is None))
         for m, kind in plan:
             m.mx_activations = None if (act_fmt is None or kind is None) else (act_fmt, mode)
         for b, on in blocks:
@@ -318,6 +354,8 @@ class QuantModel(nn.Module):
             b.mx_swin, b.mx_swin_attn = on, fused
         for a, on in attentions:
             a.mx_attention = on
+        for r, on in resunits:
+            r.mx_resunit = on
         return rep
 
     def set_weight_format(self, formats, rounding="nearest"):
